@@ -1,22 +1,28 @@
 #!/usr/bin/env python3
 """bench.py — Mrays/s + wall-clock per frame of the HIP render path on BASELINE.json's configs.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3|c2|c3room|c4|c5|c1] [--scaling weak|strong] [--no-configs]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3|c2|c3room|c4|c5|c1] [--scaling weak|strong]
+                    [--dump-outputs DIR] [--full [--no-configs] [--no-cpu-baseline] [--no-alone]]
 
 A "step" = one full frame of the workload through the hot path (camera rays -> wavefront
 trace/shade steps -> combine -> resolve [-> RCCL framebuffer gather when N > 1]).
 Headline workload (N = 1 default) = BASELINE.json configs[2], the largest single-GPU 1080p configuration: tests/scenes/c3_mesh.xml
 (100,352-triangle mesh over a textured plane), 1920x1080, 64 spp, GI depth 3, internal bounces 16, keyed RNG seed 0 — the BVH walk
-north_star is about dominates it.  The same JSON line carries, under "configs", the other configurations timed the same way with a few
+north_star is about dominates it.
+A plain run sets up, warms up, times the K steps, writes the last step's frame if --dump-outputs is given (DIR/rgb8.npy and
+DIR/radiance.npy, both float32 H x W x 3: the two buffers a caller of the render path receives; a fixed sample of 2^20 pixels plus
+DIR/pixel_index.npy where the frame would exceed 64 MB, see dump_frame) and prints the line.
+--full adds what takes work of its own beside the timed steps: under "configs", the other configurations timed the same way with a few
 steps each: c2 (BASELINE configs[1]: glass spheres, 16 spp, no mesh), c3room (the closed Cornell room of proj13.xml around the same
-mesh), c4 (3840x2160, 32 spp per GPU = 256 spp on 8) and c5 (1 M caustic photons + k-NN gather, 64 spp) — each with its own `roofline`.
+mesh), c4 (3840x2160, 32 spp per GPU = 256 spp on 8) and c5 (1 M caustic photons + k-NN gather, 64 spp) — each with its own `roofline`;
+`cpu_baseline`; the untimed frames behind `frac_alone` and the c5 gather statistics; the D2H / PNG lines (`wall_clock_extra`).
 N > 1: one process per GPU (torch.distributed, backend nccl = RCCL); interleaved 32x32 tiles (tile t -> rank t mod N),
 one all_gather of the packed tile buffers over xGMI inside the timed region.  --scaling weak (default): spp scaled with N so per-GPU
 work is fixed; --scaling strong: BASELINE's own spp (64; 256 for c4) split over the ranks by tiles, total work fixed.
 `python bench.py --gpus N` without a torchrun environment starts the N ranks itself.
 The scene is resident in HBM before the timed region; outputs stay in HBM.
 
-Prints ONE JSON line on rank 0 (see the driver contract) with `roofline` and `cpu_baseline`.
+Prints ONE JSON line on rank 0 (see the driver contract) with `roofline` (and, with --full, `cpu_baseline`).
 """
 import argparse
 import json
@@ -55,12 +61,30 @@ HBM_PEAK_GBPS = 8000.0       # MI355X HBM3E spec peak (/opt/skills/guides/MI355X
 TILE = 32
 
 
+ASSET_DIR = [os.path.join(ROOT, "tests", "scenes")]  # the directory under which the scenes' gen/mesh_224.obj lies
+
+
 def ensure_assets():
-    mesh = os.path.join(ROOT, "tests/scenes/gen/mesh_224.obj")
-    if not os.path.exists(mesh):
-        sys.path.insert(0, os.path.join(ROOT, "tools"))
-        import gen_mesh
-        gen_mesh.generate(mesh, 224)
+    """The 100,352-triangle mesh the mesh workloads name as gen/mesh_224.obj: written by the deterministic generator to tests/scenes/gen/
+    (git-ignored; tools/pmc_workload.py and the tests load it from there too).  Where the checkout is read-only, it goes to a private
+    temporary directory instead (removed at exit); the front-end then finds it through $BHRT_ASSET_ROOT, and the
+    reference harness of cpu_baseline is started in that directory."""
+    if os.path.exists(os.path.join(ASSET_DIR[0], "gen", "mesh_224.obj")):
+        return
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import gen_mesh
+    try:
+        gen_mesh.generate(os.path.join(ASSET_DIR[0], "gen", "mesh_224.obj"), 224)
+        return
+    except OSError:
+        pass
+    import atexit
+    import shutil
+    tmp = tempfile.mkdtemp(prefix="bhrt_bench_assets_")
+    atexit.register(shutil.rmtree, tmp, True)
+    gen_mesh.generate(os.path.join(tmp, "gen", "mesh_224.obj"), 224)
+    os.environ["BHRT_ASSET_ROOT"] = tmp
+    ASSET_DIR[0] = tmp
 
 
 def cpu_baseline(scene_path, spp, gi, full_spp=None):
@@ -101,7 +125,7 @@ def cpu_baseline(scene_path, spp, gi, full_spp=None):
             for k in range(cores):
                 cmd = [harness, os.path.abspath(scene_path), os.path.join(tmp, f"b{k}"), "--spp", str(spp), "--gi", str(gi),
                        "--region", "0", str(bounds[k]), str(W), str(bounds[k + 1]), "render"]
-                procs.append(subprocess.Popen(cmd, cwd=os.path.dirname(os.path.abspath(scene_path)),
+                procs.append(subprocess.Popen(cmd, cwd=ASSET_DIR[0],  # the reference opens assets relative to its cwd only
                                               stdout=subprocess.DEVNULL, stderr=subprocess.PIPE, text=True))
             errs = [p.communicate()[1] for p in procs]
             ok = all(p.returncode == 0 for p in procs)
@@ -129,8 +153,31 @@ def pmc_profile(workload):
         return {}
 
 
-def run_workload(name, steps, warmup, ctx, photons, samples_per_pass=0, timers=None, extras=False):
-    """Times `steps` frames of workload `name` (barrier + synchronize on both sides, max over ranks)."""
+DUMP_CAP_BYTES = 64_000_000   # --dump-outputs writes at most this much
+DUMP_SAMPLE_PIXELS = 1 << 20  # pixels of the fixed sample written where the whole frame would exceed the cap (c4: 8.3 M pixels)
+
+
+def dump_frame(out_dir, rgb, rad):
+    """The frame of the last timed step as DIR/rgb8.npy and DIR/radiance.npy, float32 (the dump holds float32 / float64 arrays only, so the
+    RGB8 bytes are widened).  Whole frame, H x W x 3, where both fit in DUMP_CAP_BYTES (1920x1080: 2 x 24.9 MB); otherwise the
+    same DUMP_SAMPLE_PIXELS pixels every run (numpy's PCG64, seed 0, ascending), as N x 3, with their row-major indices y * W + x in
+    DIR/pixel_index.npy (float64: 2 x 12.6 MB + 8.4 MB)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    H, W = rgb.shape[0], rgb.shape[1]
+    rgb_h = rgb.cpu().numpy().astype(np.float32)
+    rad_h = rad.cpu().numpy().astype(np.float32)
+    if rgb_h.nbytes + rad_h.nbytes > DUMP_CAP_BYTES:
+        idx = np.sort(np.random.default_rng(0).choice(H * W, size=DUMP_SAMPLE_PIXELS, replace=False))
+        rgb_h, rad_h = rgb_h.reshape(-1, 3)[idx], rad_h.reshape(-1, 3)[idx]
+        np.save(os.path.join(out_dir, "pixel_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(out_dir, "rgb8.npy"), rgb_h)
+    np.save(os.path.join(out_dir, "radiance.npy"), rad_h)
+
+
+def run_workload(name, steps, warmup, ctx, photons, samples_per_pass=0, timers=None, extras=False, full=True, dump_dir=None):
+    """Times `steps` frames of workload `name` (barrier + synchronize on both sides, max over ranks).
+    full=False: nothing beside the timed frames (no untimed frames of other settings afterwards)."""
     import torch
     import bhraytracer_amd as B
     import bhraytracer_amd.dist as BD
@@ -193,6 +240,9 @@ def run_workload(name, steps, warmup, ctx, photons, samples_per_pass=0, timers=N
         agg = d if agg is None else {k: agg[k] + d[k] for k in d}
     sync()
     elapsed = time.perf_counter() - t0
+    if dump_dir and rank == 0:  # before any untimed frame below renders into the same buffers
+        last = bufs[(frame_no[0] - 1) % n_buf]
+        dump_frame(dump_dir, last[0], last[1])
     rays_local = agg["closest_rays"] + agg["shadow_rays"]
     if N > 1:
         rdev = torch.device("cpu") if rehearse else dev
@@ -208,7 +258,7 @@ def run_workload(name, steps, warmup, ctx, photons, samples_per_pass=0, timers=N
     # inside the timed region the kernel groups share the GPU, so their HIP-event times overlap and sum to more than the frame.  Two more frames,
     # untimed, with that switched off give every group's time ALONE — what `roofline.frac_alone` is computed from.
     alone = None
-    if sc.info.n_meshes > 0 and N == 1 and opts.timers >= 1 and not ctx.get("no_alone"):
+    if full and sc.info.n_meshes > 0 and N == 1 and opts.timers >= 1 and not ctx.get("no_alone"):
         sc.knob("shadow_overlap", 0)
         step(); torch.cuda.synchronize()
         t0 = time.perf_counter()
@@ -217,14 +267,14 @@ def run_workload(name, steps, warmup, ctx, photons, samples_per_pass=0, timers=N
         alone = dict(d, ms_per_step=(time.perf_counter() - t0) * 1e3)
         sc.knob("shadow_overlap", 1)
     found_per_query = None
-    if name == "c5" and rank == 0 and N == 1:  # one more frame, untimed, with the statistics instantiation of the lane pass (7 % slower: not the timed kernel)
+    if full and name == "c5" and rank == 0 and N == 1:  # one more frame, untimed, with the statistics instantiation of the lane pass (7 % slower: not the timed kernel)
         sc.knob("gather_stats", 1)
         d = step().as_dict()
         torch.cuda.synchronize()
         sc.knob("gather_stats", 0)
         found_per_query = d.get("photon_found", 0) / max(1, d.get("photon_lane_queries", 0))
     extra = None
-    if extras and rank == 0:
+    if full and extras and rank == 0:
         # the two lines SURVEY.md 8(d) asks for beside the frame time: the device-to-host copy of the frame (RGB8 + float radiance, pinned
         # destination) and the PNG encode (RenderImage::SaveImage, scene.h:628-644 -> bhrt_save_png), each timed on its own after the run
         import numpy as np
@@ -359,6 +409,12 @@ def main():
     ap.add_argument("--workload", default=HEADLINE, choices=sorted(WORKLOADS))
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"],
                     help="N > 1: weak = spp x N, per-GPU work fixed (default); strong = BASELINE's spp (64; 256 for c4) split over the ranks by tiles")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's frame as DIR/rgb8.npy and DIR/radiance.npy (float32, H x W x 3; rank 0 after the exchange when N > 1; "
+                         "at most 64 MB: larger frames as a fixed sample of 2^20 pixels, indices in DIR/pixel_index.npy)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what a plain run leaves out: the 'configs' object, cpu_baseline, the untimed frames behind frac_alone "
+                         "and the c5 gather statistics, the D2H / PNG lines (the --no-* options below trim it)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-alone", action="store_true", help="skip the two untimed frames that time the kernel groups alone (any-hit work in front of the next step instead of beside it): profiling runs whose kernel statistics should hold frames of one kind only")
     ap.add_argument("--no-configs", action="store_true", help="headline only: skip the 'configs' object (c3, c3room, c4, c5)")
@@ -373,6 +429,8 @@ def main():
                     help="development aid: all ranks share cuda:0 and the gather goes through gloo on host copies, "
                          "to rehearse the N > 1 control flow on a one-GPU box (numbers are meaningless)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world_env = os.environ.get("WORLD_SIZE")
     if args.gpus > 1 and (world_env is None or int(world_env) != args.gpus):
@@ -405,11 +463,14 @@ def main():
         ensure_assets()
     if N > 1:
         dist.barrier()
+    if rank != 0:
+        ensure_assets()  # finds rank 0's mesh in the tree; in a read-only checkout each rank (its own process) makes its own copy
     ctx = {"rank": rank, "local_rank": local_rank, "N": N, "dev": dev, "dist": dist, "rehearse": args.rehearse_on_one_gpu, "scaling": args.scaling, "no_alone": args.no_alone}
 
-    head = run_workload(args.workload, args.steps, args.warmup, ctx, args.photons, args.samples_per_pass, args.timers, extras=True)
+    head = run_workload(args.workload, args.steps, args.warmup, ctx, args.photons, args.samples_per_pass, args.timers, extras=True,
+                        full=args.full, dump_dir=args.dump_outputs)
     configs = {}
-    if args.workload == HEADLINE and not args.no_configs:
+    if args.full and args.workload == HEADLINE and not args.no_configs:
         for name in [c for c in args.configs.split(",") if c]:
             try:  # a side workload that fails is reported as such; the headline line is printed regardless
                 configs[name] = run_workload(name, 20 if name == "c2" else args.config_steps, 3 if name == "c2" else args.config_warmup, ctx, args.photons)
@@ -445,7 +506,7 @@ def main():
             out["wall_clock_extra"] = head["wall_clock_extra"]
         if configs:
             out["configs"] = configs
-        if N == 1 and not args.no_cpu_baseline:
+        if args.full and N == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(os.path.join(ROOT, scene_rel), args.cpu_sample_spp or CPU_SAMPLE_SPP.get(args.workload, spp1), gi, full_spp=spp1)
         print(json.dumps(out), flush=True)
     if N > 1:

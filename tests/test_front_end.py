@@ -6,7 +6,9 @@ import os
 import numpy as np
 import pytest
 
-from conftest import REFERENCE, SCENES
+from conftest import GOLDEN, SCENES
+
+SHIPPED_ROOT = os.path.join(GOLDEN, "shipped")  # the reference's shipped scene files (tests/golden/make_ref_parity.py)
 
 
 def test_bvh_front_end_equals_oracle_restatement(load_scene, O):
@@ -68,12 +70,11 @@ def test_obj_rules(B, tmp_path):
     assert np.array_equal(m["fn"], m["f"])
 
 
-@pytest.mark.skipif(not os.path.isdir(REFERENCE), reason="reference scenes only exist in the development container")
 def test_all_shipped_scenes_load(B):
-    files = sorted(glob.glob(os.path.join(REFERENCE, "Resource", "**", "*.xml"), recursive=True))
+    files = sorted(glob.glob(os.path.join(SHIPPED_ROOT, "Resource", "**", "*.xml"), recursive=True))
     assert len(files) == 19
     cwd = os.getcwd()
-    os.chdir(REFERENCE)  # the reference resolves asset paths against its working directory
+    os.chdir(SHIPPED_ROOT)  # the reference resolves asset paths against its working directory
     try:
         for f in files:
             sc = B.Scene(f)

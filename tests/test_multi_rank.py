@@ -144,12 +144,12 @@ def test_the_rccl_calls_of_the_exchange_in_a_world_of_one(tmp_path):
 
 @pytest.mark.gpu
 def test_bench_line_of_the_default_run_carries_what_the_contract_asks_for():
-    """`python bench.py` as the driver runs it (fewer steps here): ONE JSON line whose headline is BASELINE config 3 with `roofline` (incl. the
-    lane-slot figures the PMC passes gave) and `cpu_baseline` (the reference where oracle/_ref travelled, else the port), the other configurations
+    """`python bench.py --full` (fewer steps here): ONE JSON line whose headline is BASELINE config 3 with `roofline` (incl. the
+    lane-slot figures the PMC passes gave) and `cpu_baseline` (the reference where oracle/_ref was built, else the port), the other configurations
     under `configs`, the D2H / PNG lines, exit code 0."""
     import json, subprocess
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--config-steps", "1", "--config-warmup", "0", "--cpu-sample-spp", "2"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "2", "--warmup", "1", "--config-steps", "1", "--config-warmup", "0", "--cpu-sample-spp", "2"],
                        env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -167,3 +167,52 @@ def test_bench_line_of_the_default_run_carries_what_the_contract_asks_for():
     assert set(d["configs"]) == {"c2", "c3room", "c4", "c5"} and all("error" not in v and v["ms_per_step"] > 0 for v in d["configs"].values())
     assert d["configs"]["c5"]["photon"]["build_s"] < 0.5 and d["configs"]["c5"]["photon"]["lane_pass_found_per_query"] > 1
     assert d["wall_clock_extra"]["d2h_ms"] > 0 and d["wall_clock_extra"]["png_encode_ms"] > 0
+
+
+@pytest.mark.gpu
+def test_plain_bench_run_times_the_steps_and_dumps_the_last_frame(tmp_path):
+    """`python bench.py --steps K --warmup W --dump-outputs DIR` without --full, on the headline (a mesh scene, so each leaked extra would
+    show): the line carries the headline fields and nothing that takes work of its own (no `configs`, no `cpu_baseline`, no D2H / PNG lines,
+    no frames without the any-hit overlap), and DIR holds the last timed frame as float32 arrays; a second run with the same arguments
+    writes the same arrays."""
+    import json, subprocess
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    frames = []
+    for k in range(2):
+        out = tmp_path / f"out{k}"
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "0", "--dump-outputs", str(out)],
+                           env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1
+        d = json.loads(lines[0])
+        assert d["steps"] == 2 and d["warmup"] == 0 and d["ms_per_step"] > 0 and d["value"] > 0 and d["unit"] == "Mrays/s"
+        assert d["higher_is_better"] is True and d["dtype"] == "f32" and "c3_mesh.xml 1920x1080, 64 spp" in d["config"]["workload"]
+        assert not {"configs", "cpu_baseline", "wall_clock_extra", "ms_per_step_without_overlap", "kernel_seconds_without_overlap"} & set(d)
+        assert "frac_alone" not in d["roofline"]
+        assert sorted(os.listdir(out)) == ["radiance.npy", "rgb8.npy"]
+        rgb, rad = np.load(out / "rgb8.npy"), np.load(out / "radiance.npy")
+        assert rgb.dtype == rad.dtype == np.float32 and rgb.shape == rad.shape == (1080, 1920, 3)
+        assert rgb.max() > 0 and rgb.max() <= 255 and np.array_equal(rgb, np.round(rgb)) and np.isfinite(rad).all() and rad.max() > 0
+        frames.append((rgb, rad))
+    assert np.array_equal(frames[0][0], frames[1][0]) and np.array_equal(frames[0][1].view(np.uint32), frames[1][1].view(np.uint32))
+
+
+@pytest.mark.gpu
+def test_dump_of_a_4k_frame_stays_within_64_mb(tmp_path):
+    """c4's 3840x2160 frame would take 199 MB as two float32 arrays: --dump-outputs writes the fixed sample of 2^20 pixels instead, with
+    their indices, under 64 MB in all."""
+    import subprocess
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    out = tmp_path / "out"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "c4", "--steps", "1", "--warmup", "0", "--dump-outputs", str(out)],
+                       env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    assert sum(os.path.getsize(out / f) for f in os.listdir(out)) <= 64_000_000
+    idx, rgb, rad = np.load(out / "pixel_index.npy"), np.load(out / "rgb8.npy"), np.load(out / "radiance.npy")
+    assert idx.dtype == np.float64 and rgb.dtype == rad.dtype == np.float32 and rgb.shape == rad.shape == (1 << 20, 3) and idx.shape == (1 << 20,)
+    assert np.all(np.diff(idx) > 0) and idx[0] >= 0 and idx[-1] < 3840 * 2160
+    assert np.array_equal(idx, np.sort(np.random.default_rng(0).choice(3840 * 2160, size=1 << 20, replace=False)).astype(np.float64))
+    assert rgb.max() > 0 and np.isfinite(rad).all() and rad.max() > 0

@@ -1,76 +1,91 @@
-"""Live comparison of the oracle with the compiled reference (oracle/_ref/ref_harness).  Only runs where
-/root/reference exists (the development container); the committed fixtures in tests/golden carry the same
-pins to the GPU box."""
+"""The oracle and the front-end against the unmodified reference (oracle/_ref/ref_harness[_pm]).  The reference's outputs were recorded
+by tests/golden/make_ref_parity.py into tests/golden/ref_parity*.npz, on inputs that are committed as well (the scenes under tests/scenes,
+the reference's shipped XMLs and their textures under tests/golden/shipped, the XML text of every random scene), so these tests need
+nothing outside the repository."""
+import glob
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import REFERENCE, REF_HARNESS, ROOT, SCENES, same_bits
+from conftest import GOLDEN, ROOT, SCENES, same_bits
 
-pytestmark = pytest.mark.skipif(not (os.path.isdir(REFERENCE) and os.path.exists(REF_HARNESS)),
-                                reason="needs /root/reference and oracle/_ref (development container only)")
-
-
-def run_ref(scene, prefix, *args, cwd):
-    subprocess.run([REF_HARNESS, scene, prefix, *map(str, args)], cwd=cwd, check=True, stdout=subprocess.DEVNULL,
-                   stderr=subprocess.DEVNULL)
+SHIPPED_ROOT = os.path.join(GOLDEN, "shipped")  # the reference resolves asset paths against its working directory: Resource/...
 
 
-def test_scene_dump_matches_front_end(B, tmp_path):
+@pytest.fixture(scope="module")
+def ref():
+    """The reference's recorded outputs, by name (tests/golden/make_ref_parity.py)."""
+    out = {}
+    for name in ("ref_parity", "ref_parity_render"):
+        with np.load(os.path.join(GOLDEN, name + ".npz")) as z:
+            out.update({k: z[k] for k in z.files})
+    return out
+
+
+def _key(rel):
+    return rel.replace("/", "__").replace(".xml", "")
+
+
+def _sha(a):
+    import hashlib
+    return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
+
+
+def test_scene_dump_matches_front_end(B, ref):
     # transforms, camera frame, light order, meshes and the BVH: bit for bit
     sc = B.Scene(os.path.join(SCENES, "c4_textured.xml"))
     fv = sc.flat_view()
-    pre = str(tmp_path / "d")
-    run_ref("c4_textured.xml", pre, "dump", cwd=SCENES)
-    nf = np.fromfile(pre + ".nodes_f32", np.uint32).reshape(-1, 21)
+    d = lambda ext: ref["dump_c4_textured_" + ext]
+    nf = d("nodes_f32").reshape(-1, 21)
     mine = np.array([list(n.xf.tm) + list(n.xf.pos) + list(n.xf.itm) for n in fv.nodes], np.float32).view(np.uint32)
     assert np.array_equal(nf, mine)
-    ni = np.fromfile(pre + ".nodes_i32", np.int32).reshape(-1, 5)
+    ni = d("nodes_i32").reshape(-1, 5)
     assert np.array_equal(ni, np.array([[n.parent, n.depth, n.obj_type, n.mesh, n.material] for n in fv.nodes], np.int32))
     m = fv.mesh_arrays(0)
-    assert np.array_equal(np.fromfile(pre + ".mesh0.bvh_u32", np.uint32), m["bvh_data"])
-    assert np.array_equal(np.fromfile(pre + ".mesh0.bvh_f32", np.uint32).reshape(-1, 6)[1:], m["bvh_bounds"].view(np.uint32)[1:])
-    assert np.array_equal(np.fromfile(pre + ".mesh0.elems_u32", np.uint32), m["elems"])
-    assert np.array_equal(np.fromfile(pre + ".mesh0.vn_f32", np.uint32), m["vn"].view(np.uint32).ravel())
-    lf = np.fromfile(pre + ".lights_f32", np.float32)
+    assert np.array_equal(d("mesh0_bvh_u32"), m["bvh_data"])
+    assert np.array_equal(d("mesh0_bvh_f32").reshape(-1, 6)[1:], m["bvh_bounds"].view(np.uint32)[1:])
+    assert np.array_equal(d("mesh0_elems_u32"), m["elems"])
+    assert np.array_equal(d("mesh0_vn_f32"), m["vn"].view(np.uint32).ravel())
+    lf = d("lights_f32")
     assert [int(t) for t in lf[:-1].reshape(-1, 8)[:, 0]] == [l.type for l in fv.lights]     # CalculateLightsIntensity sort
     assert lf[-1] == np.float32(fv.header.all_light_intensity)
 
 
 def _shipped_xmls():
-    import glob
-    return sorted(os.path.relpath(f, REFERENCE) for f in glob.glob(os.path.join(REFERENCE, "Resource", "**", "*.xml"), recursive=True))
+    return sorted(os.path.relpath(f, SHIPPED_ROOT) for f in glob.glob(os.path.join(SHIPPED_ROOT, "Resource", "**", "*.xml"), recursive=True))
 
 
-@pytest.mark.parametrize("rel", _shipped_xmls() if os.path.isdir(REFERENCE) else [])
-def test_front_end_dump_of_every_shipped_scene(rel, B, tmp_path):
+def test_all_19_shipped_scenes_are_committed():
+    assert len(_shipped_xmls()) == 19
+
+
+@pytest.mark.parametrize("rel", _shipped_xmls())
+def test_front_end_dump_of_every_shipped_scene(rel, B, ref):
     """xmlload's result on all 19 shipped XMLs (scene graph, transforms, camera frame, sorted lights,
     materials) equals the front-end's flat scene bit for bit.  Meshes are absent from the reference checkout, so their
     nodes are null objects on both sides."""
-    pre = str(tmp_path / "d")
-    run_ref(rel, pre, "dump", cwd=REFERENCE)
+    d = lambda ext: ref[f"dump_{_key(rel)}_{ext}"]
     cwd = os.getcwd()
-    os.chdir(REFERENCE)
+    os.chdir(SHIPPED_ROOT)
     try:
         fv = B.Scene(rel).flat_view()
     finally:
         os.chdir(cwd)
     u32 = lambda a: np.asarray(a, np.float32).view(np.uint32)
-    nf = np.fromfile(pre + ".nodes_f32", np.uint32).reshape(-1, 21)
+    nf = d("nodes_f32").reshape(-1, 21)
     assert np.array_equal(nf, u32([list(n.xf.tm) + list(n.xf.pos) + list(n.xf.itm) for n in fv.nodes]).reshape(-1, 21))
-    ni = np.fromfile(pre + ".nodes_i32", np.int32).reshape(-1, 5)
+    ni = d("nodes_i32").reshape(-1, 5)
     assert np.array_equal(ni, np.array([[n.parent, n.depth, n.obj_type, n.mesh, n.material] for n in fv.nodes], np.int32).reshape(-1, 5))
     c = fv.header.camera
     cam = list(c.pos) + list(c.dir) + list(c.up) + [c.fov, c.focaldist, c.width, c.height] + list(c.top_left) + list(c.dd_x) + list(c.dd_y)
-    assert np.array_equal(np.fromfile(pre + ".camera_f32", np.uint32), u32(cam))
+    assert np.array_equal(d("camera_f32"), u32(cam))
     lights = []
     for l in fv.lights:
         lights += [l.type] + list(l.intensity) + (list(l.vec) if l.type else [0, 0, 0]) + [l.size if l.type == 2 else 0]
     lights.append(fv.header.all_light_intensity)
-    assert np.array_equal(np.fromfile(pre + ".lights_f32", np.uint32), u32(lights))
-    mf = np.fromfile(pre + ".materials_f32", np.float32).reshape(-1, 26)
+    assert np.array_equal(d("lights_f32"), u32(lights))
+    mf = d("materials_f32").reshape(-1, 26)
     assert len(mf) == len(fv.materials)
     for row, m in zip(mf, fv.materials):
         if m.kind != 0:
@@ -87,26 +102,24 @@ SHIPPED = ["proj12_backfaceTest", "proj3", "proj13", "proj7", "proj10", "proj2"]
 
 
 @pytest.mark.parametrize("name", SHIPPED)
-def test_integrator_on_shipped_scenes(name, B, O, tmp_path):
-    """MtlBlinn::Shade through GI depth 3 on the reference's own scene files (meshes absent -> null objects)."""
+def test_integrator_on_shipped_scenes(name, B, O, ref):
+    """MtlBlinn::Shade through GI depth 3 on the reference's own scene files (meshes absent -> null objects; its two textures at 256x256)."""
     xml = os.path.join("Resource", "Data", name + ".xml")
     region = (330, 260, 430, 330)
     spp = 2
-    pre = str(tmp_path / name)
-    run_ref(xml, pre, "--spp", spp, "--gi", 3, "--region", *region, "render", cwd=REFERENCE)
     cwd = os.getcwd()
-    os.chdir(REFERENCE)
+    os.chdir(SHIPPED_ROOT)
     try:
         sc = B.Scene(xml)
     finally:
         os.chdir(cwd)
     r = O.render(sc.flat_bytes(), sc.width, sc.height, spp, gi=3, rng=O.RNG_SEQUENTIAL, math=O.MATH_LIBM, region=region, threads=4)
     npx = (region[2] - region[0]) * (region[3] - region[1])
-    assert same_bits(r["samples"], np.fromfile(pre + ".samples_f32", np.float32).reshape(npx, spp, 3))
-    assert np.array_equal(r["rgb8"].reshape(-1, 3), np.fromfile(pre + ".rgb8", np.uint8).reshape(npx, 3))
+    assert same_bits(r["samples"], ref[f"render_{name}_samples"].reshape(npx, spp, 3))
+    assert np.array_equal(r["rgb8"].reshape(-1, 3), ref[f"render_{name}_rgb8"].reshape(npx, 3))
 
 
-def test_large_mesh_primary_hits(B, O, tmp_path):
+def test_large_mesh_primary_hits(B, O, ref):
     """BASELINE config 3 geometry (100,352 triangles): BVH node-for-node and every primary hit bit-exact."""
     import sys
     sys.path.insert(0, os.path.join(ROOT, "tools"))
@@ -118,38 +131,30 @@ def test_large_mesh_primary_hits(B, O, tmp_path):
     xml = os.path.join(SCENES, "_tmp_c3_480.xml")
     open(xml, "w").write(txt)
     try:
-        pre = str(tmp_path / "c3")
-        run_ref("_tmp_c3_480.xml", pre, "dump", "primary", cwd=SCENES)
         sc = B.Scene(xml)
     finally:
         os.remove(xml)
     m = sc.flat_view().mesh_arrays(0)
     assert m["f"].shape[0] == 100352
-    assert np.array_equal(np.fromfile(pre + ".mesh0.bvh_u32", np.uint32), m["bvh_data"])
+    assert _sha(np.ascontiguousarray(m["bvh_data"], np.uint32)) == str(ref["mesh480_bvh_u32_sha"])
     o, d = O.primary_rays(sc.flat_view())
     r = O.trace_closest(sc.flat_bytes(), o, d, 1)
-    ri = np.fromfile(pre + ".primary_i32", np.int32).reshape(-1, 2)
-    rf = np.fromfile(pre + ".primary_f32", np.float32).reshape(-1, 16)
-    assert np.array_equal(ri[:, 0], r["node"])
+    assert np.array_equal(ref["mesh480_primary_node"], r["node"])
     hit = r["node"] >= 0
-    assert same_bits(r["attrs"][hit][:, :9], rf[hit][:, :9])
+    attrs = np.ascontiguousarray(r["attrs"][hit][:, :9], np.float32)
+    assert not np.isnan(attrs).any() and _sha(attrs) == str(ref["mesh480_hit_attrs_sha"])   # the reference's hit attributes, bit for bit
 
 
-def test_random_scenes_reference_vs_oracle(B, O, tmp_path):
+def test_random_scenes_reference_vs_oracle(B, O, ref, tmp_path):
     """tools/fuzz_ref.py on fixed seeds: random scene graphs rendered by the unmodified reference (sequential stream
     through the interposed rand()) and by the oracle in sequential / libm mode, per-sample radiance and RGB8 bit for bit.
-    (360 further seeds were run by hand when this was added: all identical.)"""
-    import shutil, sys
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
-    import fuzz_parity
+    (360 further seeds were run by hand when this was added: all identical.)  The XML of each seed is the one the reference rendered."""
+    import shutil
     shutil.copy(os.path.join(SCENES, "mesh_small.obj"), tmp_path / "mesh_small.obj")
     for seed in range(301, 313):
-        rng = np.random.default_rng(seed)
         xml = f"fuzz_{seed}.xml"
-        fuzz_parity.random_scene(rng, str(tmp_path / xml))
-        gi = int(rng.integers(0, 4))
-        pre = str(tmp_path / f"r{seed}")
-        run_ref(xml, pre, "--spp", 2, "--gi", gi, "--seed", seed, "--region", 0, 0, 96, 72, "render", cwd=str(tmp_path))
+        (tmp_path / xml).write_text(str(ref[f"fuzz_{seed}_xml"]))
+        gi = int(ref[f"fuzz_{seed}_gi"])
         cwd = os.getcwd()
         os.chdir(tmp_path)
         try:
@@ -157,30 +162,22 @@ def test_random_scenes_reference_vs_oracle(B, O, tmp_path):
         finally:
             os.chdir(cwd)
         o = O.render(sc.flat_bytes(), sc.width, sc.height, 2, gi=gi, seed=seed, rng=O.RNG_SEQUENTIAL, math=O.MATH_LIBM, region=(0, 0, 96, 72), threads=4)
-        assert same_bits(o["samples"], np.fromfile(pre + ".samples_f32", np.float32).reshape(96 * 72, 2, 3)), seed
-        assert np.array_equal(o["rgb8"].reshape(-1, 3), np.fromfile(pre + ".rgb8", np.uint8).reshape(-1, 3)), seed
+        samples = np.ascontiguousarray(o["samples"], np.float32)
+        assert samples.shape == (96 * 72, 2, 3) and _sha(samples) == str(ref[f"fuzz_{seed}_samples_sha"]), seed   # bit for bit
+        assert np.array_equal(o["rgb8"].reshape(-1, 3), ref[f"fuzz_{seed}_rgb8"].reshape(-1, 3)), seed
 
 
-def test_random_scenes_photon_map_reference_vs_oracle(B, O, tmp_path):
+def test_random_scenes_photon_map_reference_vs_oracle(B, O, ref, tmp_path):
     """BuildCausticPhotonMap + PrepareForIrradianceEstimation of the unmodified reference (oracle/_ref/ref_harness_pm) on
     seeded random scenes that have a caustic path: emitted and balanced photon bytes and the emission count equal the
     oracle's (sequential / libm mode).  (34 such scenes were run by hand; scenes without a caustic path never leave the
     reference's emission loop.)"""
-    import shutil, sys
-    from conftest import REF_HARNESS
-    harness_pm = REF_HARNESS + "_pm"
-    if not os.path.exists(harness_pm):
-        pytest.skip("oracle/_ref/ref_harness_pm not built")
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
-    import fuzz_parity
+    import shutil
     shutil.copy(os.path.join(SCENES, "mesh_small.obj"), tmp_path / "mesh_small.obj")
     for seed in (11, 14, 31, 40):
-        rng = np.random.default_rng(seed)
         xml = f"f{seed}.xml"
-        fuzz_parity.random_scene(rng, str(tmp_path / xml))
-        pre = str(tmp_path / f"p{seed}")
-        subprocess.run([harness_pm, xml, pre, "--seed", str(seed), "--photons", "1500", "photons"], cwd=str(tmp_path), check=True, timeout=120,
-                       stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
+        (tmp_path / xml).write_text(str(ref[f"pfuzz_{seed}_xml"]))
+        p = lambda what: ref[f"pfuzz_{seed}_{what}"]
         cwd = os.getcwd()
         os.chdir(tmp_path)
         try:
@@ -188,10 +185,9 @@ def test_random_scenes_photon_map_reference_vs_oracle(B, O, tmp_path):
         finally:
             os.chdir(cwd)
         bal, emitted, n_emit = O.photon_build(sc.flat_bytes(), 1500, seed=seed, rng=O.RNG_SEQUENTIAL, math=O.MATH_LIBM)
-        meta = np.fromfile(pre + ".photons_meta", np.uint64)
+        meta = p("photons_meta")
         assert n_emit == int(meta[1]), seed
-        ref_em = np.fromfile(pre + ".photons_emitted", np.uint8).reshape(-1, 24)
-        ref_bal = np.fromfile(pre + ".photons_balanced", np.uint8).reshape(-1, 24)
+        ref_em, ref_bal = p("photons_emitted"), p("photons_balanced")
         m = np.ones(24, bool)
         m[19] = False   # byte 19 = planeAndDirZ: bit 3 always defined, the split-plane bits only for internal nodes (uninitialised elsewhere)
         assert np.array_equal(emitted[:, m], ref_em[:, m]) and np.array_equal(emitted[:, 19] & 8, ref_em[:, 19] & 8), seed
@@ -199,12 +195,9 @@ def test_random_scenes_photon_map_reference_vs_oracle(B, O, tmp_path):
         internal = np.arange(1, len(ref_bal) + 1) < int(meta[3])
         assert np.array_equal(bal[internal, 19] & 3, ref_bal[internal, 19] & 3), seed
         # the global map (BuildPhotonMap) of the same scene
-        subprocess.run([harness_pm, xml, pre, "--seed", str(seed), "--photons", "1200", "gphotons"], cwd=str(tmp_path), check=True, timeout=120,
-                       stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
         bal, emitted, n_emit = O.photon_build_global(sc.flat_bytes(), 1200, seed=seed, rng=O.RNG_SEQUENTIAL, math=O.MATH_LIBM)
-        meta = np.fromfile(pre + ".gphotons_meta", np.uint64)
+        meta = p("gphotons_meta")
         assert n_emit == int(meta[1]), seed
-        ref_em = np.fromfile(pre + ".gphotons_emitted", np.uint8).reshape(-1, 24)
-        ref_bal = np.fromfile(pre + ".gphotons_balanced", np.uint8).reshape(-1, 24)
+        ref_em, ref_bal = p("gphotons_emitted"), p("gphotons_balanced")
         assert np.array_equal(emitted[:, m], ref_em[:, m]) and np.array_equal(emitted[:, 19] & 8, ref_em[:, 19] & 8), seed
         assert np.array_equal(bal[:, m], ref_bal[:, m]) and np.array_equal(bal[:, 19] & 8, ref_bal[:, 19] & 8), seed

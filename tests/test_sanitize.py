@@ -4,7 +4,7 @@ tests/sanitize/Makefile compiles the product's host front-end — scene_host.cpp
 reader, BVH build, flattening, leaf-skip bounds), mini_xml.h, png_io.cpp, photon_host.cpp, capi_host.cpp — and the oracle (oracle/bhrt_oracle.cpp)
 with AddressSanitizer + UBSan (-fno-sanitize-recover) into tests/sanitize/_build/san_driver; the two device entry points the host objects
 reference are stubs (no GPU code in that build).  The driver loads scenes through the C ABI and runs the oracle on every blob that loads.
-Inputs: every scene under tests/scenes/, the reference's own shipped XMLs where /root/reference exists, and a few hundred mutated XML / OBJ /
+Inputs: every scene under tests/scenes/, the reference's own shipped XMLs (tests/golden/shipped), and a few hundred mutated XML / OBJ /
 MTL / PNG / PPM files (truncated, bytes flipped, counts and indices huge / negative / zero / nan).  A malformed input must end in an error
 code or a warning — never in a sanitizer report, which aborts the driver."""
 import glob
@@ -15,10 +15,11 @@ import subprocess
 import numpy as np
 import pytest
 
-from conftest import REFERENCE, ROOT, SCENES, ensure_mesh
+from conftest import GOLDEN, ROOT, SCENES, ensure_mesh
 
 SAN_DIR = os.path.join(ROOT, "tests", "sanitize")
 DRIVER = os.path.join(SAN_DIR, "_build", "san_driver")
+SHIPPED_ROOT = os.path.join(GOLDEN, "shipped")
 ENV = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0:allocator_may_return_null=1", UBSAN_OPTIONS="print_stacktrace=1", OMP_NUM_THREADS="1")
 
 
@@ -42,11 +43,9 @@ def test_every_scene_of_the_repo_loads_clean_under_asan_and_ubsan(driver):
 
 
 def test_the_reference_s_shipped_scenes_load_clean(driver):
-    data = os.path.join(REFERENCE, "Resource", "Data")
-    if not os.path.isdir(data):
-        pytest.skip("the reference's own scene files are only in the development container")
+    data = os.path.join(SHIPPED_ROOT, "Resource", "Data")
     files = sorted(glob.glob(os.path.join(data, "*.xml")))
-    out = _run(driver, files, REFERENCE)  # the reference resolves asset paths against its working directory
+    out = _run(driver, files, SHIPPED_ROOT)  # the reference resolves asset paths against its working directory
     assert len(files) >= 15 and out.count(": ok ") + out.count(": error ") == len(files) and out.count(": ok ") >= 15
 
 

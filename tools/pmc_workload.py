@@ -19,6 +19,7 @@ def main():
     a = np.ones(CAL_N, np.float32); b = np.full(CAL_N, 3.0, np.float32)
     B.math_eval_dev(8, a, b)  # k_math_eval: out[i] = a[i] / b[i]
     scene_rel, W, H, spp, gi = bench.WORKLOADS[wl]
+    bench.ensure_assets()  # the mesh workloads' gen/mesh_224.obj: without it their scenes load with a null object in its place
     sc = B.Scene(os.path.join(ROOT, scene_rel)); sc.upload(0)
     opts = B.default_opts(spp=spp, gi_bounces=gi, internal_bounces=16, seed=0)
     if wl == "c5":  # BASELINE config 5: the caustic map first (its kernels appear in the counter files as well)
