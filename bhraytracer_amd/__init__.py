@@ -50,6 +50,12 @@ class Stats(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_ if n != "reserved"}
 
 
+class DenoiseOpts(C.Structure):
+    """bhrt_denoise_opts: the a-trous denoiser's levels, guide tolerances and output gamma (csrc/denoise.hip states the filter)."""
+    _fields_ = [("iterations", C.c_int32), ("sigma_normal", C.c_float), ("sigma_depth", C.c_float), ("sigma_luminance", C.c_float),
+                ("gamma", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
 class Hits(C.Structure):
     _fields_ = [("t", C.c_void_p), ("node", C.c_void_p), ("prim", C.c_void_p), ("front", C.c_void_p)]
 
@@ -66,6 +72,7 @@ EXPORTS = [
     "bhrt_tiles_block_bytes", "bhrt_tiles_pack_dev", "bhrt_tiles_unpack_dev",
     "bhrt_first_hit", "bhrt_first_hit_dev", "bhrt_zbuffer_image_dev", "bhrt_color_image_dev",
     "bhrt_scene_load_xml_ex", "bhrt_bvh_build", "bhrt_photon_emit_range", "bhrt_photon_install", "bhrt_scene_clone", "bhrt_host_alloc", "bhrt_host_free", "bhrt_photon_gather_host_ex", "bhrt_scene_knob",
+    "bhrt_default_denoise_opts", "bhrt_render_var", "bhrt_render_var_dev", "bhrt_denoise", "bhrt_denoise_dev",
 ]
 
 
@@ -89,6 +96,7 @@ def lib():
         L.bhrt_last_error.restype = C.c_char_p
         L.bhrt_scene_free.restype = None
         L.bhrt_default_opts.restype = None
+        L.bhrt_default_denoise_opts.restype = None
         _lib = L
     return _lib
 
@@ -101,6 +109,15 @@ def _check(rc):
 def default_opts(**kw) -> Opts:
     o = Opts()
     lib().bhrt_default_opts(C.byref(o))
+    for k, v in kw.items():
+        setattr(o, k, v)
+    return o
+
+
+def default_denoise_opts(**kw) -> DenoiseOpts:
+    """bhrt_default_denoise_opts (K = 4, sigma_normal = 32, sigma_depth = 0.01, sigma_luminance = 4, gamma = 1), fields overridden by kw."""
+    o = DenoiseOpts()
+    lib().bhrt_default_denoise_opts(C.byref(o))
     for k, v in kw.items():
         setattr(o, k, v)
     return o
@@ -207,6 +224,51 @@ class Scene:
         _check(lib().bhrt_render_dev(self._h, C.byref(opts), C.c_void_p(d_rgb8_ptr or None),
                                      C.c_void_p(d_radiance_ptr or None), C.byref(st), None))
         return st
+
+    def render_var(self, opts: Opts):
+        """render() plus the denoiser's noise estimate: returns (rgb8, radiance, variance), variance (H, W, 3) float32 = the per-channel
+        variance of every pixel's mean (bhrt_render_var)."""
+        W, H = self.width, self.height
+        rgb = np.zeros((H, W, 3), np.uint8)
+        rad = np.zeros((H, W, 3), np.float32)
+        var = np.zeros((H, W, 3), np.float32)
+        _check(lib().bhrt_render_var(self._h, C.byref(opts), _ptr(rgb), _ptr(rad), _ptr(var), None))
+        return rgb, rad, var
+
+    def render_var_dev(self, opts: Opts, d_rgb8_ptr: int, d_radiance_ptr: int, d_variance_ptr: int):
+        """Same with outputs left in HBM (raw device pointers; any may be 0 = not wanted)."""
+        st = Stats()
+        _check(lib().bhrt_render_var_dev(self._h, C.byref(opts), C.c_void_p(d_rgb8_ptr or None), C.c_void_p(d_radiance_ptr or None),
+                                         C.c_void_p(d_variance_ptr or None), C.byref(st), None))
+        return st
+
+    def denoise(self, opts: DenoiseOpts, radiance, variance=None, z=None, normal=None, albedo=None):
+        """DenoiseImage (bhrt_denoise) on host arrays of the scene's W x H frame: radiance (H, W, 3) linear, variance like it or None;
+        guides z (H, W), normal / albedo (H, W, 3), each None = the first hit computed on the device.  Returns (out (H, W, 3) float32 linear,
+        rgb8 (H, W, 3) uint8)."""
+        W, H = self.width, self.height
+
+        def arr(a, shape):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, np.float32)
+            if a.size != int(np.prod(shape)):
+                raise ValueError(f"expected {shape} floats, got {a.shape}")
+            return a
+        c = arr(radiance, (H, W, 3))
+        v, zz, n, a = arr(variance, (H, W, 3)), arr(z, (H, W)), arr(normal, (H, W, 3)), arr(albedo, (H, W, 3))
+        out = np.zeros((H, W, 3), np.float32)
+        rgb = np.zeros((H, W, 3), np.uint8)
+        p = lambda x: _ptr(x) if x is not None else None  # noqa: E731
+        _check(lib().bhrt_denoise(self._h, C.byref(opts), _ptr(c), p(v), p(zz), p(n), p(a), _ptr(out), _ptr(rgb)))
+        return out, rgb
+
+    def denoise_dev(self, opts: DenoiseOpts, d_radiance: int, d_variance: int = 0, d_z: int = 0, d_normal: int = 0, d_albedo: int = 0,
+                    d_out: int = 0, d_rgb8: int = 0, stream: int = 0):
+        """bhrt_denoise_dev on raw device pointers (0 = NULL); with a stream the call does not synchronise."""
+        v = lambda x: C.c_void_p(x or None)  # noqa: E731
+        _check(lib().bhrt_denoise_dev(self._h, C.byref(opts), v(d_radiance), v(d_variance), v(d_z), v(d_normal), v(d_albedo), v(d_out), v(d_rgb8),
+                                      v(stream)))
 
     # ---- images beside the colour image (RenderImage z-buffer, DenoiseImage inputs) ------------
     def first_hit(self):

@@ -6,6 +6,7 @@
 //   bhrt render <scene.xml> [-o out.png] [--spp N] [--gi N] [--bounces N] [--seed S] [--no-jitter] [--no-gamma]
 //               [--device D | --gpus N [--rehearse]] [--rank R --world N] [--tile T] [--radiance out.f32] [--leaf-skip] [--photon-exact]
 //               [--photons N] [--photon-file map.dat] [--photon-out map.dat]     (USE_PhotonMap, Main.cpp:51,53,194,383)
+//               [--denoise [--denoise-iters K]]                                  (DenoiseImage of the x64 build, Main.cpp:57-96,236-238)
 //   bhrt info   <scene.xml>
 //
 // --gpus N: ONE process drives N GPUs of the node (the reference's one process drives 16 OpenMP threads, Main.cpp:422): the
@@ -17,6 +18,9 @@
 // --gpus N --rehearse: the same N threads, rendezvous points, per-rank renders, packs and unpacks with every rank on device 0 and the
 // ncclAllGather replaced by N device-to-device copies — what a one-GPU box can run of the N > 1 control flow (tests/test_cli.py).
 // Without --gpus: one device, no RCCL involved (--rank / --world then render that rank's tiles only, for process-per-GPU launchers).
+// --denoise: the PNG is the denoised frame (bhrt_denoise, as the reference's 64-bit build saves it); --radiance stays the render's own
+// radiance.  With --gpus N the ranks' variance tiles travel in a second block beside the first and GPU 0 denoises the gathered frame; a
+// partial frame (--world > 1) cannot be denoised.
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
@@ -50,6 +54,8 @@ struct Args {
     bhrt_opts o;
     int device = 0, gpus = 0;
     bool rehearse = false; // --rehearse: the N ranks of --gpus N all on device 0, the all-gather as N device-to-device copies (no RCCL)
+    bool denoise = false;
+    bhrt_denoise_opts dn;
 };
 
 // Everything render_multi owns besides the caller's scene: released on every way out (the early returns included).
@@ -141,14 +147,14 @@ static int render_multi(bhrt_scene *first, const Args &A, const bhrt_info &info,
     // collective a thread never blocks in a stream synchronise: it polls its stream and the failure flag, and when a peer has failed it
     // aborts its communicator (ncclCommAbort) and leaves.
     std::vector<double> gather_s(N, 0.0);
-    std::vector<uint8_t *> mine_of(N, nullptr); // --rehearse: where every rank's packed block lies (all on device 0)
+    std::vector<uint8_t *> mine_of(N, nullptr), mine_v_of(N, nullptr); // --rehearse: where every rank's packed blocks lie (all on device 0)
     std::atomic<int> ready(0), rendered(0), packed(0), exchanged(0);
     auto rendezvous = [&](std::atomic<int> &c) { c.fetch_add(1); while (c.load() < N) std::this_thread::yield(); return !failed.load(); };
     std::vector<std::thread> th;
     for (int r = 0; r < N; r++)
         th.emplace_back([&, r]() {
-            uint8_t *d_rgb = nullptr, *d_mine = nullptr, *d_all = nullptr;
-            float *d_rad = nullptr;
+            uint8_t *d_rgb = nullptr, *d_mine = nullptr, *d_all = nullptr, *d_mine_v = nullptr, *d_all_v = nullptr;
+            float *d_rad = nullptr, *d_var = nullptr;
             hipStream_t s = nullptr;
             auto setup = [&]() {
                 HOST_CHECK(bhrt_scene_upload(scenes[r], devs[r]), "upload");
@@ -160,24 +166,33 @@ static int render_multi(bhrt_scene *first, const Args &A, const bhrt_info &info,
                 HOST_CHECK(hipMalloc(&d_all, bb * N), "hipMalloc");
                 HOST_CHECK(hipMemsetAsync(d_rgb, 0, npx * 3, s), "memset");
                 HOST_CHECK(hipMemsetAsync(d_rad, 0, npx * 3 * sizeof(float), s), "memset");
+                if (A.denoise) { // the variance tiles: a second block of the same shape (its RGB8 section repeats the first block's)
+                    HOST_CHECK(hipMalloc(&d_var, npx * 3 * sizeof(float)), "hipMalloc");
+                    HOST_CHECK(hipMalloc(&d_mine_v, bb), "hipMalloc");
+                    HOST_CHECK(hipMalloc(&d_all_v, bb * N), "hipMalloc");
+                    HOST_CHECK(hipMemsetAsync(d_var, 0, npx * 3 * sizeof(float), s), "memset");
+                }
                 HOST_CHECK(hipStreamSynchronize(s), "sync");
             };
             setup();
             auto release = [&]() {
                 (void)hipFree(d_rgb); (void)hipFree(d_rad); (void)hipFree(d_mine); (void)hipFree(d_all);
+                (void)hipFree(d_var); (void)hipFree(d_mine_v); (void)hipFree(d_all_v);
                 if (s) (void)hipStreamDestroy(s);
             };
             if (!rendezvous(ready)) { release(); return; }
             bhrt_opts o = A.o;
             o.rank = r; o.world_size = N; o.tile_size = tile;
             if (A.photons || !A.photon_file.empty()) o.photon_map = 1;
-            if (bhrt_render_dev(scenes[r], &o, d_rgb, d_rad, &stats[r], nullptr)) { fprintf(stderr, "bhrt: GPU %d: BeginRender: %s\n", r, bhrt_last_error()); failed.store(true); }
+            if (bhrt_render_var_dev(scenes[r], &o, d_rgb, d_rad, d_var, &stats[r], nullptr)) { fprintf(stderr, "bhrt: GPU %d: BeginRender: %s\n", r, bhrt_last_error()); failed.store(true); }
             if (!rendezvous(rendered)) { release(); return; }
             const auto t0 = std::chrono::steady_clock::now();
             auto pack = [&]() {
                 HOST_CHECK(bhrt_tiles_pack_dev(d_rgb, d_rad, W, H, tile, r, N, d_mine, s), "pack");
+                if (A.denoise) HOST_CHECK(bhrt_tiles_pack_dev(d_rgb, d_var, W, H, tile, r, N, d_mine_v, s), "pack");
                 HOST_CHECK(hipStreamSynchronize(s), "sync");
                 mine_of[r] = d_mine;
+                mine_v_of[r] = d_mine_v;
             };
             pack();
             if (getenv("BHRT_TEST_FAIL_PACK") && atoi(getenv("BHRT_TEST_FAIL_PACK")) == r) { fprintf(stderr, "bhrt: GPU %d: pack failed (test knob)\n", r); failed.store(true); }
@@ -198,14 +213,22 @@ static int render_multi(bhrt_scene *first, const Args &A, const bhrt_info &info,
             auto exchange = [&]() {
                 if (A.rehearse) { // the all-gather of N ranks on ONE device: every rank copies every block into its own receive buffer
                     for (int k = 0; k < N; k++) HOST_CHECK(hipMemcpyAsync(d_all + (size_t)k * bb, mine_of[k], bb, hipMemcpyDeviceToDevice, s), "copy of a peer's block");
-                } else if (ncclAllGather(d_mine, d_all, bb, ncclUint8, G.comms[r], s) != ncclSuccess) {
+                    if (A.denoise)
+                        for (int k = 0; k < N; k++) HOST_CHECK(hipMemcpyAsync(d_all_v + (size_t)k * bb, mine_v_of[k], bb, hipMemcpyDeviceToDevice, s), "copy of a peer's block");
+                } else if (ncclAllGather(d_mine, d_all, bb, ncclUint8, G.comms[r], s) != ncclSuccess ||
+                           (A.denoise && ncclAllGather(d_mine_v, d_all_v, bb, ncclUint8, G.comms[r], s) != ncclSuccess)) {
                     fprintf(stderr, "bhrt: GPU %d: ncclAllGather failed\n", r);
                     failed.store(true);
                 }
                 if (!wait_stream()) return;
                 HOST_CHECK(bhrt_tiles_unpack_dev(d_all, W, H, tile, N, d_rgb, d_rad, s), "unpack");
+                if (A.denoise) HOST_CHECK(bhrt_tiles_unpack_dev(d_all_v, W, H, tile, N, d_rgb, d_var, s), "unpack"); // the same RGB8 bytes again
                 HOST_CHECK(hipStreamSynchronize(s), "sync");
                 gather_s[r] = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+                if (r == 0 && A.denoise) { // DenoiseImage on the gathered frame (Main.cpp:236-238): the PNG bytes become the filter's
+                    HOST_CHECK(bhrt_denoise_dev(scenes[0], &A.dn, d_rad, d_var, nullptr, nullptr, nullptr, nullptr, d_rgb, s), "denoise");
+                    HOST_CHECK(hipStreamSynchronize(s), "sync");
+                }
                 if (r == 0) {
                     HOST_CHECK(hipMemcpy(rgb.data(), d_rgb, npx * 3, hipMemcpyDeviceToHost), "copy");
                     if (!rad.empty()) HOST_CHECK(hipMemcpy(rad.data(), d_rad, npx * 3 * sizeof(float), hipMemcpyDeviceToHost), "copy");
@@ -232,6 +255,7 @@ int main(int argc, char **argv)
     A.scene = argv[2];
     bhrt_opts &o = A.o;
     bhrt_default_opts(&o);
+    bhrt_default_denoise_opts(&A.dn);
     for (int a = 3; a < argc; a++) {
         std::string s = argv[a];
         auto next = [&]() -> const char * { if (a + 1 >= argc) { fprintf(stderr, "bhrt: %s needs a value\n", s.c_str()); exit(2); } return argv[++a]; };
@@ -254,9 +278,17 @@ int main(int argc, char **argv)
         else if (s == "--photons") A.photons = (uint32_t)strtoul(next(), nullptr, 10);
         else if (s == "--photon-file") A.photon_file = next();
         else if (s == "--photon-out") A.photon_out = next();
+        else if (s == "--denoise") A.denoise = true;
+        else if (s == "--denoise-iters") A.dn.iterations = atoi(next());
         else { fprintf(stderr, "bhrt: unknown option %s\n", s.c_str()); return 2; }
     }
     if (A.gpus < 0 || A.gpus > 64 || (A.gpus > 0 && (o.rank != 0 || o.world_size != 1))) { fprintf(stderr, "bhrt: --gpus N drives all N ranks itself (no --rank / --world)\n"); return 2; }
+    if (A.denoise && o.world_size > 1) { // before any device is touched
+        fprintf(stderr, "bhrt: usage: --denoise filters the whole frame; a rank of --world %d renders part of it (use --gpus N)\n", o.world_size);
+        return 2;
+    }
+    if (A.denoise && (A.dn.iterations < 0 || A.dn.iterations > 16)) { fprintf(stderr, "bhrt: usage: --denoise-iters must be in 0..16\n"); return 2; }
+    A.dn.gamma = o.gamma;
     bhrt_scene *scene = nullptr;
     if (bhrt_scene_load_xml(A.scene.c_str(), &scene)) return fail("LoadScene");
     bhrt_info info;
@@ -270,7 +302,7 @@ int main(int argc, char **argv)
            info.n_meshes, info.n_triangles, info.n_bvh_nodes, info.n_materials, info.n_lights, info.n_textures, (unsigned long long)info.flat_bytes);
     if (!render) { bhrt_scene_free(scene); return 0; }
     std::vector<uint8_t> rgb((size_t)info.width * info.height * 3, 0);
-    std::vector<float> rad(A.radiance_out.empty() ? 0 : (size_t)info.width * info.height * 3, 0.f);
+    std::vector<float> rad(A.radiance_out.empty() && !A.denoise ? 0 : (size_t)info.width * info.height * 3, 0.f);
     bhrt_stats st;
     memset(&st, 0, sizeof st);
     if (A.gpus > 0) {
@@ -301,7 +333,11 @@ int main(int argc, char **argv)
             o.photon_map = 1;
         }
         if (o.photon_map && !A.photon_out.empty() && bhrt_photon_export(scene, A.photon_out.c_str())) return fail("photon export");
-        if (bhrt_render(scene, &o, rgb.data(), rad.empty() ? nullptr : rad.data(), &st)) return fail("BeginRender");
+        if (A.denoise) {
+            std::vector<float> var(rad.size(), 0.f);
+            if (bhrt_render_var(scene, &o, rgb.data(), rad.data(), var.data(), &st)) return fail("BeginRender");
+            if (bhrt_denoise(scene, &A.dn, rad.data(), var.data(), nullptr, nullptr, nullptr, nullptr, rgb.data())) return fail("DenoiseImage");
+        } else if (bhrt_render(scene, &o, rgb.data(), rad.empty() ? nullptr : rad.data(), &st)) return fail("BeginRender");
     }
     const double rays = (double)st.closest_rays + (double)st.shadow_rays;
     printf("rendered %llu camera samples, %.0f rays (%llu closest + %llu shadow), %u wave steps in %u pass(es): %.3f s, %.1f Mrays/s\n",

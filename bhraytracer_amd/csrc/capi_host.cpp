@@ -41,6 +41,17 @@ void bhrt_default_opts(bhrt_opts *o)
     o->samples_per_pass = 0;
 }
 
+void bhrt_default_denoise_opts(bhrt_denoise_opts *o)
+{
+    if (!o) return;
+    memset(o, 0, sizeof *o);
+    o->iterations = 4;
+    o->sigma_normal = 32.f;
+    o->sigma_depth = 0.01f;
+    o->sigma_luminance = 4.f; // K, sigma_*: the lowest MSE of a grid over 4-spp frames of c3_mesh_small, c3_room_small, c2_glass_small
+    o->gamma = 1; // as bhrt_opts.gamma (Main.cpp:128)
+}
+
 int bhrt_scene_load_xml(const char *path, bhrt_scene **out) { return bhrt_scene_load_xml_ex(path, -1, out); }
 
 int bhrt_scene_load_xml_ex(const char *path, int bvh_device, bhrt_scene **out)

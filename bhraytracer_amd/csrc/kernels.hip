@@ -14,6 +14,7 @@
 //   k_combine       MtlBlinn.cpp:117-137,343,431,470,511,539  folds finished frames into their parents, deepest
 //                                              wave step first (the per-level clamps forbid a running throughput)
 //   k_resolve       Main.cpp:170,220-230       in-order sample sum, /spp, gamma, Color24
+//   k_variance      (DenoiseImage's input)     per-channel variance of the pixel mean, only when a variance image is asked for
 //   k_photon_*      Main.cpp:319-386, cyPhotonMap.h   caustic photon map: emission, and the k-NN gather in three passes
 //   k_tiles_*       (no counterpart)           multi-GPU framebuffer exchange: pack / unpack of a rank's tiles
 // The recursion of the reference becomes: ray kinds (continuations) + a tree of shading frames.
@@ -30,6 +31,8 @@
 #include <vector>
 
 #include "bhrt.h"
+#include "denoise.h"
+#include "device_color24.h"
 #include "device_photon.h"
 #include "photon_host.h"
 #include "scene_internal.h"
@@ -1183,16 +1186,29 @@ __global__ void __launch_bounds__(kBlock) k_resolve(PassInfo P, const float *sam
     V3 out = sum / (float)P.spp;
     const size_t pix = (size_t)j * P.W + i;
     if (radiance) st3(radiance, (uint32_t)pix, out);
-    if (rgb8) {
-        if (P.gamma) {
-            const float inv = 1 / 2.2f;
-            out = v3(dm::powf_(out.x, inv), dm::powf_(out.y, inv), dm::powf_(out.z, inv));
+    if (rgb8) store_color24(rgb8, pix, out, P.gamma);
+}
+
+// The denoiser's noise estimate: per-channel variance of the pixel mean, same layout as the radiance image.  m is k_resolve's mean
+// (same operations, same order); var = sum_s (x_s - m)^2 / (spp - 1) / spp, summed in sample order; 0 with one sample.
+__global__ void __launch_bounds__(kBlock) k_variance(PassInfo P, const float *samples, float *variance)
+{
+    const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= P.n_pixels) return;
+    int i, j;
+    if (!pixel_of(P, P.q0 + q, i, j)) return;
+    V3 sum = v3(0, 0, 0);
+    for (int s = 0; s < P.spp; s++) sum = sum + ld3i(samples, (uint32_t)s * P.n_pixels + q);
+    const V3 m = sum / (float)P.spp;
+    V3 acc = v3(0, 0, 0);
+    if (P.spp > 1) {
+        for (int s = 0; s < P.spp; s++) {
+            const V3 d = ld3i(samples, (uint32_t)s * P.n_pixels + q) - m;
+            acc = acc + d * d;
         }
-        int r = int(out.x * 255 + 0.5f), g = int(out.y * 255 + 0.5f), b = int(out.z * 255 + 0.5f);
-        rgb8[pix * 3] = (uint8_t)(r < 0 ? 0 : (r > 255 ? 255 : r));
-        rgb8[pix * 3 + 1] = (uint8_t)(g < 0 ? 0 : (g > 255 ? 255 : g));
-        rgb8[pix * 3 + 2] = (uint8_t)(b < 0 ? 0 : (b > 255 ? 255 : b));
+        acc = (acc / (float)(P.spp - 1)) / (float)P.spp;
     }
+    st3(variance, (uint32_t)((size_t)j * P.W + i), acc);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1775,6 +1791,12 @@ struct DeviceState {
     uint8_t *d_frame_rgb = nullptr;
     float *d_frame_rad = nullptr;
     size_t frame_px = 0;
+    // bhrt_render_var: the device copy of the variance image, allocated on first use
+    float *d_frame_var = nullptr;
+    size_t frame_var_px = 0;
+    // bhrt_denoise_dev: the filter's planes (DenoisePlaneBytes), then the first-hit guides it computes itself; grown on demand
+    uint8_t *d_dn = nullptr;
+    size_t dn_bytes = 0;
     // scratch for the public trace API
     float *d_api_f = nullptr;
     int32_t *d_api_i = nullptr;
@@ -1789,7 +1811,7 @@ void DestroyDeviceState(DeviceState *d)
     fr(d->d_blob); fr(d->d_chain);
     for (int k = 0; k < 2; k++) { fr(d->d_rayf[k]); fr(d->d_rayu[k]); }
     fr(d->d_hitf); fr(d->d_hiti); fr(d->d_shf); fr(d->d_shu); fr(d->d_fu); fr(d->d_fcode); fr(d->d_ff); fr(d->d_samples); fr(d->d_order); fr(d->d_park); fr(d->d_seg); fr(d->d_cnt); fr(d->d_aux);
-    fr(d->d_frame_rgb); fr(d->d_frame_rad); fr(d->d_sel); fr(d->d_slowf); fr(d->d_slowu);
+    fr(d->d_frame_rgb); fr(d->d_frame_rad); fr(d->d_frame_var); fr(d->d_dn); fr(d->d_sel); fr(d->d_slowf); fr(d->d_slowu);
     fr(d->d_shf2); fr(d->d_shu2); fr(d->d_order_sh); fr(d->d_seg_sh); fr(d->d_cnt_sh);
     if (d->ev_shade) (void)hipEventDestroy(d->ev_shade);
     for (int k = 0; k < 2; k++) if (d->ev_shadow[k]) (void)hipEventDestroy(d->ev_shadow[k]);
@@ -2121,9 +2143,9 @@ static int RunGather(DeviceState *D, const Sink &sink, uint32_t q0, uint32_t cnt
 
 
 // Renders owned pixels [q_begin, q_end) of this rank; samples_out (device) receives the per-sample buffer
-// of the region when requested (parity tests).
+// of the region when requested (parity tests); d_variance (W*H*3, like d_radiance) the variance of every owned pixel's mean.
 static int RenderRange(bhrt_scene *scene, const bhrt_opts &o, uint8_t *d_rgb8, float *d_radiance, bhrt_stats *st, float *d_region_samples, int x0,
-                       int y0, int x1, int y1)
+                       int y0, int x1, int y1, float *d_variance = nullptr)
 {
     DeviceState *D = scene->dev;
     const bhrt_flat_header *H = scene->flat.hdr();
@@ -2474,6 +2496,7 @@ static int RenderRange(bhrt_scene *scene, const bhrt_opts &o, uint8_t *d_rgb8, f
                 if (f1 > f0) hipLaunchKernelGGL(k_combine, dim3((f1 - f0 + kBlock - 1) / kBlock), dim3(kBlock), 0, D->stream, D->S, P, F, f0, f1, D->d_samples, o.photon_map);
             }
             hipLaunchKernelGGL(k_resolve, dim3((npx + kBlock - 1) / kBlock), dim3(kBlock), 0, D->stream, P, D->d_samples, d_radiance, d_rgb8);
+            if (d_variance) hipLaunchKernelGGL(k_variance, dim3((npx + kBlock - 1) / kBlock), dim3(kBlock), 0, D->stream, P, D->d_samples, d_variance);
             if (d_region_samples)
                 hipLaunchKernelGGL(k_copy_samples, dim3((npx + kBlock - 1) / kBlock), dim3(kBlock), 0, D->stream, P, D->d_samples, x0, y0, x1, y1, d_region_samples);
             t.Stop();
@@ -2719,7 +2742,7 @@ try {
     return BHRT_OK;
 } catch (...) { return bhrt::AbiException(); }
 
-int bhrt_render_dev(bhrt_scene *scene, const bhrt_opts *opts, uint8_t *d_rgb8, float *d_radiance, bhrt_stats *stats, void *stream)
+int bhrt_render_var_dev(bhrt_scene *scene, const bhrt_opts *opts, uint8_t *d_rgb8, float *d_radiance, float *d_variance, bhrt_stats *stats, void *stream)
 try {
     (void)stream; // the render pipeline synchronises its own stream per wave step
     int rc = EnsureUploaded(scene);
@@ -2728,12 +2751,22 @@ try {
     if (opts->photon_map && !scene->dev->d_photons) { SetError("photon_map = 1 needs bhrt_photon_build first"); return BHRT_ERR_ARG; }
     bhrt_stats local;
     memset(&local, 0, sizeof local);
-    rc = RenderRange(scene, *opts, d_rgb8, d_radiance, &local, nullptr, 0, 0, 0, 0);
+    rc = RenderRange(scene, *opts, d_rgb8, d_radiance, &local, nullptr, 0, 0, 0, 0, d_variance);
     if (stats) *stats = local;
     return rc;
 } catch (...) { return bhrt::AbiException(); }
 
+int bhrt_render_dev(bhrt_scene *scene, const bhrt_opts *opts, uint8_t *d_rgb8, float *d_radiance, bhrt_stats *stats, void *stream)
+{
+    return bhrt_render_var_dev(scene, opts, d_rgb8, d_radiance, nullptr, stats, stream);
+}
+
 int bhrt_render(bhrt_scene *scene, const bhrt_opts *opts, uint8_t *rgb8, float *radiance, bhrt_stats *stats)
+{
+    return bhrt_render_var(scene, opts, rgb8, radiance, nullptr, stats);
+}
+
+int bhrt_render_var(bhrt_scene *scene, const bhrt_opts *opts, uint8_t *rgb8, float *radiance, float *variance, bhrt_stats *stats)
 try {
     int rc = EnsureUploaded(scene);
     if (rc) return rc;
@@ -2751,14 +2784,22 @@ try {
         HIP_CHECK(hipMalloc(&D->d_frame_rad, npix * 3 * sizeof(float)));
         D->frame_px = npix;
     }
+    if (variance && D->frame_var_px < npix) {
+        if (D->d_frame_var) (void)hipFree(D->d_frame_var);
+        D->d_frame_var = nullptr; D->frame_var_px = 0;
+        HIP_CHECK(hipMalloc(&D->d_frame_var, npix * 3 * sizeof(float)));
+        D->frame_var_px = npix;
+    }
     if (opts->world_size > 1) { // pixels of tiles owned by other ranks keep the caller's values: they have to be in the device copy first
         if (rgb8) HIP_CHECK(hipMemcpyAsync(D->d_frame_rgb, rgb8, npix * 3, hipMemcpyHostToDevice, D->stream));
         if (radiance) HIP_CHECK(hipMemcpyAsync(D->d_frame_rad, radiance, npix * 12, hipMemcpyHostToDevice, D->stream));
+        if (variance) HIP_CHECK(hipMemcpyAsync(D->d_frame_var, variance, npix * 12, hipMemcpyHostToDevice, D->stream));
     }
-    rc = bhrt_render_dev(scene, opts, rgb8 ? D->d_frame_rgb : nullptr, radiance ? D->d_frame_rad : nullptr, stats, nullptr);
+    rc = bhrt_render_var_dev(scene, opts, rgb8 ? D->d_frame_rgb : nullptr, radiance ? D->d_frame_rad : nullptr, variance ? D->d_frame_var : nullptr, stats, nullptr);
     if (rc) return rc;
     if (rgb8) HIP_CHECK(hipMemcpyAsync(rgb8, D->d_frame_rgb, npix * 3, hipMemcpyDeviceToHost, D->stream));
     if (radiance) HIP_CHECK(hipMemcpyAsync(radiance, D->d_frame_rad, npix * 12, hipMemcpyDeviceToHost, D->stream));
+    if (variance) HIP_CHECK(hipMemcpyAsync(variance, D->d_frame_var, npix * 12, hipMemcpyDeviceToHost, D->stream));
     HIP_CHECK(hipStreamSynchronize(D->stream));
     return BHRT_OK;
 } catch (...) { return bhrt::AbiException(); }
@@ -2862,6 +2903,85 @@ try {
     if (n_pixels) hipLaunchKernelGGL(k_color_image, dim3(((uint32_t)(n_pixels * 3) + kBlock - 1) / kBlock), dim3(kBlock), 0, st, d_radiance, (uint32_t)(n_pixels * 3), gamma, d_color);
     HIP_CHECK(hipGetLastError());
     if (!stream) HIP_CHECK(hipStreamSynchronize(st));
+    return BHRT_OK;
+} catch (...) { return bhrt::AbiException(); }
+
+// ---- denoiser (denoise.hip) ------------------------------------------------------------------------------
+int bhrt_denoise_dev(bhrt_scene *scene, const bhrt_denoise_opts *opts, const float *d_radiance, const float *d_variance, const float *d_z, const float *d_normal,
+                     const float *d_albedo, float *d_out, uint8_t *d_rgb8, void *stream)
+try {
+    int rc = EnsureUploaded(scene);
+    if (rc) return rc;
+    if (!opts || !d_radiance) { SetError("denoise: null opts or radiance"); return BHRT_ERR_ARG; }
+    const char *bad = DenoiseOptsError(*opts);
+    if (*bad) { SetError(bad); return BHRT_ERR_ARG; }
+    if (!d_out && !d_rgb8) return BHRT_OK;
+    DeviceState *D = scene->dev;
+    const bhrt_flat_header *H = scene->flat.hdr();
+    const int W = H->camera.width, Hh = H->camera.height;
+    const size_t n = (size_t)W * Hh;
+    if (n == 0 || n > 0x7fffffffull) { SetError("denoise: frame size out of range"); return BHRT_ERR_ARG; }
+    hipStream_t st = stream ? (hipStream_t)stream : D->stream;
+    DenoiseJob J;
+    J.W = W; J.H = Hh; J.o = *opts;
+    J.radiance = d_radiance; J.variance = d_variance; J.z = d_z; J.normal = d_normal; J.albedo = d_albedo; J.out = d_out; J.rgb8 = d_rgb8;
+    J.planes = nullptr;
+    const bool guides = opts->iterations > 0 && (!d_z || !d_normal || !d_albedo); // K = 0 reads no guide
+    if (opts->iterations > 0) {
+        const size_t need = DenoisePlaneBytes(W, Hh) + (guides ? n * 7 * sizeof(float) : 0);
+        if (D->dn_bytes < need) {
+            if (D->d_dn) HIP_CHECK(hipFree(D->d_dn)); // waits for the device: a previous call's kernels may still read it
+            D->d_dn = nullptr; D->dn_bytes = 0;
+            HIP_CHECK(hipMalloc(&D->d_dn, need));
+            D->dn_bytes = need;
+        }
+        J.planes = (float4 *)D->d_dn;
+        if (guides) { // the first hit of bhrt_first_hit_dev, into the scratch behind the planes, for the guides not given
+            float *g = (float *)(D->d_dn + DenoisePlaneBytes(W, Hh));
+            float *gz = d_z ? nullptr : g, *gn = d_normal ? nullptr : g + n, *ga = d_albedo ? nullptr : g + 4 * n;
+            hipLaunchKernelGGL(k_first_hit, dim3(((uint32_t)n + kBlock - 1) / kBlock), dim3(kBlock), 0, st, D->S, W, Hh, gz, gn, ga);
+            if (gz) J.z = gz;
+            if (gn) J.normal = gn;
+            if (ga) J.albedo = ga;
+        }
+    }
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(DenoiseLaunch(J, st));
+    if (!stream) HIP_CHECK(hipStreamSynchronize(st));
+    return BHRT_OK;
+} catch (...) { return bhrt::AbiException(); }
+
+int bhrt_denoise(bhrt_scene *scene, const bhrt_denoise_opts *opts, const float *radiance, const float *variance, const float *z, const float *normal,
+                 const float *albedo, float *out, uint8_t *rgb8)
+try {
+    int rc = EnsureUploaded(scene);
+    if (rc) return rc;
+    if (!opts || !radiance) { SetError("denoise: null opts or radiance"); return BHRT_ERR_ARG; }
+    const char *bad = DenoiseOptsError(*opts);
+    if (*bad) { SetError(bad); return BHRT_ERR_ARG; }
+    if (!out && !rgb8) return BHRT_OK;
+    DeviceState *D = scene->dev;
+    const bhrt_flat_header *H = scene->flat.hdr();
+    const size_t n = (size_t)H->camera.width * H->camera.height;
+    // device copies, back to back: radiance, variance, normal, albedo, out (3n floats each), z (n), rgb8 (3n bytes)
+    uint8_t *d = nullptr;
+    HIP_CHECK(hipMalloc(&d, n * 67));
+    float *f = (float *)d;
+    float *d_c = f, *d_v = f + 3 * n, *d_n = f + 6 * n, *d_a = f + 9 * n, *d_o = f + 12 * n, *d_z = f + 15 * n;
+    uint8_t *d_rgb = d + n * 64;
+    hipError_t e = hipMemcpyAsync(d_c, radiance, n * 12, hipMemcpyHostToDevice, D->stream);
+    if (e == hipSuccess && variance) e = hipMemcpyAsync(d_v, variance, n * 12, hipMemcpyHostToDevice, D->stream);
+    if (e == hipSuccess && normal) e = hipMemcpyAsync(d_n, normal, n * 12, hipMemcpyHostToDevice, D->stream);
+    if (e == hipSuccess && albedo) e = hipMemcpyAsync(d_a, albedo, n * 12, hipMemcpyHostToDevice, D->stream);
+    if (e == hipSuccess && z) e = hipMemcpyAsync(d_z, z, n * 4, hipMemcpyHostToDevice, D->stream);
+    if (e == hipSuccess)
+        rc = bhrt_denoise_dev(scene, opts, d_c, variance ? d_v : nullptr, z ? d_z : nullptr, normal ? d_n : nullptr, albedo ? d_a : nullptr, out ? d_o : nullptr,
+                              rgb8 ? d_rgb : nullptr, nullptr);
+    if (e == hipSuccess && !rc && out) e = hipMemcpy(out, d_o, n * 12, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && !rc && rgb8) e = hipMemcpy(rgb8, d_rgb, n * 3, hipMemcpyDeviceToHost);
+    (void)hipFree(d);
+    if (rc) return rc;
+    HIP_CHECK(e);
     return BHRT_OK;
 } catch (...) { return bhrt::AbiException(); }
 

@@ -230,6 +230,34 @@ int bhrt_zbuffer_image_dev(bhrt_scene *scene, const float *d_z, size_t n, uint8_
  * (Main.cpp:60-69).  d_radiance = the radiance image of bhrt_render_dev. */
 int bhrt_color_image_dev(bhrt_scene *scene, const float *d_radiance, size_t n_pixels, int gamma, float *d_color, void *stream);
 
+/* ---- denoiser: the DenoiseImage step of the reference's 64-bit build (Main.cpp:57-96, applied at Main.cpp:236-238) --------------
+ * An edge-avoiding a-trous wavelet filter guided by the first hit (z, normal, albedo) and, when given, the per-pixel variance of the
+ * render; the filter is stated exactly in csrc/denoise.hip.  Not OIDN (a neural network): the same step, not its bits. */
+typedef struct bhrt_denoise_opts {
+    int32_t iterations;    /* K: a-trous levels, step 2^k for k < K (0 = the identity: out = radiance, rgb8 = the render's bytes); default 4 */
+    float sigma_normal;    /* exponent of the normal weight, default 32 */
+    float sigma_depth;     /* relative depth tolerance per pixel of distance, default 0.01 */
+    float sigma_luminance; /* luminance tolerance in standard deviations of the noise (used with a variance image), default 4 */
+    int32_t gamma;         /* rgb8: 1 = pow(c, 1/2.2f) before Color24, as bhrt_opts.gamma; default 1 */
+    int32_t reserved[3];
+} bhrt_denoise_opts;
+void bhrt_default_denoise_opts(bhrt_denoise_opts *opts);
+/* bhrt_render_dev / bhrt_render plus the denoiser's noise estimate: variance = W*H*3 floats, the per-channel variance of each pixel's
+ * mean, sum_s (x_s - m)^2 / (spp - 1) / spp (0 at spp = 1), laid out like radiance (pixels of other ranks' tiles untouched, so it travels
+ * through bhrt_tiles_pack_dev / _unpack_dev as the radiance section of a second block).  variance = NULL: exactly bhrt_render_dev / bhrt_render. */
+int bhrt_render_var_dev(bhrt_scene *scene, const bhrt_opts *opts, uint8_t *d_rgb8, float *d_radiance, float *d_variance, bhrt_stats *stats, void *stream);
+int bhrt_render_var(bhrt_scene *scene, const bhrt_opts *opts, uint8_t *rgb8, float *radiance, float *variance, bhrt_stats *stats);
+/* DenoiseImage(colorArray, renderImage) (Main.cpp:236-238) on the whole W x H frame of the scene's camera.
+ * radiance: W*H*3 linear floats (bhrt_render*'s radiance, before gamma).  variance: bhrt_render_var*'s, or NULL (no luminance weight).
+ * z (W*H), normal, albedo (W*H*3 each): the first-hit images of bhrt_first_hit*; each may be NULL = computed here by the same kernel.
+ * out: W*H*3 linear floats, rgb8: W*H*3 bytes (gamma + Color24 as in bhrt_render); either may be NULL.
+ * _dev: device pointers; with a stream the call does not synchronise.  Scratch (48 B per pixel, + 28 B when guides are computed) belongs
+ * to the scene: calls on one scene must not overlap, a call on another stream included. */
+int bhrt_denoise_dev(bhrt_scene *scene, const bhrt_denoise_opts *opts, const float *d_radiance, const float *d_variance, const float *d_z, const float *d_normal,
+                     const float *d_albedo, float *d_out, uint8_t *d_rgb8, void *stream);
+int bhrt_denoise(bhrt_scene *scene, const bhrt_denoise_opts *opts, const float *radiance, const float *variance, const float *z, const float *normal,
+                 const float *albedo, float *out, uint8_t *rgb8);
+
 /* ---- test hook: csrc/bhrt_detmath.h evaluated on the device, to prove host and device produce the same bits.
  * fn: 0 sin 1 cos 2 tan 3 acos 4 asin 5 atan2(a,b) 6 pow(a,b) 7 rand_to_unit(bits of a) 8 a/b 9 sqrt(a); host pointers */
 int bhrt_math_eval_dev(int fn, const float *a, const float *b, size_t n, float *out);
