@@ -56,6 +56,11 @@ class DenoiseOpts(C.Structure):
                 ("gamma", C.c_int32), ("reserved", C.c_int32 * 3)]
 
 
+class AdaptiveOpts(C.Structure):
+    """bhrt_adaptive_opts: round-0 samples, the retirement threshold and its luminance floor (include/bhrt.h states the rounds and the test)."""
+    _fields_ = [("min_spp", C.c_int32), ("threshold", C.c_float), ("floor", C.c_float), ("reserved", C.c_int32 * 5)]
+
+
 class Hits(C.Structure):
     _fields_ = [("t", C.c_void_p), ("node", C.c_void_p), ("prim", C.c_void_p), ("front", C.c_void_p)]
 
@@ -73,6 +78,8 @@ EXPORTS = [
     "bhrt_first_hit", "bhrt_first_hit_dev", "bhrt_zbuffer_image_dev", "bhrt_color_image_dev",
     "bhrt_scene_load_xml_ex", "bhrt_bvh_build", "bhrt_photon_emit_range", "bhrt_photon_install", "bhrt_scene_clone", "bhrt_host_alloc", "bhrt_host_free", "bhrt_photon_gather_host_ex", "bhrt_scene_knob",
     "bhrt_default_denoise_opts", "bhrt_render_var", "bhrt_render_var_dev", "bhrt_denoise", "bhrt_denoise_dev",
+    "bhrt_default_adaptive_opts", "bhrt_render_adaptive", "bhrt_render_adaptive_dev", "bhrt_sample_count_image", "bhrt_sample_count_image_dev",
+    "bhrt_save_png_gray",
 ]
 
 
@@ -97,6 +104,7 @@ def lib():
         L.bhrt_scene_free.restype = None
         L.bhrt_default_opts.restype = None
         L.bhrt_default_denoise_opts.restype = None
+        L.bhrt_default_adaptive_opts.restype = None
         _lib = L
     return _lib
 
@@ -118,6 +126,15 @@ def default_denoise_opts(**kw) -> DenoiseOpts:
     """bhrt_default_denoise_opts (K = 4, sigma_normal = 32, sigma_depth = 0.01, sigma_luminance = 4, gamma = 1), fields overridden by kw."""
     o = DenoiseOpts()
     lib().bhrt_default_denoise_opts(C.byref(o))
+    for k, v in kw.items():
+        setattr(o, k, v)
+    return o
+
+
+def default_adaptive_opts(**kw) -> AdaptiveOpts:
+    """bhrt_default_adaptive_opts (min_spp = 16, threshold and floor from DESIGN.md 10), fields overridden by kw."""
+    o = AdaptiveOpts()
+    lib().bhrt_default_adaptive_opts(C.byref(o))
     for k, v in kw.items():
         setattr(o, k, v)
     return o
@@ -241,6 +258,36 @@ class Scene:
         _check(lib().bhrt_render_var_dev(self._h, C.byref(opts), C.c_void_p(d_rgb8_ptr or None), C.c_void_p(d_radiance_ptr or None),
                                          C.c_void_p(d_variance_ptr or None), C.byref(st), None))
         return st
+
+    def render_adaptive(self, opts: Opts, aopts: AdaptiveOpts):
+        """Adaptive sampling (bhrt_render_adaptive): opts.spp is the per-pixel maximum.  Returns (rgb8 (H, W, 3) uint8, radiance (H, W, 3),
+        variance (H, W, 3) float32, count (H, W) uint32 samples per pixel, Stats); pixels of other ranks' tiles stay 0."""
+        W, H = self.width, self.height
+        rgb = np.zeros((H, W, 3), np.uint8)
+        rad = np.zeros((H, W, 3), np.float32)
+        var = np.zeros((H, W, 3), np.float32)
+        cnt = np.zeros((H, W), np.uint32)
+        st = Stats()
+        _check(lib().bhrt_render_adaptive(self._h, C.byref(opts), C.byref(aopts), _ptr(rgb), _ptr(rad), _ptr(var), _ptr(cnt), C.byref(st)))
+        return rgb, rad, var, cnt, st
+
+    def render_adaptive_dev(self, opts: Opts, aopts: AdaptiveOpts, d_rgb8_ptr: int = 0, d_radiance_ptr: int = 0, d_variance_ptr: int = 0,
+                            d_count_ptr: int = 0):
+        """Same with outputs left in HBM (raw device pointers; any may be 0 = not wanted).  Returns Stats."""
+        st = Stats()
+        v = lambda x: C.c_void_p(x or None)  # noqa: E731
+        _check(lib().bhrt_render_adaptive_dev(self._h, C.byref(opts), C.byref(aopts), v(d_rgb8_ptr), v(d_radiance_ptr), v(d_variance_ptr), v(d_count_ptr),
+                                              C.byref(st), None))
+        return st
+
+    def sample_count_image(self, count):
+        """RenderImage::ComputeSampleCountImage (scene.h:603-626, bhrt_sample_count_image) of a count image: returns (img uint8 shaped like
+        count, smax)."""
+        c = np.ascontiguousarray(count, np.uint32)
+        img = np.zeros(c.shape, np.uint8)
+        smax = C.c_uint32(0)
+        _check(lib().bhrt_sample_count_image(self._h, _ptr(c), C.c_size_t(c.size), _ptr(img), C.byref(smax)))
+        return img, smax.value
 
     def denoise(self, opts: DenoiseOpts, radiance, variance=None, z=None, normal=None, albedo=None):
         """DenoiseImage (bhrt_denoise) on host arrays of the scene's W x H frame: radiance (H, W, 3) linear, variance like it or None;

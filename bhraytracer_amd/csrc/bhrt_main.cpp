@@ -7,6 +7,7 @@
 //               [--device D | --gpus N [--rehearse]] [--rank R --world N] [--tile T] [--radiance out.f32] [--leaf-skip] [--photon-exact]
 //               [--photons N] [--photon-file map.dat] [--photon-out map.dat]     (USE_PhotonMap, Main.cpp:51,53,194,383)
 //               [--denoise [--denoise-iters K]]                                  (DenoiseImage of the x64 build, Main.cpp:57-96,236-238)
+//               [--adaptive [--spp-min N] [--adaptive-threshold X] [--samples-png path]]  (RenderImage::sampleCount, scene.h:534,603-630)
 //   bhrt info   <scene.xml>
 //
 // --gpus N: ONE process drives N GPUs of the node (the reference's one process drives 16 OpenMP threads, Main.cpp:422): the
@@ -21,6 +22,9 @@
 // --denoise: the PNG is the denoised frame (bhrt_denoise, as the reference's 64-bit build saves it); --radiance stays the render's own
 // radiance.  With --gpus N the ranks' variance tiles travel in a second block beside the first and GPU 0 denoises the gathered frame; a
 // partial frame (--world > 1) cannot be denoised.
+// --adaptive: bhrt_render_adaptive; --spp is the per-pixel maximum, --spp-min round 0's samples.  --samples-png writes the
+// sample-count image as SaveSampleCountImage does (scene.h:630); its normalisation needs the whole frame, so --world > 1 refuses it.  With
+// --gpus N the counts travel as the float section of a further block (exact below 2^24); with --denoise the adaptive variance is the filter's.
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
@@ -56,7 +60,23 @@ struct Args {
     bool rehearse = false; // --rehearse: the N ranks of --gpus N all on device 0, the all-gather as N device-to-device copies (no RCCL)
     bool denoise = false;
     bhrt_denoise_opts dn;
+    bool adaptive = false;
+    bhrt_adaptive_opts ad;
+    std::string samples_png;
 };
+
+// the adaptive frame's round count (doubling from min_spp up to the largest count) and the spp statistics of its rendered pixels (count > 0)
+static void print_adaptive(const std::vector<uint32_t> &cnt, const bhrt_opts &o, const bhrt_adaptive_opts &ad)
+{
+    uint64_t total = 0, px = 0;
+    uint32_t cmin = 0xffffffffu, cmax = 0;
+    for (uint32_t c : cnt)
+        if (c) { total += c; px++; cmin = std::min(cmin, c); cmax = std::max(cmax, c); }
+    int rounds = px ? 1 : 0;
+    for (uint32_t n = (uint32_t)ad.min_spp; px && n < cmax; rounds++) n = std::min<uint32_t>((uint32_t)o.spp, 2 * n);
+    printf("adaptive: %d round(s), spp mean %.3f min %u max %u, %llu samples\n", rounds, px ? (double)total / (double)px : 0.0, px ? cmin : 0, cmax,
+           (unsigned long long)total);
+}
 
 // Everything render_multi owns besides the caller's scene: released on every way out (the early returns included).
 struct MultiGuard {
@@ -73,8 +93,8 @@ struct MultiGuard {
 };
 
 // BeginRender over N GPUs of this node; rgb / rad: the whole frame on the host (rad may be empty)
-static int render_multi(bhrt_scene *first, const Args &A, const bhrt_info &info, std::vector<uint8_t> &rgb, std::vector<float> &rad, std::vector<bhrt_stats> &stats,
-                        double &gather_seconds)
+static int render_multi(bhrt_scene *first, const Args &A, const bhrt_info &info, std::vector<uint8_t> &rgb, std::vector<float> &rad, std::vector<uint32_t> &cnt,
+                        std::vector<bhrt_stats> &stats, double &gather_seconds)
 {
     const int N = A.gpus, W = info.width, H = info.height, tile = A.o.tile_size > 0 ? A.o.tile_size : 32;
     int have = 0;
@@ -147,14 +167,15 @@ static int render_multi(bhrt_scene *first, const Args &A, const bhrt_info &info,
     // collective a thread never blocks in a stream synchronise: it polls its stream and the failure flag, and when a peer has failed it
     // aborts its communicator (ncclCommAbort) and leaves.
     std::vector<double> gather_s(N, 0.0);
-    std::vector<uint8_t *> mine_of(N, nullptr), mine_v_of(N, nullptr); // --rehearse: where every rank's packed blocks lie (all on device 0)
+    std::vector<uint8_t *> mine_of(N, nullptr), mine_v_of(N, nullptr), mine_c_of(N, nullptr); // --rehearse: where every rank's packed blocks lie (all on device 0)
     std::atomic<int> ready(0), rendered(0), packed(0), exchanged(0);
     auto rendezvous = [&](std::atomic<int> &c) { c.fetch_add(1); while (c.load() < N) std::this_thread::yield(); return !failed.load(); };
     std::vector<std::thread> th;
     for (int r = 0; r < N; r++)
         th.emplace_back([&, r]() {
-            uint8_t *d_rgb = nullptr, *d_mine = nullptr, *d_all = nullptr, *d_mine_v = nullptr, *d_all_v = nullptr;
-            float *d_rad = nullptr, *d_var = nullptr;
+            uint8_t *d_rgb = nullptr, *d_mine = nullptr, *d_all = nullptr, *d_mine_v = nullptr, *d_all_v = nullptr, *d_mine_c = nullptr, *d_all_c = nullptr;
+            float *d_rad = nullptr, *d_var = nullptr, *d_cntf = nullptr;
+            uint32_t *d_cnt = nullptr;
             hipStream_t s = nullptr;
             auto setup = [&]() {
                 HOST_CHECK(bhrt_scene_upload(scenes[r], devs[r]), "upload");
@@ -172,27 +193,46 @@ static int render_multi(bhrt_scene *first, const Args &A, const bhrt_info &info,
                     HOST_CHECK(hipMalloc(&d_all_v, bb * N), "hipMalloc");
                     HOST_CHECK(hipMemsetAsync(d_var, 0, npx * 3 * sizeof(float), s), "memset");
                 }
+                if (A.adaptive) { // the counts: a further block whose float section holds them (channel 0 of a W x H x 3 float image)
+                    HOST_CHECK(hipMalloc(&d_cnt, npx * sizeof(uint32_t)), "hipMalloc");
+                    HOST_CHECK(hipMalloc(&d_cntf, npx * 3 * sizeof(float)), "hipMalloc");
+                    HOST_CHECK(hipMalloc(&d_mine_c, bb), "hipMalloc");
+                    HOST_CHECK(hipMalloc(&d_all_c, bb * N), "hipMalloc");
+                    HOST_CHECK(hipMemsetAsync(d_cnt, 0, npx * sizeof(uint32_t), s), "memset");
+                }
                 HOST_CHECK(hipStreamSynchronize(s), "sync");
             };
             setup();
             auto release = [&]() {
                 (void)hipFree(d_rgb); (void)hipFree(d_rad); (void)hipFree(d_mine); (void)hipFree(d_all);
                 (void)hipFree(d_var); (void)hipFree(d_mine_v); (void)hipFree(d_all_v);
+                (void)hipFree(d_cnt); (void)hipFree(d_cntf); (void)hipFree(d_mine_c); (void)hipFree(d_all_c);
                 if (s) (void)hipStreamDestroy(s);
             };
             if (!rendezvous(ready)) { release(); return; }
             bhrt_opts o = A.o;
             o.rank = r; o.world_size = N; o.tile_size = tile;
             if (A.photons || !A.photon_file.empty()) o.photon_map = 1;
-            if (bhrt_render_var_dev(scenes[r], &o, d_rgb, d_rad, d_var, &stats[r], nullptr)) { fprintf(stderr, "bhrt: GPU %d: BeginRender: %s\n", r, bhrt_last_error()); failed.store(true); }
+            const int rc = A.adaptive ? bhrt_render_adaptive_dev(scenes[r], &o, &A.ad, d_rgb, d_rad, d_var, d_cnt, &stats[r], nullptr)
+                                      : bhrt_render_var_dev(scenes[r], &o, d_rgb, d_rad, d_var, &stats[r], nullptr);
+            if (rc) { fprintf(stderr, "bhrt: GPU %d: BeginRender: %s\n", r, bhrt_last_error()); failed.store(true); }
+            if (!rc && A.adaptive) { // counts -> floats (exact below 2^24): through the host, W x H words
+                std::vector<uint32_t> hc(npx);
+                std::vector<float> hf(npx * 3, 0.f);
+                if (hipMemcpy(hc.data(), d_cnt, npx * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess) failed.store(true);
+                for (size_t k = 0; k < npx; k++) hf[3 * k] = (float)hc[k];
+                if (hipMemcpy(d_cntf, hf.data(), npx * 3 * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) failed.store(true);
+            }
             if (!rendezvous(rendered)) { release(); return; }
             const auto t0 = std::chrono::steady_clock::now();
             auto pack = [&]() {
                 HOST_CHECK(bhrt_tiles_pack_dev(d_rgb, d_rad, W, H, tile, r, N, d_mine, s), "pack");
                 if (A.denoise) HOST_CHECK(bhrt_tiles_pack_dev(d_rgb, d_var, W, H, tile, r, N, d_mine_v, s), "pack");
+                if (A.adaptive) HOST_CHECK(bhrt_tiles_pack_dev(d_rgb, d_cntf, W, H, tile, r, N, d_mine_c, s), "pack");
                 HOST_CHECK(hipStreamSynchronize(s), "sync");
                 mine_of[r] = d_mine;
                 mine_v_of[r] = d_mine_v;
+                mine_c_of[r] = d_mine_c;
             };
             pack();
             if (getenv("BHRT_TEST_FAIL_PACK") && atoi(getenv("BHRT_TEST_FAIL_PACK")) == r) { fprintf(stderr, "bhrt: GPU %d: pack failed (test knob)\n", r); failed.store(true); }
@@ -215,14 +255,18 @@ static int render_multi(bhrt_scene *first, const Args &A, const bhrt_info &info,
                     for (int k = 0; k < N; k++) HOST_CHECK(hipMemcpyAsync(d_all + (size_t)k * bb, mine_of[k], bb, hipMemcpyDeviceToDevice, s), "copy of a peer's block");
                     if (A.denoise)
                         for (int k = 0; k < N; k++) HOST_CHECK(hipMemcpyAsync(d_all_v + (size_t)k * bb, mine_v_of[k], bb, hipMemcpyDeviceToDevice, s), "copy of a peer's block");
+                    if (A.adaptive)
+                        for (int k = 0; k < N; k++) HOST_CHECK(hipMemcpyAsync(d_all_c + (size_t)k * bb, mine_c_of[k], bb, hipMemcpyDeviceToDevice, s), "copy of a peer's block");
                 } else if (ncclAllGather(d_mine, d_all, bb, ncclUint8, G.comms[r], s) != ncclSuccess ||
-                           (A.denoise && ncclAllGather(d_mine_v, d_all_v, bb, ncclUint8, G.comms[r], s) != ncclSuccess)) {
+                           (A.denoise && ncclAllGather(d_mine_v, d_all_v, bb, ncclUint8, G.comms[r], s) != ncclSuccess) ||
+                           (A.adaptive && ncclAllGather(d_mine_c, d_all_c, bb, ncclUint8, G.comms[r], s) != ncclSuccess)) {
                     fprintf(stderr, "bhrt: GPU %d: ncclAllGather failed\n", r);
                     failed.store(true);
                 }
                 if (!wait_stream()) return;
                 HOST_CHECK(bhrt_tiles_unpack_dev(d_all, W, H, tile, N, d_rgb, d_rad, s), "unpack");
                 if (A.denoise) HOST_CHECK(bhrt_tiles_unpack_dev(d_all_v, W, H, tile, N, d_rgb, d_var, s), "unpack"); // the same RGB8 bytes again
+                if (A.adaptive) HOST_CHECK(bhrt_tiles_unpack_dev(d_all_c, W, H, tile, N, d_rgb, d_cntf, s), "unpack");
                 HOST_CHECK(hipStreamSynchronize(s), "sync");
                 gather_s[r] = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
                 if (r == 0 && A.denoise) { // DenoiseImage on the gathered frame (Main.cpp:236-238): the PNG bytes become the filter's
@@ -232,6 +276,12 @@ static int render_multi(bhrt_scene *first, const Args &A, const bhrt_info &info,
                 if (r == 0) {
                     HOST_CHECK(hipMemcpy(rgb.data(), d_rgb, npx * 3, hipMemcpyDeviceToHost), "copy");
                     if (!rad.empty()) HOST_CHECK(hipMemcpy(rad.data(), d_rad, npx * 3 * sizeof(float), hipMemcpyDeviceToHost), "copy");
+                    if (A.adaptive) {
+                        std::vector<float> hf(npx * 3);
+                        HOST_CHECK(hipMemcpy(hf.data(), d_cntf, npx * 3 * sizeof(float), hipMemcpyDeviceToHost), "copy");
+                        cnt.assign(npx, 0);
+                        for (size_t k = 0; k < npx; k++) cnt[k] = (uint32_t)hf[3 * k];
+                    }
                 }
             };
             exchange();
@@ -256,6 +306,7 @@ int main(int argc, char **argv)
     bhrt_opts &o = A.o;
     bhrt_default_opts(&o);
     bhrt_default_denoise_opts(&A.dn);
+    bhrt_default_adaptive_opts(&A.ad);
     for (int a = 3; a < argc; a++) {
         std::string s = argv[a];
         auto next = [&]() -> const char * { if (a + 1 >= argc) { fprintf(stderr, "bhrt: %s needs a value\n", s.c_str()); exit(2); } return argv[++a]; };
@@ -280,6 +331,10 @@ int main(int argc, char **argv)
         else if (s == "--photon-out") A.photon_out = next();
         else if (s == "--denoise") A.denoise = true;
         else if (s == "--denoise-iters") A.dn.iterations = atoi(next());
+        else if (s == "--adaptive") A.adaptive = true;
+        else if (s == "--spp-min") A.ad.min_spp = atoi(next());
+        else if (s == "--adaptive-threshold") A.ad.threshold = (float)atof(next());
+        else if (s == "--samples-png") A.samples_png = next();
         else { fprintf(stderr, "bhrt: unknown option %s\n", s.c_str()); return 2; }
     }
     if (A.gpus < 0 || A.gpus > 64 || (A.gpus > 0 && (o.rank != 0 || o.world_size != 1))) { fprintf(stderr, "bhrt: --gpus N drives all N ranks itself (no --rank / --world)\n"); return 2; }
@@ -288,6 +343,15 @@ int main(int argc, char **argv)
         return 2;
     }
     if (A.denoise && (A.dn.iterations < 0 || A.dn.iterations > 16)) { fprintf(stderr, "bhrt: usage: --denoise-iters must be in 0..16\n"); return 2; }
+    if (!A.adaptive && !A.samples_png.empty()) { fprintf(stderr, "bhrt: usage: --samples-png needs --adaptive\n"); return 2; }
+    if (A.adaptive && !A.samples_png.empty() && o.world_size > 1) { // before any device is touched
+        fprintf(stderr, "bhrt: usage: --samples-png normalises over the whole frame; a rank of --world %d renders part of it (use --gpus N)\n", o.world_size);
+        return 2;
+    }
+    if (A.adaptive && (A.ad.min_spp < 2 || A.ad.min_spp > o.spp || o.spp > 65535 || A.ad.threshold != A.ad.threshold)) {
+        fprintf(stderr, "bhrt: usage: --adaptive needs 2 <= --spp-min <= --spp <= 65535 and a number for --adaptive-threshold\n");
+        return 2;
+    }
     A.dn.gamma = o.gamma;
     bhrt_scene *scene = nullptr;
     if (bhrt_scene_load_xml(A.scene.c_str(), &scene)) return fail("LoadScene");
@@ -303,13 +367,14 @@ int main(int argc, char **argv)
     if (!render) { bhrt_scene_free(scene); return 0; }
     std::vector<uint8_t> rgb((size_t)info.width * info.height * 3, 0);
     std::vector<float> rad(A.radiance_out.empty() && !A.denoise ? 0 : (size_t)info.width * info.height * 3, 0.f);
+    std::vector<uint32_t> cnt(A.adaptive ? (size_t)info.width * info.height : 0, 0u);
     bhrt_stats st;
     memset(&st, 0, sizeof st);
     if (A.gpus > 0) {
         std::vector<bhrt_stats> per;
         double gather_s = 0;
         const auto t0 = std::chrono::steady_clock::now();
-        if (render_multi(scene, A, info, rgb, rad, per, gather_s)) return 1;
+        if (render_multi(scene, A, info, rgb, rad, cnt, per, gather_s)) return 1;
         const double wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         double slowest = 0;
         for (int r = 0; r < A.gpus; r++) {
@@ -333,7 +398,12 @@ int main(int argc, char **argv)
             o.photon_map = 1;
         }
         if (o.photon_map && !A.photon_out.empty() && bhrt_photon_export(scene, A.photon_out.c_str())) return fail("photon export");
-        if (A.denoise) {
+        if (A.adaptive) {
+            std::vector<float> var(A.denoise ? rad.size() : 0, 0.f);
+            if (bhrt_render_adaptive(scene, &o, &A.ad, rgb.data(), rad.empty() ? nullptr : rad.data(), var.empty() ? nullptr : var.data(), cnt.data(), &st))
+                return fail("BeginRender (adaptive)");
+            if (A.denoise && bhrt_denoise(scene, &A.dn, rad.data(), var.data(), nullptr, nullptr, nullptr, nullptr, rgb.data())) return fail("DenoiseImage");
+        } else if (A.denoise) {
             std::vector<float> var(rad.size(), 0.f);
             if (bhrt_render_var(scene, &o, rgb.data(), rad.data(), var.data(), &st)) return fail("BeginRender");
             if (bhrt_denoise(scene, &A.dn, rad.data(), var.data(), nullptr, nullptr, nullptr, nullptr, rgb.data())) return fail("DenoiseImage");
@@ -343,7 +413,14 @@ int main(int argc, char **argv)
     printf("rendered %llu camera samples, %.0f rays (%llu closest + %llu shadow), %u wave steps in %u pass(es): %.3f s, %.1f Mrays/s\n",
            (unsigned long long)st.camera_samples, rays, (unsigned long long)st.closest_rays, (unsigned long long)st.shadow_rays, st.wave_iterations,
            st.passes, st.seconds_total, rays / st.seconds_total / 1e6);
+    if (A.adaptive) print_adaptive(cnt, o, A.ad);
     if (bhrt_save_png(A.out.c_str(), rgb.data(), info.width, info.height)) return fail("SaveImage");
+    if (!A.samples_png.empty()) { // ComputeSampleCountImage + SaveSampleCountImage (scene.h:603-630)
+        std::vector<uint8_t> img(cnt.size());
+        uint32_t smax = 0;
+        if (bhrt_sample_count_image(scene, cnt.data(), cnt.size(), img.data(), &smax)) return fail("ComputeSampleCountImage");
+        if (bhrt_save_png_gray(A.samples_png.c_str(), img.data(), info.width, info.height)) return fail("SaveSampleCountImage");
+    }
     if (!A.radiance_out.empty()) {
         FILE *fp = fopen(A.radiance_out.c_str(), "wb");
         if (!fp) { fprintf(stderr, "bhrt: cannot write %s\n", A.radiance_out.c_str()); return 1; }

@@ -52,6 +52,15 @@ void bhrt_default_denoise_opts(bhrt_denoise_opts *o)
     o->gamma = 1; // as bhrt_opts.gamma (Main.cpp:128)
 }
 
+void bhrt_default_adaptive_opts(bhrt_adaptive_opts *a)
+{
+    if (!a) return;
+    memset(a, 0, sizeof *a);
+    a->min_spp = 16;
+    a->threshold = 0.01f;
+    a->floor = 0.1f; // threshold, floor: the quality grid of tools/adaptive_quality.py over c3_room, c2_glass, c3_mesh
+}
+
 int bhrt_scene_load_xml(const char *path, bhrt_scene **out) { return bhrt_scene_load_xml_ex(path, -1, out); }
 
 int bhrt_scene_load_xml_ex(const char *path, int bvh_device, bhrt_scene **out)
@@ -126,6 +135,13 @@ int bhrt_save_png(const char *path, const uint8_t *rgb8, int w, int h)
 try {
     if (!path || !rgb8) { bhrt::SetError("bhrt_save_png: null argument"); return BHRT_ERR_ARG; }
     if (!bhrt::SavePng(path, rgb8, w, h, 3)) { bhrt::SetError(std::string("cannot write ") + path); return BHRT_ERR_IO; }
+    return BHRT_OK;
+} catch (...) { return bhrt::AbiException(); }
+
+int bhrt_save_png_gray(const char *path, const uint8_t *gray, int w, int h)
+try {
+    if (!path || !gray) { bhrt::SetError("bhrt_save_png_gray: null argument"); return BHRT_ERR_ARG; }
+    if (!bhrt::SavePng(path, gray, w, h, 1)) { bhrt::SetError(std::string("cannot write ") + path); return BHRT_ERR_IO; }
     return BHRT_OK;
 } catch (...) { return bhrt::AbiException(); }
 

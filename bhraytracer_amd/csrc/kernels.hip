@@ -15,6 +15,7 @@
 //                                              wave step first (the per-level clamps forbid a running throughput)
 //   k_resolve       Main.cpp:170,220-230       in-order sample sum, /spp, gamma, Color24
 //   k_variance      (DenoiseImage's input)     per-channel variance of the pixel mean, only when a variance image is asked for
+//   k_adapt_fold    scene.h:534,570 (sampleCount)  adaptive rounds: folds a pass into each pixel's state, retires converged pixels, lists the rest
 //   k_photon_*      Main.cpp:319-386, cyPhotonMap.h   caustic photon map: emission, and the k-NN gather in three passes
 //   k_tiles_*       (no counterpart)           multi-GPU framebuffer exchange: pack / unpack of a rank's tiles
 // The recursion of the reference becomes: ray kinds (continuations) + a tree of shading frames.
@@ -80,9 +81,11 @@ __device__ inline void fdivmod(uint32_t n, const FastDiv &f, uint32_t &q, uint32
 
 struct PassInfo {
     int32_t W, H, tile, tiles_x, tiles_y, rank, world;
-    uint32_t q0;       // first owned-pixel index of this pass
-    uint32_t n_pixels; // owned pixels in this pass (incl. out-of-image pixels of edge tiles)
-    int32_t spp;
+    uint32_t q0;          // first owned-pixel index of this pass (list == nullptr)
+    uint32_t n_pixels;    // pixels in this pass (incl. out-of-image pixels of edge tiles)
+    const uint32_t *list; // owned-pixel indices of this pass's pixels (an adaptive round's active list); nullptr = the range q0 + q_local
+    uint32_t s0;          // sample index of the pass's first sample of every pixel (adaptive rounds; 0 for a uniform render)
+    int32_t spp;          // samples per pixel in this pass
     uint32_t seed;
     int32_t jitter, gamma;
     // per-frame constants of RandomPositionInPixel (Main.cpp:132-139), formed once on the host with the same float
@@ -107,6 +110,17 @@ __device__ inline bool pixel_of(const PassInfo &P, uint32_t q, int &i, int &j)
     i = (int)(tx * P.tile + wx);
     j = (int)(ty * P.tile + wy);
     return ty < (uint32_t)P.tiles_y && i < P.W && j < P.H;
+}
+
+// Slot -> (pixel, sample): the ONE place that maps a slot of the pass (pass-local pixel q_local, sample s of the pass) to its owned-pixel
+// index and its image pixel.  `list` is a kernel argument: the branch is uniform across the wave.  The sample's RNG key is
+// bhrt_sample_key(seed, j * W + i, P.s0 + s), so its value does not depend on the pass or round it runs in.
+__device__ inline uint32_t pass_pixel(const PassInfo &P, uint32_t q_local) { return P.list ? P.list[q_local] : P.q0 + q_local; }
+__device__ inline bool slot_pixel(const PassInfo &P, uint32_t slot, int &i, int &j, uint32_t &s)
+{
+    uint32_t q_local;
+    fdivmod(slot, P.by_spp, q_local, s);
+    return pixel_of(P, pass_pixel(P, q_local), i, j);
 }
 
 // Queue compaction: wave64 ballot + prefix popcount inside each wave, wave totals combined through LDS,
@@ -184,17 +198,16 @@ __device__ inline V3 ld3i(const float *a, uint32_t i) { return v3(a[3 * (size_t)
 __device__ inline bool camera_ray(const DevScene &S, const PassInfo &P, uint32_t idx, V3 &o, V3 &d)
 {
     int i = 0, j = 0;
-    uint32_t q_local, s;
-    fdivmod(idx, P.by_spp, q_local, s);
+    uint32_t s;
     o = v3(0, 0, 0); d = v3(0, 0, 0);
-    if (!pixel_of(P, P.q0 + q_local, i, j)) return false;
+    if (!slot_pixel(P, idx, i, j, s)) return false;
     // PathTracing(), Main.cpp:145: pixel "centre" = corner because 1/2 == 0
     const V3 topLeft = ld3(S.cam.top_left), ddx = ld3(S.cam.dd_x), ddy = ld3(S.cam.dd_y), pos = ld3(S.cam.pos);
     V3 target = (topLeft + (float)i * ddx) - (float)j * ddy;
     if (P.jitter) { // RandomPositionInPixel, Main.cpp:132-139: two raw rand() draws in double
         const float pixelLen = P.pixel_len;
         const V3 ux = ld3(P.jx), uy = ld3(P.jy);
-        const uint32_t key = bhrt_sample_key(P.seed, (uint32_t)(j * P.W + i), s);
+        const uint32_t key = bhrt_sample_key(P.seed, (uint32_t)(j * P.W + i), P.s0 + s);
         float fx = (float)(((double)bhrt_rand31(key, 0) / (BHRT_RAND_MAX)) * 2 - 1);
         target = target + ((ux * fx) * pixelLen) / 2.f;
         float fy = (float)(((double)bhrt_rand31(key, 1) / (BHRT_RAND_MAX)) * 2 - 1);
@@ -972,10 +985,9 @@ __device__ __forceinline__ void shade_block(const DevScene &S, const RenderParam
         V3 mult = v3(1, 1, 1);
         if (kind == RK_CAMERA) {
             int pi, pj;
-            uint32_t opx, osmp;
-            fdivmod(owner, P.by_spp, opx, osmp);
-            pixel_of(P, P.q0 + opx, pi, pj);
-            skey = bhrt_sample_key(P.seed, (uint32_t)(pj * P.W + pi), osmp);
+            uint32_t osmp;
+            slot_pixel(P, owner, pi, pj, osmp);
+            skey = bhrt_sample_key(P.seed, (uint32_t)(pj * P.W + pi), P.s0 + osmp);
             gi = R.gi_bounces;
             bounce = R.internal_bounces;
             how = FH_ROOT;
@@ -1016,7 +1028,8 @@ __device__ __forceinline__ void shade_block(const DevScene &S, const RenderParam
         if (kind == RK_CAMERA) {
             // background.Sample((i/W, j/H, 0)), Main.cpp:166-167
             int pi, pj;
-            pixel_of(P, P.q0 + fdiv(owner, P.by_spp), pi, pj);
+            uint32_t osmp;
+            slot_pixel(P, owner, pi, pj, osmp);
             st3(samples, sample_addr(P, owner), kTex ? tc_sample(S, S.background, v3((float)pi / S.cam.width, (float)pj / S.cam.height, 0.0f)) : ld3(S.background.color));
         } else if (kind == RK_GI) {
             V3 mult = ld3i(F.gi_mult, owner);
@@ -1180,7 +1193,7 @@ __global__ void __launch_bounds__(kBlock) k_resolve(PassInfo P, const float *sam
     const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
     if (q >= P.n_pixels) return;
     int i, j;
-    if (!pixel_of(P, P.q0 + q, i, j)) return;
+    if (!pixel_of(P, pass_pixel(P, q), i, j)) return;
     V3 sum = v3(0, 0, 0);
     for (int s = 0; s < P.spp; s++) sum = sum + ld3i(samples, (uint32_t)s * P.n_pixels + q);
     V3 out = sum / (float)P.spp;
@@ -1196,7 +1209,7 @@ __global__ void __launch_bounds__(kBlock) k_variance(PassInfo P, const float *sa
     const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
     if (q >= P.n_pixels) return;
     int i, j;
-    if (!pixel_of(P, P.q0 + q, i, j)) return;
+    if (!pixel_of(P, pass_pixel(P, q), i, j)) return;
     V3 sum = v3(0, 0, 0);
     for (int s = 0; s < P.spp; s++) sum = sum + ld3i(samples, (uint32_t)s * P.n_pixels + q);
     const V3 m = sum / (float)P.spp;
@@ -1209,6 +1222,119 @@ __global__ void __launch_bounds__(kBlock) k_variance(PassInfo P, const float *sa
         acc = (acc / (float)(P.spp - 1)) / (float)P.spp;
     }
     st3(variance, (uint32_t)((size_t)j * P.W + i), acc);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Adaptive sampling.  Round 0 gives every owned pixel samples [0, min_spp); round r >= 1 gives every pixel still active samples
+// [n_{r-1}, n_r), n_r = min(max_spp, 2 n_{r-1}).  The state a pixel carries between its rounds, indexed by its owned-pixel index q, 36 B:
+//   a[q] = (S.x, S.y, S.z, mu.x), b[q] = (mu.y, mu.z, M2.x, M2.y), c[q] = M2.z      (n is the round's s0: every active pixel has the same)
+struct AdaptState {
+    float4 *a, *b;
+    float *c;
+};
+struct AdaptParams {
+    uint32_t n_max;        // bhrt_opts.spp
+    float threshold, floor;
+    float *radiance, *variance; // W*H*3 each (may be NULL)
+    uint8_t *rgb8;              // W*H*3 (may be NULL)
+    uint32_t *count;            // W*H (may be NULL)
+    uint32_t *next, *n_next;    // the next round's list and its length (zeroed by the host before the round)
+};
+
+// One lane per pixel of the pass (P.list, or round 0's range).  In float32, in sample order, for k = s0 + 1 .. n (x = sample k - 1):
+//   S += x;   d = x - mu;   mu += d / (float)k;   M2 += d * (x - mu)                  (no contraction: -ffp-contract=off)
+// then   m = S / (float)n                                   (k_resolve's mean: the same additions from 0 in the same order, the same division)
+//        v = (M2 / (float)(n - 1)) / (float)n                (per-channel variance of the mean)
+//        L = (0.2126 m.r + 0.7152 m.g) + 0.0722 m.b,   vL = (0.2126^2 v.r + 0.7152^2 v.g) + 0.0722^2 v.b   (the denoiser's luminance)
+// The pixel retires when n == n_max or sqrtf(vL) <= threshold * fmaxf(L, floor): it writes radiance m, rgb8 (store_color24, k_resolve's
+// gamma rule), variance v and count n, once.  Otherwise it stores its state and is appended to the next round's list (wave ballot + prefix
+// popcount, one atomic per workgroup).  Round 0 reads no state, and drops the edge-tile pixels outside the image.
+__global__ void __launch_bounds__(kBlock) k_adapt_fold(PassInfo P, const float *samples, AdaptState A, AdaptParams R)
+{
+    __shared__ uint32_t s_base[kBlock / 64 + 1];
+    const uint32_t ql = blockIdx.x * blockDim.x + threadIdx.x;
+    uint32_t q = 0;
+    int i = 0, j = 0;
+    bool keep = false;
+    if (ql < P.n_pixels) {
+        q = pass_pixel(P, ql);
+        if (pixel_of(P, q, i, j)) {
+            V3 S = v3(0, 0, 0), mu = v3(0, 0, 0), M2 = v3(0, 0, 0);
+            if (P.s0) {
+                const float4 a = A.a[q], b = A.b[q];
+                S = v3(a.x, a.y, a.z); mu = v3(a.w, b.x, b.y); M2 = v3(b.z, b.w, A.c[q]);
+            }
+            uint32_t k = P.s0;
+            for (int s = 0; s < P.spp; s++) {
+                const V3 x = ld3i(samples, (uint32_t)s * P.n_pixels + ql);
+                S = S + x;
+                k++;
+                const V3 d = x - mu;
+                mu = mu + d / (float)k;
+                M2 = M2 + d * (x - mu);
+            }
+            const uint32_t n = k;
+            const V3 m = S / (float)n;
+            const V3 v = (M2 / (float)(n - 1)) / (float)n;
+            const float L = (0.2126f * m.x + 0.7152f * m.y) + 0.0722f * m.z;
+            const float vL = ((0.2126f * 0.2126f) * v.x + (0.7152f * 0.7152f) * v.y) + (0.0722f * 0.0722f) * v.z;
+            if (n >= R.n_max || sqrtf(vL) <= R.threshold * fmaxf(L, R.floor)) {
+                const size_t pix = (size_t)j * P.W + i;
+                if (R.radiance) st3(R.radiance, (uint32_t)pix, m);
+                if (R.rgb8) store_color24(R.rgb8, pix, m, P.gamma);
+                if (R.variance) st3(R.variance, (uint32_t)pix, v);
+                if (R.count) R.count[pix] = n;
+            } else {
+                A.a[q] = make_float4(S.x, S.y, S.z, mu.x);
+                A.b[q] = make_float4(mu.y, mu.z, M2.x, M2.y);
+                A.c[q] = M2.z;
+                keep = true;
+            }
+        }
+    }
+    const uint32_t lane = __lane_id(), wave = threadIdx.x >> 6;
+    const uint64_t mk = __ballot(keep);
+    if (lane == 0) s_base[wave] = (uint32_t)__popcll(mk);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t sum = 0;
+        for (int w = 0; w < kBlock / 64; w++) { const uint32_t t = s_base[w]; s_base[w] = sum; sum += t; }
+        s_base[kBlock / 64] = sum ? atomicAdd(R.n_next, sum) : 0u;
+    }
+    __syncthreads();
+    if (keep) R.next[s_base[kBlock / 64] + s_base[wave] + (uint32_t)__popcll(mk & ((1ull << lane) - 1ull))] = q;
+}
+
+// RenderImage::ComputeSampleCountImage (scene.h:603-626): min / max of the counts (exact in any order; one workgroup strides over the
+// image), then (255 (s - smin)) / (smax - smin) in integers, clamped to 0..255; 0 everywhere when smax == smin.
+__global__ void __launch_bounds__(1024) k_count_range(const uint32_t *cnt, uint32_t n, uint32_t *range)
+{
+    __shared__ uint32_t s_min[1024], s_max[1024];
+    uint32_t cmin = 0xffffffffu, cmax = 0;
+    for (uint32_t k = threadIdx.x; k < n; k += 1024) {
+        const uint32_t v = cnt[k];
+        cmin = v < cmin ? v : cmin;
+        cmax = v > cmax ? v : cmax;
+    }
+    s_min[threadIdx.x] = cmin; s_max[threadIdx.x] = cmax;
+    __syncthreads();
+    for (uint32_t w = 512; w > 0; w >>= 1) {
+        if (threadIdx.x < w) {
+            if (s_min[threadIdx.x] > s_min[threadIdx.x + w]) s_min[threadIdx.x] = s_min[threadIdx.x + w];
+            if (s_max[threadIdx.x] < s_max[threadIdx.x + w]) s_max[threadIdx.x] = s_max[threadIdx.x + w];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) { range[0] = s_min[0]; range[1] = s_max[0]; }
+}
+__global__ void __launch_bounds__(kBlock) k_count_image(const uint32_t *cnt, uint32_t n, const uint32_t *range, uint8_t *img)
+{
+    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n) return;
+    const uint32_t smin = range[0], smax = range[1];
+    if (smax == smin) { img[k] = 0; return; }
+    const uint64_t c = (255ull * (uint64_t)(cnt[k] - smin)) / (uint64_t)(smax - smin);
+    img[k] = (uint8_t)(c > 255 ? 255 : c);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1312,7 +1438,7 @@ __global__ void k_copy_samples(PassInfo P, const float *samples, int x0, int y0,
     const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
     if (q >= P.n_pixels) return;
     int i, j;
-    if (!pixel_of(P, P.q0 + q, i, j)) return;
+    if (!pixel_of(P, pass_pixel(P, q), i, j)) return;
     if (i < x0 || i >= x1 || j < y0 || j >= y1) return;
     const size_t pix = (size_t)(j - y0) * (x1 - x0) + (i - x0);
     for (int s = 0; s < P.spp; s++)
@@ -1794,6 +1920,12 @@ struct DeviceState {
     // bhrt_render_var: the device copy of the variance image, allocated on first use
     float *d_frame_var = nullptr;
     size_t frame_var_px = 0;
+    // bhrt_render_adaptive_dev: the per-pixel state of the rounds (AdaptState: 36 B per owned pixel), two lists of owned-pixel indices (4 B each)
+    // and the next list's length; grown on demand.  bhrt_render_adaptive: the device copy of the count image.
+    uint8_t *d_ad = nullptr;
+    size_t ad_px = 0;
+    uint32_t *d_frame_cnt = nullptr;
+    size_t frame_cnt_px = 0;
     // bhrt_denoise_dev: the filter's planes (DenoisePlaneBytes), then the first-hit guides it computes itself; grown on demand
     uint8_t *d_dn = nullptr;
     size_t dn_bytes = 0;
@@ -1811,7 +1943,7 @@ void DestroyDeviceState(DeviceState *d)
     fr(d->d_blob); fr(d->d_chain);
     for (int k = 0; k < 2; k++) { fr(d->d_rayf[k]); fr(d->d_rayu[k]); }
     fr(d->d_hitf); fr(d->d_hiti); fr(d->d_shf); fr(d->d_shu); fr(d->d_fu); fr(d->d_fcode); fr(d->d_ff); fr(d->d_samples); fr(d->d_order); fr(d->d_park); fr(d->d_seg); fr(d->d_cnt); fr(d->d_aux);
-    fr(d->d_frame_rgb); fr(d->d_frame_rad); fr(d->d_frame_var); fr(d->d_dn); fr(d->d_sel); fr(d->d_slowf); fr(d->d_slowu);
+    fr(d->d_frame_rgb); fr(d->d_frame_rad); fr(d->d_frame_var); fr(d->d_ad); fr(d->d_frame_cnt); fr(d->d_dn); fr(d->d_sel); fr(d->d_slowf); fr(d->d_slowu);
     fr(d->d_shf2); fr(d->d_shu2); fr(d->d_order_sh); fr(d->d_seg_sh); fr(d->d_cnt_sh);
     if (d->ev_shade) (void)hipEventDestroy(d->ev_shade);
     for (int k = 0; k < 2; k++) if (d->ev_shadow[k]) (void)hipEventDestroy(d->ev_shadow[k]);
@@ -2142,12 +2274,10 @@ static int RunGather(DeviceState *D, const Sink &sink, uint32_t q0, uint32_t cnt
 }
 
 
-// Renders owned pixels [q_begin, q_end) of this rank; samples_out (device) receives the per-sample buffer
-// of the region when requested (parity tests); d_variance (W*H*3, like d_radiance) the variance of every owned pixel's mean.
-static int RenderRange(bhrt_scene *scene, const bhrt_opts &o, uint8_t *d_rgb8, float *d_radiance, bhrt_stats *st, float *d_region_samples, int x0,
-                       int y0, int x1, int y1, float *d_variance = nullptr)
+// The frame's constants of every pass (PassInfo without its pixels and samples) and the number of owned pixels of this rank (edge-tile
+// pixels outside the image included); checks the options.
+static int FramePassInfo(bhrt_scene *scene, const bhrt_opts &o, PassInfo &P, uint64_t &owned_pixels)
 {
-    DeviceState *D = scene->dev;
     const bhrt_flat_header *H = scene->flat.hdr();
     const int W = H->camera.width, Hh = H->camera.height;
     const int tile = o.tile_size > 0 ? o.tile_size : 32;
@@ -2156,9 +2286,10 @@ static int RenderRange(bhrt_scene *scene, const bhrt_opts &o, uint8_t *d_rgb8, f
     if (o.spp <= 0 || o.spp > 65535) { SetError("spp must be in 1..65535"); return BHRT_ERR_ARG; }
     if (o.internal_bounces < 0 || o.internal_bounces > 255 || o.gi_bounces < -1 || o.gi_bounces > 60) { SetError("bounce counts out of range"); return BHRT_ERR_ARG; }
     if (H->n_materials > 4095 || H->n_lights > 255) { SetError("too many materials/lights for the frame record"); return BHRT_ERR_UNSUPPORTED; }
-    PassInfo P;
+    P = PassInfo();
     P.W = W; P.H = Hh; P.tile = tile; P.tiles_x = (W + tile - 1) / tile; P.tiles_y = (Hh + tile - 1) / tile;
     P.rank = o.rank; P.world = world; P.spp = o.spp; P.seed = o.seed; P.jitter = o.jitter; P.gamma = o.gamma;
+    P.list = nullptr; P.s0 = 0;
     P.by_spp = MakeFastDiv((uint32_t)o.spp); P.by_tile_px = MakeFastDiv((uint32_t)(tile * tile)); P.by_tiles_x = MakeFastDiv((uint32_t)P.tiles_x);
     P.by_tile = MakeFastDiv((uint32_t)tile);
     {
@@ -2169,7 +2300,23 @@ static int RenderRange(bhrt_scene *scene, const bhrt_opts &o, uint8_t *d_rgb8, f
     }
     const uint32_t n_tiles = (uint32_t)(P.tiles_x * P.tiles_y);
     const uint32_t owned_tiles = n_tiles > (uint32_t)o.rank ? (n_tiles - (uint32_t)o.rank + (uint32_t)world - 1) / (uint32_t)world : 0;
-    const uint64_t owned_pixels = (uint64_t)owned_tiles * tile * tile;
+    owned_pixels = (uint64_t)owned_tiles * tile * tile;
+    return BHRT_OK;
+}
+
+// Renders samples [s0, s0 + spp) of n_items owned pixels of this rank: the range [0, n_items) of owned-pixel indices (d_list == nullptr) or
+// the entries of the device list d_list (an adaptive round), in passes.  Pass sizing, the halve-and-redo of a pass that overflows, the photon
+// gather per pass, the slow queue and the any-hit overlap are the same for both.  consume(P, npx) launches, on D->stream, what reads a finished
+// pass's sample-major buffer D->d_samples: k_resolve / k_variance / k_copy_samples for a uniform render (RenderRange), k_adapt_fold for an
+// adaptive round (RenderAdaptive).  The caller synchronises and flushes the timers.
+template <class Consume>
+static int RenderPixels(bhrt_scene *scene, const bhrt_opts &o, PassInfo P, const uint32_t *d_list, uint64_t n_items, uint32_t s0, uint32_t spp, bhrt_stats *st,
+                        const Consume &consume)
+{
+    DeviceState *D = scene->dev;
+    const bhrt_flat_header *H = scene->flat.hdr();
+    const int tile = P.tile, world = P.world;
+    P.spp = (int32_t)spp; P.by_spp = MakeFastDiv(spp); P.s0 = s0;
 
     // Sized for 288 GB of HBM: few, large passes (every pass ends in a tail of nearly empty wavefront steps, and the big launches of a pass's
     // first steps run the denser the more rays they hold: ONE pass of 1.3e8 samples instead of two of 6.6e7 takes 7-9 % off the C3 and closed-room
@@ -2178,18 +2325,18 @@ static int RenderRange(bhrt_scene *scene, const bhrt_opts &o, uint8_t *d_rgb8, f
     // Shade() frames per sample slot: six are provided for (an overflow halves the pass and redoes it).  A frame that does not fit into one pass
     // with six — C4's 2.7e8 samples per GPU — takes what the earlier passes of the same render (scene, options) have needed, + 30 %: C4 needs 1.1
     // frames per sample, and with 1.7 provided its 2^28 slots fit into 180 GB: one pass per frame instead of two.
-    const uint64_t frames_key = ((uint64_t)(uint32_t)o.spp << 48) ^ ((uint64_t)(uint32_t)(o.gi_bounces + 1) << 40) ^ ((uint64_t)(uint32_t)o.internal_bounces << 32) ^
+    const uint64_t frames_key = ((uint64_t)spp << 48) ^ ((uint64_t)(uint32_t)(o.gi_bounces + 1) << 40) ^ ((uint64_t)(uint32_t)o.internal_bounces << 32) ^
                                 ((uint64_t)(uint32_t)world << 24) ^ ((uint64_t)(uint32_t)tile << 8) ^ (uint64_t)(o.photon_map ? 1 : 0);
     double frames_per_sample = 6.0;
     bool frames_learned = false;
     if (o.samples_per_pass <= 0 && D->frames_seen_key == frames_key && D->frames_seen > 0 && D->frames_seen < 4.0 &&
-        owned_pixels * (uint64_t)o.spp > DefaultPassSamples(D, o.photon_map != 0, 6.0)) {
+        n_items * (uint64_t)spp > DefaultPassSamples(D, o.photon_map != 0, 6.0)) {
         frames_per_sample = std::min(6.0, D->frames_seen * 1.3 + 0.25);
         frames_learned = true;
     }
     uint32_t pass_samples = o.samples_per_pass > 0 ? (uint32_t)o.samples_per_pass : DefaultPassSamples(D, o.photon_map != 0, frames_per_sample);
-    pass_samples = (uint32_t)std::min<uint64_t>(pass_samples, std::max<uint64_t>(owned_pixels * (uint64_t)o.spp, 1)); // never more than this render needs
-    if (pass_samples < (uint32_t)o.spp) pass_samples = (uint32_t)o.spp;
+    pass_samples = (uint32_t)std::min<uint64_t>(pass_samples, std::max<uint64_t>(n_items * (uint64_t)spp, 1)); // never more than this render needs
+    if (pass_samples < spp) pass_samples = spp;
     D->timers = o.timers;
     D->photon_exact = o.photon_exact;
     const bool ls = o.leaf_skip != 0; // the walks' instantiations with device_trace.h::leaf_skip compiled in
@@ -2209,10 +2356,10 @@ static int RenderRange(bhrt_scene *scene, const bhrt_opts &o, uint8_t *d_rgb8, f
 
     uint64_t q = 0;
     uint32_t pass_limit = 0; // samples actually put in flight per pass (<= buffer capacity)
-    const uint64_t hint_key = ((uint64_t)(uint32_t)o.spp << 48) ^ ((uint64_t)(uint32_t)(o.gi_bounces + 1) << 40) ^ ((uint64_t)(uint32_t)o.internal_bounces << 32) ^
+    const uint64_t hint_key = ((uint64_t)spp << 48) ^ ((uint64_t)(uint32_t)(o.gi_bounces + 1) << 40) ^ ((uint64_t)(uint32_t)o.internal_bounces << 32) ^
                               ((uint64_t)(uint32_t)world << 24) ^ ((uint64_t)(uint32_t)tile << 8) ^ (uint64_t)(o.photon_map ? 1 : 0) ^ ((uint64_t)pass_samples << 1);
     if (D->pass_hint_key == hint_key && D->pass_hint) pass_limit = D->pass_hint;
-    while (q < owned_pixels) {
+    while (q < n_items) {
         int rc = EnsureWorkspace(D, pass_samples, frames_per_sample);
         if (rc) return rc;
         R.cap_rays = D->cap_rays; R.cap_shadow = D->cap_rays; R.cap_frames = D->cap_frames;
@@ -2227,9 +2374,10 @@ static int RenderRange(bhrt_scene *scene, const bhrt_opts &o, uint8_t *d_rgb8, f
         }
         if (pass_limit == 0) pass_limit = pass_samples;
         if (pass_limit > D->cap_samples) pass_limit = D->cap_samples;
-        const uint32_t px_per_pass = pass_limit / (uint32_t)o.spp;
-        const uint32_t npx = (uint32_t)std::min<uint64_t>(px_per_pass, owned_pixels - q);
-        P.q0 = (uint32_t)q; P.n_pixels = npx;
+        const uint32_t px_per_pass = pass_limit / spp;
+        const uint32_t npx = (uint32_t)std::min<uint64_t>(px_per_pass, n_items - q);
+        if (d_list) { P.list = d_list + q; P.q0 = 0; } else P.q0 = (uint32_t)q;
+        P.n_pixels = npx;
         RayQueue Q[2] = {MakeRayQueue(D->d_rayf[0], D->d_rayu[0], D->cap_rays), MakeRayQueue(D->d_rayf[1], D->d_rayu[1], D->cap_rays)};
         HitBuf HB; HB.t = D->d_hitf; HB.node = D->d_hiti; HB.prim = D->d_hiti + D->cap_rays; HB.front = D->d_hiti + 2 * (size_t)D->cap_rays;
         ShadowQueue SQ; { float *p = D->d_shf; const size_t c = D->cap_rays; SQ.ox = p; SQ.oy = p + c; SQ.oz = p + 2 * c; SQ.dx = p + 3 * c; SQ.dy = p + 4 * c; SQ.dz = p + 5 * c; SQ.tmax = p + 6 * c; SQ.frame = D->d_shu; }
@@ -2247,7 +2395,7 @@ static int RenderRange(bhrt_scene *scene, const bhrt_opts &o, uint8_t *d_rgb8, f
         HIP_CHECK(hipMemsetAsync(D->d_cnt, 0, sizeof(Counters), D->stream));
         // d_samples needs no clearing: every slot of a valid pixel is written exactly once (k_shade: background of a camera
         // miss; k_combine: root frame), and k_resolve never reads the slots of edge-tile pixels outside the image
-        const uint32_t total = npx * (uint32_t)o.spp;
+        const uint32_t total = npx * spp;
         uint32_t n_cur = total; // first wave step: one slot per (pixel, sample); the kernels compute the camera rays themselves
         bool first_step = true;
         int cur = 0;
@@ -2418,8 +2566,8 @@ static int RenderRange(bhrt_scene *scene, const bhrt_opts &o, uint8_t *d_rgb8, f
             FlushTimers(D);
             if (hc.overflow) { overflow = true; break; }
             if (first_step) { // camera step: dead rays of edge tiles are not rays
-                const uint64_t valid_px = CountValidPixels(P, npx);
-                pass_closest = valid_px * (uint64_t)o.spp;
+                const uint64_t valid_px = d_list ? npx : CountValidPixels(P, npx); // a list holds pixels inside the image only
+                pass_closest = valid_px * (uint64_t)spp;
                 pass_camera = pass_closest;
                 first_step = false;
             } else if (!injected) pass_closest += n_cur;
@@ -2450,8 +2598,8 @@ static int RenderRange(bhrt_scene *scene, const bhrt_opts &o, uint8_t *d_rgb8, f
         if (overflow) {
             // a capacity was exceeded: redo this pass with half the pixels in the same buffers
             // (results do not depend on the pass size: every sample has its own RNG key)
-            if (pass_limit <= (uint32_t)o.spp) { SetError("wavefront buffers overflow even with one pixel per pass"); return BHRT_ERR_OVERFLOW; }
-            pass_limit = std::max<uint32_t>((uint32_t)o.spp, pass_limit / 2);
+            if (pass_limit <= spp) { SetError("wavefront buffers overflow even with one pixel per pass"); return BHRT_ERR_OVERFLOW; }
+            pass_limit = std::max<uint32_t>(spp, pass_limit / 2);
             D->pass_hint_key = hint_key; D->pass_hint = pass_limit;
             if (frames_learned) D->frames_seen = 6.0; // the smaller frame pool was not enough after all: the next render of this kind provides six again
             continue;
@@ -2473,7 +2621,7 @@ static int RenderRange(bhrt_scene *scene, const bhrt_opts &o, uint8_t *d_rgb8, f
 #endif
         st->camera_samples += pass_camera; st->shadow_rays += pass_shadow; st->wave_iterations += pass_steps; st->deferred_rays += pass_deferred;
         { // what this pass needed of its frame pool, per sample slot
-            const double seen = (double)frame_marks.back() / (double)std::max<uint64_t>((uint64_t)npx * (uint64_t)o.spp, 1);
+            const double seen = (double)frame_marks.back() / (double)std::max<uint64_t>((uint64_t)npx * (uint64_t)spp, 1);
             if (D->frames_seen_key != frames_key) { D->frames_seen_key = frames_key; D->frames_seen = 0; }
             D->frames_seen = std::max(D->frames_seen, seen);
         }
@@ -2495,15 +2643,84 @@ static int RenderRange(bhrt_scene *scene, const bhrt_opts &o, uint8_t *d_rgb8, f
                 const uint32_t f0 = frame_marks[k - 1], f1 = frame_marks[k];
                 if (f1 > f0) hipLaunchKernelGGL(k_combine, dim3((f1 - f0 + kBlock - 1) / kBlock), dim3(kBlock), 0, D->stream, D->S, P, F, f0, f1, D->d_samples, o.photon_map);
             }
-            hipLaunchKernelGGL(k_resolve, dim3((npx + kBlock - 1) / kBlock), dim3(kBlock), 0, D->stream, P, D->d_samples, d_radiance, d_rgb8);
-            if (d_variance) hipLaunchKernelGGL(k_variance, dim3((npx + kBlock - 1) / kBlock), dim3(kBlock), 0, D->stream, P, D->d_samples, d_variance);
-            if (d_region_samples)
-                hipLaunchKernelGGL(k_copy_samples, dim3((npx + kBlock - 1) / kBlock), dim3(kBlock), 0, D->stream, P, D->d_samples, x0, y0, x1, y1, d_region_samples);
+            consume(P, npx);
             t.Stop();
         }
         HIP_CHECK(hipGetLastError());
         st->passes++;
         q += npx;
+    }
+    return BHRT_OK;
+}
+
+// Renders owned pixels [q_begin, q_end) of this rank; samples_out (device) receives the per-sample buffer
+// of the region when requested (parity tests); d_variance (W*H*3, like d_radiance) the variance of every owned pixel's mean.
+static int RenderRange(bhrt_scene *scene, const bhrt_opts &o, uint8_t *d_rgb8, float *d_radiance, bhrt_stats *st, float *d_region_samples, int x0,
+                       int y0, int x1, int y1, float *d_variance = nullptr)
+{
+    DeviceState *D = scene->dev;
+    PassInfo P;
+    uint64_t owned_pixels = 0;
+    int rc = FramePassInfo(scene, o, P, owned_pixels);
+    if (rc) return rc;
+    const auto wall0 = std::chrono::steady_clock::now();
+    rc = RenderPixels(scene, o, P, nullptr, owned_pixels, 0, (uint32_t)o.spp, st, [&](const PassInfo &Pp, uint32_t npx) {
+        hipLaunchKernelGGL(k_resolve, dim3((npx + kBlock - 1) / kBlock), dim3(kBlock), 0, D->stream, Pp, D->d_samples, d_radiance, d_rgb8);
+        if (d_variance) hipLaunchKernelGGL(k_variance, dim3((npx + kBlock - 1) / kBlock), dim3(kBlock), 0, D->stream, Pp, D->d_samples, d_variance);
+        if (d_region_samples)
+            hipLaunchKernelGGL(k_copy_samples, dim3((npx + kBlock - 1) / kBlock), dim3(kBlock), 0, D->stream, Pp, D->d_samples, x0, y0, x1, y1, d_region_samples);
+    });
+    if (rc) return rc;
+    HIP_CHECK(hipStreamSynchronize(D->stream));
+    FlushTimers(D, true);
+    st->seconds_total += std::chrono::duration<double>(std::chrono::steady_clock::now() - wall0).count();
+    return BHRT_OK;
+}
+
+// The adaptive render: rounds of RenderPixels over the pixels still active, each pass folded by k_adapt_fold.  The host reads
+// the next list's length once per round (4 bytes).  Options checked by the caller (AdaptiveArgsError).
+static int RenderAdaptive(bhrt_scene *scene, const bhrt_opts &o, const bhrt_adaptive_opts &ao, uint8_t *d_rgb8, float *d_radiance, float *d_variance,
+                          uint32_t *d_count, bhrt_stats *st)
+{
+    DeviceState *D = scene->dev;
+    PassInfo P;
+    uint64_t owned_pixels = 0;
+    int rc = FramePassInfo(scene, o, P, owned_pixels);
+    if (rc) return rc;
+    if (owned_pixels > 0xffffffffull) { SetError("adaptive render: more than 2^32 owned pixels"); return BHRT_ERR_ARG; }
+    if (D->ad_px < owned_pixels) {
+        if (D->d_ad) HIP_CHECK(hipFree(D->d_ad));
+        D->d_ad = nullptr; D->ad_px = 0;
+        HIP_CHECK(hipMalloc(&D->d_ad, (size_t)owned_pixels * 44 + 16));
+        D->ad_px = (size_t)owned_pixels;
+    }
+    const size_t N = D->ad_px;
+    AdaptState A;
+    A.a = (float4 *)D->d_ad; A.b = A.a + N; A.c = (float *)(A.b + N);
+    uint32_t *lists[2] = {(uint32_t *)(A.c + N), (uint32_t *)(A.c + N) + N};
+    AdaptParams R;
+    R.n_max = (uint32_t)o.spp; R.threshold = ao.threshold; R.floor = ao.floor;
+    R.radiance = d_radiance; R.variance = d_variance; R.rgb8 = d_rgb8; R.count = d_count;
+    R.n_next = lists[1] + N;
+    const auto wall0 = std::chrono::steady_clock::now();
+    uint32_t n_prev = 0, n = (uint32_t)ao.min_spp;
+    uint64_t items = owned_pixels;
+    const uint32_t *list = nullptr; // round 0: the contiguous range
+    for (int cur = 0; items > 0; cur ^= 1) {
+        R.next = lists[cur];
+        HIP_CHECK(hipMemsetAsync(R.n_next, 0, sizeof(uint32_t), D->stream));
+        rc = RenderPixels(scene, o, P, list, items, n_prev, n - n_prev, st, [&](const PassInfo &Pp, uint32_t npx) {
+            hipLaunchKernelGGL(k_adapt_fold, dim3((npx + kBlock - 1) / kBlock), dim3(kBlock), 0, D->stream, Pp, D->d_samples, A, R);
+        });
+        if (rc) return rc;
+        uint32_t active = 0;
+        HIP_CHECK(hipMemcpyAsync(&active, R.n_next, sizeof active, hipMemcpyDeviceToHost, D->stream));
+        HIP_CHECK(hipStreamSynchronize(D->stream));
+        if (n >= (uint32_t)o.spp && active) { SetError("adaptive render: pixels active after the last round"); return BHRT_ERR_HIP; }
+        items = active;
+        list = lists[cur];
+        n_prev = n;
+        n = (uint32_t)std::min<uint64_t>((uint64_t)o.spp, 2ull * n);
     }
     HIP_CHECK(hipStreamSynchronize(D->stream));
     FlushTimers(D, true);
@@ -2802,6 +3019,121 @@ try {
     if (variance) HIP_CHECK(hipMemcpyAsync(variance, D->d_frame_var, npix * 12, hipMemcpyDeviceToHost, D->stream));
     HIP_CHECK(hipStreamSynchronize(D->stream));
     return BHRT_OK;
+} catch (...) { return bhrt::AbiException(); }
+
+// ---- adaptive sampling (RenderAdaptive) -----------------------------------------------------------------
+// checked before any device is touched; "" = valid
+static const char *AdaptiveArgsError(const bhrt_opts *o, const bhrt_adaptive_opts *a)
+{
+    if (!o || !a) return "adaptive render: null opts";
+    if (a->min_spp < 2) return "adaptive render: min_spp must be >= 2";
+    if (o->spp > 65535) return "adaptive render: spp (the per-pixel maximum) must be <= 65535";
+    if (a->min_spp > o->spp) return "adaptive render: min_spp must be <= spp (the per-pixel maximum)";
+    if (!(a->floor > 0.f)) return "adaptive render: floor must be > 0";
+    if (a->threshold != a->threshold) return "adaptive render: threshold is NaN";
+    return "";
+}
+
+int bhrt_render_adaptive_dev(bhrt_scene *scene, const bhrt_opts *opts, const bhrt_adaptive_opts *aopts, uint8_t *d_rgb8, float *d_radiance, float *d_variance,
+                             uint32_t *d_count, bhrt_stats *stats, void *stream)
+try {
+    (void)stream; // the render pipeline synchronises its own stream per wave step
+    const char *bad = AdaptiveArgsError(opts, aopts);
+    if (*bad) { SetError(bad); return BHRT_ERR_ARG; }
+    int rc = EnsureUploaded(scene);
+    if (rc) return rc;
+    if (opts->photon_map && !scene->dev->d_photons) { SetError("photon_map = 1 needs bhrt_photon_build first"); return BHRT_ERR_ARG; }
+    bhrt_stats local;
+    memset(&local, 0, sizeof local);
+    rc = RenderAdaptive(scene, *opts, *aopts, d_rgb8, d_radiance, d_variance, d_count, &local);
+    if (stats) *stats = local;
+    return rc;
+} catch (...) { return bhrt::AbiException(); }
+
+int bhrt_render_adaptive(bhrt_scene *scene, const bhrt_opts *opts, const bhrt_adaptive_opts *aopts, uint8_t *rgb8, float *radiance, float *variance,
+                         uint32_t *count, bhrt_stats *stats)
+try {
+    const char *bad = AdaptiveArgsError(opts, aopts);
+    if (*bad) { SetError(bad); return BHRT_ERR_ARG; }
+    int rc = EnsureUploaded(scene);
+    if (rc) return rc;
+    DeviceState *D = scene->dev;
+    const bhrt_flat_header *H = scene->flat.hdr();
+    const size_t npix = (size_t)H->camera.width * H->camera.height;
+    // the device copies of bhrt_render_var, and one of the count image
+    if (D->frame_px < npix) {
+        if (D->d_frame_rgb) (void)hipFree(D->d_frame_rgb);
+        if (D->d_frame_rad) (void)hipFree(D->d_frame_rad);
+        D->d_frame_rgb = nullptr; D->d_frame_rad = nullptr; D->frame_px = 0;
+        HIP_CHECK(hipMalloc(&D->d_frame_rgb, npix * 3));
+        HIP_CHECK(hipMalloc(&D->d_frame_rad, npix * 3 * sizeof(float)));
+        D->frame_px = npix;
+    }
+    if (variance && D->frame_var_px < npix) {
+        if (D->d_frame_var) (void)hipFree(D->d_frame_var);
+        D->d_frame_var = nullptr; D->frame_var_px = 0;
+        HIP_CHECK(hipMalloc(&D->d_frame_var, npix * 3 * sizeof(float)));
+        D->frame_var_px = npix;
+    }
+    if (count && D->frame_cnt_px < npix) {
+        if (D->d_frame_cnt) (void)hipFree(D->d_frame_cnt);
+        D->d_frame_cnt = nullptr; D->frame_cnt_px = 0;
+        HIP_CHECK(hipMalloc(&D->d_frame_cnt, npix * sizeof(uint32_t)));
+        D->frame_cnt_px = npix;
+    }
+    if (opts->world_size > 1) { // pixels of tiles owned by other ranks keep the caller's values
+        if (rgb8) HIP_CHECK(hipMemcpyAsync(D->d_frame_rgb, rgb8, npix * 3, hipMemcpyHostToDevice, D->stream));
+        if (radiance) HIP_CHECK(hipMemcpyAsync(D->d_frame_rad, radiance, npix * 12, hipMemcpyHostToDevice, D->stream));
+        if (variance) HIP_CHECK(hipMemcpyAsync(D->d_frame_var, variance, npix * 12, hipMemcpyHostToDevice, D->stream));
+        if (count) HIP_CHECK(hipMemcpyAsync(D->d_frame_cnt, count, npix * 4, hipMemcpyHostToDevice, D->stream));
+    }
+    rc = bhrt_render_adaptive_dev(scene, opts, aopts, rgb8 ? D->d_frame_rgb : nullptr, radiance ? D->d_frame_rad : nullptr, variance ? D->d_frame_var : nullptr,
+                                  count ? D->d_frame_cnt : nullptr, stats, nullptr);
+    if (rc) return rc;
+    if (rgb8) HIP_CHECK(hipMemcpyAsync(rgb8, D->d_frame_rgb, npix * 3, hipMemcpyDeviceToHost, D->stream));
+    if (radiance) HIP_CHECK(hipMemcpyAsync(radiance, D->d_frame_rad, npix * 12, hipMemcpyDeviceToHost, D->stream));
+    if (variance) HIP_CHECK(hipMemcpyAsync(variance, D->d_frame_var, npix * 12, hipMemcpyDeviceToHost, D->stream));
+    if (count) HIP_CHECK(hipMemcpyAsync(count, D->d_frame_cnt, npix * 4, hipMemcpyDeviceToHost, D->stream));
+    HIP_CHECK(hipStreamSynchronize(D->stream));
+    return BHRT_OK;
+} catch (...) { return bhrt::AbiException(); }
+
+int bhrt_sample_count_image_dev(bhrt_scene *scene, const uint32_t *d_count, size_t n, uint8_t *d_img, uint32_t *smax, void *stream)
+try {
+    if (!d_count || !d_img || n == 0 || n > 0xffffffffull) { SetError("bad sample-count image arguments"); return BHRT_ERR_ARG; }
+    int rc = EnsureUploaded(scene);
+    if (rc) return rc;
+    DeviceState *D = scene->dev;
+    rc = EnsureApiScratch(D, 16);
+    if (rc) return rc;
+    hipStream_t st = stream ? (hipStream_t)stream : D->stream;
+    uint32_t *range = (uint32_t *)D->d_api_f;
+    hipLaunchKernelGGL(k_count_range, dim3(1), dim3(1024), 0, st, d_count, (uint32_t)n, range);
+    hipLaunchKernelGGL(k_count_image, dim3(((uint32_t)n + kBlock - 1) / kBlock), dim3(kBlock), 0, st, d_count, (uint32_t)n, (const uint32_t *)range, d_img);
+    HIP_CHECK(hipGetLastError());
+    uint32_t r[2] = {0, 0};
+    HIP_CHECK(hipMemcpyAsync(r, range, sizeof r, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st)); // the range scratch is shared with the other API calls
+    if (smax) *smax = r[1];
+    return BHRT_OK;
+} catch (...) { return bhrt::AbiException(); }
+
+int bhrt_sample_count_image(bhrt_scene *scene, const uint32_t *count, size_t n, uint8_t *img, uint32_t *smax)
+try {
+    if (!count || !img || n == 0 || n > 0xffffffffull) { SetError("bad sample-count image arguments"); return BHRT_ERR_ARG; }
+    int rc = EnsureUploaded(scene);
+    if (rc) return rc;
+    uint32_t *d_c = nullptr;
+    HIP_CHECK(hipMalloc(&d_c, n * (sizeof(uint32_t) + 1)));
+    uint8_t *d_i = (uint8_t *)(d_c + n);
+    hipError_t e = hipMemcpy(d_c, count, n * sizeof(uint32_t), hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        rc = bhrt_sample_count_image_dev(scene, d_c, n, d_i, smax, nullptr);
+        if (rc == BHRT_OK) e = hipMemcpy(img, d_i, n, hipMemcpyDeviceToHost);
+    }
+    (void)hipFree(d_c);
+    HIP_CHECK(e);
+    return rc;
 } catch (...) { return bhrt::AbiException(); }
 
 // pinned host memory for frame buffers handed to bhrt_render (and anything else that crosses PCIe)

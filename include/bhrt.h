@@ -258,6 +258,43 @@ int bhrt_denoise_dev(bhrt_scene *scene, const bhrt_denoise_opts *opts, const flo
 int bhrt_denoise(bhrt_scene *scene, const bhrt_denoise_opts *opts, const float *radiance, const float *variance, const float *z, const float *normal,
                  const float *albedo, float *out, uint8_t *rgb8);
 
+/* ---- adaptive sampling: RenderImage's per-pixel sample counts (Scenes/scene.h:534,570), which BeginRender only ever sets to 0
+ * (Main.cpp:214), filled by a render that stops sampling a pixel once its mean is good enough ------------------------
+ * Rounds: round 0 gives every owned pixel samples [0, min_spp); round r >= 1 gives every pixel still active samples [n_{r-1}, n_r),
+ * n_r = min(max_spp, 2 n_{r-1}), max_spp = bhrt_opts.spp: ceil(log2(max / min)) + 1 rounds at most.  Every sample has the RNG key of
+ * bhrt_render's (seed, pixel, sample index), so a pixel's outputs are bit-identical to bhrt_render_var's at that pixel's count.
+ * A pixel keeps, in float32 and in sample order, the running sum S (mean = S / (float)n, bhrt_render's operations) and a Welford
+ * recurrence per channel (d = x - mu; mu += d / k; M2 += d (x - mu), k = 1..n).  After each round it takes part in:
+ *   v_c = (M2_c / (n - 1)) / n      (variance of the mean, per channel)
+ *   L   = (0.2126 m_r + 0.7152 m_g) + 0.0722 m_b,   vL = (0.2126^2 v_r + 0.7152^2 v_g) + 0.0722^2 v_b
+ *   the pixel retires when n == max_spp or sqrt(vL) <= threshold * max(L, floor).
+ * The test reads the pixel's own samples only: results do not depend on rank, world size, tile size or pass size.  A retiring pixel
+ * writes its radiance, RGB8 bytes (bhrt_opts.gamma as bhrt_render), variance (laid out like bhrt_render_var's) and count n once;
+ * pixels of other ranks' tiles are left untouched.  Ranks may finish unevenly: adaptive work is not rebalanced between them. */
+typedef struct bhrt_adaptive_opts {
+    int32_t min_spp;  /* samples of round 0, >= 2; bhrt_opts.spp is the per-pixel maximum (<= 65535); default 16 */
+    float threshold;  /* relative standard error of the mean's luminance; < 0 = never retire early (every pixel reaches spp), +inf = every
+                       * pixel retires at min_spp; default: DESIGN.md 10 */
+    float floor;      /* luminance below which the error is taken relative to `floor` (> 0); default: DESIGN.md 10 */
+    int32_t reserved[5];
+} bhrt_adaptive_opts;
+void bhrt_default_adaptive_opts(bhrt_adaptive_opts *a);
+/* The arguments are checked before any device is touched: 2 <= min_spp <= spp <= 65535, floor > 0, threshold not NaN, else BHRT_ERR_ARG.
+ * rgb8 / radiance / variance: as bhrt_render_var's (each may be NULL); count: W*H uint32 samples per pixel (may be NULL).
+ * stats->camera_samples = the sum of the counts of the owned pixels inside the image.  _dev: device pointers (the render synchronises its
+ * own stream); the state of the rounds (44 B per owned pixel) belongs to the scene. */
+int bhrt_render_adaptive_dev(bhrt_scene *scene, const bhrt_opts *opts, const bhrt_adaptive_opts *aopts, uint8_t *d_rgb8, float *d_radiance, float *d_variance,
+                             uint32_t *d_count, bhrt_stats *stats, void *stream);
+int bhrt_render_adaptive(bhrt_scene *scene, const bhrt_opts *opts, const bhrt_adaptive_opts *aopts, uint8_t *rgb8, float *radiance, float *variance,
+                         uint32_t *count, bhrt_stats *stats);
+/* RenderImage::ComputeSampleCountImage (scene.h:603-626): smin / smax over the n counts, img = (255 (s - smin)) / (smax - smin) in integers,
+ * clamped to 0..255, 0 everywhere when smax == smin; *smax (a host pointer, may be NULL) = smax, the function's return value there.
+ * _dev: device count and image, synchronises (the range scratch is shared with the other API calls); the other: host pointers. */
+int bhrt_sample_count_image_dev(bhrt_scene *scene, const uint32_t *d_count, size_t n, uint8_t *d_img, uint32_t *smax, void *stream);
+int bhrt_sample_count_image(bhrt_scene *scene, const uint32_t *count, size_t n, uint8_t *img, uint32_t *smax);
+/* RenderImage::SaveSampleCountImage (scene.h:630): an 8-bit one-channel PNG of w x h bytes */
+int bhrt_save_png_gray(const char *path, const uint8_t *gray, int width, int height);
+
 /* ---- test hook: csrc/bhrt_detmath.h evaluated on the device, to prove host and device produce the same bits.
  * fn: 0 sin 1 cos 2 tan 3 acos 4 asin 5 atan2(a,b) 6 pow(a,b) 7 rand_to_unit(bits of a) 8 a/b 9 sqrt(a); host pointers */
 int bhrt_math_eval_dev(int fn, const float *a, const float *b, size_t n, float *out);
