@@ -1,0 +1,202 @@
+// device_state.h — what a scene owns on its device: memory, streams, events, the installed photon map.
+// Part of the kernels.hip translation unit, included there behind the kernels (it uses their argument types and HIP_CHECK); not a header for
+// other files: they see `struct DeviceState;` (scene_internal.h) and DestroyDeviceState.
+#pragma once
+
+namespace bhrt {
+
+// Device memory owned by its holder; grow-only.  n: capacity in elements.
+template <class T> struct DevBuf {
+    T *p = nullptr;
+    size_t n = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    DevBuf(DevBuf &&o) noexcept : p(o.p), n(o.n) { o.p = nullptr; o.n = 0; }
+    DevBuf &operator=(DevBuf &&o) noexcept
+    {
+        if (this != &o) { Free(); p = o.p; n = o.n; o.p = nullptr; o.n = 0; }
+        return *this;
+    }
+    ~DevBuf() { Free(); }
+    // n >= want: nothing.  Otherwise the old memory is freed FIRST and the contents are not kept; a failed allocation leaves an empty buffer with
+    // capacity 0, so the next call tries again.  (hipFree waits for the device: kernels of an earlier call may still read the old memory.)
+    int Reserve(size_t want)
+    {
+        if (n >= want) return BHRT_OK;
+        Free();
+        HIP_CHECK(hipMalloc(&p, want * sizeof(T)));
+        n = want;
+        return BHRT_OK;
+    }
+    void Free()
+    {
+        if (p) (void)hipFree(p);
+        p = nullptr; n = 0;
+    }
+    T *Release() // hands the memory to the caller
+    {
+        T *r = p;
+        p = nullptr; n = 0;
+        return r;
+    }
+    operator T *() const { return p; }
+    T *operator->() const { return p; }
+};
+
+// The pinned-host twin (one allocation, never regrown).
+template <class T> struct PinnedBuf {
+    T *p = nullptr;
+    PinnedBuf() = default;
+    PinnedBuf(const PinnedBuf &) = delete;
+    PinnedBuf &operator=(const PinnedBuf &) = delete;
+    ~PinnedBuf() { if (p) (void)hipHostFree(p); }
+    int Alloc(size_t count, unsigned flags = hipHostMallocDefault)
+    {
+        HIP_CHECK(hipHostMalloc(&p, count * sizeof(T), flags));
+        return BHRT_OK;
+    }
+    operator T *() const { return p; }
+    T *operator->() const { return p; }
+};
+
+// Streams and events of a DeviceState.  A base class, so that it is destroyed AFTER the members of DeviceState: device memory is released
+// (hipFree waits for the device) before the streams go.
+struct DeviceQueues {
+    hipStream_t stream = nullptr;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    hipStream_t stream2 = nullptr;             // k_trace_slow runs here, beside the pass
+    std::vector<hipEvent_t> slow_events;       // one per k_trace_slow launch of a pass (its hits are in place)
+    hipStream_t stream3 = nullptr;             // any-hit work of a wave step beside the next step's closest-hit work (RenderPixels, knobs.shadow_overlap)
+    hipEvent_t ev_shade = nullptr, ev_shadow[2] = {nullptr, nullptr};
+    std::vector<hipEvent_t> ev_pool;           // Timer
+    DeviceQueues() = default;
+    DeviceQueues(const DeviceQueues &) = delete;
+    DeviceQueues &operator=(const DeviceQueues &) = delete;
+    ~DeviceQueues()
+    {
+        if (ev_shade) (void)hipEventDestroy(ev_shade);
+        for (int k = 0; k < 2; k++) if (ev_shadow[k]) (void)hipEventDestroy(ev_shadow[k]);
+        if (stream3) (void)hipStreamDestroy(stream3);
+        for (int k = 0; k < 2; k++) if (ev[k]) (void)hipEventDestroy(ev[k]);
+        for (hipEvent_t e : ev_pool) (void)hipEventDestroy(e);
+        for (hipEvent_t e : slow_events) (void)hipEventDestroy(e);
+        if (stream2) (void)hipStreamDestroy(stream2);
+        if (stream) (void)hipStreamDestroy(stream);
+    }
+};
+
+struct DeviceState : DeviceQueues {
+    int device = -1;
+    uint32_t n_cus = 256; // compute units of the device (hipDeviceProp_t::multiProcessorCount): sizes the grids of the resident-wave kernels
+    DevBuf<uint8_t> d_blob;
+    DevBuf<int32_t> d_chain;
+    DevBuf<float> d_aux; // mat_r0 + light_pick (DevScene)
+    DevScene S;
+    // wavefront workspace (EnsureWorkspace)
+    uint32_t cap_samples = 0, cap_rays = 0, cap_frames = 0;
+    DevBuf<float> d_rayf[2];                   // 6 * cap_rays floats each
+    DevBuf<uint32_t> d_rayu[2];                // 3 * cap_rays
+    DevBuf<float> d_hitf;                      // cap_rays
+    DevBuf<int32_t> d_hiti;                    // 3 * cap_rays
+    DevBuf<float> d_shf;                       // 7 * cap_rays
+    DevBuf<uint32_t> d_shu;                    // cap_rays
+    DevBuf<uint32_t> d_fu;                     // 4 * cap_frames
+    DevBuf<uint64_t> d_fcode;                  // cap_frames
+    DevBuf<float> d_ff;                        // (3*7 + 2) * cap_frames
+    DevBuf<float> d_samples;                   // 3 * cap_samples
+    DevBuf<uint32_t> d_order;                  // 4 * BHRT_ORDER_SHARDS * order_shard_cap (shading order, device_types.h::RayOrder)
+    uint32_t order_shard_cap = 0;
+    DevBuf<uint32_t> d_seg;                    // seg_start[97] + seg_count[96] + mesh_start[33] + mesh_count[33] + frame_base[96]
+    DevBuf<uint32_t> d_park;                   // park_key[cap_rays] + park_sorted[cap_rays] + park_rank[cap_rays] + buckets + tile sums (RayOrder)
+    DevBuf<float> d_slowf;                     // slow queue (SlowQueue): 6 * kSlowCap floats, then kSlowCap hit distances
+    DevBuf<uint32_t> d_slowu;                  // 3 * kSlowCap, then 3 * kSlowCap hit words (node, prim, front)
+    // the any-hit work beside the pass (stream3): the second shadow queue, its own parked list (the RC_MESH part of a RayOrder), segment table
+    // and counters
+    DevBuf<float> d_shf2;                      // 7 * cap_rays
+    DevBuf<uint32_t> d_shu2;                   // cap_rays
+    DevBuf<uint32_t> d_order_sh;               // BHRT_ORDER_SHARDS * order_shard_cap
+    DevBuf<uint32_t> d_seg_sh;                 // mesh_start[33] + mesh_count[33]
+    DevBuf<Counters> d_cnt_sh;
+    DevBuf<Counters> d_cnt;
+    PinnedBuf<HostCounters> h_pub; // device-visible: written by publish_counters
+    HostCounters *d_pub = nullptr; // the device's address of h_pub
+    uint32_t pub_seq = 0;
+    int timers = 0;                // bhrt_opts.timers of the running call
+    int photon_exact = 0;          // bhrt_opts.photon_exact of the running call
+    uint32_t *d_knn = nullptr;     // test hook of bhrt_photon_gather_host_ex (which owns the memory): the selection pass's photon lists
+    DevBuf<uint32_t> d_sel;        // candidate scratch of the selection pass's waves
+    struct PendingTimer { int e0, e1; double *acc; };
+    std::vector<PendingTimer> ev_pending;
+    std::vector<int> ev_free;                  // indices of ev_pool not in use
+    // caustic photon map (balanced, heap order, slot 0 unused) + gather scratch
+    DevBuf<DPhoton> d_photons;
+    uint32_t n_photons = 0;
+    std::vector<HostPhoton> h_photons; // balanced copy for bhrt_photon_export
+    DevBuf<float> d_ph_frames;         // 15 * cap_frames floats (p, N, V, kd, ks per frame), only with photon_map
+    DevBuf<float4> d_ph_hot, d_ph_cold, d_ph_dbox; // decoded copy the gather walks (PhotonMapDev)
+    PhotonMapDev pm;
+    DevBuf<unsigned long long> d_scr; // candidate heaps of the heavy queries: (K+1) x scr_lanes, element-major
+    uint32_t scr_lanes = 0;
+    uint32_t heavy_cap = 0;       // entries of each of the next six, and what d_sort_temp is sized for
+    DevBuf<uint32_t> d_heavy;     // queries that met 1000 photons in pass 1
+    DevBuf<uint32_t> d_long;      // queries whose walk outlasted the lane budget in pass 1
+    DevBuf<uint32_t> d_cell_of, d_gorder, d_rank_of, d_keys_out; // gather order (cell sort)
+    DevBuf<uint8_t> d_sort_temp;
+    size_t sort_temp_bytes = 0;
+    DevBuf<uint32_t> d_n_heavy;   // [0] heavy, [1] long, [2..3] nodes visited (64-bit), [4] selection rounds, [5] compactions, [8..11] lane pass: found, answered
+    PinnedBuf<uint32_t> h_n_heavy;
+    DevBuf<uint32_t> d_cells, d_tile_sums;
+    // Development switches, read from the environment ONCE, when the scene is uploaded (none changes a result), and the two test knobs, which
+    // no environment variable reaches: only bhrt_scene_knob sets them.
+    struct Knobs {
+        int stream_waves = -1;          // BHRT_STREAM_WAVES: resident waves of k_trace_mesh_stream; 0 = the launch-per-64-rays kernel; -1 = default
+        bool fused_camera = true;       // BHRT_FUSED_CAMERA=0: two-kernel camera step in mesh-free scenes
+        bool no_slow_queue = false;     // BHRT_NO_SLOW_QUEUE: axis-parallel rays stay in their wave steps
+        bool debug_slow = false, debug_gather = false, debug_drain = false; // BHRT_DEBUG_*: statistics on stderr
+        bool balance_host = false;      // BHRT_PHOTON_BALANCE_HOST: photon_host.cpp instead of k_pb_level (the tests' second opinion)
+        int frame_cap = 0;              // knob "frame_cap": a frame pool that overflows (the retry path under test); 0 = off
+        int gather_lane_budget = 0;     // knob "gather_lane_budget": photons a lane may visit before its query goes to the one-wave pass; 0 = default
+        bool gather_counting_sort = false; // BHRT_GATHER_COUNTING_SORT=1: the cell order by the counting sort instead of the radix sort of pairs
+        bool shadow_overlap = true;     // BHRT_SHADOW_OVERLAP=0: the any-hit kernels of a wave step on the pass's own stream, in front of the next step
+        int gather_stats = 0;           // knob "gather_stats": the lane pass counts the photons its answers are made of (bhrt_stats.photon_found), 7 % slower
+        void FromEnv()
+        {
+            if (const char *e = getenv("BHRT_STREAM_WAVES")) stream_waves = atoi(e);
+            if (const char *e = getenv("BHRT_FUSED_CAMERA")) fused_camera = atoi(e) != 0;
+            no_slow_queue = getenv("BHRT_NO_SLOW_QUEUE") != nullptr;
+            debug_slow = getenv("BHRT_DEBUG_SLOW") != nullptr; debug_gather = getenv("BHRT_DEBUG_GATHER") != nullptr; debug_drain = getenv("BHRT_DEBUG_DRAIN") != nullptr;
+            if (const char *e = getenv("BHRT_PHOTON_BALANCE_HOST")) balance_host = atoi(e) != 0;
+            if (const char *e = getenv("BHRT_GATHER_COUNTING_SORT")) gather_counting_sort = atoi(e) != 0;
+            if (const char *e = getenv("BHRT_SHADOW_OVERLAP")) shadow_overlap = atoi(e) != 0;
+        }
+    } knobs;
+    // a capacity overflow halves the pass (RenderPixels); later frames of the same scene and options start from the reduced size
+    uint64_t pass_hint_key = 0;
+    uint32_t pass_hint = 0;
+    uint64_t frames_seen_key = 0; // Shade() frames per sample slot the passes of a render (scene, options: the key) have needed so far (max)
+    double frames_seen = 0;
+    // bhrt_render / _var / _adaptive: the device copy of the frame, kept between calls (FrameStage); the variance and count images on first use
+    size_t frame_px = 0; // pixels of d_frame_rgb and d_frame_rad
+    DevBuf<uint8_t> d_frame_rgb;
+    DevBuf<float> d_frame_rad, d_frame_var;
+    DevBuf<uint32_t> d_frame_cnt;
+    // bhrt_render_adaptive_dev: the per-pixel state of the rounds (AdaptState: 36 B per owned pixel), two lists of owned-pixel indices (4 B each)
+    // and the next list's length; grown on demand
+    DevBuf<uint8_t> d_ad;
+    // bhrt_denoise_dev: the filter's planes (DenoisePlaneBytes), then the first-hit guides it computes itself; grown on demand
+    DevBuf<uint8_t> d_dn;
+    // scratch for the public trace API (EnsureApiScratch)
+    size_t api_cap = 0; // rays
+    DevBuf<float> d_api_f;   // 9 * api_cap
+    DevBuf<int32_t> d_api_i; // 3 * api_cap
+};
+
+void DestroyDeviceState(DeviceState *d)
+{
+    if (!d) return;
+    if (d->device >= 0) (void)hipSetDevice(d->device);
+    delete d; // the buffers, then (DeviceQueues) the events and streams
+}
+
+} // namespace bhrt

@@ -48,6 +48,12 @@ namespace bhrt {
             return BHRT_ERR_HIP;                                                                               \
         }                                                                                                      \
     } while (0)
+// the same for a call that returns a BHRT_* code (and has set the error text)
+#define BHRT_TRY(expr)                                                                                         \
+    do {                                                                                                       \
+        const int rc_ = (expr);                                                                                \
+        if (rc_) return rc_;                                                                                   \
+    } while (0)
 
 constexpr int kBlock = 256;
 
@@ -1816,148 +1822,9 @@ __global__ void __launch_bounds__(kBlock) k_tiles_unpack(const uint8_t *gathered
 // ================================================================================================
 // host side
 // ================================================================================================
-struct DeviceState {
-    int device = -1;
-    uint32_t n_cus = 256; // compute units of the device (hipDeviceProp_t::multiProcessorCount): sizes the grids of the resident-wave kernels
-    uint8_t *d_blob = nullptr;
-    int32_t *d_chain = nullptr;
-    float *d_aux = nullptr; // mat_r0 + light_pick (DevScene)
-    DevScene S;
-    // wavefront workspace
-    uint32_t cap_samples = 0, cap_rays = 0, cap_frames = 0;
-    float *d_rayf[2] = {nullptr, nullptr};     // 6 * cap_rays floats each
-    uint32_t *d_rayu[2] = {nullptr, nullptr};  // 3 * cap_rays
-    float *d_hitf = nullptr;                   // cap_rays
-    int32_t *d_hiti = nullptr;                 // 3 * cap_rays
-    float *d_shf = nullptr;                    // 7 * cap_rays
-    uint32_t *d_shu = nullptr;                 // cap_rays
-    uint32_t *d_fu = nullptr;                  // 4 * cap_frames
-    uint64_t *d_fcode = nullptr;               // cap_frames
-    float *d_ff = nullptr;                     // (3*7 + 2) * cap_frames
-    float *d_samples = nullptr;                // 3 * cap_samples
-    uint32_t *d_order = nullptr;               // 4 * BHRT_ORDER_SHARDS * order_shard_cap (shading order, device_types.h::RayOrder)
-    uint32_t order_shard_cap = 0;
-    uint32_t *d_seg = nullptr;                 // seg_start[97] + seg_count[96] + mesh_start[33] + mesh_count[33] + frame_base[96]
-    uint32_t *d_park = nullptr;                // park_key[cap_rays] + park_sorted[cap_rays] + park_rank[cap_rays] + buckets + tile sums (RayOrder)
-    float *d_slowf = nullptr;                  // slow queue (SlowQueue): 6 * kSlowCap floats, then kSlowCap hit distances
-    uint32_t *d_slowu = nullptr;               // 3 * kSlowCap, then 3 * kSlowCap hit words (node, prim, front)
-    hipStream_t stream2 = nullptr;             // k_trace_slow runs here, beside the pass
-    std::vector<hipEvent_t> slow_events;       // one per k_trace_slow launch of a pass (its hits are in place)
-    // any-hit work of a wave step beside the next step's closest-hit work (RenderRange, knobs.shadow_overlap): its own stream, the second shadow queue,
-    // its own parked list (the RC_MESH part of a RayOrder), segment table and counters
-    hipStream_t stream3 = nullptr;
-    float *d_shf2 = nullptr;                   // 7 * cap_rays
-    uint32_t *d_shu2 = nullptr;                // cap_rays
-    uint32_t *d_order_sh = nullptr;            // BHRT_ORDER_SHARDS * order_shard_cap
-    uint32_t *d_seg_sh = nullptr;              // mesh_start[33] + mesh_count[33]
-    Counters *d_cnt_sh = nullptr;
-    hipEvent_t ev_shade = nullptr, ev_shadow[2] = {nullptr, nullptr};
-    Counters *d_cnt = nullptr;
-    HostCounters *h_pub = nullptr; // pinned, device-visible: written by publish_counters
-    HostCounters *d_pub = nullptr; // the device's address of h_pub
-    uint32_t pub_seq = 0;
-    int timers = 0;                // bhrt_opts.timers of the running call
-    int photon_exact = 0;          // bhrt_opts.photon_exact of the running call
-    uint32_t *d_knn = nullptr;     // test hook of bhrt_photon_gather_host_ex: the selection pass's photon lists
-    uint32_t *d_sel = nullptr;     // candidate scratch of the selection pass's waves
-    hipStream_t stream = nullptr;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    struct PendingTimer { int e0, e1; double *acc; };
-    std::vector<hipEvent_t> ev_pool;
-    std::vector<PendingTimer> ev_pending;
-    std::vector<int> ev_free;                  // pool indices not in use
-    // caustic photon map (balanced, heap order, slot 0 unused) + gather scratch
-    DPhoton *d_photons = nullptr;
-    uint32_t n_photons = 0;
-    std::vector<HostPhoton> h_photons; // balanced copy for bhrt_photon_export
-    float *d_ph_frames = nullptr;      // 15 * cap_frames floats (p, N, V, kd, ks per frame), only with photon_map
-    uint32_t ph_frames_cap = 0;
-    float4 *d_ph_hot = nullptr, *d_ph_cold = nullptr, *d_ph_dbox = nullptr; // decoded copy the gather walks (PhotonMapDev)
-    PhotonMapDev pm;
-    unsigned long long *d_scr = nullptr; // candidate heaps of the heavy queries: (K+1) x scr_lanes, element-major
-    uint32_t scr_lanes = 0;
-    uint32_t *d_heavy = nullptr; // queries that met 1000 photons in pass 1
-    uint32_t heavy_cap = 0;
-    uint32_t *d_n_heavy = nullptr, *h_n_heavy = nullptr; // [0] heavy, [1] long
-    uint32_t *d_long = nullptr;  // queries whose walk outlasted the lane budget in pass 1
-    uint32_t *d_cell_of = nullptr, *d_gorder = nullptr, *d_rank_of = nullptr, *d_keys_out = nullptr; // gather order (cell sort): heavy_cap entries each
-    void *d_sort_temp = nullptr;
-    size_t sort_temp_bytes = 0;
-    // Development switches, read from the environment ONCE, when the scene is uploaded (none changes a result), and the two test knobs, which
-    // no environment variable reaches: only bhrt_scene_knob sets them.
-    struct Knobs {
-        int stream_waves = -1;          // BHRT_STREAM_WAVES: resident waves of k_trace_mesh_stream; 0 = the launch-per-64-rays kernel; -1 = default
-        bool fused_camera = true;       // BHRT_FUSED_CAMERA=0: two-kernel camera step in mesh-free scenes
-        bool no_slow_queue = false;     // BHRT_NO_SLOW_QUEUE: axis-parallel rays stay in their wave steps
-        bool debug_slow = false, debug_gather = false, debug_drain = false; // BHRT_DEBUG_*: statistics on stderr
-        bool balance_host = false;      // BHRT_PHOTON_BALANCE_HOST: photon_host.cpp instead of k_pb_level (the tests' second opinion)
-        int frame_cap = 0;              // knob "frame_cap": a frame pool that overflows (the retry path under test); 0 = off
-        int gather_lane_budget = 0;     // knob "gather_lane_budget": photons a lane may visit before its query goes to the one-wave pass; 0 = default
-        bool gather_counting_sort = false; // BHRT_GATHER_COUNTING_SORT=1: the cell order by the counting sort instead of the radix sort of pairs
-        bool shadow_overlap = true;     // BHRT_SHADOW_OVERLAP=0: the any-hit kernels of a wave step on the pass's own stream, in front of the next step
-        int gather_stats = 0;           // knob "gather_stats": the lane pass counts the photons its answers are made of (bhrt_stats.photon_found), 7 % slower
-        void FromEnv()
-        {
-            if (const char *e = getenv("BHRT_STREAM_WAVES")) stream_waves = atoi(e);
-            if (const char *e = getenv("BHRT_FUSED_CAMERA")) fused_camera = atoi(e) != 0;
-            no_slow_queue = getenv("BHRT_NO_SLOW_QUEUE") != nullptr;
-            debug_slow = getenv("BHRT_DEBUG_SLOW") != nullptr; debug_gather = getenv("BHRT_DEBUG_GATHER") != nullptr; debug_drain = getenv("BHRT_DEBUG_DRAIN") != nullptr;
-            if (const char *e = getenv("BHRT_PHOTON_BALANCE_HOST")) balance_host = atoi(e) != 0;
-            if (const char *e = getenv("BHRT_GATHER_COUNTING_SORT")) gather_counting_sort = atoi(e) != 0;
-            if (const char *e = getenv("BHRT_SHADOW_OVERLAP")) shadow_overlap = atoi(e) != 0;
-        }
-    } knobs;
-    uint32_t *d_cells = nullptr, *d_tile_sums = nullptr;
-    // a capacity overflow halves the pass (RenderRange); later frames of the same scene and options start from the reduced size
-    uint64_t pass_hint_key = 0;
-    uint32_t pass_hint = 0;
-    uint64_t frames_seen_key = 0; // Shade() frames per sample slot the passes of a render (scene, options: the key) have needed so far (max)
-    double frames_seen = 0;
-    // bhrt_render: the device copy of the frame, kept between calls
-    uint8_t *d_frame_rgb = nullptr;
-    float *d_frame_rad = nullptr;
-    size_t frame_px = 0;
-    // bhrt_render_var: the device copy of the variance image, allocated on first use
-    float *d_frame_var = nullptr;
-    size_t frame_var_px = 0;
-    // bhrt_render_adaptive_dev: the per-pixel state of the rounds (AdaptState: 36 B per owned pixel), two lists of owned-pixel indices (4 B each)
-    // and the next list's length; grown on demand.  bhrt_render_adaptive: the device copy of the count image.
-    uint8_t *d_ad = nullptr;
-    size_t ad_px = 0;
-    uint32_t *d_frame_cnt = nullptr;
-    size_t frame_cnt_px = 0;
-    // bhrt_denoise_dev: the filter's planes (DenoisePlaneBytes), then the first-hit guides it computes itself; grown on demand
-    uint8_t *d_dn = nullptr;
-    size_t dn_bytes = 0;
-    // scratch for the public trace API
-    float *d_api_f = nullptr;
-    int32_t *d_api_i = nullptr;
-    size_t api_cap = 0;
-};
-
-void DestroyDeviceState(DeviceState *d)
-{
-    if (!d) return;
-    if (d->device >= 0) (void)hipSetDevice(d->device);
-    auto fr = [](void *p) { if (p) (void)hipFree(p); };
-    fr(d->d_blob); fr(d->d_chain);
-    for (int k = 0; k < 2; k++) { fr(d->d_rayf[k]); fr(d->d_rayu[k]); }
-    fr(d->d_hitf); fr(d->d_hiti); fr(d->d_shf); fr(d->d_shu); fr(d->d_fu); fr(d->d_fcode); fr(d->d_ff); fr(d->d_samples); fr(d->d_order); fr(d->d_park); fr(d->d_seg); fr(d->d_cnt); fr(d->d_aux);
-    fr(d->d_frame_rgb); fr(d->d_frame_rad); fr(d->d_frame_var); fr(d->d_ad); fr(d->d_frame_cnt); fr(d->d_dn); fr(d->d_sel); fr(d->d_slowf); fr(d->d_slowu);
-    fr(d->d_shf2); fr(d->d_shu2); fr(d->d_order_sh); fr(d->d_seg_sh); fr(d->d_cnt_sh);
-    if (d->ev_shade) (void)hipEventDestroy(d->ev_shade);
-    for (int k = 0; k < 2; k++) if (d->ev_shadow[k]) (void)hipEventDestroy(d->ev_shadow[k]);
-    if (d->stream3) (void)hipStreamDestroy(d->stream3);
-    fr(d->d_api_f); fr(d->d_api_i); fr(d->d_photons); fr(d->d_ph_frames); fr(d->d_scr); fr(d->d_ph_hot); fr(d->d_ph_cold); fr(d->d_ph_dbox); fr(d->d_heavy); fr(d->d_long); fr(d->d_n_heavy); fr(d->d_cell_of); fr(d->d_gorder); fr(d->d_rank_of); fr(d->d_keys_out); if (d->d_sort_temp) (void)hipFree(d->d_sort_temp); fr(d->d_cells); fr(d->d_tile_sums);
-    if (d->h_n_heavy) (void)hipHostFree(d->h_n_heavy);
-    if (d->h_pub) (void)hipHostFree(d->h_pub);
-    for (int k = 0; k < 2; k++) if (d->ev[k]) (void)hipEventDestroy(d->ev[k]);
-    for (hipEvent_t e : d->ev_pool) (void)hipEventDestroy(e);
-    for (hipEvent_t e : d->slow_events) (void)hipEventDestroy(e);
-    if (d->stream2) (void)hipStreamDestroy(d->stream2);
-    if (d->stream) (void)hipStreamDestroy(d->stream);
-    delete d;
-}
+} // namespace bhrt
+#include "device_state.h" // DevBuf, DeviceState, DestroyDeviceState
+namespace bhrt {
 
 static RayQueue MakeRayQueue(float *f, uint32_t *u, size_t cap)
 {
@@ -1965,6 +1832,21 @@ static RayQueue MakeRayQueue(float *f, uint32_t *u, size_t cap)
     q.ox = f; q.oy = f + cap; q.oz = f + 2 * cap; q.dx = f + 3 * cap; q.dy = f + 4 * cap; q.dz = f + 5 * cap;
     q.frame = u; q.meta = u ? u + cap : nullptr; q.rng_ctr = u ? u + 2 * cap : nullptr;
     return q;
+}
+
+static ShadowQueue MakeShadowQueue(float *f, uint32_t *frame, size_t cap)
+{
+    ShadowQueue q;
+    q.ox = f; q.oy = f + cap; q.oz = f + 2 * cap; q.dx = f + 3 * cap; q.dy = f + 4 * cap; q.dz = f + 5 * cap; q.tmax = f + 6 * cap;
+    q.frame = frame;
+    return q;
+}
+// distances and, in one block of 3 * cap words, node, prim, front
+static HitBuf MakeHitBuf(float *t, int32_t *words, size_t cap)
+{
+    HitBuf h;
+    h.t = t; h.node = words; h.prim = words ? words + cap : nullptr; h.front = words ? words + 2 * cap : nullptr;
+    return h;
 }
 
 static int EnsureUploaded(bhrt_scene *scene)
@@ -1979,46 +1861,41 @@ static int EnsureWorkspace(DeviceState *D, uint32_t cap_samples, double frames_p
     const size_t cf_wanted = (size_t)std::ceil((double)cap_samples * frames_per_sample);
     if (cf_wanted > 0xffffffffull) { SetError("frame pool beyond 2^32 frames"); return BHRT_ERR_ARG; }
     if (D->cap_samples >= cap_samples && D->cap_frames >= cf_wanted) return BHRT_OK;
-    auto fr = [](void *p) { if (p) (void)hipFree(p); };
-    for (int k = 0; k < 2; k++) { fr(D->d_rayf[k]); fr(D->d_rayu[k]); D->d_rayf[k] = nullptr; D->d_rayu[k] = nullptr; }
-    fr(D->d_shf2); fr(D->d_shu2); fr(D->d_order_sh); D->d_shf2 = nullptr; D->d_shu2 = nullptr; D->d_order_sh = nullptr;
-    fr(D->d_hitf); fr(D->d_hiti); fr(D->d_shf); fr(D->d_shu); fr(D->d_fu); fr(D->d_fcode); fr(D->d_ff); fr(D->d_samples); fr(D->d_order); fr(D->d_park);
-    D->d_order = nullptr; D->d_park = nullptr;
-    D->d_hitf = nullptr; D->d_hiti = nullptr; D->d_shf = nullptr; D->d_shu = nullptr; D->d_fu = nullptr; D->d_fcode = nullptr; D->d_ff = nullptr; D->d_samples = nullptr;
-    D->cap_samples = 0;
     const size_t cr = (size_t)cap_samples * 2, cf = cf_wanted;
-    for (int k = 0; k < 2; k++) {
-        HIP_CHECK(hipMalloc(&D->d_rayf[k], cr * 6 * sizeof(float)));
-        HIP_CHECK(hipMalloc(&D->d_rayu[k], cr * 3 * sizeof(uint32_t)));
-    }
-    HIP_CHECK(hipMalloc(&D->d_hitf, cr * sizeof(float)));
-    HIP_CHECK(hipMalloc(&D->d_hiti, cr * 3 * sizeof(int32_t)));
-    HIP_CHECK(hipMalloc(&D->d_shf, cr * 7 * sizeof(float)));
-    HIP_CHECK(hipMalloc(&D->d_shu, cr * sizeof(uint32_t)));
-    HIP_CHECK(hipMalloc(&D->d_fu, cf * 4 * sizeof(uint32_t)));
-    HIP_CHECK(hipMalloc(&D->d_fcode, cf * sizeof(uint64_t)));
-    HIP_CHECK(hipMalloc(&D->d_ff, cf * 23 * sizeof(float)));
-    HIP_CHECK(hipMalloc(&D->d_samples, (size_t)cap_samples * 3 * sizeof(float)));
     // rays [1024 g, 1024 g + 1024) file under shard g mod 32 (k_trace_closest); k_trace_mesh files its workgroups round-robin:
     // at most (all parked rays) / 32 + one workgroup more per shard -> twice the even share always fits
-    D->order_shard_cap = (uint32_t)(2 * ((((cr + 1023) / 1024 + BHRT_ORDER_SHARDS - 1) / BHRT_ORDER_SHARDS) * 1024 + 1024));
-    HIP_CHECK(hipMalloc(&D->d_order, (size_t)4 * BHRT_ORDER_SHARDS * D->order_shard_cap * sizeof(uint32_t)));
-    HIP_CHECK(hipMalloc(&D->d_park, (3 * cr + (1u << BHRT_PARK_KEY_BITS) + kScanBlock) * sizeof(uint32_t)));
-    if (D->stream3) {
-        HIP_CHECK(hipMalloc(&D->d_shf2, cr * 7 * sizeof(float)));
-        HIP_CHECK(hipMalloc(&D->d_shu2, cr * sizeof(uint32_t)));
-        HIP_CHECK(hipMalloc(&D->d_order_sh, (size_t)BHRT_ORDER_SHARDS * D->order_shard_cap * sizeof(uint32_t)));
-    }
+    const uint32_t shard_cap = (uint32_t)(2 * ((((cr + 1023) / 1024 + BHRT_ORDER_SHARDS - 1) / BHRT_ORDER_SHARDS) * 1024 + 1024));
+    // the workspace: every buffer and its size, once.  f(buffer, elements) until one fails
+    auto each = [&](auto f) -> int {
+        int rc = BHRT_OK;
+        auto go = [&](auto &buf, size_t n) { if (!rc) rc = f(buf, n); };
+        for (int k = 0; k < 2; k++) { go(D->d_rayf[k], cr * 6); go(D->d_rayu[k], cr * 3); }
+        go(D->d_hitf, cr); go(D->d_hiti, cr * 3); go(D->d_shf, cr * 7); go(D->d_shu, cr);
+        go(D->d_fu, cf * 4); go(D->d_fcode, cf); go(D->d_ff, cf * 23);
+        go(D->d_samples, (size_t)cap_samples * 3);
+        go(D->d_order, (size_t)4 * BHRT_ORDER_SHARDS * shard_cap);
+        go(D->d_park, 3 * cr + (1u << BHRT_PARK_KEY_BITS) + kScanBlock);
+        if (D->stream3) { go(D->d_shf2, cr * 7); go(D->d_shu2, cr); go(D->d_order_sh, (size_t)BHRT_ORDER_SHARDS * shard_cap); }
+        return rc;
+    };
+    // everything is released before anything is allocated: DefaultPassSamples counts the old workspace as free
+    each([](auto &buf, size_t) { buf.Free(); return BHRT_OK; });
+    D->cap_samples = 0;
+    BHRT_TRY(each([](auto &buf, size_t n) { return buf.Reserve(n); }));
+    D->order_shard_cap = shard_cap;
     D->cap_samples = cap_samples; D->cap_rays = (uint32_t)cr; D->cap_frames = (uint32_t)cf;
-    if (D->d_ph_frames) { (void)hipFree(D->d_ph_frames); D->d_ph_frames = nullptr; D->ph_frames_cap = 0; }
+    D->d_ph_frames.Free(); // sized by cap_frames: RenderPixels allocates it again when a render needs it
     return BHRT_OK;
 }
 
 // The largest power of two of camera samples in flight (<= 2^28) whose wavefront buffers fit into 85 % of what the device has free, the present
 // workspace counted as free (EnsureWorkspace releases it before it allocates).  Per sample: two ray slots (72 B each: 36 B in each of the two
-// queues), their hit (16 B) and shadow (32 B) slots, shading order and park lists (40 B per ray slot), in scenes with meshes the second shadow queue and
-// the any-hit kernels' own parked list (32 + 8 B: RenderRange, "any-hit work beside the pass"), 12 B of radiance, and `frames_per_sample`
-// Shade() frames (116 B each, + 60 B with the photon map): six by default = 1.03-1.11 KB per sample, 2^27 samples = 138-149 GB.
+// queues), their hit (16 B) and shadow (32 B) slots, shading order and park lists (counted as 40 B per ray slot: 32 B of order entries — four classes of
+// 4 B, twice over for the shards' slack — and 4 B each of park_key and park_sorted; the 4 B of park_rank, which came later, are NOT counted: the
+// workspace takes 44 B, the constant decides the pass size and stays as measured, and the 15 % of headroom below covers the rest), in scenes
+// with meshes the second shadow queue and the any-hit kernels' own parked list (32 + 8 B: RenderPixels, "any-hit work beside the pass"), 12 B of
+// radiance, and `frames_per_sample` Shade() frames (116 B each, + 60 B with the photon map): six by default = 1.03-1.11 KB per sample, 2^27 samples
+// = 138-149 GB.
 static uint32_t DefaultPassSamples(DeviceState *D, bool photon_map, double frames_per_sample)
 {
     const double frame_b = 116 + (photon_map ? 60 : 0);
@@ -2129,16 +2006,6 @@ static void FlushTimers(DeviceState *D, bool final = false)
     D->ev_pending.resize(keep);
 }
 
-static int EnsurePhotonScratch(DeviceState *D, uint32_t lanes)
-{
-    if (D->scr_lanes >= lanes) return BHRT_OK;
-    if (D->d_scr) (void)hipFree(D->d_scr);
-    D->d_scr = nullptr; D->scr_lanes = 0;
-    HIP_CHECK(hipMalloc(&D->d_scr, (size_t)lanes * BHRT_HEAP_COLUMN * sizeof(unsigned long long)));
-    D->scr_lanes = lanes;
-    return BHRT_OK;
-}
-
 // Caustic gather of queries [q0, q0+cnt) of `sink`: pass 1 without candidate lists over all of them, pass 2 with the
 // candidate heap for the few that met 1000 photons (in chunks of the scratch columns).
 template <class Sink>
@@ -2146,26 +2013,20 @@ static int RunGather(DeviceState *D, const Sink &sink, uint32_t q0, uint32_t cnt
 {
     if (cnt == 0) return BHRT_OK;
     if (D->heavy_cap < cnt) {
-        auto fr = [](uint32_t *&p) { if (p) (void)hipFree(p); p = nullptr; };
-        fr(D->d_heavy); fr(D->d_long); fr(D->d_cell_of); fr(D->d_gorder); fr(D->d_rank_of); fr(D->d_keys_out);
-        if (D->d_sort_temp) (void)hipFree(D->d_sort_temp);
-        D->d_sort_temp = nullptr; D->sort_temp_bytes = 0;
         D->heavy_cap = 0;
-        HIP_CHECK(hipMalloc(&D->d_heavy, (size_t)cnt * sizeof(uint32_t)));
-        HIP_CHECK(hipMalloc(&D->d_long, (size_t)cnt * sizeof(uint32_t)));
-        HIP_CHECK(hipMalloc(&D->d_cell_of, (size_t)cnt * sizeof(uint32_t)));
-        HIP_CHECK(hipMalloc(&D->d_gorder, (size_t)cnt * sizeof(uint32_t)));
-        HIP_CHECK(hipMalloc(&D->d_rank_of, (size_t)cnt * sizeof(uint32_t)));
-        HIP_CHECK(hipMalloc(&D->d_keys_out, (size_t)cnt * sizeof(uint32_t)));
+        DevBuf<uint32_t> *const lists[] = {&D->d_heavy, &D->d_long, &D->d_cell_of, &D->d_gorder, &D->d_rank_of, &D->d_keys_out};
+        for (DevBuf<uint32_t> *buf : lists) buf->Free();
+        D->d_sort_temp.Free();
+        for (DevBuf<uint32_t> *buf : lists) BHRT_TRY(buf->Reserve(cnt));
         if (GatherSortPairs(nullptr, nullptr, nullptr, nullptr, cnt, nullptr, &D->sort_temp_bytes, 28, D->stream) != 0) { SetError("gather sort: temp size"); return BHRT_ERR_HIP; }
-        HIP_CHECK(hipMalloc(&D->d_sort_temp, std::max<size_t>(D->sort_temp_bytes, 16)));
+        BHRT_TRY(D->d_sort_temp.Reserve(std::max<size_t>(D->sort_temp_bytes, 16)));
         D->heavy_cap = cnt;
     }
     if (!D->d_n_heavy) {
-        HIP_CHECK(hipMalloc(&D->d_n_heavy, 12 * sizeof(uint32_t))); // [0] heavy, [1] long, [2..3] nodes visited (64-bit), [4] selection rounds, [5] compactions, [8..11] lane pass: found, answered
-        HIP_CHECK(hipHostMalloc(&D->h_n_heavy, 12 * sizeof(uint32_t)));
-        HIP_CHECK(hipMalloc(&D->d_cells, ((size_t)BHRT_GATHER_CELLS + 1) * sizeof(uint32_t)));
-        HIP_CHECK(hipMalloc(&D->d_tile_sums, (size_t)(BHRT_GATHER_CELLS / kScanTile + kScanBlock) * sizeof(uint32_t)));
+        BHRT_TRY(D->d_n_heavy.Reserve(12));
+        BHRT_TRY(D->h_n_heavy.Alloc(12));
+        BHRT_TRY(D->d_cells.Reserve((size_t)BHRT_GATHER_CELLS + 1));
+        BHRT_TRY(D->d_tile_sums.Reserve((size_t)(BHRT_GATHER_CELLS / kScanTile + kScanBlock)));
     }
     dim3 grid((cnt + kBlock - 1) / kBlock);
     const dim3 block(kBlock);
@@ -2236,7 +2097,7 @@ static int RunGather(DeviceState *D, const Sink &sink, uint32_t q0, uint32_t cnt
     if (n_sel_heavy + n_long) {
         HIP_CHECK(hipMemsetAsync(D->d_n_heavy, 0, 8 * sizeof(uint32_t), D->stream));
         const uint32_t sel_waves = D->n_cus * BHRT_SEL_WAVES_PER_CU; // persistent one-wave workgroups, each with its scratch (candidates 24 KB + stack spill 48 KB)
-        if (!D->d_sel) HIP_CHECK(hipMalloc(&D->d_sel, (size_t)sel_waves * BHRT_SEL_SCRATCH_WORDS * sizeof(uint32_t)));
+        BHRT_TRY(D->d_sel.Reserve((size_t)sel_waves * BHRT_SEL_SCRATCH_WORDS));
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_photon_gather_select<Sink>), dim3(std::min<uint32_t>(n_sel_heavy + n_long, sel_waves)), dim3(64), 0, D->stream, sink, D->d_heavy,
                            n_sel_heavy, D->d_long, n_long, D->pm, radius, undecided, D->d_n_heavy, D->d_knn, D->d_sel, D->photon_exact);
         HIP_CHECK(hipMemcpyAsync(D->h_n_heavy, D->d_n_heavy, 8 * sizeof(uint32_t), hipMemcpyDeviceToHost, D->stream));
@@ -2253,7 +2114,8 @@ static int RunGather(DeviceState *D, const Sink &sink, uint32_t q0, uint32_t cnt
         const uint32_t m_all = part == 0 ? n_exact : (D->photon_exact ? n_heavy : 0u);
         if (!m_all) continue;
         const uint32_t heap_lanes = 1u << 20; // as many heaps in flight as possible: the pass is a chain of dependent accesses per query (65 k lanes: 1.8x slower)
-        int rc = EnsurePhotonScratch(D, std::min<uint32_t>(heap_lanes, (m_all + 4095u) & ~4095u));
+        const int rc = D->d_scr.Reserve((size_t)std::min<uint32_t>(heap_lanes, (m_all + 4095u) & ~4095u) * BHRT_HEAP_COLUMN);
+        D->scr_lanes = (uint32_t)(D->d_scr.n / BHRT_HEAP_COLUMN);
         if (rc) return rc;
         HIP_CHECK(hipMemsetAsync(D->d_n_heavy + 2, 0, 2 * sizeof(uint32_t), D->stream));
         const uint32_t chunk = std::min<uint32_t>(D->scr_lanes, heap_lanes);
@@ -2304,6 +2166,64 @@ static int FramePassInfo(bhrt_scene *scene, const bhrt_opts &o, PassInfo &P, uin
     return BHRT_OK;
 }
 
+// What a render's learned sizes (DeviceState::frames_seen, pass_hint) are filed under: the options that decide how many frames and rays a sample needs
+static uint64_t RenderKey(const bhrt_opts &o, uint32_t spp, int world, int tile)
+{
+    return ((uint64_t)spp << 48) ^ ((uint64_t)(uint32_t)(o.gi_bounces + 1) << 40) ^ ((uint64_t)(uint32_t)o.internal_bounces << 32) ^
+           ((uint64_t)(uint32_t)world << 24) ^ ((uint64_t)(uint32_t)tile << 8) ^ (uint64_t)(o.photon_map ? 1 : 0);
+}
+
+// A pass's views of the workspace (EnsureWorkspace) and of the slow queue
+struct PassViews {
+    RayQueue Q[2];
+    HitBuf HB;
+    ShadowQueue SQ, SQ2; // SQ2: the queue of the odd steps when the any-hit work runs beside the pass (sh_overlap), else SQ again
+    Frames F;
+    RayOrder RO, RO_sh;  // RO_sh: the parked list of the any-hit rays when they run beside the pass: only its RC_MESH part exists
+    SlowQueue slowq;     // rays set aside (SlowQueue): collected while the pass runs, traced and shaded in wave steps of their own once the queue is empty
+    HitBuf slow_hits;
+};
+static PassViews MakePassViews(DeviceState *D, bool sh_overlap)
+{
+    PassViews V;
+    const size_t c = D->cap_rays;
+    for (int k = 0; k < 2; k++) V.Q[k] = MakeRayQueue(D->d_rayf[k], D->d_rayu[k], c);
+    V.HB = MakeHitBuf(D->d_hitf, D->d_hiti, c);
+    V.SQ = MakeShadowQueue(D->d_shf, D->d_shu, c);
+    V.SQ2 = sh_overlap ? MakeShadowQueue(D->d_shf2, D->d_shu2, c) : V.SQ;
+    V.F = MakeFrames(D);
+    uint32_t *seg = D->d_seg, *park = D->d_park;
+    V.RO = {D->d_order, D->order_shard_cap, seg, seg + 3 * BHRT_ORDER_SHARDS + 1, seg + 6 * BHRT_ORDER_SHARDS + 1, seg + 7 * BHRT_ORDER_SHARDS + 2,
+            park, park + c, park + 3 * c, seg + 8 * BHRT_ORDER_SHARDS + 3, park + 2 * c};
+    V.RO_sh = V.RO;
+    if (sh_overlap) {
+        // The kernels index ord.idx with the class offset of RC_MESH (k_trace_shadow_park, k_shadow_mesh), so the base of a list that holds this one class
+        // lies IN FRONT of its allocation.  Only entries of RC_MESH are ever addressed through it; a base inside the allocation needs a change to the kernels.
+        V.RO_sh.idx = D->d_order_sh.p - (size_t)RC_MESH * BHRT_ORDER_SHARDS * D->order_shard_cap;
+        V.RO_sh.mesh_start = D->d_seg_sh; V.RO_sh.mesh_count = D->d_seg_sh + BHRT_ORDER_SHARDS + 1;
+    }
+    V.slowq.q = MakeRayQueue(D->d_slowf, D->d_slowu, kSlowCap);
+    V.slowq.cap = D->d_slowf && !D->knobs.no_slow_queue ? kSlowCap : 0u;
+    V.slow_hits = MakeHitBuf(D->d_slowf ? D->d_slowf + (size_t)6 * kSlowCap : nullptr, (int32_t *)(D->d_slowu ? D->d_slowu + (size_t)3 * kSlowCap : nullptr), kSlowCap);
+    return V;
+}
+
+// The any-hit kernels of one wave step on `stream`: the first n rays of `sq` into `vis`.  n_dev != nullptr: the queue's length is read on the device and n is
+// the bound the grids cover.  With meshes the rays that enter one are parked in `order` (counted in `counters`) and finished in dense workgroups.
+static void LaunchAnyHit(DeviceState *D, hipStream_t stream, bool meshes, const ShadowQueue &sq, uint32_t n, const uint32_t *n_dev, float *vis, const RayOrder &order,
+                         Counters *counters, int path_mode, bool ls, double *seconds)
+{
+    Timer t(D, seconds, 1, stream);
+    const dim3 hg((n + kBlock - 1) / kBlock), hb(kBlock);
+    if (meshes) {
+        hipLaunchKernelGGL(k_trace_shadow_park, hg, hb, 0, stream, D->S, sq, n, n_dev, vis, order, counters);
+        hipLaunchKernelGGL(k_mesh_prefix, dim3(1), dim3(64), 0, stream, counters, order);
+        // (streamed like k_trace_mesh_stream the any-hit walks gain nothing: they are short, C4 +4 ms, closed room -2 ms)
+        hipLaunchKernelGGL(path_mode == 1 ? (ls ? k_shadow_mesh<1, true> : k_shadow_mesh<1>) : path_mode == 2 ? (ls ? k_shadow_mesh<2, true> : k_shadow_mesh<2>) : k_shadow_mesh<0>, dim3((hg.x + BHRT_ORDER_SHARDS) * (kBlock / kShadowBlock)), dim3(kShadowBlock), 0, stream, D->S, sq, vis, order);
+    } else hipLaunchKernelGGL(k_trace_shadow<false>, hg, hb, 0, stream, D->S, sq, n, n_dev, vis);
+    t.Stop();
+}
+
 // Renders samples [s0, s0 + spp) of n_items owned pixels of this rank: the range [0, n_items) of owned-pixel indices (d_list == nullptr) or
 // the entries of the device list d_list (an adaptive round), in passes.  Pass sizing, the halve-and-redo of a pass that overflows, the photon
 // gather per pass, the slow queue and the any-hit overlap are the same for both.  consume(P, npx) launches, on D->stream, what reads a finished
@@ -2325,8 +2245,7 @@ static int RenderPixels(bhrt_scene *scene, const bhrt_opts &o, PassInfo P, const
     // Shade() frames per sample slot: six are provided for (an overflow halves the pass and redoes it).  A frame that does not fit into one pass
     // with six — C4's 2.7e8 samples per GPU — takes what the earlier passes of the same render (scene, options) have needed, + 30 %: C4 needs 1.1
     // frames per sample, and with 1.7 provided its 2^28 slots fit into 180 GB: one pass per frame instead of two.
-    const uint64_t frames_key = ((uint64_t)spp << 48) ^ ((uint64_t)(uint32_t)(o.gi_bounces + 1) << 40) ^ ((uint64_t)(uint32_t)o.internal_bounces << 32) ^
-                                ((uint64_t)(uint32_t)world << 24) ^ ((uint64_t)(uint32_t)tile << 8) ^ (uint64_t)(o.photon_map ? 1 : 0);
+    const uint64_t frames_key = RenderKey(o, spp, world, tile);
     double frames_per_sample = 6.0;
     bool frames_learned = false;
     if (o.samples_per_pass <= 0 && D->frames_seen_key == frames_key && D->frames_seen > 0 && D->frames_seen < 4.0 &&
@@ -2356,42 +2275,28 @@ static int RenderPixels(bhrt_scene *scene, const bhrt_opts &o, PassInfo P, const
 
     uint64_t q = 0;
     uint32_t pass_limit = 0; // samples actually put in flight per pass (<= buffer capacity)
-    const uint64_t hint_key = ((uint64_t)spp << 48) ^ ((uint64_t)(uint32_t)(o.gi_bounces + 1) << 40) ^ ((uint64_t)(uint32_t)o.internal_bounces << 32) ^
-                              ((uint64_t)(uint32_t)world << 24) ^ ((uint64_t)(uint32_t)tile << 8) ^ (uint64_t)(o.photon_map ? 1 : 0) ^ ((uint64_t)pass_samples << 1);
+    const uint64_t hint_key = frames_key ^ ((uint64_t)pass_samples << 1);
     if (D->pass_hint_key == hint_key && D->pass_hint) pass_limit = D->pass_hint;
     while (q < n_items) {
         int rc = EnsureWorkspace(D, pass_samples, frames_per_sample);
         if (rc) return rc;
         R.cap_rays = D->cap_rays; R.cap_shadow = D->cap_rays; R.cap_frames = D->cap_frames;
         if (D->knobs.frame_cap > 0) R.cap_frames = std::min<uint32_t>(R.cap_frames, (uint32_t)D->knobs.frame_cap); // test knob: a pass that overflows
-        if (o.photon_map) {
-            if (D->ph_frames_cap < D->cap_frames) {
-                if (D->d_ph_frames) (void)hipFree(D->d_ph_frames);
-                D->d_ph_frames = nullptr;
-                HIP_CHECK(hipMalloc(&D->d_ph_frames, (size_t)D->cap_frames * 15 * sizeof(float)));
-                D->ph_frames_cap = D->cap_frames;
-            }
-        }
+        if (o.photon_map) BHRT_TRY(D->d_ph_frames.Reserve((size_t)D->cap_frames * 15));
         if (pass_limit == 0) pass_limit = pass_samples;
         if (pass_limit > D->cap_samples) pass_limit = D->cap_samples;
         const uint32_t px_per_pass = pass_limit / spp;
         const uint32_t npx = (uint32_t)std::min<uint64_t>(px_per_pass, n_items - q);
         if (d_list) { P.list = d_list + q; P.q0 = 0; } else P.q0 = (uint32_t)q;
         P.n_pixels = npx;
-        RayQueue Q[2] = {MakeRayQueue(D->d_rayf[0], D->d_rayu[0], D->cap_rays), MakeRayQueue(D->d_rayf[1], D->d_rayu[1], D->cap_rays)};
-        HitBuf HB; HB.t = D->d_hitf; HB.node = D->d_hiti; HB.prim = D->d_hiti + D->cap_rays; HB.front = D->d_hiti + 2 * (size_t)D->cap_rays;
-        ShadowQueue SQ; { float *p = D->d_shf; const size_t c = D->cap_rays; SQ.ox = p; SQ.oy = p + c; SQ.oz = p + 2 * c; SQ.dx = p + 3 * c; SQ.dy = p + 4 * c; SQ.dz = p + 5 * c; SQ.tmax = p + 6 * c; SQ.frame = D->d_shu; }
         // Any-hit work beside the next step's closest-hit work (stream3): the shadow rays of step s are only needed by k_combine at the end of the pass, so their
         // kernels go to a stream of their own as soon as k_shade has written them, with a shadow queue per step parity, and fill what the pass's stream leaves
         // idle — above all the tail of every k_trace_mesh_stream launch (the longest walks of its last batch: 0.1-0.5 ms per wave step).
-        const bool sh_overlap = D->knobs.shadow_overlap && D->stream3 != nullptr && D->d_shf2 != nullptr;
-        ShadowQueue SQ2 = SQ; if (sh_overlap) { float *p = D->d_shf2; const size_t c = D->cap_rays; SQ2.ox = p; SQ2.oy = p + c; SQ2.oz = p + 2 * c; SQ2.dx = p + 3 * c; SQ2.dy = p + 4 * c; SQ2.dz = p + 5 * c; SQ2.tmax = p + 6 * c; SQ2.frame = D->d_shu2; }
+        const bool sh_overlap = D->knobs.shadow_overlap && D->stream3 != nullptr && D->d_shf2.p != nullptr;
+        const PassViews V = MakePassViews(D, sh_overlap);
+        const Frames &F = V.F;
+        const RayOrder &RO = V.RO;
         bool sh_pending[2] = {false, false};
-        Frames F = MakeFrames(D);
-        RayOrder RO = {D->d_order, D->order_shard_cap, D->d_seg, D->d_seg + 3 * BHRT_ORDER_SHARDS + 1, D->d_seg + 6 * BHRT_ORDER_SHARDS + 1, D->d_seg + 7 * BHRT_ORDER_SHARDS + 2,
-                       D->d_park, D->d_park + D->cap_rays, D->d_park + 3 * (size_t)D->cap_rays, D->d_seg + 8 * BHRT_ORDER_SHARDS + 3, D->d_park + 2 * (size_t)D->cap_rays};
-        RayOrder RO_sh = RO; // the parked list of the any-hit rays when they run beside the pass: only its RC_MESH part exists
-        if (sh_overlap) { RO_sh.idx = D->d_order_sh - (size_t)RC_MESH * BHRT_ORDER_SHARDS * D->order_shard_cap; RO_sh.mesh_start = D->d_seg_sh; RO_sh.mesh_count = D->d_seg_sh + BHRT_ORDER_SHARDS + 1; }
         HIP_CHECK(hipMemsetAsync(D->d_cnt, 0, sizeof(Counters), D->stream));
         // d_samples needs no clearing: every slot of a valid pixel is written exactly once (k_shade: background of a camera
         // miss; k_combine: root frame), and k_resolve never reads the slots of edge-tile pixels outside the image
@@ -2403,14 +2308,7 @@ static int RenderPixels(bhrt_scene *scene, const bhrt_opts &o, PassInfo P, const
         bool overflow = false;
         uint64_t pass_closest = 0, pass_camera = 0, pass_shadow = 0, pass_deferred = 0;
         uint32_t pass_steps = 0; // ray counters of this pass: added to *st only when the pass completes (an overflowing pass is redone)
-        // rays set aside (SlowQueue): collected while the pass runs, traced and shaded in wave steps of their own once the queue is empty
-        SlowQueue slowq;
-        slowq.q = MakeRayQueue(D->d_slowf, D->d_slowu, kSlowCap);
-        slowq.cap = D->d_slowf ? kSlowCap : 0u;
-        if (D->knobs.no_slow_queue) slowq.cap = 0;
-        const SlowQueue no_slow = {slowq.q, 0u};
-        HitBuf slow_hits; slow_hits.t = D->d_slowf ? D->d_slowf + (size_t)6 * kSlowCap : nullptr; slow_hits.node = (int32_t *)(D->d_slowu ? D->d_slowu + (size_t)3 * kSlowCap : nullptr);
-        slow_hits.prim = slow_hits.node ? slow_hits.node + kSlowCap : nullptr; slow_hits.front = slow_hits.node ? slow_hits.node + 2 * (size_t)kSlowCap : nullptr;
+        const SlowQueue no_slow = {V.slowq.q, 0u};
         uint32_t slow_pending = 0, slow_traced = 0, slow_injected = 0; // set aside so far this pass / of those handed to k_trace_slow / of those moved into a wave step
         struct SlowBatch { uint32_t end; uint32_t step; hipEvent_t done; };
         std::vector<SlowBatch> slow_batches; // k_trace_slow launches of this pass, in order
@@ -2430,16 +2328,8 @@ static int RenderPixels(bhrt_scene *scene, const bhrt_opts &o, PassInfo P, const
             if (!sh_wait_n) return BHRT_OK;
             const int par = sh_wait_par; const uint32_t n_sh = sh_wait_n;
             sh_wait_n = 0;
-            const ShadowQueue &sq_s = par ? SQ2 : SQ;
             HIP_CHECK(hipStreamWaitEvent(D->stream3, after, 0));
-            Timer t(D, &st->seconds_trace_shadow, 1, D->stream3);
-            const dim3 hg((n_sh + kBlock - 1) / kBlock), hb(kBlock);
-            if (H->n_meshes > 0) {
-                hipLaunchKernelGGL(k_trace_shadow_park, hg, hb, 0, D->stream3, D->S, sq_s, n_sh, (const uint32_t *)nullptr, F.vis, RO_sh, D->d_cnt_sh);
-                hipLaunchKernelGGL(k_mesh_prefix, dim3(1), dim3(64), 0, D->stream3, D->d_cnt_sh, RO_sh);
-                hipLaunchKernelGGL(path_mode == 1 ? (ls ? k_shadow_mesh<1, true> : k_shadow_mesh<1>) : path_mode == 2 ? (ls ? k_shadow_mesh<2, true> : k_shadow_mesh<2>) : k_shadow_mesh<0>, dim3((hg.x + BHRT_ORDER_SHARDS) * (kBlock / kShadowBlock)), dim3(kShadowBlock), 0, D->stream3, D->S, sq_s, F.vis, RO_sh);
-            } else hipLaunchKernelGGL(k_trace_shadow<false>, hg, hb, 0, D->stream3, D->S, sq_s, n_sh, (const uint32_t *)nullptr, F.vis);
-            t.Stop();
+            LaunchAnyHit(D, D->stream3, H->n_meshes > 0, par ? V.SQ2 : V.SQ, n_sh, nullptr, F.vis, V.RO_sh, D->d_cnt_sh, path_mode, ls, &st->seconds_trace_shadow);
             HIP_CHECK(hipEventRecord(D->ev_shadow[par], D->stream3));
             sh_pending[par] = true;
             return BHRT_OK;
@@ -2454,7 +2344,7 @@ static int RenderPixels(bhrt_scene *scene, const bhrt_opts &o, PassInfo P, const
                     fprintf(stderr, "slow rays: %u moved in after wave step %u, waited %.1f ms for their hits, pass time so far %.1f ms\n", slow_pending, pass_steps,
                             std::chrono::duration<double>(std::chrono::steady_clock::now() - w0).count() * 1e3, std::chrono::duration<double>(std::chrono::steady_clock::now() - wall0).count() * 1e3);
                 n_cur = slow_pending - slow_injected;
-                hipLaunchKernelGGL(k_inject_slow, dim3((n_cur + kBlock - 1) / kBlock), dim3(kBlock), 0, D->stream, slowq.q, slow_hits, slow_injected, n_cur, Q[cur], HB, 0u);
+                hipLaunchKernelGGL(k_inject_slow, dim3((n_cur + kBlock - 1) / kBlock), dim3(kBlock), 0, D->stream, V.slowq.q, V.slow_hits, slow_injected, n_cur, V.Q[cur], V.HB, 0u);
                 pass_deferred += n_cur;
                 slow_injected = slow_pending;
                 slow_batch_next = slow_batches.size();
@@ -2466,30 +2356,30 @@ static int RenderPixels(bhrt_scene *scene, const bhrt_opts &o, PassInfo P, const
                 if (upto > slow_injected && (uint64_t)n_cur + (upto - slow_injected) <= D->cap_rays) {
                     HIP_CHECK(hipStreamWaitEvent(D->stream, slow_batches[b - 1].done, 0)); // stream2 runs its launches in order: the last one's event covers them all
                     n_extra = upto - slow_injected;
-                    hipLaunchKernelGGL(k_inject_slow, dim3((n_extra + kBlock - 1) / kBlock), dim3(kBlock), 0, D->stream, slowq.q, slow_hits, slow_injected, n_extra, Q[cur], HB, n_cur);
+                    hipLaunchKernelGGL(k_inject_slow, dim3((n_extra + kBlock - 1) / kBlock), dim3(kBlock), 0, D->stream, V.slowq.q, V.slow_hits, slow_injected, n_extra, V.Q[cur], V.HB, n_cur);
                     if (D->knobs.debug_slow) fprintf(stderr, "slow rays: %u ride along with wave step %u (%u rays)\n", n_extra, pass_steps, n_cur);
                     pass_deferred += n_extra;
                     slow_injected = upto;
                     slow_batch_next = b;
                 }
             }
-            const SlowQueue &sq = slowq;
+            const SlowQueue &sq = V.slowq;
             // the camera step of a scene without meshes: k_shade traces its rays itself (shade_block's kFused); BHRT_FUSED_CAMERA=0: the two-kernel form
             const bool fused = first_step && H->n_meshes == 0 && D->knobs.fused_camera;
             if (fused) {
             } else if (injected) {
                 Timer t(D, &st->seconds_trace_closest);
-                hipLaunchKernelGGL(k_file_all, dim3((n_cur + kBlock - 1) / kBlock), dim3(kBlock), 0, D->stream, Q[cur], HB, 0u, n_cur, RO, D->d_cnt);
+                hipLaunchKernelGGL(k_file_all, dim3((n_cur + kBlock - 1) / kBlock), dim3(kBlock), 0, D->stream, V.Q[cur], V.HB, 0u, n_cur, RO, D->d_cnt);
                 t.Stop();
             } else {
                 Timer t(D, &st->seconds_trace_closest);
                 const dim3 tg((n_cur + kBlock - 1) / kBlock), tb(kBlock);
                 if (H->n_meshes > 0) { // park the mesh rays, then finish them in dense workgroups
                     const uint32_t n_buckets = 1u << BHRT_PARK_KEY_BITS, n_tiles = n_buckets / kScanTile;
-                    if (first_step) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_trace_closest<true, true>), tg, tb, 0, D->stream, D->S, P, Q[cur], n_cur, 0, HB, RO, D->d_cnt, sq);
+                    if (first_step) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_trace_closest<true, true>), tg, tb, 0, D->stream, D->S, P, V.Q[cur], n_cur, 0, V.HB, RO, D->d_cnt, sq);
                     else {
                         HIP_CHECK(hipMemsetAsync(RO.park_bucket, 0, n_buckets * sizeof(uint32_t), D->stream)); // the trace kernel counts the keys as it parks
-                        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_trace_closest<true, false>), tg, tb, 0, D->stream, D->S, P, Q[cur], n_cur, 0, HB, RO, D->d_cnt, sq);
+                        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_trace_closest<true, false>), tg, tb, 0, D->stream, D->S, P, V.Q[cur], n_cur, 0, V.HB, RO, D->d_cnt, sq);
                     }
                     hipLaunchKernelGGL(k_mesh_prefix, dim3(1), dim3(64), 0, D->stream, D->d_cnt, RO);
                     if (!first_step) { // counting sort of the parked rays by coherence key (the camera step keeps slot order)
@@ -2511,7 +2401,7 @@ static int RenderPixels(bhrt_scene *scene, const bhrt_opts &o, PassInfo P, const
                         { unsigned long long t0[4] = {~0ull, ~0ull, 0, 0}; HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(g_stream_t), t0, sizeof(t0))); }
 #endif
                         hipLaunchKernelGGL(path_mode == 1 ? (ls ? k_trace_mesh_stream<1, true> : k_trace_mesh_stream<1>) : (ls ? k_trace_mesh_stream<2, true> : k_trace_mesh_stream<2>), dim3(std::min<uint32_t>((n_cur + 63) / 64, stream_waves)), dim3(64), 0, D->stream, D->S,
-                                           Q[cur], HB, RO, D->d_cnt);
+                                           V.Q[cur], V.HB, RO, D->d_cnt);
 #ifdef BHRT_DEBUG_DRAIN
                         unsigned long long t1[4];
                         HIP_CHECK(hipMemcpyFromSymbol(t1, HIP_SYMBOL(g_stream_t), sizeof(t1)));
@@ -2522,13 +2412,13 @@ static int RenderPixels(bhrt_scene *scene, const bhrt_opts &o, PassInfo P, const
                     }
                     else
                     hipLaunchKernelGGL(mesh_kernel, first_step ? dim3(tg.x + BHRT_ORDER_SHARDS) /* shard segments padded to whole slices */ : dim3((n_cur + kMeshBlock - 1) / kMeshBlock),
-                                       first_step ? tb : dim3(kMeshBlock), 0, D->stream, D->S, P, Q[cur], HB, RO, D->d_cnt);
-                    if (!first_step) hipLaunchKernelGGL(k_file_parked, dim3(tg.x + BHRT_ORDER_SHARDS), tb, 0, D->stream, Q[cur], HB, RO, D->d_cnt);
-                } else if (first_step) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_trace_closest<false, true, false>), tg, tb, 0, D->stream, D->S, P, Q[cur], n_cur, 0, HB, RO, D->d_cnt, no_slow);
-                else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_trace_closest<false, false, false>), tg, tb, 0, D->stream, D->S, P, Q[cur], n_cur, 0, HB, RO, D->d_cnt, no_slow);
+                                       first_step ? tb : dim3(kMeshBlock), 0, D->stream, D->S, P, V.Q[cur], V.HB, RO, D->d_cnt);
+                    if (!first_step) hipLaunchKernelGGL(k_file_parked, dim3(tg.x + BHRT_ORDER_SHARDS), tb, 0, D->stream, V.Q[cur], V.HB, RO, D->d_cnt);
+                } else if (first_step) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_trace_closest<false, true, false>), tg, tb, 0, D->stream, D->S, P, V.Q[cur], n_cur, 0, V.HB, RO, D->d_cnt, no_slow);
+                else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_trace_closest<false, false, false>), tg, tb, 0, D->stream, D->S, P, V.Q[cur], n_cur, 0, V.HB, RO, D->d_cnt, no_slow);
                 t.Stop();
             }
-            if (n_extra) hipLaunchKernelGGL(k_file_all, dim3((n_extra + kBlock - 1) / kBlock), dim3(kBlock), 0, D->stream, Q[cur], HB, n_cur, n_cur + n_extra, RO, D->d_cnt);
+            if (n_extra) hipLaunchKernelGGL(k_file_all, dim3((n_extra + kBlock - 1) / kBlock), dim3(kBlock), 0, D->stream, V.Q[cur], V.HB, n_cur, n_cur + n_extra, RO, D->d_cnt);
             if (!fused) {
                 st->launches_trace_closest++;
                 hipLaunchKernelGGL(k_order_prefix, dim3(1), dim3(128), 0, D->stream, D->d_cnt, RO);
@@ -2543,22 +2433,14 @@ static int RenderPixels(bhrt_scene *scene, const bhrt_opts &o, PassInfo P, const
                 const int par = (int)(pass_steps & 1u);
                 if (sh_wait_n) { HIP_CHECK(hipEventRecord(D->ev_shade, D->stream)); rc = launch_any_hit(D->ev_shade); if (rc) return rc; }
                 if (sh_overlap && sh_pending[par]) { HIP_CHECK(hipStreamWaitEvent(D->stream, D->ev_shadow[par], 0)); sh_pending[par] = false; } // the any-hit kernels of two steps ago still read this queue
-                hipLaunchKernelGGL(shade, sg, sb, 0, D->stream, D->S, R, P, Q[cur], HB, n_cur + n_extra, Q[cur ^ 1], (sh_overlap && par) ? SQ2 : SQ, F, D->d_samples, D->d_cnt, RO, D->d_pub, seq); // + n_next, n_shadow, n_frames, overflow to the host
+                hipLaunchKernelGGL(shade, sg, sb, 0, D->stream, D->S, R, P, V.Q[cur], V.HB, n_cur + n_extra, V.Q[cur ^ 1], (sh_overlap && par) ? V.SQ2 : V.SQ, F, D->d_samples, D->d_cnt, RO, D->d_pub, seq); // + n_next, n_shadow, n_frames, overflow to the host
                 t.Stop();
                 if (sh_overlap) HIP_CHECK(hipEventRecord(D->ev_shade, D->stream));
             }
             if (!sh_overlap) { // the shadow trace of this step goes out before the host has the counters: its grid covers the upper bound
               // (<= 1 shadow ray per shaded ray, <= the queue's capacity) and the kernels read the length on the device
-                Timer t(D, &st->seconds_trace_shadow);
-                const uint32_t bound = std::min<uint32_t>(n_cur + n_extra, R.cap_shadow);
-                const dim3 hg((bound + kBlock - 1) / kBlock), hb(kBlock);
-                if (H->n_meshes > 0) {
-                    hipLaunchKernelGGL(k_trace_shadow_park, hg, hb, 0, D->stream, D->S, SQ, bound, &D->d_cnt->n_shadow.v, F.vis, RO, D->d_cnt);
-                    hipLaunchKernelGGL(k_mesh_prefix, dim3(1), dim3(64), 0, D->stream, D->d_cnt, RO);
-                    // (streamed like k_trace_mesh_stream the any-hit walks gain nothing: they are short, C4 +4 ms, closed room -2 ms)
-                    hipLaunchKernelGGL(path_mode == 1 ? (ls ? k_shadow_mesh<1, true> : k_shadow_mesh<1>) : path_mode == 2 ? (ls ? k_shadow_mesh<2, true> : k_shadow_mesh<2>) : k_shadow_mesh<0>, dim3((hg.x + BHRT_ORDER_SHARDS) * (kBlock / kShadowBlock)), dim3(kShadowBlock), 0, D->stream, D->S, SQ, F.vis, RO);
-                } else hipLaunchKernelGGL(k_trace_shadow<false>, hg, hb, 0, D->stream, D->S, SQ, bound, &D->d_cnt->n_shadow.v, F.vis);
-                t.Stop();
+                LaunchAnyHit(D, D->stream, H->n_meshes > 0, V.SQ, std::min<uint32_t>(n_cur + n_extra, R.cap_shadow), &D->d_cnt->n_shadow.v, F.vis, RO, D->d_cnt, path_mode, ls,
+                             &st->seconds_trace_shadow);
             }
             rc = WaitPublished(D, seq);
             if (rc) return rc;
@@ -2574,7 +2456,7 @@ static int RenderPixels(bhrt_scene *scene, const bhrt_opts &o, PassInfo P, const
             slow_pending = std::min<uint32_t>(hc.n_slow, kSlowCap);
             if (slow_pending > slow_traced) { // the rays this step set aside: traced beside the pass
                 const uint32_t cnt_new = slow_pending - slow_traced;
-                hipLaunchKernelGGL(k_trace_slow, dim3(cnt_new), dim3(64), 0, D->stream2, D->S, slowq, slow_traced, slow_pending, slow_hits);
+                hipLaunchKernelGGL(k_trace_slow, dim3(cnt_new), dim3(64), 0, D->stream2, D->S, V.slowq, slow_traced, slow_pending, V.slow_hits);
                 if (D->knobs.debug_slow) fprintf(stderr, "slow rays: %u set aside in wave step %u at %.1f ms\n", cnt_new, pass_steps, std::chrono::duration<double>(std::chrono::steady_clock::now() - wall0).count() * 1e3);
                 slow_traced = slow_pending;
                 const size_t bi = slow_batches.size();
@@ -2688,15 +2570,10 @@ static int RenderAdaptive(bhrt_scene *scene, const bhrt_opts &o, const bhrt_adap
     int rc = FramePassInfo(scene, o, P, owned_pixels);
     if (rc) return rc;
     if (owned_pixels > 0xffffffffull) { SetError("adaptive render: more than 2^32 owned pixels"); return BHRT_ERR_ARG; }
-    if (D->ad_px < owned_pixels) {
-        if (D->d_ad) HIP_CHECK(hipFree(D->d_ad));
-        D->d_ad = nullptr; D->ad_px = 0;
-        HIP_CHECK(hipMalloc(&D->d_ad, (size_t)owned_pixels * 44 + 16));
-        D->ad_px = (size_t)owned_pixels;
-    }
-    const size_t N = D->ad_px;
+    BHRT_TRY(D->d_ad.Reserve((size_t)owned_pixels * 44 + 16));
+    const size_t N = (D->d_ad.n - 16) / 44; // the pixels the buffer was sized for
     AdaptState A;
-    A.a = (float4 *)D->d_ad; A.b = A.a + N; A.c = (float *)(A.b + N);
+    A.a = (float4 *)D->d_ad.p; A.b = A.a + N; A.c = (float *)(A.b + N);
     uint32_t *lists[2] = {(uint32_t *)(A.c + N), (uint32_t *)(A.c + N) + N};
     AdaptParams R;
     R.n_max = (uint32_t)o.spp; R.threshold = ao.threshold; R.floor = ao.floor;
@@ -2727,6 +2604,62 @@ static int RenderAdaptive(bhrt_scene *scene, const bhrt_opts &o, const bhrt_adap
     st->seconds_total += std::chrono::duration<double>(std::chrono::steady_clock::now() - wall0).count();
     return BHRT_OK;
 }
+
+// What the render entry points share: the photon map that photon_map = 1 needs, and statistics that start at zero and reach the caller also when
+// the render fails.  render(bhrt_stats *) does the work.
+template <class Render>
+static int RenderWithStats(bhrt_scene *scene, const bhrt_opts *opts, bhrt_stats *stats, const Render &render)
+{
+    if (opts->photon_map && !scene->dev->d_photons) { SetError("photon_map = 1 needs bhrt_photon_build first"); return BHRT_ERR_ARG; }
+    bhrt_stats local;
+    memset(&local, 0, sizeof local);
+    const int rc = render(&local);
+    if (stats) *stats = local;
+    return rc;
+}
+
+// The device copy of the frame behind bhrt_render_var and bhrt_render_adaptive.  It lives in HBM between calls (no allocation per frame); the variance
+// and count images are allocated when first asked for.  The copies run at the full PCIe rate when the caller's buffers are pinned (bhrt_host_alloc);
+// pageable buffers work at about half of it.
+struct FrameStage {
+    uint8_t *rgb8; float *radiance, *variance; uint32_t *count; // the caller's images; nullptr: not asked for
+    uint8_t *d_rgb8 = nullptr; float *d_radiance = nullptr, *d_variance = nullptr; uint32_t *d_count = nullptr; // their device copies, nullptr likewise
+    size_t npix = 0;
+    int Reserve(bhrt_scene *scene)
+    {
+        DeviceState *D = scene->dev;
+        npix = (size_t)scene->flat.hdr()->camera.width * scene->flat.hdr()->camera.height;
+        if (D->frame_px < npix) {
+            D->frame_px = 0;
+            BHRT_TRY(D->d_frame_rgb.Reserve(npix * 3));
+            BHRT_TRY(D->d_frame_rad.Reserve(npix * 3));
+            D->frame_px = npix;
+        }
+        if (variance) BHRT_TRY(D->d_frame_var.Reserve(npix * 3));
+        if (count) BHRT_TRY(D->d_frame_cnt.Reserve(npix));
+        d_rgb8 = rgb8 ? D->d_frame_rgb.p : nullptr; d_radiance = radiance ? D->d_frame_rad.p : nullptr;
+        d_variance = variance ? D->d_frame_var.p : nullptr; d_count = count ? D->d_frame_cnt.p : nullptr;
+        return BHRT_OK;
+    }
+    // world_size > 1: pixels of tiles owned by other ranks keep the caller's values, so they have to be in the device copy first
+    int Upload(hipStream_t s) const
+    {
+        if (rgb8) HIP_CHECK(hipMemcpyAsync(d_rgb8, rgb8, npix * 3, hipMemcpyHostToDevice, s));
+        if (radiance) HIP_CHECK(hipMemcpyAsync(d_radiance, radiance, npix * 12, hipMemcpyHostToDevice, s));
+        if (variance) HIP_CHECK(hipMemcpyAsync(d_variance, variance, npix * 12, hipMemcpyHostToDevice, s));
+        if (count) HIP_CHECK(hipMemcpyAsync(d_count, count, npix * 4, hipMemcpyHostToDevice, s));
+        return BHRT_OK;
+    }
+    int Download(hipStream_t s) const // and waits for the copies
+    {
+        if (rgb8) HIP_CHECK(hipMemcpyAsync(rgb8, d_rgb8, npix * 3, hipMemcpyDeviceToHost, s));
+        if (radiance) HIP_CHECK(hipMemcpyAsync(radiance, d_radiance, npix * 12, hipMemcpyDeviceToHost, s));
+        if (variance) HIP_CHECK(hipMemcpyAsync(variance, d_variance, npix * 12, hipMemcpyDeviceToHost, s));
+        if (count) HIP_CHECK(hipMemcpyAsync(count, d_count, npix * 4, hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipStreamSynchronize(s));
+        return BHRT_OK;
+    }
+};
 
 } // namespace bhrt
 
@@ -2784,7 +2717,7 @@ try {
     HIP_CHECK(hipStreamCreate(&D->stream));
     HIP_CHECK(hipEventCreate(&D->ev[0]));
     HIP_CHECK(hipEventCreate(&D->ev[1]));
-    HIP_CHECK(hipMalloc(&D->d_blob, blob.size()));
+    BHRT_TRY(D->d_blob.Reserve(blob.size()));
     HIP_CHECK(hipMemcpy(D->d_blob, blob.data(), blob.size(), hipMemcpyHostToDevice));
     // ancestor chains (depth-1 ancestor first, the node itself last)
     std::vector<int32_t> chain((size_t)std::max<uint32_t>(H->n_nodes, 1) * BHRT_MAX_NODE_DEPTH, 0);
@@ -2793,12 +2726,12 @@ try {
         int k = nodes[n].depth - 1, c = (int)n;
         while (c >= 0 && k >= 0) { chain[(size_t)n * BHRT_MAX_NODE_DEPTH + k] = c; c = nodes[c].parent; k--; }
     }
-    HIP_CHECK(hipMalloc(&D->d_chain, chain.size() * sizeof(int32_t)));
+    BHRT_TRY(D->d_chain.Reserve(chain.size()));
     HIP_CHECK(hipMemcpy(D->d_chain, chain.data(), chain.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-    HIP_CHECK(hipMalloc(&D->d_cnt, sizeof(Counters)));
+    BHRT_TRY(D->d_cnt.Reserve(1));
     if (H->n_meshes > 0) { // SlowQueue: the rays parallel to a coordinate axis of the mesh they enter
-        HIP_CHECK(hipMalloc(&D->d_slowf, (size_t)kSlowCap * 7 * sizeof(float)));
-        HIP_CHECK(hipMalloc(&D->d_slowu, (size_t)kSlowCap * 6 * sizeof(uint32_t)));
+        BHRT_TRY(D->d_slowf.Reserve((size_t)kSlowCap * 7));
+        BHRT_TRY(D->d_slowu.Reserve((size_t)kSlowCap * 6));
         {
             int lo_prio = 0, hi_prio = 0;
             (void)hipDeviceGetStreamPriorityRange(&lo_prio, &hi_prio);
@@ -2807,14 +2740,14 @@ try {
                 HIP_CHECK(hipStreamCreateWithPriority(&D->stream3, hipStreamNonBlocking, hi_prio));
                 HIP_CHECK(hipEventCreateWithFlags(&D->ev_shade, hipEventDisableTiming));
                 for (int k = 0; k < 2; k++) HIP_CHECK(hipEventCreateWithFlags(&D->ev_shadow[k], hipEventDisableTiming));
-                HIP_CHECK(hipMalloc(&D->d_seg_sh, (2 * BHRT_ORDER_SHARDS + 2) * sizeof(uint32_t)));
-                HIP_CHECK(hipMalloc(&D->d_cnt_sh, sizeof(Counters)));
+                BHRT_TRY(D->d_seg_sh.Reserve(2 * BHRT_ORDER_SHARDS + 2));
+                BHRT_TRY(D->d_cnt_sh.Reserve(1));
                 HIP_CHECK(hipMemset(D->d_cnt_sh, 0, sizeof(Counters)));
             }
         }
     }
-    HIP_CHECK(hipMalloc(&D->d_seg, (11 * BHRT_ORDER_SHARDS + 3) * sizeof(uint32_t)));
-    HIP_CHECK(hipHostMalloc(&D->h_pub, sizeof(HostCounters), hipHostMallocMapped));
+    BHRT_TRY(D->d_seg.Reserve(11 * BHRT_ORDER_SHARDS + 3));
+    BHRT_TRY(D->h_pub.Alloc(1, hipHostMallocMapped));
     memset(D->h_pub, 0, sizeof(HostCounters));
     HIP_CHECK(hipHostGetDevicePointer((void **)&D->d_pub, D->h_pub, 0));
     DevScene &S = D->S;
@@ -2851,7 +2784,7 @@ try {
             aux[m] = (float)(r0d * r0d);
         }
         for (uint32_t l = 0; l < H->n_lights; l++) aux[H->n_materials + l] = ((lts[l].intensity[0] + lts[l].intensity[1] + lts[l].intensity[2]) / 3.0f) / H->all_light_intensity;
-        HIP_CHECK(hipMalloc(&D->d_aux, aux.size() * sizeof(float)));
+        BHRT_TRY(D->d_aux.Reserve(aux.size()));
         HIP_CHECK(hipMemcpy(D->d_aux, aux.data(), aux.size() * sizeof(float), hipMemcpyHostToDevice));
         S.mat_r0 = D->d_aux;
         S.light_pick = D->d_aux + H->n_materials;
@@ -2873,11 +2806,9 @@ try {
 static int EnsureApiScratch(DeviceState *D, size_t n)
 {
     if (D->api_cap >= n) return BHRT_OK;
-    if (D->d_api_f) (void)hipFree(D->d_api_f);
-    if (D->d_api_i) (void)hipFree(D->d_api_i);
-    D->d_api_f = nullptr; D->d_api_i = nullptr; D->api_cap = 0;
-    HIP_CHECK(hipMalloc(&D->d_api_f, n * 9 * sizeof(float)));
-    HIP_CHECK(hipMalloc(&D->d_api_i, n * 3 * sizeof(int32_t)));
+    D->api_cap = 0;
+    BHRT_TRY(D->d_api_f.Reserve(n * 9));
+    BHRT_TRY(D->d_api_i.Reserve(n * 3));
     D->api_cap = n;
     return BHRT_OK;
 }
@@ -2929,10 +2860,8 @@ try {
     if (!d_rays_soa || !d_tmax || !d_vis) { SetError("null buffer"); return BHRT_ERR_ARG; }
     if (n == 0) return BHRT_OK;
     if (n > 0x7fffffffu) { SetError("too many rays for one call"); return BHRT_ERR_ARG; }
-    ShadowQueue q;
-    float *f = const_cast<float *>(d_rays_soa);
-    q.ox = f; q.oy = f + n; q.oz = f + 2 * n; q.dx = f + 3 * n; q.dy = f + 4 * n; q.dz = f + 5 * n;
-    q.tmax = const_cast<float *>(d_tmax); q.frame = nullptr;
+    ShadowQueue q = MakeShadowQueue(const_cast<float *>(d_rays_soa), nullptr, n);
+    q.tmax = const_cast<float *>(d_tmax);
     hipStream_t s = stream ? (hipStream_t)stream : scene->dev->stream;
     auto shadow_kernel = scene->flat.hdr()->n_meshes > 0 ? k_trace_shadow<true> : k_trace_shadow<false>;
     hipLaunchKernelGGL(shadow_kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, scene->dev->S, q,
@@ -2965,12 +2894,7 @@ try {
     int rc = EnsureUploaded(scene);
     if (rc) return rc;
     if (!opts) { SetError("null opts"); return BHRT_ERR_ARG; }
-    if (opts->photon_map && !scene->dev->d_photons) { SetError("photon_map = 1 needs bhrt_photon_build first"); return BHRT_ERR_ARG; }
-    bhrt_stats local;
-    memset(&local, 0, sizeof local);
-    rc = RenderRange(scene, *opts, d_rgb8, d_radiance, &local, nullptr, 0, 0, 0, 0, d_variance);
-    if (stats) *stats = local;
-    return rc;
+    return RenderWithStats(scene, opts, stats, [&](bhrt_stats *st) { return RenderRange(scene, *opts, d_rgb8, d_radiance, st, nullptr, 0, 0, 0, 0, d_variance); });
 } catch (...) { return bhrt::AbiException(); }
 
 int bhrt_render_dev(bhrt_scene *scene, const bhrt_opts *opts, uint8_t *d_rgb8, float *d_radiance, bhrt_stats *stats, void *stream)
@@ -2988,37 +2912,11 @@ try {
     int rc = EnsureUploaded(scene);
     if (rc) return rc;
     if (!opts) { SetError("null opts"); return BHRT_ERR_ARG; }
-    DeviceState *D = scene->dev;
-    const bhrt_flat_header *H = scene->flat.hdr();
-    const size_t npix = (size_t)H->camera.width * H->camera.height;
-    // The frame lives in HBM between calls (no allocation per frame).  The copies run at the full PCIe rate when the caller's
-    // buffers are pinned (bhrt_host_alloc); pageable buffers work at about half of it.
-    if (D->frame_px < npix) {
-        if (D->d_frame_rgb) (void)hipFree(D->d_frame_rgb);
-        if (D->d_frame_rad) (void)hipFree(D->d_frame_rad);
-        D->d_frame_rgb = nullptr; D->d_frame_rad = nullptr; D->frame_px = 0;
-        HIP_CHECK(hipMalloc(&D->d_frame_rgb, npix * 3));
-        HIP_CHECK(hipMalloc(&D->d_frame_rad, npix * 3 * sizeof(float)));
-        D->frame_px = npix;
-    }
-    if (variance && D->frame_var_px < npix) {
-        if (D->d_frame_var) (void)hipFree(D->d_frame_var);
-        D->d_frame_var = nullptr; D->frame_var_px = 0;
-        HIP_CHECK(hipMalloc(&D->d_frame_var, npix * 3 * sizeof(float)));
-        D->frame_var_px = npix;
-    }
-    if (opts->world_size > 1) { // pixels of tiles owned by other ranks keep the caller's values: they have to be in the device copy first
-        if (rgb8) HIP_CHECK(hipMemcpyAsync(D->d_frame_rgb, rgb8, npix * 3, hipMemcpyHostToDevice, D->stream));
-        if (radiance) HIP_CHECK(hipMemcpyAsync(D->d_frame_rad, radiance, npix * 12, hipMemcpyHostToDevice, D->stream));
-        if (variance) HIP_CHECK(hipMemcpyAsync(D->d_frame_var, variance, npix * 12, hipMemcpyHostToDevice, D->stream));
-    }
-    rc = bhrt_render_var_dev(scene, opts, rgb8 ? D->d_frame_rgb : nullptr, radiance ? D->d_frame_rad : nullptr, variance ? D->d_frame_var : nullptr, stats, nullptr);
-    if (rc) return rc;
-    if (rgb8) HIP_CHECK(hipMemcpyAsync(rgb8, D->d_frame_rgb, npix * 3, hipMemcpyDeviceToHost, D->stream));
-    if (radiance) HIP_CHECK(hipMemcpyAsync(radiance, D->d_frame_rad, npix * 12, hipMemcpyDeviceToHost, D->stream));
-    if (variance) HIP_CHECK(hipMemcpyAsync(variance, D->d_frame_var, npix * 12, hipMemcpyDeviceToHost, D->stream));
-    HIP_CHECK(hipStreamSynchronize(D->stream));
-    return BHRT_OK;
+    FrameStage fs = {rgb8, radiance, variance, nullptr};
+    BHRT_TRY(fs.Reserve(scene));
+    if (opts->world_size > 1) BHRT_TRY(fs.Upload(scene->dev->stream));
+    BHRT_TRY(bhrt_render_var_dev(scene, opts, fs.d_rgb8, fs.d_radiance, fs.d_variance, stats, nullptr));
+    return fs.Download(scene->dev->stream);
 } catch (...) { return bhrt::AbiException(); }
 
 // ---- adaptive sampling (RenderAdaptive) -----------------------------------------------------------------
@@ -3042,12 +2940,7 @@ try {
     if (*bad) { SetError(bad); return BHRT_ERR_ARG; }
     int rc = EnsureUploaded(scene);
     if (rc) return rc;
-    if (opts->photon_map && !scene->dev->d_photons) { SetError("photon_map = 1 needs bhrt_photon_build first"); return BHRT_ERR_ARG; }
-    bhrt_stats local;
-    memset(&local, 0, sizeof local);
-    rc = RenderAdaptive(scene, *opts, *aopts, d_rgb8, d_radiance, d_variance, d_count, &local);
-    if (stats) *stats = local;
-    return rc;
+    return RenderWithStats(scene, opts, stats, [&](bhrt_stats *st) { return RenderAdaptive(scene, *opts, *aopts, d_rgb8, d_radiance, d_variance, d_count, st); });
 } catch (...) { return bhrt::AbiException(); }
 
 int bhrt_render_adaptive(bhrt_scene *scene, const bhrt_opts *opts, const bhrt_adaptive_opts *aopts, uint8_t *rgb8, float *radiance, float *variance,
@@ -3057,45 +2950,11 @@ try {
     if (*bad) { SetError(bad); return BHRT_ERR_ARG; }
     int rc = EnsureUploaded(scene);
     if (rc) return rc;
-    DeviceState *D = scene->dev;
-    const bhrt_flat_header *H = scene->flat.hdr();
-    const size_t npix = (size_t)H->camera.width * H->camera.height;
-    // the device copies of bhrt_render_var, and one of the count image
-    if (D->frame_px < npix) {
-        if (D->d_frame_rgb) (void)hipFree(D->d_frame_rgb);
-        if (D->d_frame_rad) (void)hipFree(D->d_frame_rad);
-        D->d_frame_rgb = nullptr; D->d_frame_rad = nullptr; D->frame_px = 0;
-        HIP_CHECK(hipMalloc(&D->d_frame_rgb, npix * 3));
-        HIP_CHECK(hipMalloc(&D->d_frame_rad, npix * 3 * sizeof(float)));
-        D->frame_px = npix;
-    }
-    if (variance && D->frame_var_px < npix) {
-        if (D->d_frame_var) (void)hipFree(D->d_frame_var);
-        D->d_frame_var = nullptr; D->frame_var_px = 0;
-        HIP_CHECK(hipMalloc(&D->d_frame_var, npix * 3 * sizeof(float)));
-        D->frame_var_px = npix;
-    }
-    if (count && D->frame_cnt_px < npix) {
-        if (D->d_frame_cnt) (void)hipFree(D->d_frame_cnt);
-        D->d_frame_cnt = nullptr; D->frame_cnt_px = 0;
-        HIP_CHECK(hipMalloc(&D->d_frame_cnt, npix * sizeof(uint32_t)));
-        D->frame_cnt_px = npix;
-    }
-    if (opts->world_size > 1) { // pixels of tiles owned by other ranks keep the caller's values
-        if (rgb8) HIP_CHECK(hipMemcpyAsync(D->d_frame_rgb, rgb8, npix * 3, hipMemcpyHostToDevice, D->stream));
-        if (radiance) HIP_CHECK(hipMemcpyAsync(D->d_frame_rad, radiance, npix * 12, hipMemcpyHostToDevice, D->stream));
-        if (variance) HIP_CHECK(hipMemcpyAsync(D->d_frame_var, variance, npix * 12, hipMemcpyHostToDevice, D->stream));
-        if (count) HIP_CHECK(hipMemcpyAsync(D->d_frame_cnt, count, npix * 4, hipMemcpyHostToDevice, D->stream));
-    }
-    rc = bhrt_render_adaptive_dev(scene, opts, aopts, rgb8 ? D->d_frame_rgb : nullptr, radiance ? D->d_frame_rad : nullptr, variance ? D->d_frame_var : nullptr,
-                                  count ? D->d_frame_cnt : nullptr, stats, nullptr);
-    if (rc) return rc;
-    if (rgb8) HIP_CHECK(hipMemcpyAsync(rgb8, D->d_frame_rgb, npix * 3, hipMemcpyDeviceToHost, D->stream));
-    if (radiance) HIP_CHECK(hipMemcpyAsync(radiance, D->d_frame_rad, npix * 12, hipMemcpyDeviceToHost, D->stream));
-    if (variance) HIP_CHECK(hipMemcpyAsync(variance, D->d_frame_var, npix * 12, hipMemcpyDeviceToHost, D->stream));
-    if (count) HIP_CHECK(hipMemcpyAsync(count, D->d_frame_cnt, npix * 4, hipMemcpyDeviceToHost, D->stream));
-    HIP_CHECK(hipStreamSynchronize(D->stream));
-    return BHRT_OK;
+    FrameStage fs = {rgb8, radiance, variance, count};
+    BHRT_TRY(fs.Reserve(scene));
+    if (opts->world_size > 1) BHRT_TRY(fs.Upload(scene->dev->stream));
+    BHRT_TRY(bhrt_render_adaptive_dev(scene, opts, aopts, fs.d_rgb8, fs.d_radiance, fs.d_variance, fs.d_count, stats, nullptr));
+    return fs.Download(scene->dev->stream);
 } catch (...) { return bhrt::AbiException(); }
 
 int bhrt_sample_count_image_dev(bhrt_scene *scene, const uint32_t *d_count, size_t n, uint8_t *d_img, uint32_t *smax, void *stream)
@@ -3107,7 +2966,7 @@ try {
     rc = EnsureApiScratch(D, 16);
     if (rc) return rc;
     hipStream_t st = stream ? (hipStream_t)stream : D->stream;
-    uint32_t *range = (uint32_t *)D->d_api_f;
+    uint32_t *range = (uint32_t *)D->d_api_f.p;
     hipLaunchKernelGGL(k_count_range, dim3(1), dim3(1024), 0, st, d_count, (uint32_t)n, range);
     hipLaunchKernelGGL(k_count_image, dim3(((uint32_t)n + kBlock - 1) / kBlock), dim3(kBlock), 0, st, d_count, (uint32_t)n, (const uint32_t *)range, d_img);
     HIP_CHECK(hipGetLastError());
@@ -3123,17 +2982,13 @@ try {
     if (!count || !img || n == 0 || n > 0xffffffffull) { SetError("bad sample-count image arguments"); return BHRT_ERR_ARG; }
     int rc = EnsureUploaded(scene);
     if (rc) return rc;
-    uint32_t *d_c = nullptr;
-    HIP_CHECK(hipMalloc(&d_c, n * (sizeof(uint32_t) + 1)));
+    DevBuf<uint32_t> d_c; // the counts, then the image's n bytes
+    BHRT_TRY(d_c.Reserve(n + (n + 3) / 4));
     uint8_t *d_i = (uint8_t *)(d_c + n);
-    hipError_t e = hipMemcpy(d_c, count, n * sizeof(uint32_t), hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        rc = bhrt_sample_count_image_dev(scene, d_c, n, d_i, smax, nullptr);
-        if (rc == BHRT_OK) e = hipMemcpy(img, d_i, n, hipMemcpyDeviceToHost);
-    }
-    (void)hipFree(d_c);
-    HIP_CHECK(e);
-    return rc;
+    HIP_CHECK(hipMemcpy(d_c, count, n * sizeof(uint32_t), hipMemcpyHostToDevice));
+    BHRT_TRY(bhrt_sample_count_image_dev(scene, d_c, n, d_i, smax, nullptr));
+    HIP_CHECK(hipMemcpy(img, d_i, n, hipMemcpyDeviceToHost));
+    return BHRT_OK;
 } catch (...) { return bhrt::AbiException(); }
 
 // pinned host memory for frame buffers handed to bhrt_render (and anything else that crosses PCIe)
@@ -3158,18 +3013,15 @@ try {
     if (!opts || !samples) { SetError("null argument"); return BHRT_ERR_ARG; }
     const bhrt_flat_header *H = scene->flat.hdr();
     if (x0 < 0 || y0 < 0 || x1 > H->camera.width || y1 > H->camera.height || x0 >= x1 || y0 >= y1) { SetError("bad region"); return BHRT_ERR_ARG; }
-    if (opts->photon_map && !scene->dev->d_photons) { SetError("photon_map = 1 needs bhrt_photon_build first"); return BHRT_ERR_ARG; }
     const size_t nfl = (size_t)(x1 - x0) * (y1 - y0) * opts->spp * 3;
-    float *d_s = nullptr;
-    HIP_CHECK(hipMalloc(&d_s, nfl * sizeof(float)));
-    HIP_CHECK(hipMemset(d_s, 0, nfl * sizeof(float)));
-    bhrt_stats local;
-    memset(&local, 0, sizeof local);
-    rc = RenderRange(scene, *opts, nullptr, nullptr, &local, d_s, x0, y0, x1, y1);
-    if (rc == BHRT_OK) HIP_CHECK(hipMemcpy(samples, d_s, nfl * sizeof(float), hipMemcpyDeviceToHost));
-    (void)hipFree(d_s);
-    if (stats) *stats = local;
-    return rc;
+    DevBuf<float> d_s;
+    return RenderWithStats(scene, opts, stats, [&](bhrt_stats *st) -> int {
+        BHRT_TRY(d_s.Reserve(nfl));
+        HIP_CHECK(hipMemset(d_s, 0, nfl * sizeof(float)));
+        BHRT_TRY(RenderRange(scene, *opts, nullptr, nullptr, st, d_s, x0, y0, x1, y1));
+        HIP_CHECK(hipMemcpy(samples, d_s, nfl * sizeof(float), hipMemcpyDeviceToHost));
+        return BHRT_OK;
+    });
 } catch (...) { return bhrt::AbiException(); }
 
 // ---- images beside the colour image ---------------------------------------------------------------
@@ -3192,20 +3044,14 @@ int bhrt_first_hit(bhrt_scene *scene, float *z, float *normal, float *albedo)
 try {
     int rc = EnsureUploaded(scene);
     if (rc) return rc;
-    DeviceState *D = scene->dev;
     const bhrt_flat_header *H = scene->flat.hdr();
     const size_t n = (size_t)H->camera.width * H->camera.height;
-    float *d = nullptr;
-    HIP_CHECK(hipMalloc(&d, n * 7 * sizeof(float)));
-    rc = bhrt_first_hit_dev(scene, z ? d : nullptr, normal ? d + n : nullptr, albedo ? d + 4 * n : nullptr, nullptr);
-    hipError_t e = hipSuccess;
-    if (!rc && z) e = hipMemcpy(z, d, n * sizeof(float), hipMemcpyDeviceToHost);
-    if (!rc && e == hipSuccess && normal) e = hipMemcpy(normal, d + n, 3 * n * sizeof(float), hipMemcpyDeviceToHost);
-    if (!rc && e == hipSuccess && albedo) e = hipMemcpy(albedo, d + 4 * n, 3 * n * sizeof(float), hipMemcpyDeviceToHost);
-    (void)hipFree(d);
-    (void)D;
-    if (rc) return rc;
-    HIP_CHECK(e);
+    DevBuf<float> d;
+    BHRT_TRY(d.Reserve(n * 7));
+    BHRT_TRY(bhrt_first_hit_dev(scene, z ? d.p : nullptr, normal ? d + n : nullptr, albedo ? d + 4 * n : nullptr, nullptr));
+    if (z) HIP_CHECK(hipMemcpy(z, d, n * sizeof(float), hipMemcpyDeviceToHost));
+    if (normal) HIP_CHECK(hipMemcpy(normal, d + n, 3 * n * sizeof(float), hipMemcpyDeviceToHost));
+    if (albedo) HIP_CHECK(hipMemcpy(albedo, d + 4 * n, 3 * n * sizeof(float), hipMemcpyDeviceToHost));
     return BHRT_OK;
 } catch (...) { return bhrt::AbiException(); }
 
@@ -3261,15 +3107,10 @@ try {
     const bool guides = opts->iterations > 0 && (!d_z || !d_normal || !d_albedo); // K = 0 reads no guide
     if (opts->iterations > 0) {
         const size_t need = DenoisePlaneBytes(W, Hh) + (guides ? n * 7 * sizeof(float) : 0);
-        if (D->dn_bytes < need) {
-            if (D->d_dn) HIP_CHECK(hipFree(D->d_dn)); // waits for the device: a previous call's kernels may still read it
-            D->d_dn = nullptr; D->dn_bytes = 0;
-            HIP_CHECK(hipMalloc(&D->d_dn, need));
-            D->dn_bytes = need;
-        }
-        J.planes = (float4 *)D->d_dn;
+        BHRT_TRY(D->d_dn.Reserve(need));
+        J.planes = (float4 *)D->d_dn.p;
         if (guides) { // the first hit of bhrt_first_hit_dev, into the scratch behind the planes, for the guides not given
-            float *g = (float *)(D->d_dn + DenoisePlaneBytes(W, Hh));
+            float *g = (float *)(D->d_dn.p + DenoisePlaneBytes(W, Hh));
             float *gz = d_z ? nullptr : g, *gn = d_normal ? nullptr : g + n, *ga = d_albedo ? nullptr : g + 4 * n;
             hipLaunchKernelGGL(k_first_hit, dim3(((uint32_t)n + kBlock - 1) / kBlock), dim3(kBlock), 0, st, D->S, W, Hh, gz, gn, ga);
             if (gz) J.z = gz;
@@ -3296,24 +3137,20 @@ try {
     const bhrt_flat_header *H = scene->flat.hdr();
     const size_t n = (size_t)H->camera.width * H->camera.height;
     // device copies, back to back: radiance, variance, normal, albedo, out (3n floats each), z (n), rgb8 (3n bytes)
-    uint8_t *d = nullptr;
-    HIP_CHECK(hipMalloc(&d, n * 67));
-    float *f = (float *)d;
+    DevBuf<uint8_t> d;
+    BHRT_TRY(d.Reserve(n * 67));
+    float *f = (float *)d.p;
     float *d_c = f, *d_v = f + 3 * n, *d_n = f + 6 * n, *d_a = f + 9 * n, *d_o = f + 12 * n, *d_z = f + 15 * n;
-    uint8_t *d_rgb = d + n * 64;
-    hipError_t e = hipMemcpyAsync(d_c, radiance, n * 12, hipMemcpyHostToDevice, D->stream);
-    if (e == hipSuccess && variance) e = hipMemcpyAsync(d_v, variance, n * 12, hipMemcpyHostToDevice, D->stream);
-    if (e == hipSuccess && normal) e = hipMemcpyAsync(d_n, normal, n * 12, hipMemcpyHostToDevice, D->stream);
-    if (e == hipSuccess && albedo) e = hipMemcpyAsync(d_a, albedo, n * 12, hipMemcpyHostToDevice, D->stream);
-    if (e == hipSuccess && z) e = hipMemcpyAsync(d_z, z, n * 4, hipMemcpyHostToDevice, D->stream);
-    if (e == hipSuccess)
-        rc = bhrt_denoise_dev(scene, opts, d_c, variance ? d_v : nullptr, z ? d_z : nullptr, normal ? d_n : nullptr, albedo ? d_a : nullptr, out ? d_o : nullptr,
-                              rgb8 ? d_rgb : nullptr, nullptr);
-    if (e == hipSuccess && !rc && out) e = hipMemcpy(out, d_o, n * 12, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && !rc && rgb8) e = hipMemcpy(rgb8, d_rgb, n * 3, hipMemcpyDeviceToHost);
-    (void)hipFree(d);
-    if (rc) return rc;
-    HIP_CHECK(e);
+    uint8_t *d_rgb = d.p + n * 64;
+    HIP_CHECK(hipMemcpyAsync(d_c, radiance, n * 12, hipMemcpyHostToDevice, D->stream));
+    if (variance) HIP_CHECK(hipMemcpyAsync(d_v, variance, n * 12, hipMemcpyHostToDevice, D->stream));
+    if (normal) HIP_CHECK(hipMemcpyAsync(d_n, normal, n * 12, hipMemcpyHostToDevice, D->stream));
+    if (albedo) HIP_CHECK(hipMemcpyAsync(d_a, albedo, n * 12, hipMemcpyHostToDevice, D->stream));
+    if (z) HIP_CHECK(hipMemcpyAsync(d_z, z, n * 4, hipMemcpyHostToDevice, D->stream));
+    BHRT_TRY(bhrt_denoise_dev(scene, opts, d_c, variance ? d_v : nullptr, z ? d_z : nullptr, normal ? d_n : nullptr, albedo ? d_a : nullptr, out ? d_o : nullptr,
+                              rgb8 ? d_rgb : nullptr, nullptr));
+    if (out) HIP_CHECK(hipMemcpy(out, d_o, n * 12, hipMemcpyDeviceToHost));
+    if (rgb8) HIP_CHECK(hipMemcpy(rgb8, d_rgb, n * 3, hipMemcpyDeviceToHost));
     return BHRT_OK;
 } catch (...) { return bhrt::AbiException(); }
 
@@ -3363,30 +3200,26 @@ try {
     if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) { SetError("no HIP device available"); return BHRT_ERR_NO_DEVICE; }
     if (!a || !out || fn < 0 || fn > 9) { SetError("bad argument"); return BHRT_ERR_ARG; }
     if (n == 0) return BHRT_OK;
-    float *d = nullptr;
-    HIP_CHECK(hipMalloc(&d, n * 3 * sizeof(float)));
+    DevBuf<float> d;
+    BHRT_TRY(d.Reserve(n * 3));
     HIP_CHECK(hipMemcpy(d, a, n * sizeof(float), hipMemcpyHostToDevice));
     if (b) HIP_CHECK(hipMemcpy(d + n, b, n * sizeof(float), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_math_eval, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, 0, fn, d, b ? d + n : nullptr, (uint32_t)n, d + 2 * n);
+    hipLaunchKernelGGL(k_math_eval, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, 0, fn, d.p, b ? d + n : nullptr, (uint32_t)n, d + 2 * n);
     HIP_CHECK(hipDeviceSynchronize());
     HIP_CHECK(hipMemcpy(out, d + 2 * n, n * sizeof(float), hipMemcpyDeviceToHost));
-    (void)hipFree(d);
     return BHRT_OK;
 } catch (...) { return bhrt::AbiException(); }
 
 // PrepareForIrradianceEstimation (cyPhotonMap.h:236-258) on the device (device_photon_build.h): d_in = n + 1 records in emission order, slot 0
-// zero, powers scaled; *d_out = a new buffer with the balanced map in heap order (the caller owns it).
-static int BalanceOnDevice(DeviceState *D, const DPhoton *d_in, uint32_t n, DPhoton **d_out)
+// zero, powers scaled; out (empty on entry) receives the balanced map in heap order.
+static int BalanceOnDevice(DeviceState *D, const DPhoton *d_in, uint32_t n, DevBuf<DPhoton> &out)
 {
-    struct Bufs {
-        uint32_t *id = nullptr, *la = nullptr, *lb = nullptr, *count = nullptr; float *key = nullptr; PbSeg *seg[2] = {nullptr, nullptr}; DPhoton *out = nullptr;
-        ~Bufs() { (void)hipFree(id); (void)hipFree(la); (void)hipFree(lb); (void)hipFree(count); (void)hipFree(key); (void)hipFree(seg[0]); (void)hipFree(seg[1]); (void)hipFree(out); }
-    } b;
+    struct { DevBuf<uint32_t> id, la, lb, count; DevBuf<float> key; DevBuf<PbSeg> seg[2]; } b;
     const size_t n2 = (size_t)n + 2, max_segs = (size_t)n / 2 + 2;
-    HIP_CHECK(hipMalloc(&b.id, n2 * 4)); HIP_CHECK(hipMalloc(&b.la, n2 * 4)); HIP_CHECK(hipMalloc(&b.lb, n2 * 4)); HIP_CHECK(hipMalloc(&b.key, n2 * 4));
-    HIP_CHECK(hipMalloc(&b.count, 4)); HIP_CHECK(hipMalloc(&b.seg[0], max_segs * sizeof(PbSeg))); HIP_CHECK(hipMalloc(&b.seg[1], max_segs * sizeof(PbSeg)));
-    HIP_CHECK(hipMalloc(&b.out, ((size_t)n + 1) * sizeof(DPhoton)));
-    HIP_CHECK(hipMemsetAsync(b.out, 0, ((size_t)n + 1) * sizeof(DPhoton), D->stream));
+    BHRT_TRY(b.id.Reserve(n2)); BHRT_TRY(b.la.Reserve(n2)); BHRT_TRY(b.lb.Reserve(n2)); BHRT_TRY(b.key.Reserve(n2));
+    BHRT_TRY(b.count.Reserve(1)); BHRT_TRY(b.seg[0].Reserve(max_segs)); BHRT_TRY(b.seg[1].Reserve(max_segs));
+    BHRT_TRY(out.Reserve((size_t)n + 1));
+    HIP_CHECK(hipMemsetAsync(out, 0, ((size_t)n + 1) * sizeof(DPhoton), D->stream));
     hipLaunchKernelGGL(k_pb_root, dim3(1), dim3(1024), 0, D->stream, d_in, n, b.seg[0], b.id);
     uint32_t count = 1;
     int cur = 0;
@@ -3394,73 +3227,55 @@ static int BalanceOnDevice(DeviceState *D, const DPhoton *d_in, uint32_t n, DPho
         if (level > 64) { SetError("photon balance: more than 64 levels"); return BHRT_ERR_HIP; }
         HIP_CHECK(hipMemsetAsync(b.count, 0, 4, D->stream));
         const uint64_t avg = (uint64_t)n / count; // segments of a level have nearly equal sizes: the workgroup that suits them
-        if (avg > 2048) hipLaunchKernelGGL(k_pb_level<1024>, dim3(count), dim3(1024), 0, D->stream, d_in, b.id, b.key, b.la, b.lb, b.seg[cur], count, b.seg[cur ^ 1], b.count, b.out);
-        else if (avg > 64) hipLaunchKernelGGL(k_pb_level<256>, dim3(count), dim3(256), 0, D->stream, d_in, b.id, b.key, b.la, b.lb, b.seg[cur], count, b.seg[cur ^ 1], b.count, b.out);
-        else hipLaunchKernelGGL(k_pb_level<64>, dim3(count), dim3(64), 0, D->stream, d_in, b.id, b.key, b.la, b.lb, b.seg[cur], count, b.seg[cur ^ 1], b.count, b.out);
+        if (avg > 2048) hipLaunchKernelGGL(k_pb_level<1024>, dim3(count), dim3(1024), 0, D->stream, d_in, b.id, b.key, b.la, b.lb, b.seg[cur], count, b.seg[cur ^ 1], b.count, out);
+        else if (avg > 64) hipLaunchKernelGGL(k_pb_level<256>, dim3(count), dim3(256), 0, D->stream, d_in, b.id, b.key, b.la, b.lb, b.seg[cur], count, b.seg[cur ^ 1], b.count, out);
+        else hipLaunchKernelGGL(k_pb_level<64>, dim3(count), dim3(64), 0, D->stream, d_in, b.id, b.key, b.la, b.lb, b.seg[cur], count, b.seg[cur ^ 1], b.count, out);
         HIP_CHECK(hipMemcpyAsync(&count, b.count, 4, hipMemcpyDeviceToHost, D->stream));
         HIP_CHECK(hipStreamSynchronize(D->stream));
         if (count > max_segs) { SetError("photon balance: segment list overflow"); return BHRT_ERR_HIP; }
         cur ^= 1;
     }
-    *d_out = b.out;
-    b.out = nullptr;
     return BHRT_OK;
 }
 
-// A balanced map (heap order, slot 0 unused) that lies in HBM -> installed for the gather: the 24-byte records stay where they are (the device
-// owns them from here on), the decoded hot / cold copy the gather walks (PhotonMapDev), the direction bounds of the top levels and the bounds of
-// the positions are formed on the device.  The host copy (bhrt_photon_get / _export) is fetched when somebody asks for it.
-static int InstallPhotonMapDev(DeviceState *D, DPhoton *d_balanced, uint32_t n)
+// A balanced map (heap order, slot 0 unused) that lies in HBM -> installed for the gather: the 24-byte records stay where they are (the scene owns
+// them from here on), the decoded hot / cold copy the gather walks (PhotonMapDev), the direction bounds of the top levels and the bounds of the
+// positions are formed on the device.  The map that was installed before stays in place until all of that is there.  The host copy
+// (bhrt_photon_get / _export) is fetched when somebody asks for it.
+static int InstallPhotonMapDev(DeviceState *D, DevBuf<DPhoton> balanced, uint32_t n)
 {
-    if (D->d_photons && D->d_photons != d_balanced) (void)hipFree(D->d_photons);
-    D->d_photons = d_balanced;
-    D->n_photons = n;
-    D->h_photons.clear();
-    if (D->d_ph_hot) (void)hipFree(D->d_ph_hot);
-    if (D->d_ph_cold) (void)hipFree(D->d_ph_cold);
-    D->d_ph_hot = nullptr; D->d_ph_cold = nullptr;
-    HIP_CHECK(hipMalloc(&D->d_ph_hot, ((size_t)n + 1) * sizeof(float4)));
-    HIP_CHECK(hipMalloc(&D->d_ph_cold, ((size_t)n + 1) * 2 * sizeof(float4)));
-    hipLaunchKernelGGL(k_photon_expand, dim3((n + 1 + kBlock - 1) / kBlock), dim3(kBlock), 0, D->stream, D->d_photons, n, D->d_ph_hot, D->d_ph_cold);
-    D->pm.hot = D->d_ph_hot; D->pm.cold = D->d_ph_cold; D->pm.n = (int)n; D->pm.half = (int)n / 2 - 1;
-    { // PhotonMapDev::dbox, bottom up, one heap level per launch
-        struct Tmp { float *lo = nullptr, *hi = nullptr, *b6 = nullptr; ~Tmp() { (void)hipFree(lo); (void)hipFree(hi); (void)hipFree(b6); } } t;
-        HIP_CHECK(hipMalloc(&t.lo, ((size_t)n + 1) * 3 * sizeof(float)));
-        HIP_CHECK(hipMalloc(&t.hi, ((size_t)n + 1) * 3 * sizeof(float)));
-        HIP_CHECK(hipMalloc(&t.b6, 6 * sizeof(float)));
-        int top = 0;
-        while ((2ull << top) <= (uint64_t)n) top++; // level of node n
-        for (int L = top; L >= 0; L--) {
-            const uint32_t first = 1u << L, last = (uint32_t)std::min<uint64_t>((2ull << L) - 1, n);
-            hipLaunchKernelGGL(k_pb_dbox_level, dim3((last - first + 256) / 256), dim3(256), 0, D->stream, D->d_photons, n, D->pm.half, first, last, t.lo, t.hi);
-        }
-        const uint32_t nb = std::min<uint32_t>(n + 1, 1u << BHRT_DBOX_LEVELS);
-        if (D->d_ph_dbox) (void)hipFree(D->d_ph_dbox);
-        D->d_ph_dbox = nullptr;
-        HIP_CHECK(hipMalloc(&D->d_ph_dbox, (size_t)nb * 2 * sizeof(float4)));
-        hipLaunchKernelGGL(k_pb_dbox_pack, dim3((nb + 255) / 256), dim3(256), 0, D->stream, t.lo, t.hi, nb, D->d_ph_dbox);
-        D->pm.dbox = D->d_ph_dbox; D->pm.n_dbox = (int)nb;
-        hipLaunchKernelGGL(k_pb_bounds, dim3(1), dim3(1024), 0, D->stream, D->d_photons, n, t.b6);
-        float b6[6];
-        HIP_CHECK(hipMemcpyAsync(b6, t.b6, sizeof b6, hipMemcpyDeviceToHost, D->stream));
-        HIP_CHECK(hipStreamSynchronize(D->stream));
-        for (int k = 0; k < 3; k++) { D->pm.lo[k] = b6[k]; D->pm.hi[k] = b6[3 + k]; }
+    DevBuf<float4> hot, cold, dbox;
+    DevBuf<float> lo, hi, d_b6;
+    PhotonMapDev pm = D->pm;
+    BHRT_TRY(hot.Reserve((size_t)n + 1));
+    BHRT_TRY(cold.Reserve(((size_t)n + 1) * 2));
+    hipLaunchKernelGGL(k_photon_expand, dim3((n + 1 + kBlock - 1) / kBlock), dim3(kBlock), 0, D->stream, balanced.p, n, hot.p, cold.p);
+    pm.hot = hot; pm.cold = cold; pm.n = (int)n; pm.half = (int)n / 2 - 1;
+    // PhotonMapDev::dbox, bottom up, one heap level per launch
+    BHRT_TRY(lo.Reserve(((size_t)n + 1) * 3));
+    BHRT_TRY(hi.Reserve(((size_t)n + 1) * 3));
+    BHRT_TRY(d_b6.Reserve(6));
+    int top = 0;
+    while ((2ull << top) <= (uint64_t)n) top++; // level of node n
+    for (int L = top; L >= 0; L--) {
+        const uint32_t first = 1u << L, last = (uint32_t)std::min<uint64_t>((2ull << L) - 1, n);
+        hipLaunchKernelGGL(k_pb_dbox_level, dim3((last - first + 256) / 256), dim3(256), 0, D->stream, balanced.p, n, pm.half, first, last, lo.p, hi.p);
     }
+    const uint32_t nb = std::min<uint32_t>(n + 1, 1u << BHRT_DBOX_LEVELS);
+    BHRT_TRY(dbox.Reserve((size_t)nb * 2));
+    hipLaunchKernelGGL(k_pb_dbox_pack, dim3((nb + 255) / 256), dim3(256), 0, D->stream, lo.p, hi.p, nb, dbox.p);
+    pm.dbox = dbox; pm.n_dbox = (int)nb;
+    hipLaunchKernelGGL(k_pb_bounds, dim3(1), dim3(1024), 0, D->stream, balanced.p, n, d_b6.p);
+    float b6[6];
+    HIP_CHECK(hipMemcpyAsync(b6, d_b6, sizeof b6, hipMemcpyDeviceToHost, D->stream));
+    HIP_CHECK(hipStreamSynchronize(D->stream));
+    for (int k = 0; k < 3; k++) { pm.lo[k] = b6[k]; pm.hi[k] = b6[3 + k]; }
+    // all of it is there: the new map takes the place of the old one
+    D->d_photons = std::move(balanced); D->d_ph_hot = std::move(hot); D->d_ph_cold = std::move(cold); D->d_ph_dbox = std::move(dbox);
+    D->n_photons = n;
+    D->pm = pm;
+    D->h_photons.clear();
     return BHRT_OK;
-}
-// the same for a map that lies on the host (a file: bhrt_photon_import)
-static int InstallPhotonMap(DeviceState *D)
-{
-    const uint32_t n = (uint32_t)D->h_photons.size() - 1;
-    DPhoton *d = nullptr;
-    HIP_CHECK(hipMalloc(&d, ((size_t)n + 1) * sizeof(DPhoton)));
-    const hipError_t e = hipMemcpy(d, D->h_photons.data(), ((size_t)n + 1) * sizeof(DPhoton), hipMemcpyHostToDevice);
-    if (e != hipSuccess) { (void)hipFree(d); HIP_CHECK(e); }
-    std::vector<HostPhoton> keep;
-    keep.swap(D->h_photons);
-    const int rc = InstallPhotonMapDev(D, d, n);
-    D->h_photons.swap(keep); // the host copy is already there
-    return rc;
 }
 // host copy of the installed map, fetched on demand (bhrt_photon_get / bhrt_photon_export)
 static int EnsureHostPhotons(DeviceState *D)
@@ -3472,92 +3287,95 @@ static int EnsureHostPhotons(DeviceState *D)
     return BHRT_OK;
 }
 // the balance of n + 1 emission-order records in HBM: on the device, or (BHRT_PHOTON_BALANCE_HOST=1: the tests' second opinion) by photon_host.cpp
-static int BalanceRecords(DeviceState *D, const DPhoton *d_in, uint32_t n, DPhoton **d_out)
+static int BalanceRecords(DeviceState *D, const DPhoton *d_in, uint32_t n, DevBuf<DPhoton> &out)
 {
-    if (!D->knobs.balance_host) return BalanceOnDevice(D, d_in, n, d_out);
+    if (!D->knobs.balance_host) return BalanceOnDevice(D, d_in, n, out);
     std::vector<HostPhoton> h((size_t)n + 1);
     HIP_CHECK(hipMemcpy(h.data(), d_in, ((size_t)n + 1) * sizeof(DPhoton), hipMemcpyDeviceToHost));
     memset(&h[0], 0, sizeof(HostPhoton));
     BalancePhotons(h);
-    DPhoton *d = nullptr;
-    HIP_CHECK(hipMalloc(&d, ((size_t)n + 1) * sizeof(DPhoton)));
-    const hipError_t e = hipMemcpy(d, h.data(), ((size_t)n + 1) * sizeof(DPhoton), hipMemcpyHostToDevice);
-    if (e != hipSuccess) { (void)hipFree(d); HIP_CHECK(e); }
-    *d_out = d;
+    BHRT_TRY(out.Reserve((size_t)n + 1));
+    HIP_CHECK(hipMemcpy(out, h.data(), ((size_t)n + 1) * sizeof(DPhoton), hipMemcpyHostToDevice));
     return BHRT_OK;
 }
 
-// Emission + stable compaction + ScalePhotonPowers + balance, all in HBM: *d_balanced = the balanced records (n + 1, slot 0 unused; the caller
-// owns the buffer).  Per batch of emissions only two words reach the host (the largest count of a path, the photons of the batch).
-// global_map: BuildPhotonMap / TracePhotonRay / RandomPhotonBounce instead of the caustic variants.
-static int BuildPhotons(bhrt_scene *scene, const bhrt_opts *opts, uint32_t max_photons, bool global_map, DPhoton **d_balanced, uint32_t *n_out)
+// BuildCausticPhotonMap, Main.cpp:346-361: the scene's point lights sorted by Gray * GetSize() (int size, lights.h:76), and the sum of those keys
+static int PhotonLights(const bhrt_scene *scene, std::vector<int32_t> &pl, float &sum)
 {
-    int rc = EnsureUploaded(scene);
-    if (rc) return rc;
-    if (!opts || max_photons == 0 || max_photons > (1u << 28)) { SetError("bad photon budget"); return BHRT_ERR_ARG; }
-    DeviceState *D = scene->dev;
     const bhrt_flat_header *H = scene->flat.hdr();
     const bhrt_light *lights = (const bhrt_light *)(scene->flat.blob.data() + H->off_lights);
-    // BuildCausticPhotonMap, Main.cpp:346-361: point lights sorted by Gray * GetSize() (int size, lights.h:76)
-    std::vector<int32_t> pl;
     for (uint32_t i = 0; i < H->n_lights; i++)
         if (lights[i].type == BHRT_LIGHT_POINT) pl.push_back((int32_t)i);
     if (pl.empty()) { SetError("photon map: the scene has no point light (BuildCausticPhotonMap returns false)"); return BHRT_ERR_UNSUPPORTED; }
     auto key = [&](int32_t i) { return ((lights[i].intensity[0] + lights[i].intensity[1] + lights[i].intensity[2]) / 3.0f) * (int)lights[i].size; };
     std::sort(pl.begin(), pl.end(), [&](int32_t a, int32_t b) { return key(a) < key(b); });
-    float sum = 0;
+    sum = 0;
     for (int32_t i : pl) sum += key(i);
+    return BHRT_OK;
+}
+// emissions [e0, e0 + count) (count: a multiple of kBlock): up to `cap` photons per path into tmp, their number into counts
+static void LaunchPhotonEmit(DeviceState *D, bool global_map, uint32_t seed, uint64_t e0, uint32_t count, const int32_t *d_pl, int n_pl, float sum, DPhoton *tmp, uint32_t cap,
+                             uint32_t *counts)
+{
+    if (global_map) hipLaunchKernelGGL(k_photon_emit<true>, dim3(count / kBlock), dim3(kBlock), 0, D->stream, D->S, seed, e0, count, d_pl, n_pl, sum, tmp, cap, counts);
+    else hipLaunchKernelGGL(k_photon_emit<false>, dim3(count / kBlock), dim3(kBlock), 0, D->stream, D->S, seed, e0, count, d_pl, n_pl, sum, tmp, cap, counts);
+}
 
-    struct Bufs { // freed on every return path, HIP_CHECK's included
-        DPhoton *out = nullptr, *tmp = nullptr; uint32_t *counts = nullptr, *offsets = nullptr, *sums = nullptr, *stats = nullptr; int32_t *pl = nullptr;
-        ~Bufs() { (void)hipFree(out); (void)hipFree(tmp); (void)hipFree(counts); (void)hipFree(offsets); (void)hipFree(sums); (void)hipFree(stats); (void)hipFree(pl); }
-    } bufs;
-    DPhoton *&d_out = bufs.out, *&d_tmp = bufs.tmp;
-    uint32_t *&d_counts = bufs.counts, *&d_offsets = bufs.offsets;
-    int32_t *&d_pl = bufs.pl;
-    HIP_CHECK(hipMalloc(&d_out, ((size_t)max_photons + 1) * sizeof(DPhoton)));
+// Emission + stable compaction + ScalePhotonPowers + balance, all in HBM: `balanced` (empty on entry) receives the balanced records (n + 1, slot 0
+// unused).  Per batch of emissions only two words reach the host (the largest count of a path, the photons of the batch).
+// global_map: BuildPhotonMap / TracePhotonRay / RandomPhotonBounce instead of the caustic variants.
+static int BuildPhotons(bhrt_scene *scene, const bhrt_opts *opts, uint32_t max_photons, bool global_map, DevBuf<DPhoton> &balanced, uint32_t *n_out)
+{
+    int rc = EnsureUploaded(scene);
+    if (rc) return rc;
+    if (!opts || max_photons == 0 || max_photons > (1u << 28)) { SetError("bad photon budget"); return BHRT_ERR_ARG; }
+    DeviceState *D = scene->dev;
+    std::vector<int32_t> pl;
+    float sum = 0;
+    BHRT_TRY(PhotonLights(scene, pl, sum));
+    DevBuf<DPhoton> d_out, d_tmp;
+    DevBuf<uint32_t> d_counts, d_offsets, d_sums, d_stats;
+    DevBuf<int32_t> d_pl;
+    BHRT_TRY(d_out.Reserve((size_t)max_photons + 1));
     HIP_CHECK(hipMemset(d_out, 0, ((size_t)max_photons + 1) * sizeof(DPhoton)));
     const uint32_t E = global_map ? 1u << 16 : 1u << 20; // emissions per batch (nearly every emission of the global map stores photons)
     uint32_t cap = 8;            // photons one path may store before the batch is redone with more room
-    HIP_CHECK(hipMalloc(&d_counts, E * sizeof(uint32_t)));
-    HIP_CHECK(hipMalloc(&d_offsets, E * sizeof(uint32_t)));
-    HIP_CHECK(hipMalloc(&d_pl, pl.size() * sizeof(int32_t)));
+    BHRT_TRY(d_counts.Reserve(E));
+    BHRT_TRY(d_offsets.Reserve(E));
+    BHRT_TRY(d_pl.Reserve(pl.size()));
     HIP_CHECK(hipMemcpy(d_pl, pl.data(), pl.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-    HIP_CHECK(hipMalloc(&d_tmp, (size_t)E * cap * sizeof(DPhoton)));
+    BHRT_TRY(d_tmp.Reserve((size_t)E * cap));
     const uint32_t n_tiles = (E + kScanTile - 1) / kScanTile;
-    HIP_CHECK(hipMalloc(&bufs.sums, n_tiles * sizeof(uint32_t)));
-    HIP_CHECK(hipMalloc(&bufs.stats, 2 * sizeof(uint32_t)));
+    BHRT_TRY(d_sums.Reserve(n_tiles));
+    BHRT_TRY(d_stats.Reserve(2));
     uint64_t e0 = 0, stored = 0;
     const uint64_t emission_budget = (uint64_t)max_photons * 4096ull + (1ull << 24);
     while (stored < max_photons && e0 < emission_budget) {
-        if (global_map) hipLaunchKernelGGL(k_photon_emit<true>, dim3(E / kBlock), dim3(kBlock), 0, D->stream, D->S, opts->seed, e0, E, d_pl, (int)pl.size(), sum, d_tmp, cap, d_counts);
-        else hipLaunchKernelGGL(k_photon_emit<false>, dim3(E / kBlock), dim3(kBlock), 0, D->stream, D->S, opts->seed, e0, E, d_pl, (int)pl.size(), sum, d_tmp, cap, d_counts);
+        LaunchPhotonEmit(D, global_map, opts->seed, e0, E, d_pl, (int)pl.size(), sum, d_tmp, cap, d_counts);
         // where every path's photons go: exclusive prefix of the counts, on the device; two words come back
         HIP_CHECK(hipMemcpyAsync(d_offsets, d_counts, E * sizeof(uint32_t), hipMemcpyDeviceToDevice, D->stream));
-        hipLaunchKernelGGL(k_scan_tiles, dim3(n_tiles), dim3(kScanBlock), 0, D->stream, d_offsets, E, bufs.sums);
-        hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(kScanBlock), 0, D->stream, bufs.sums, n_tiles);
-        hipLaunchKernelGGL(k_scan_add, dim3(n_tiles), dim3(kScanBlock), 0, D->stream, d_offsets, E, bufs.sums);
-        HIP_CHECK(hipMemsetAsync(bufs.stats, 0, 2 * sizeof(uint32_t), D->stream));
-        hipLaunchKernelGGL(k_pb_batch_stats, dim3(64), dim3(256), 0, D->stream, d_counts, d_offsets, E, bufs.stats);
+        hipLaunchKernelGGL(k_scan_tiles, dim3(n_tiles), dim3(kScanBlock), 0, D->stream, d_offsets.p, E, d_sums.p);
+        hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(kScanBlock), 0, D->stream, d_sums.p, n_tiles);
+        hipLaunchKernelGGL(k_scan_add, dim3(n_tiles), dim3(kScanBlock), 0, D->stream, d_offsets.p, E, d_sums.p);
+        HIP_CHECK(hipMemsetAsync(d_stats, 0, 2 * sizeof(uint32_t), D->stream));
+        hipLaunchKernelGGL(k_pb_batch_stats, dim3(64), dim3(256), 0, D->stream, d_counts.p, d_offsets.p, E, d_stats.p);
         uint32_t stats[2];
-        HIP_CHECK(hipMemcpyAsync(stats, bufs.stats, sizeof stats, hipMemcpyDeviceToHost, D->stream));
+        HIP_CHECK(hipMemcpyAsync(stats, d_stats, sizeof stats, hipMemcpyDeviceToHost, D->stream));
         HIP_CHECK(hipStreamSynchronize(D->stream));
         if (stats[0] > cap) { // a path stored more than `cap` photons: redo this batch with room for all of them
-            (void)hipFree(d_tmp);
-            d_tmp = nullptr;
             cap = stats[0];
-            HIP_CHECK(hipMalloc(&d_tmp, (size_t)E * cap * sizeof(DPhoton)));
+            BHRT_TRY(d_tmp.Reserve((size_t)E * cap));
             continue;
         }
-        hipLaunchKernelGGL(k_photon_compact, dim3(E / kBlock), dim3(kBlock), 0, D->stream, d_tmp, cap, d_counts, d_offsets, (uint32_t)std::min<uint64_t>(stored, max_photons), E, max_photons, d_out);
+        hipLaunchKernelGGL(k_photon_compact, dim3(E / kBlock), dim3(kBlock), 0, D->stream, d_tmp.p, cap, d_counts.p, d_offsets.p, (uint32_t)std::min<uint64_t>(stored, max_photons), E, max_photons, d_out.p);
         stored += stats[1];
         e0 += E;
     }
     const uint32_t n = (uint32_t)std::min<uint64_t>(stored, max_photons);
     if (n == 0) { SetError("photon map: no photon reached a photon surface"); return BHRT_ERR_UNSUPPORTED; }
-    hipLaunchKernelGGL(k_photon_scale, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, D->stream, d_out, n, 1.f / (float)(int)n); // Main.cpp:380
+    hipLaunchKernelGGL(k_photon_scale, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, D->stream, d_out.p, n, 1.f / (float)(int)n); // Main.cpp:380
     *n_out = n;
-    return BalanceRecords(D, d_out, n, d_balanced); // PrepareForIrradianceEstimation (cyPhotonMap.h:236-258)
+    return BalanceRecords(D, d_out, n, balanced); // PrepareForIrradianceEstimation (cyPhotonMap.h:236-258)
 }
 
 // ---- multi-GPU photon build: emission is keyed by the emission index, so ranks emit disjoint index ranges,
@@ -3570,32 +3388,20 @@ try {
     if (rc) return rc;
     if (!opts || !photons_out || !n_photons || count == 0 || count % kBlock != 0 || count > (1u << 24)) { SetError("photon emit range: bad arguments (count must be a multiple of 256)"); return BHRT_ERR_ARG; }
     DeviceState *D = scene->dev;
-    const bhrt_flat_header *H = scene->flat.hdr();
-    const bhrt_light *lights = (const bhrt_light *)(scene->flat.blob.data() + H->off_lights);
-    std::vector<int32_t> pl; // BuildCausticPhotonMap, Main.cpp:346-361 (same order as BuildPhotons)
-    for (uint32_t i = 0; i < H->n_lights; i++)
-        if (lights[i].type == BHRT_LIGHT_POINT) pl.push_back((int32_t)i);
-    if (pl.empty()) { SetError("photon map: the scene has no point light (BuildCausticPhotonMap returns false)"); return BHRT_ERR_UNSUPPORTED; }
-    auto key = [&](int32_t i) { return ((lights[i].intensity[0] + lights[i].intensity[1] + lights[i].intensity[2]) / 3.0f) * (int)lights[i].size; };
-    std::sort(pl.begin(), pl.end(), [&](int32_t a, int32_t b) { return key(a) < key(b); });
+    std::vector<int32_t> pl;
     float sum = 0;
-    for (int32_t i : pl) sum += key(i);
-    struct Bufs {
-        DPhoton *tmp = nullptr, *out = nullptr; uint32_t *counts = nullptr, *offsets = nullptr; int32_t *pl = nullptr;
-        ~Bufs() { (void)hipFree(tmp); (void)hipFree(out); (void)hipFree(counts); (void)hipFree(offsets); (void)hipFree(pl); }
-    } b;
-    HIP_CHECK(hipMalloc(&b.counts, count * sizeof(uint32_t)));
-    HIP_CHECK(hipMalloc(&b.offsets, count * sizeof(uint32_t)));
-    HIP_CHECK(hipMalloc(&b.pl, pl.size() * sizeof(int32_t)));
+    BHRT_TRY(PhotonLights(scene, pl, sum));
+    struct { DevBuf<DPhoton> tmp, out; DevBuf<uint32_t> counts, offsets; DevBuf<int32_t> pl; } b;
+    BHRT_TRY(b.counts.Reserve(count));
+    BHRT_TRY(b.offsets.Reserve(count));
+    BHRT_TRY(b.pl.Reserve(pl.size()));
     HIP_CHECK(hipMemcpy(b.pl, pl.data(), pl.size() * sizeof(int32_t), hipMemcpyHostToDevice));
     std::vector<uint32_t> counts(count), offsets(count);
     uint32_t cap = 8;
     uint64_t total = 0;
     for (int attempt = 0; attempt < 2; attempt++) {
-        (void)hipFree(b.tmp); b.tmp = nullptr;
-        HIP_CHECK(hipMalloc(&b.tmp, (size_t)count * cap * sizeof(DPhoton)));
-        if (global_map) hipLaunchKernelGGL(k_photon_emit<true>, dim3(count / kBlock), dim3(kBlock), 0, D->stream, D->S, opts->seed, e0, count, b.pl, (int)pl.size(), sum, b.tmp, cap, b.counts);
-        else hipLaunchKernelGGL(k_photon_emit<false>, dim3(count / kBlock), dim3(kBlock), 0, D->stream, D->S, opts->seed, e0, count, b.pl, (int)pl.size(), sum, b.tmp, cap, b.counts);
+        BHRT_TRY(b.tmp.Reserve((size_t)count * cap));
+        LaunchPhotonEmit(D, global_map != 0, opts->seed, e0, count, b.pl, (int)pl.size(), sum, b.tmp, cap, b.counts);
         HIP_CHECK(hipMemcpyAsync(counts.data(), b.counts, count * sizeof(uint32_t), hipMemcpyDeviceToHost, D->stream));
         HIP_CHECK(hipStreamSynchronize(D->stream));
         uint32_t maxc = 0;
@@ -3607,9 +3413,9 @@ try {
     *n_photons = (uint32_t)std::min<uint64_t>(total, 0xffffffffull);
     if (total > capacity) { SetError("photon emit range: photons_out too small"); return BHRT_ERR_ARG; }
     if (total == 0) return BHRT_OK;
-    HIP_CHECK(hipMalloc(&b.out, ((size_t)total + 1) * sizeof(DPhoton)));
+    BHRT_TRY(b.out.Reserve((size_t)total + 1));
     HIP_CHECK(hipMemcpyAsync(b.offsets, offsets.data(), count * sizeof(uint32_t), hipMemcpyHostToDevice, D->stream));
-    hipLaunchKernelGGL(k_photon_compact, dim3(count / kBlock), dim3(kBlock), 0, D->stream, b.tmp, cap, b.counts, b.offsets, 0u, count, (uint32_t)total, b.out);
+    hipLaunchKernelGGL(k_photon_compact, dim3(count / kBlock), dim3(kBlock), 0, D->stream, b.tmp.p, cap, b.counts.p, b.offsets.p, 0u, count, (uint32_t)total, b.out.p);
     HIP_CHECK(hipMemcpyAsync(photons_out, b.out + 1, (size_t)total * sizeof(DPhoton), hipMemcpyDefault, D->stream)); // host or device destination
     HIP_CHECK(hipStreamSynchronize(D->stream));
     return BHRT_OK;
@@ -3622,30 +3428,24 @@ try {
     if (rc) return rc;
     if (!records || n == 0 || n > (1u << 28)) { SetError("photon install: bad arguments"); return BHRT_ERR_ARG; }
     DeviceState *D = scene->dev;
-    DPhoton *d = nullptr;
-    HIP_CHECK(hipMalloc(&d, ((size_t)n + 1) * sizeof(DPhoton)));
-    hipError_t e = hipMemset(d, 0, sizeof(DPhoton));
-    if (e == hipSuccess) e = hipMemcpy(d + 1, records, (size_t)n * sizeof(DPhoton), hipMemcpyDefault); // host or device source
-    if (e != hipSuccess) { (void)hipFree(d); HIP_CHECK(e); }
-    hipLaunchKernelGGL(k_photon_scale, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, D->stream, d, n, 1.f / (float)(int)n);
-    DPhoton *bal = nullptr;
-    rc = BalanceRecords(D, d, n, &bal); // the records stay in HBM from the caller's buffer to the installed map
-    (void)hipFree(d);
-    if (rc) return rc;
-    return InstallPhotonMapDev(D, bal, n);
+    DevBuf<DPhoton> d, bal;
+    BHRT_TRY(d.Reserve((size_t)n + 1));
+    HIP_CHECK(hipMemset(d, 0, sizeof(DPhoton)));
+    HIP_CHECK(hipMemcpy(d + 1, records, (size_t)n * sizeof(DPhoton), hipMemcpyDefault)); // host or device source
+    hipLaunchKernelGGL(k_photon_scale, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, D->stream, d.p, n, 1.f / (float)(int)n);
+    BHRT_TRY(BalanceRecords(D, d, n, bal)); // the records stay in HBM from the caller's buffer to the installed map
+    d.Free();
+    return InstallPhotonMapDev(D, std::move(bal), n);
 } catch (...) { return bhrt::AbiException(); }
 
 int bhrt_photon_build(bhrt_scene *scene, const bhrt_opts *opts, uint32_t max_photons, uint32_t *n_stored)
 try {
     if (!scene) { SetError("null scene"); return BHRT_ERR_ARG; }
-    DPhoton *bal = nullptr;
+    DevBuf<DPhoton> bal;
     uint32_t n = 0;
-    int rc = BuildPhotons(scene, opts, max_photons, false, &bal, &n);
-    if (rc) return rc;
-    DeviceState *D = scene->dev;
-    rc = InstallPhotonMapDev(D, bal, n);
-    if (rc) return rc;
-    if (n_stored) *n_stored = D->n_photons;
+    BHRT_TRY(BuildPhotons(scene, opts, max_photons, false, bal, &n));
+    BHRT_TRY(InstallPhotonMapDev(scene->dev, std::move(bal), n));
+    if (n_stored) *n_stored = scene->dev->n_photons;
     return BHRT_OK;
 } catch (...) { return bhrt::AbiException(); }
 
@@ -3653,14 +3453,12 @@ int bhrt_photon_build_global(bhrt_scene *scene, const bhrt_opts *opts, uint32_t 
                              const char *dat_path)
 try {
     if (!scene) { SetError("null scene"); return BHRT_ERR_ARG; }
-    DPhoton *bal = nullptr;
+    DevBuf<DPhoton> bal;
     uint32_t n = 0;
-    int rc = BuildPhotons(scene, opts, max_photons, true, &bal, &n);
-    if (rc) return rc;
+    BHRT_TRY(BuildPhotons(scene, opts, max_photons, true, bal, &n));
     std::vector<HostPhoton> balanced((size_t)n + 1);
-    const hipError_t ce = hipMemcpy(balanced.data(), bal, ((size_t)n + 1) * sizeof(DPhoton), hipMemcpyDeviceToHost);
-    (void)hipFree(bal);
-    HIP_CHECK(ce);
+    HIP_CHECK(hipMemcpy(balanced.data(), bal, ((size_t)n + 1) * sizeof(DPhoton), hipMemcpyDeviceToHost));
+    bal.Free();
     if (n_stored) *n_stored = n;
     if (photons_out) {
         if (capacity < n) { SetError("photon buffer too small"); return BHRT_ERR_ARG; }
@@ -3689,13 +3487,13 @@ try {
     if (!p || !nrm || !irrad || !dir) { SetError("null buffer"); return BHRT_ERR_ARG; }
     if (cnt == 0) return BHRT_OK;
     const uint32_t chunk = (knn || knn_count || d2max) ? 1u << 14 : 1u << 20;
-    struct Bufs { float *f = nullptr; uint32_t *knn = nullptr; DeviceState *D; ~Bufs() { (void)hipFree(f); (void)hipFree(knn); D->d_knn = nullptr; } } b;
-    b.D = D;
-    HIP_CHECK(hipMalloc(&b.f, (size_t)chunk * 12 * sizeof(float)));
-    float *d_buf = b.f;
+    struct Hook { DeviceState *D; DevBuf<uint32_t> knn; ~Hook() { D->d_knn = nullptr; } } b = {D, {}}; // the test hook never outlives its memory
+    DevBuf<float> d_f;
+    BHRT_TRY(d_f.Reserve((size_t)chunk * 12));
+    float *d_buf = d_f;
     const size_t kw = BHRT_PHOTON_K + 2;
     std::vector<uint32_t> h_knn;
-    if (knn || knn_count || d2max) { HIP_CHECK(hipMalloc(&b.knn, (size_t)chunk * kw * sizeof(uint32_t))); h_knn.resize((size_t)chunk * kw); }
+    if (knn || knn_count || d2max) { BHRT_TRY(b.knn.Reserve((size_t)chunk * kw)); h_knn.resize((size_t)chunk * kw); }
     for (size_t c0 = 0; c0 < cnt; c0 += chunk) {
         const uint32_t m = (uint32_t)std::min<size_t>(chunk, cnt - c0);
         HIP_CHECK(hipMemcpy(d_buf, p + c0 * 3, (size_t)m * 3 * sizeof(float), hipMemcpyHostToDevice));
@@ -3772,22 +3570,21 @@ try {
     }
     const size_t n = (size_t)bytes / sizeof(HostPhoton);
     DeviceState *D = scene->dev;
-    D->h_photons.assign(n + 1, HostPhoton());
-    const bool ok = fread(&D->h_photons[1], sizeof(HostPhoton), n, fp) == n;
+    std::vector<HostPhoton> h(n + 1); // slot 0 unused and zero
+    const bool ok = fread(&h[1], sizeof(HostPhoton), n, fp) == n;
     fclose(fp);
-    if (!ok) { D->h_photons.clear(); SetError("photon file: short read"); return BHRT_ERR_IO; }
-    memset(&D->h_photons[0], 0, sizeof(HostPhoton));
+    if (!ok) { SetError("photon file: short read"); return BHRT_ERR_IO; }
+    DevBuf<DPhoton> d, bal;
+    BHRT_TRY(d.Reserve(n + 1));
+    HIP_CHECK(hipMemcpy(d, h.data(), (n + 1) * sizeof(DPhoton), hipMemcpyHostToDevice));
     if (rebalance) { // InitializePhotonMapByFile runs PrepareForIrradianceEstimation again (cyPhotonMap.h:409-417): on the device like the build's
-        DPhoton *d = nullptr, *bal = nullptr;
-        HIP_CHECK(hipMalloc(&d, (n + 1) * sizeof(DPhoton)));
-        hipError_t e = hipMemcpy(d, D->h_photons.data(), (n + 1) * sizeof(DPhoton), hipMemcpyHostToDevice);
-        if (e == hipSuccess) rc = BalanceRecords(D, d, (uint32_t)n, &bal);
-        (void)hipFree(d);
-        HIP_CHECK(e);
-        if (rc) return rc;
-        return InstallPhotonMapDev(D, bal, (uint32_t)n); // the host copy is fetched again when somebody asks for it
+        BHRT_TRY(BalanceRecords(D, d, (uint32_t)n, bal));
+        d.Free();
+        return InstallPhotonMapDev(D, std::move(bal), (uint32_t)n); // the host copy is fetched again when somebody asks for it
     }
-    return InstallPhotonMap(D);
+    BHRT_TRY(InstallPhotonMapDev(D, std::move(d), (uint32_t)n));
+    D->h_photons.swap(h); // the map is installed: its host copy is already there
+    return BHRT_OK;
 } catch (...) { return bhrt::AbiException(); }
 
 } // extern "C"

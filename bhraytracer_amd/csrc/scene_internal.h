@@ -8,7 +8,7 @@
 #include "scene_host.h"
 
 namespace bhrt {
-struct DeviceState; // device_state.h (HIP side)
+struct DeviceState; // device_state.h (part of the kernels.hip translation unit)
 void SetError(const std::string &msg);
 // No C++ exception crosses the C ABI: every `int bhrt_*` entry point is a function-try-block that ends in this handler
 // (std::bad_alloc from a file-sized allocation, std::length_error, ...): sets bhrt_last_error() and returns an error code.

@@ -182,6 +182,15 @@ def test_gpu_photon_map_vs_oracle(B, load_scene, O):
     assert same_bits(gi3, oi3) and same_bits(gd3, od3)
     with pytest.raises(B.BhrtError):
         sc2.photon_import(path + ".missing")
+    # a failed import leaves the installed map alone.  (Both of these fail before anything is touched: the control.  A failure inside the
+    # rebalance or the install cannot be provoked without a knob for it; that path is covered by review of InstallPhotonMapDev.)
+    assert np.array_equal(sc2.photon_get(), rebal)
+    odd = path + ".odd"
+    with open(odd, "wb") as f:
+        f.write(bal.tobytes()[:-5])                                         # not a multiple of the 24-byte record
+    with pytest.raises(B.BhrtError):
+        sc2.photon_import(odd)
+    assert np.array_equal(sc2.photon_get(), rebal)
 
 
 @pytest.mark.gpu
