@@ -32,7 +32,7 @@ class Opts(C.Structure):
     _fields_ = [("spp", C.c_int32), ("gi_bounces", C.c_int32), ("internal_bounces", C.c_int32), ("seed", C.c_uint32),
                 ("jitter", C.c_int32), ("gamma", C.c_int32), ("photon_map", C.c_int32),
                 ("rank", C.c_int32), ("world_size", C.c_int32), ("tile_size", C.c_int32),
-                ("samples_per_pass", C.c_int32), ("timers", C.c_int32), ("photon_exact", C.c_int32), ("leaf_skip", C.c_int32), ("photon_radius", C.c_float), ("reserved", C.c_int32 * 1)]
+                ("samples_per_pass", C.c_int32), ("timers", C.c_int32), ("photon_exact", C.c_int32), ("leaf_skip", C.c_int32), ("photon_radius", C.c_float), ("lens", C.c_int32)]
 
 
 class Stats(C.Structure):
@@ -80,6 +80,7 @@ EXPORTS = [
     "bhrt_default_denoise_opts", "bhrt_render_var", "bhrt_render_var_dev", "bhrt_denoise", "bhrt_denoise_dev",
     "bhrt_default_adaptive_opts", "bhrt_render_adaptive", "bhrt_render_adaptive_dev", "bhrt_sample_count_image", "bhrt_sample_count_image_dev",
     "bhrt_save_png_gray",
+    "bhrt_scene_set_lens", "bhrt_camera_rays",
 ]
 
 
@@ -200,6 +201,21 @@ class Scene:
 
     def upload(self, device: int = 0):
         _check(lib().bhrt_scene_upload(self._h, device))
+
+    def set_lens(self, focaldist: float = 0.0, dof: float = 0.0):
+        """bhrt_scene_set_lens: the camera's <focaldist> (<= 0 keeps the current one) and <dof> of the loaded scene; the camera frame is derived
+        again, and an uploaded scene's camera is refreshed.  Opts.lens = 1 then renders through a thin lens of aperture radius dof."""
+        _check(lib().bhrt_scene_set_lens(self._h, C.c_float(focaldist), C.c_float(dof)))
+        self._flat = None
+
+    def camera_rays(self, opts: Opts, region=None):
+        """Test hook (bhrt_camera_rays): the camera rays of region (x0, y0, x1, y1) — default the whole frame — as the render's first wave step forms
+        them on the device, pinhole (opts.lens = 0) or thin lens.  Returns (origins, dirs), each (region_pixels, spp, 3) float32, in the order
+        of render_samples."""
+        x0, y0, x1, y1 = region if region is not None else (0, 0, self.width, self.height)
+        out = np.zeros(((y1 - y0) * (x1 - x0), opts.spp, 6), np.float32)
+        _check(lib().bhrt_camera_rays(self._h, C.byref(opts), int(x0), int(y0), int(x1), int(y1), _ptr(out)))
+        return np.ascontiguousarray(out[..., :3]), np.ascontiguousarray(out[..., 3:])
 
     # ---- hot path, host buffers -------------------------------------------------------------
     def trace_closest(self, origins, dirs, hit_side=SIDE_FRONT):

@@ -8,6 +8,7 @@
 //               [--photons N] [--photon-file map.dat] [--photon-out map.dat]     (USE_PhotonMap, Main.cpp:51,53,194,383)
 //               [--denoise [--denoise-iters K]]                                  (DenoiseImage of the x64 build, Main.cpp:57-96,236-238)
 //               [--adaptive [--spp-min N] [--adaptive-threshold X] [--samples-png path]]  (RenderImage::sampleCount, scene.h:534,603-630)
+//               [--lens [--dof R] [--focaldist D]]                               (the viewport's depth of field, viewport.cpp:236-243, rendered)
 //   bhrt info   <scene.xml>
 //
 // --gpus N: ONE process drives N GPUs of the node (the reference's one process drives 16 OpenMP threads, Main.cpp:422): the
@@ -25,6 +26,9 @@
 // --adaptive: bhrt_render_adaptive; --spp is the per-pixel maximum, --spp-min round 0's samples.  --samples-png writes the
 // sample-count image as SaveSampleCountImage does (scene.h:630); its normalisation needs the whole frame, so --world > 1 refuses it.  With
 // --gpus N the counts travel as the float section of a further block (exact below 2^24); with --denoise the adaptive variance is the filter's.
+// --lens: bhrt_opts.lens = 1, a thin-lens camera with the scene's <dof> as aperture radius, focused at <focaldist>.  --dof R and
+// --focaldist D replace the scene's values (bhrt_scene_set_lens, before the upload) and imply --lens.  The option travels in bhrt_opts, so it
+// works with --gpus, --adaptive and --denoise; the denoiser's guides stay those of the pinhole ray.
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
@@ -40,6 +44,7 @@
 #include <vector>
 
 #include "bhrt.h"
+#include "bhrt_flat.h"
 
 static int fail(const char *what)
 {
@@ -63,7 +68,20 @@ struct Args {
     bool adaptive = false;
     bhrt_adaptive_opts ad;
     std::string samples_png;
+    float dof = -1.f, focaldist = 0.f; // --dof / --focaldist: values for bhrt_scene_set_lens; dof < 0: not given
 };
+
+// a finite number >= 0 (--dof) or > 0 (--focaldist), else a usage error
+static float lens_value(const char *opt, const char *text, bool positive)
+{
+    char *end = nullptr;
+    const float v = strtof(text, &end);
+    if (end == text || *end || !(v >= 0.f && v <= 3.402823466e38f) || (positive && !(v > 0.f))) {
+        fprintf(stderr, "bhrt: usage: %s needs a finite number %s, got \"%s\"\n", opt, positive ? "> 0" : ">= 0", text);
+        exit(2);
+    }
+    return v;
+}
 
 // the adaptive frame's round count (doubling from min_spp up to the largest count) and the spp statistics of its rendered pixels (count > 0)
 static void print_adaptive(const std::vector<uint32_t> &cnt, const bhrt_opts &o, const bhrt_adaptive_opts &ad)
@@ -335,6 +353,9 @@ int main(int argc, char **argv)
         else if (s == "--spp-min") A.ad.min_spp = atoi(next());
         else if (s == "--adaptive-threshold") A.ad.threshold = (float)atof(next());
         else if (s == "--samples-png") A.samples_png = next();
+        else if (s == "--lens") o.lens = 1;
+        else if (s == "--dof") { A.dof = lens_value("--dof", next(), false); o.lens = 1; }
+        else if (s == "--focaldist") { A.focaldist = lens_value("--focaldist", next(), true); o.lens = 1; }
         else { fprintf(stderr, "bhrt: unknown option %s\n", s.c_str()); return 2; }
     }
     if (A.gpus < 0 || A.gpus > 64 || (A.gpus > 0 && (o.rank != 0 || o.world_size != 1))) { fprintf(stderr, "bhrt: --gpus N drives all N ranks itself (no --rank / --world)\n"); return 2; }
@@ -365,6 +386,15 @@ int main(int argc, char **argv)
     printf("nodes %u, meshes %u (%u triangles, %u BVH nodes), materials %u, lights %u, textures %u, scene blob %llu bytes\n", info.n_nodes,
            info.n_meshes, info.n_triangles, info.n_bvh_nodes, info.n_materials, info.n_lights, info.n_textures, (unsigned long long)info.flat_bytes);
     if (!render) { bhrt_scene_free(scene); return 0; }
+    if (o.lens) { // before the upload and before --gpus N clones the scene
+        const bhrt_flat_header *fh = nullptr;
+        uint64_t fb = 0;
+        if (bhrt_scene_flat(scene, (const void **)&fh, &fb)) return fail("scene blob");
+        if ((A.dof >= 0.f || A.focaldist > 0.f) && bhrt_scene_set_lens(scene, A.focaldist, A.dof >= 0.f ? A.dof : fh->camera.dof)) return fail("set lens");
+        if (!(fh->camera.dof >= 0.f && fh->camera.dof <= 3.402823466e38f)) { fprintf(stderr, "bhrt: usage: --lens: the scene's <dof> must be a finite number >= 0 (or give --dof)\n"); return 2; }
+        printf("lens: focal distance %g, aperture radius %g%s\n", fh->camera.focaldist, fh->camera.dof, fh->camera.dof > 0.f ? "" : " (pinhole)");
+        if (A.denoise) printf("note: --denoise guides (depth, normal, albedo) are those of the pinhole ray; lens-averaged guides are not implemented\n");
+    }
     std::vector<uint8_t> rgb((size_t)info.width * info.height * 3, 0);
     std::vector<float> rad(A.radiance_out.empty() && !A.denoise ? 0 : (size_t)info.width * info.height * 3, 0.f);
     std::vector<uint32_t> cnt(A.adaptive ? (size_t)info.width * info.height : 0, 0u);

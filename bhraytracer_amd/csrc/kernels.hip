@@ -2,6 +2,7 @@
 //
 // One launch of each kernel processes one "wave step" of all paths in flight:
 //   camera_ray()    Main.cpp:132-153,179-192   the camera ray of a (pixel, sample) slot, computed inside the first step's kernels
+//   k_lens_rays     viewport.cpp:236-243       bhrt_opts.lens: the thin-lens camera rays of a pass, written into its ray queue
 //   k_trace_closest Main.cpp:389-413 + Objects/* ordered scene-graph closest hit -> compact hits; files every ray under its
 //                                              shading class; with meshes in the scene it parks the rays that enter a mesh
 //   k_trace_mesh    TriObj.cpp:17-39,192-270   the parked rays, key-sorted, in dense workgroups: BVH traversal + rest of the scene graph
@@ -89,6 +90,8 @@ struct PassInfo {
     int32_t W, H, tile, tiles_x, tiles_y, rank, world;
     uint32_t q0;          // first owned-pixel index of this pass (list == nullptr)
     uint32_t n_pixels;    // pixels in this pass (incl. out-of-image pixels of edge tiles)
+    float lens_r;         // aperture radius of the thin-lens camera (bhrt_opts.lens with camera.dof > 0); 0 = pinhole.  Here it fills the padding in
+                          // front of `list`: the kernel arguments of every kernel that takes a PassInfo stay where they were
     const uint32_t *list; // owned-pixel indices of this pass's pixels (an adaptive round's active list); nullptr = the range q0 + q_local
     uint32_t s0;          // sample index of the pass's first sample of every pixel (adaptive rounds; 0 for a uniform render)
     int32_t spp;          // samples per pixel in this pass
@@ -99,6 +102,7 @@ struct PassInfo {
     float jx[3], jy[3], pixel_len;
     FastDiv by_spp, by_tile_px, by_tiles_x, by_tile; // divisions by spp, tile * tile, tiles_x, tile
 };
+static_assert(sizeof(PassInfo) == 160, "PassInfo: lens_r is meant to fill the padding in front of `list`");
 struct RenderParams {
     int32_t internal_bounces, gi_bounces;
     uint32_t cap_rays, cap_shadow, cap_frames;
@@ -201,6 +205,12 @@ __device__ inline V3 ld3i(const float *a, uint32_t i) { return v3(a[3 * (size_t)
 // Camera rays are never stored: the first wave step's kernels (k_trace_closest / k_trace_mesh / k_shade with
 // kCamera) each call this — ~300 VALU instructions instead of a 36-byte record written once and read twice.
 // false: the slot is a pixel of an edge tile outside the image (a dead ray).
+// kLens (bhrt_opts.lens with an open aperture, P.lens_r > 0; k_lens_rays only — the first step's kernels keep the pinhole form): the thin-lens
+// ray.  The eye moves to a point of the disc of radius lens_r in the camera's x/y plane and the ray still goes through the sample's point on
+// the image plane, which BeginRender puts at <focaldist> (Main.cpp:181-189): the plane of focus (viewport.cpp:236-243 as a render).  The two
+// draws are a stream of their own: section BHRT_SEC_LENS of path code 0, which no Shade() call has; the jitter draws and the Shade()
+// streams of the sample stay what they are.
+template <bool kLens = false>
 __device__ inline bool camera_ray(const DevScene &S, const PassInfo &P, uint32_t idx, V3 &o, V3 &d)
 {
     int i = 0, j = 0;
@@ -218,6 +228,20 @@ __device__ inline bool camera_ray(const DevScene &S, const PassInfo &P, uint32_t
         target = target + ((ux * fx) * pixelLen) / 2.f;
         float fy = (float)(((double)bhrt_rand31(key, 1) / (BHRT_RAND_MAX)) * 2 - 1);
         target = target + ((uy * fy) * pixelLen) / 2.f;
+    }
+    if (kLens) {
+        const uint32_t lkey = bhrt_section_key(bhrt_sample_key(P.seed, (uint32_t)(j * P.W + i), P.s0 + s), 0, BHRT_SEC_LENS);
+        const float u1 = dm::rand_to_unit(bhrt_rand31(lkey, 0));
+        const float u2 = dm::rand_to_unit(bhrt_rand31(lkey, 1));
+        const float r = dm::sqrt_f(u1) * P.lens_r; // uniform on the disc, viewport.cpp:240
+        const float a = ((float)M_PI * 2.0f) * u2; // viewport.cpp:241
+        float sn, cs;
+        dm::sincos_f(a, &sn, &cs);
+        const V3 ux = ld3(P.jx), uy = ld3(P.jy);   // unit dd_x, dd_y: the reference's v = dir ^ up and up (camXAxis, camYAxis, Main.cpp:185-187)
+        const V3 off = (ux * (r * cs)) + (uy * (r * sn));
+        o = pos + off;
+        d = target - o;
+        return true;
     }
     o = pos;
     d = target - pos;
@@ -1451,6 +1475,35 @@ __global__ void k_copy_samples(PassInfo P, const float *samples, int x0, int y0,
         for (int c = 0; c < 3; c++) out[(pix * P.spp + s) * 3 + c] = samples[((size_t)s * P.n_pixels + q) * 3 + c];
 }
 
+// The thin-lens camera rays of a pass (bhrt_opts.lens): one lane per slot writes its ray into the pass's ray queue, owner = the
+// sample slot, as the rays set aside by the camera step come back (k_trace_closest: slow.q.frame).  The pass's first wave step then runs the
+// queue instantiations of the trace and shade kernels, so no pinhole kernel carries lens code.  Slots of edge-tile pixels outside the image
+// are written as RK_DEAD: nothing traces, files or shades them.  36 B per slot in consecutive dwords of nine arrays; no LDS, no atomics.
+__global__ void __launch_bounds__(kBlock) k_lens_rays(DevScene S, PassInfo P, RayQueue q, uint32_t n)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    V3 o, d;
+    const bool valid = camera_ray<true>(S, P, i, o, d);
+    put_ray(q, i, o, d, i, make_meta(valid ? RK_CAMERA : RK_DEAD, BHRT_HIT_FRONT, 0), 0u);
+}
+// test hook (bhrt_camera_rays): the camera ray of every slot of a pass through the render's own device function, the rays of the
+// pixels inside the region written as ox, oy, oz, dx, dy, dz per sample in the order of k_copy_samples
+__global__ void __launch_bounds__(kBlock) k_camera_rays(DevScene S, PassInfo P, uint32_t n, int x0, int y0, int x1, int y1, float *out)
+{
+    const uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x;
+    if (slot >= n) return;
+    V3 o, d;
+    const bool valid = P.lens_r > 0.f ? camera_ray<true>(S, P, slot, o, d) : camera_ray(S, P, slot, o, d); // a kernel argument: uniform
+    int i, j;
+    uint32_t s;
+    if (!valid || !slot_pixel(P, slot, i, j, s)) return;
+    if (i < x0 || i >= x1 || j < y0 || j >= y1) return;
+    const size_t pix = (size_t)(j - y0) * (x1 - x0) + (i - x0);
+    float *r = out + (pix * P.spp + s) * 6;
+    r[0] = o.x; r[1] = o.y; r[2] = o.z; r[3] = d.x; r[4] = d.y; r[5] = d.z;
+}
+
 // ------------------------------------------------------------------------------------------------
 // photon map kernels
 template <bool kGlobal>
@@ -2152,6 +2205,7 @@ static int FramePassInfo(bhrt_scene *scene, const bhrt_opts &o, PassInfo &P, uin
     P.W = W; P.H = Hh; P.tile = tile; P.tiles_x = (W + tile - 1) / tile; P.tiles_y = (Hh + tile - 1) / tile;
     P.rank = o.rank; P.world = world; P.spp = o.spp; P.seed = o.seed; P.jitter = o.jitter; P.gamma = o.gamma;
     P.list = nullptr; P.s0 = 0;
+    P.lens_r = o.lens == 1 ? H->camera.dof : 0.f; // checked by LensArgsError
     P.by_spp = MakeFastDiv((uint32_t)o.spp); P.by_tile_px = MakeFastDiv((uint32_t)(tile * tile)); P.by_tiles_x = MakeFastDiv((uint32_t)P.tiles_x);
     P.by_tile = MakeFastDiv((uint32_t)tile);
     {
@@ -2303,6 +2357,15 @@ static int RenderPixels(bhrt_scene *scene, const bhrt_opts &o, PassInfo P, const
         const uint32_t total = npx * spp;
         uint32_t n_cur = total; // first wave step: one slot per (pixel, sample); the kernels compute the camera rays themselves
         bool first_step = true;
+        // Thin-lens camera: k_lens_rays writes the pass's camera rays into the queue (one per slot, dead slots included: the queue holds two rays per
+        // sample slot) and the first step runs the kernels of every later step, key sort included — lens rays of one pixel enter a mesh less
+        // coherently than pinhole rays.  Inside the pass, so a pass that overflows and is redone in halves forms its rays again.
+        const bool lens = P.lens_r > 0.f;
+        if (lens) {
+            Timer t(D, &st->seconds_other);
+            hipLaunchKernelGGL(k_lens_rays, dim3((total + kBlock - 1) / kBlock), dim3(kBlock), 0, D->stream, D->S, P, V.Q[0], total);
+            t.Stop();
+        }
         int cur = 0;
         std::vector<uint32_t> frame_marks = {0};
         bool overflow = false;
@@ -2365,7 +2428,8 @@ static int RenderPixels(bhrt_scene *scene, const bhrt_opts &o, PassInfo P, const
             }
             const SlowQueue &sq = V.slowq;
             // the camera step of a scene without meshes: k_shade traces its rays itself (shade_block's kFused); BHRT_FUSED_CAMERA=0: the two-kernel form
-            const bool fused = first_step && H->n_meshes == 0 && D->knobs.fused_camera;
+            const bool cam_step = first_step && !lens; // the step's kernels form the camera rays themselves (kCamera)
+            const bool fused = cam_step && H->n_meshes == 0 && D->knobs.fused_camera;
             if (fused) {
             } else if (injected) {
                 Timer t(D, &st->seconds_trace_closest);
@@ -2376,26 +2440,26 @@ static int RenderPixels(bhrt_scene *scene, const bhrt_opts &o, PassInfo P, const
                 const dim3 tg((n_cur + kBlock - 1) / kBlock), tb(kBlock);
                 if (H->n_meshes > 0) { // park the mesh rays, then finish them in dense workgroups
                     const uint32_t n_buckets = 1u << BHRT_PARK_KEY_BITS, n_tiles = n_buckets / kScanTile;
-                    if (first_step) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_trace_closest<true, true>), tg, tb, 0, D->stream, D->S, P, V.Q[cur], n_cur, 0, V.HB, RO, D->d_cnt, sq);
+                    if (cam_step) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_trace_closest<true, true>), tg, tb, 0, D->stream, D->S, P, V.Q[cur], n_cur, 0, V.HB, RO, D->d_cnt, sq);
                     else {
                         HIP_CHECK(hipMemsetAsync(RO.park_bucket, 0, n_buckets * sizeof(uint32_t), D->stream)); // the trace kernel counts the keys as it parks
                         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_trace_closest<true, false>), tg, tb, 0, D->stream, D->S, P, V.Q[cur], n_cur, 0, V.HB, RO, D->d_cnt, sq);
                     }
                     hipLaunchKernelGGL(k_mesh_prefix, dim3(1), dim3(64), 0, D->stream, D->d_cnt, RO);
-                    if (!first_step) { // counting sort of the parked rays by coherence key (the camera step keeps slot order)
+                    if (!cam_step) { // counting sort of the parked rays by coherence key (the camera step keeps slot order)
                         const dim3 pg(std::min<uint32_t>(tg.x + BHRT_ORDER_SHARDS, 4096u));
                         hipLaunchKernelGGL(k_scan_tiles, dim3(n_tiles), dim3(kScanBlock), 0, D->stream, RO.park_bucket, n_buckets, RO.park_bucket + n_buckets);
                         hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(kScanBlock), 0, D->stream, RO.park_bucket + n_buckets, n_tiles);
                         hipLaunchKernelGGL(k_scan_add, dim3(n_tiles), dim3(kScanBlock), 0, D->stream, RO.park_bucket, n_buckets, RO.park_bucket + n_buckets);
                         hipLaunchKernelGGL(k_park_scatter, pg, tb, 0, D->stream, RO);
                     }
-                    auto mesh_kernel = first_step ? (path_mode == 1 ? (ls ? k_trace_mesh<true, 1, true> : k_trace_mesh<true, 1>) : path_mode == 2 ? (ls ? k_trace_mesh<true, 2, true> : k_trace_mesh<true, 2>) : k_trace_mesh<true, 0>)
+                    auto mesh_kernel = cam_step ? (path_mode == 1 ? (ls ? k_trace_mesh<true, 1, true> : k_trace_mesh<true, 1>) : path_mode == 2 ? (ls ? k_trace_mesh<true, 2, true> : k_trace_mesh<true, 2>) : k_trace_mesh<true, 0>)
                                                   : (path_mode == 1 ? k_trace_mesh<false, 1> : path_mode == 2 ? k_trace_mesh<false, 2> : k_trace_mesh<false, 0>);
                     if (sh_wait_n) { // the last step's any-hit kernels start with this step's mesh walk: they get the SIMDs its finished waves leave
                         HIP_CHECK(hipEventRecord(D->ev_shade, D->stream));
                         rc = launch_any_hit(D->ev_shade); if (rc) return rc;
                     }
-                    if (!first_step && path_mode != 0 && stream_waves > 0)
+                    if (!cam_step && path_mode != 0 && stream_waves > 0)
                     {
 #ifdef BHRT_DEBUG_DRAIN
                         { unsigned long long t0[4] = {~0ull, ~0ull, 0, 0}; HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(g_stream_t), t0, sizeof(t0))); }
@@ -2411,10 +2475,10 @@ static int RenderPixels(bhrt_scene *scene, const bhrt_opts &o, PassInfo P, const
 #endif
                     }
                     else
-                    hipLaunchKernelGGL(mesh_kernel, first_step ? dim3(tg.x + BHRT_ORDER_SHARDS) /* shard segments padded to whole slices */ : dim3((n_cur + kMeshBlock - 1) / kMeshBlock),
-                                       first_step ? tb : dim3(kMeshBlock), 0, D->stream, D->S, P, V.Q[cur], V.HB, RO, D->d_cnt);
-                    if (!first_step) hipLaunchKernelGGL(k_file_parked, dim3(tg.x + BHRT_ORDER_SHARDS), tb, 0, D->stream, V.Q[cur], V.HB, RO, D->d_cnt);
-                } else if (first_step) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_trace_closest<false, true, false>), tg, tb, 0, D->stream, D->S, P, V.Q[cur], n_cur, 0, V.HB, RO, D->d_cnt, no_slow);
+                    hipLaunchKernelGGL(mesh_kernel, cam_step ? dim3(tg.x + BHRT_ORDER_SHARDS) /* shard segments padded to whole slices */ : dim3((n_cur + kMeshBlock - 1) / kMeshBlock),
+                                       cam_step ? tb : dim3(kMeshBlock), 0, D->stream, D->S, P, V.Q[cur], V.HB, RO, D->d_cnt);
+                    if (!cam_step) hipLaunchKernelGGL(k_file_parked, dim3(tg.x + BHRT_ORDER_SHARDS), tb, 0, D->stream, V.Q[cur], V.HB, RO, D->d_cnt);
+                } else if (cam_step) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_trace_closest<false, true, false>), tg, tb, 0, D->stream, D->S, P, V.Q[cur], n_cur, 0, V.HB, RO, D->d_cnt, no_slow);
                 else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_trace_closest<false, false, false>), tg, tb, 0, D->stream, D->S, P, V.Q[cur], n_cur, 0, V.HB, RO, D->d_cnt, no_slow);
                 t.Stop();
             }
@@ -2429,7 +2493,7 @@ static int RenderPixels(bhrt_scene *scene, const bhrt_opts &o, PassInfo P, const
                 const dim3 sg((n_cur + n_extra + kShadeBlock - 1) / kShadeBlock + (fused ? 0 : 3 * BHRT_ORDER_SHARDS)), sb(kShadeBlock);
                 const bool tex = H->n_texmaps > 0;
                 auto shade = fused ? (tex ? k_shade<true, true, true> : k_shade<true, false, true>)
-                                   : first_step ? (tex ? k_shade<true, true> : k_shade<true, false>) : (tex ? k_shade<false, true> : k_shade<false, false>);
+                                   : cam_step ? (tex ? k_shade<true, true> : k_shade<true, false>) : (tex ? k_shade<false, true> : k_shade<false, false>);
                 const int par = (int)(pass_steps & 1u);
                 if (sh_wait_n) { HIP_CHECK(hipEventRecord(D->ev_shade, D->stream)); rc = launch_any_hit(D->ev_shade); if (rc) return rc; }
                 if (sh_overlap && sh_pending[par]) { HIP_CHECK(hipStreamWaitEvent(D->stream, D->ev_shadow[par], 0)); sh_pending[par] = false; } // the any-hit kernels of two steps ago still read this queue
@@ -2604,6 +2668,21 @@ static int RenderAdaptive(bhrt_scene *scene, const bhrt_opts &o, const bhrt_adap
     st->seconds_total += std::chrono::duration<double>(std::chrono::steady_clock::now() - wall0).count();
     return BHRT_OK;
 }
+
+// bhrt_opts.lens against the scene's camera, checked before any device is touched; "" = valid
+static const char *LensArgsError(const bhrt_scene *scene, const bhrt_opts *o)
+{
+    if (!scene || !o) return ""; // reported by the entry point
+    if (o->lens != 0 && o->lens != 1) return "lens must be 0 (pinhole) or 1 (thin lens)";
+    const float dof = scene->flat.hdr()->camera.dof;
+    if (o->lens == 1 && !(dof >= 0.f && dof <= 3.402823466e38f)) return "lens = 1 needs a finite camera dof >= 0";
+    return "";
+}
+#define BHRT_CHECK_LENS(scene, opts)                                                                           \
+    do {                                                                                                       \
+        const char *bad_ = LensArgsError(scene, opts);                                                         \
+        if (*bad_) { SetError(bad_); return BHRT_ERR_ARG; }                                                    \
+    } while (0)
 
 // What the render entry points share: the photon map that photon_map = 1 needs, and statistics that start at zero and reach the caller also when
 // the render fails.  render(bhrt_stats *) does the work.
@@ -2891,6 +2970,7 @@ try {
 int bhrt_render_var_dev(bhrt_scene *scene, const bhrt_opts *opts, uint8_t *d_rgb8, float *d_radiance, float *d_variance, bhrt_stats *stats, void *stream)
 try {
     (void)stream; // the render pipeline synchronises its own stream per wave step
+    BHRT_CHECK_LENS(scene, opts);
     int rc = EnsureUploaded(scene);
     if (rc) return rc;
     if (!opts) { SetError("null opts"); return BHRT_ERR_ARG; }
@@ -2909,6 +2989,7 @@ int bhrt_render(bhrt_scene *scene, const bhrt_opts *opts, uint8_t *rgb8, float *
 
 int bhrt_render_var(bhrt_scene *scene, const bhrt_opts *opts, uint8_t *rgb8, float *radiance, float *variance, bhrt_stats *stats)
 try {
+    BHRT_CHECK_LENS(scene, opts);
     int rc = EnsureUploaded(scene);
     if (rc) return rc;
     if (!opts) { SetError("null opts"); return BHRT_ERR_ARG; }
@@ -2938,6 +3019,7 @@ try {
     (void)stream; // the render pipeline synchronises its own stream per wave step
     const char *bad = AdaptiveArgsError(opts, aopts);
     if (*bad) { SetError(bad); return BHRT_ERR_ARG; }
+    BHRT_CHECK_LENS(scene, opts);
     int rc = EnsureUploaded(scene);
     if (rc) return rc;
     return RenderWithStats(scene, opts, stats, [&](bhrt_stats *st) { return RenderAdaptive(scene, *opts, *aopts, d_rgb8, d_radiance, d_variance, d_count, st); });
@@ -2948,6 +3030,7 @@ int bhrt_render_adaptive(bhrt_scene *scene, const bhrt_opts *opts, const bhrt_ad
 try {
     const char *bad = AdaptiveArgsError(opts, aopts);
     if (*bad) { SetError(bad); return BHRT_ERR_ARG; }
+    BHRT_CHECK_LENS(scene, opts);
     int rc = EnsureUploaded(scene);
     if (rc) return rc;
     FrameStage fs = {rgb8, radiance, variance, count};
@@ -3008,6 +3091,7 @@ void bhrt_host_free(void *ptr)
 
 int bhrt_render_samples(bhrt_scene *scene, const bhrt_opts *opts, int x0, int y0, int x1, int y1, float *samples, bhrt_stats *stats)
 try {
+    BHRT_CHECK_LENS(scene, opts);
     int rc = EnsureUploaded(scene);
     if (rc) return rc;
     if (!opts || !samples) { SetError("null argument"); return BHRT_ERR_ARG; }
@@ -3022,6 +3106,49 @@ try {
         HIP_CHECK(hipMemcpy(samples, d_s, nfl * sizeof(float), hipMemcpyDeviceToHost));
         return BHRT_OK;
     });
+} catch (...) { return bhrt::AbiException(); }
+
+// test hook: the camera rays of a region, formed on the device by the function the render's first wave step uses
+int bhrt_camera_rays(bhrt_scene *scene, const bhrt_opts *opts, int x0, int y0, int x1, int y1, float *rays)
+try {
+    BHRT_CHECK_LENS(scene, opts);
+    int rc = EnsureUploaded(scene);
+    if (rc) return rc;
+    if (!opts || !rays) { SetError("null argument"); return BHRT_ERR_ARG; }
+    const bhrt_flat_header *H = scene->flat.hdr();
+    if (x0 < 0 || y0 < 0 || x1 > H->camera.width || y1 > H->camera.height || x0 >= x1 || y0 >= y1) { SetError("bad region"); return BHRT_ERR_ARG; }
+    bhrt_opts o = *opts;
+    o.rank = 0; o.world_size = 1; // every pixel of the frame is this call's own
+    PassInfo P;
+    uint64_t owned_pixels = 0;
+    BHRT_TRY(FramePassInfo(scene, o, P, owned_pixels));
+    const uint64_t slots = owned_pixels * (uint64_t)o.spp;
+    if (slots > 0xffffffffull) { SetError("bhrt_camera_rays: more than 2^32 sample slots"); return BHRT_ERR_ARG; }
+    P.q0 = 0; P.n_pixels = (uint32_t)owned_pixels;
+    const size_t nfl = (size_t)(x1 - x0) * (y1 - y0) * o.spp * 6;
+    DevBuf<float> d_r;
+    BHRT_TRY(d_r.Reserve(nfl));
+    DeviceState *D = scene->dev;
+    HIP_CHECK(hipMemsetAsync(d_r, 0, nfl * sizeof(float), D->stream));
+    hipLaunchKernelGGL(k_camera_rays, dim3((unsigned)((slots + kBlock - 1) / kBlock)), dim3(kBlock), 0, D->stream, D->S, P, (uint32_t)slots, x0, y0, x1, y1, d_r.p);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipMemcpyAsync(rays, d_r, nfl * sizeof(float), hipMemcpyDeviceToHost, D->stream));
+    HIP_CHECK(hipStreamSynchronize(D->stream));
+    return BHRT_OK;
+} catch (...) { return bhrt::AbiException(); }
+
+// bhrt_scene_set_lens lives in this translation unit because it refreshes the kernels' copy of the camera (DeviceState::S)
+int bhrt_scene_set_lens(bhrt_scene *scene, float focaldist, float dof)
+try {
+    if (!scene) { SetError("bhrt_scene_set_lens: null scene"); return BHRT_ERR_ARG; }
+    if (!(dof >= 0.f && dof <= 3.402823466e38f)) { SetError("bhrt_scene_set_lens: dof must be finite and >= 0"); return BHRT_ERR_ARG; }
+    if (!(focaldist >= -3.402823466e38f && focaldist <= 3.402823466e38f)) { SetError("bhrt_scene_set_lens: focaldist is not finite"); return BHRT_ERR_ARG; }
+    bhrt_flat_header *H = reinterpret_cast<bhrt_flat_header *>(scene->flat.blob.data());
+    if (focaldist > 0.f) H->camera.focaldist = focaldist;
+    H->camera.dof = dof;
+    DeriveCameraFrame(H->camera);
+    if (scene->dev) scene->dev->S.cam = H->camera;
+    return BHRT_OK;
 } catch (...) { return bhrt::AbiException(); }
 
 // ---- images beside the colour image ---------------------------------------------------------------

@@ -1033,6 +1033,26 @@ void BuildBvh(HostMesh &m, unsigned maxPer)
 // ------------------------------------------------------------------------------------------------
 // LoadSceneXml
 // ------------------------------------------------------------------------------------------------
+// BeginRender's camera frame, Main.cpp:179-192 (tan in double, PI = 3.14159265), from the camera's pos, dir, up (orthonormal, as the loader
+// stores them), fov, focaldist and size.  The loader and bhrt_scene_set_lens both run this: one copy of the arithmetic.
+void DeriveCameraFrame(bhrt_camera &C)
+{
+    const V3 pos = {C.pos[0], C.pos[1], C.pos[2]}, dir = {C.dir[0], C.dir[1], C.dir[2]}, up = {C.up[0], C.up[1], C.up[2]};
+    const int w = C.width, h = C.height;
+    float aor = w / (float)h;
+    float tan_h_pov = (float)tan(C.fov / 2 * 3.14159265 / 180.0);
+    float l = C.focaldist;
+    float hh = 2 * l * tan_h_pov;
+    float ww = aor * hh;
+    V3 camZ = -dir, camY = up, camX = cross(camY, camZ);
+    V3 topLeft = pos - camZ * l + camY * hh / 2 - camX * ww / 2;
+    V3 ddx = camX * ww / (float)w; // int -> float promotion in Vec3 / T
+    V3 ddy = camY * hh / (float)h;
+    C.top_left[0] = topLeft.x; C.top_left[1] = topLeft.y; C.top_left[2] = topLeft.z;
+    C.dd_x[0] = ddx.x; C.dd_x[1] = ddx.y; C.dd_x[2] = ddx.z;
+    C.dd_y[0] = ddy.x; C.dd_y[1] = ddy.y; C.dd_y[2] = ddy.z;
+}
+
 int LoadSceneXml(const char *path, FlatScene &out, std::string &err, int bvh_device)
 {
     out.blob.clear();
@@ -1094,19 +1114,7 @@ int LoadSceneXml(const char *path, FlatScene &out, std::string &err, int bvh_dev
         C.dir[0] = dir.x; C.dir[1] = dir.y; C.dir[2] = dir.z;
         C.up[0] = up.x; C.up[1] = up.y; C.up[2] = up.z;
         C.fov = fov; C.focaldist = focaldist; C.dof = dof; C.width = w; C.height = h;
-        // BeginRender's camera frame, Main.cpp:179-192 (tan in double, PI = 3.14159265)
-        float aor = w / (float)h;
-        float tan_h_pov = (float)tan(fov / 2 * 3.14159265 / 180.0);
-        float l = focaldist;
-        float hh = 2 * l * tan_h_pov;
-        float ww = aor * hh;
-        V3 camZ = -dir, camY = up, camX = cross(camY, camZ);
-        V3 topLeft = pos - camZ * l + camY * hh / 2 - camX * ww / 2;
-        V3 ddx = camX * ww / (float)w; // int -> float promotion in Vec3 / T
-        V3 ddy = camY * hh / (float)h;
-        C.top_left[0] = topLeft.x; C.top_left[1] = topLeft.y; C.top_left[2] = topLeft.z;
-        C.dd_x[0] = ddx.x; C.dd_x[1] = ddx.y; C.dd_x[2] = ddx.z;
-        C.dd_y[0] = ddy.x; C.dd_y[1] = ddy.y; C.dd_y[2] = ddy.z;
+        DeriveCameraFrame(C);
     }
 
     // CalculateLightsIntensity (Main.cpp:116-123): std::sort ascending by Gray(), then a float sum

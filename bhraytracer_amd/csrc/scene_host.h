@@ -19,6 +19,9 @@ struct FlatScene {
 // bvh_device >= 0: the mesh BVHs are built on that HIP device (bvh_build.hip) instead of by BuildBvh below; same result.
 int LoadSceneXml(const char *path, FlatScene &out, std::string &err, int bvh_device = -1);
 
+// top_left, dd_x, dd_y of a camera whose other fields are set (the loader's own derivation; bhrt_scene_set_lens runs it again)
+void DeriveCameraFrame(bhrt_camera &C);
+
 // OBJ mesh -> arrays, same face/index rules as cyTriMesh::LoadFromFileObj (cyTriMesh.h:263-547)
 struct HostMesh {
     std::vector<float> v, vn, vt;       // xyz triples

@@ -81,7 +81,11 @@ typedef struct bhrt_opts {
     float photon_radius;      /* gather radius of the caustic term, MAX_Area (MtlBlinn.cpp:29); 0 = the reference's 0.5.  The photon count of an estimate,
                                * MAX_PhotonCountInArea = 1000 (MtlBlinn.cpp:28), is a TEMPLATE argument in the reference too (EstimateIrradiance<1000>,
                                * MtlBlinn.cpp:333) and sizes the candidate lists of the kernels: compile-time here as there (device_photon.h: BHRT_PHOTON_K) */
-    int32_t reserved[1];
+    int32_t lens;             /* thin-lens camera: 0 (default) = pinhole, BeginRender's frame whatever the scene's <dof>; 1 = when camera.dof > 0 the
+                               * ray of a sample starts on the disc of radius dof around the eye, in the camera's x/y plane, and goes through the sample's point on
+                               * the image plane, which lies at <focaldist> (Main.cpp:181-189): the viewport's preview (viewport.cpp:236-243) as a render.  With
+                               * dof == 0 the render is the pinhole one, bit for bit.  Any other value, or 1 with a negative / non-finite dof: BHRT_ERR_ARG,
+                               * before a device is touched.  The images beside the colour image (bhrt_first_hit*) and the denoiser's guides stay the pinhole ray's */
 } bhrt_opts;
 
 typedef struct bhrt_stats {
@@ -139,6 +143,11 @@ void bhrt_scene_free(bhrt_scene *scene);
 int bhrt_scene_info(const bhrt_scene *scene, bhrt_info *info);
 int bhrt_scene_warning(const bhrt_scene *scene, uint32_t i, const char **text); /* the reference printf()s these */
 int bhrt_scene_flat(const bhrt_scene *scene, const void **blob, uint64_t *bytes); /* host copy of the HBM image (include/bhrt_flat.h) */
+/* The camera's <focaldist> and <dof> of a loaded scene (xmlload.cpp:119-120): focaldist <= 0 keeps the current one; dof < 0 or not finite, a NaN
+ * or infinite focaldist: BHRT_ERR_ARG.  The camera frame (top_left, dd_x, dd_y) is derived again by the loader's own code, so bhrt_scene_flat is
+ * afterwards byte-identical to the blob of the same XML with the two values written into its <camera>.  Needs no device; on an uploaded scene
+ * the device's copy of the camera is refreshed (nothing else is uploaded again).  The pointer bhrt_scene_flat returned stays valid. */
+int bhrt_scene_set_lens(bhrt_scene *scene, float focaldist, float dof);
 
 /* ---- device residency ---------------------------------------------------------------------------- */
 int bhrt_scene_upload(bhrt_scene *scene, int device); /* copies the flat scene into HBM of `device`; idempotent */
@@ -173,6 +182,11 @@ void bhrt_host_free(void *ptr);
 int bhrt_render_dev(bhrt_scene *scene, const bhrt_opts *opts, uint8_t *d_rgb8, float *d_radiance, bhrt_stats *stats, void *stream);
 /* per-sample radiance for a pixel region, keyed RNG (parity tests): out = region_pixels*spp*3 floats, host */
 int bhrt_render_samples(bhrt_scene *scene, const bhrt_opts *opts, int x0, int y0, int x1, int y1, float *samples, bhrt_stats *stats);
+
+/* test hook: the camera rays of a pixel region as the render's first wave step forms them (bhrt_opts.lens 0: the device function the camera
+ * kernels inline; 1: the lens kernel's body), on the device.  rays: region_pixels * spp * 6 floats (ox, oy, oz, dx, dy, dz per sample), host,
+ * in the order of bhrt_render_samples.  Uses spp, seed, jitter and lens of the options. */
+int bhrt_camera_rays(bhrt_scene *scene, const bhrt_opts *opts, int x0, int y0, int x1, int y1, float *rays);
 
 /* ---- caustic photon map (Main.cpp:342-386, DataStructure/cyPhotonMap.h) -------------------------- */
 int bhrt_photon_build(bhrt_scene *scene, const bhrt_opts *opts, uint32_t max_photons, uint32_t *n_stored);

@@ -33,6 +33,8 @@
 #define BHRT_SEC_REFRACTION 0u
 #define BHRT_SEC_GI 1u
 #define BHRT_SEC_DIRECT 2u
+/* the thin-lens camera's aperture point (bhrt_opts.lens): section 3 of path code 0, which no Shade() call has (the root is 1) */
+#define BHRT_SEC_LENS 3u
 
 static inline BHRT_HD uint32_t bhrt_mix32(uint32_t x)
 {
