@@ -650,12 +650,15 @@ __global__ void __launch_bounds__(kBlock) k_inject_slow(RayQueue sq, HitBuf sh, 
     q.frame[b] = sq.frame[a]; q.meta[b] = sq.meta[a]; q.rng_ctr[b] = sq.rng_ctr[a];
     h.t[b] = sh.t[a]; h.node[b] = sh.node[a]; h.prim[b] = sh.prim[a]; h.front[b] = sh.front[a];
 }
-// files rays [first, n) (their hits are there) under their shading classes
+// files rays [first, n) (their hits are there) under their shading classes.  `first` is any number (a ride-along's n_cur), and file_ray's shard has to be
+// wave-uniform: the waves cover ALIGNED runs of 64 slots from (first & ~63) on, so no wave straddles a 1024-slot shard boundary (one that did filed part of
+// its rays at positions reserved in another shard's list: rays lost or shaded twice).  Grid: kFileAllBlocks(first, n).
+static inline uint32_t kFileAllBlocks(uint32_t first, uint32_t n) { return (n - (first & ~63u) + kBlock - 1) / kBlock; }
 __global__ void __launch_bounds__(kBlock) k_file_all(RayQueue q, HitBuf h, uint32_t first, uint32_t n, RayOrder ord, Counters *cnt)
 {
-    const uint32_t i = first + blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t i = (first & ~63u) + blockIdx.x * blockDim.x + threadIdx.x;
     uint32_t cls = RC_NONE;
-    if (i < n) {
+    if (i >= first && i < n) {
         Hit hit;
         hit.t = h.t[i]; hit.node = h.node[i]; hit.prim = h.prim[i]; hit.front = h.front[i];
         cls = shading_class(q.meta[i], hit);
@@ -2482,7 +2485,7 @@ static int RenderPixels(bhrt_scene *scene, const bhrt_opts &o, PassInfo P, const
                 else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_trace_closest<false, false, false>), tg, tb, 0, D->stream, D->S, P, V.Q[cur], n_cur, 0, V.HB, RO, D->d_cnt, no_slow);
                 t.Stop();
             }
-            if (n_extra) hipLaunchKernelGGL(k_file_all, dim3((n_extra + kBlock - 1) / kBlock), dim3(kBlock), 0, D->stream, V.Q[cur], V.HB, n_cur, n_cur + n_extra, RO, D->d_cnt);
+            if (n_extra) hipLaunchKernelGGL(k_file_all, dim3(kFileAllBlocks(n_cur, n_cur + n_extra)), dim3(kBlock), 0, D->stream, V.Q[cur], V.HB, n_cur, n_cur + n_extra, RO, D->d_cnt);
             if (!fused) {
                 st->launches_trace_closest++;
                 hipLaunchKernelGGL(k_order_prefix, dim3(1), dim3(128), 0, D->stream, D->d_cnt, RO);

@@ -155,7 +155,8 @@ int bhrt_scene_upload(bhrt_scene *scene, int device); /* copies the flat scene i
  * "gather_stats"; "shadow_overlap" (default 1; 0 = the any-hit kernels of a wave step run in front of the next step on the pass's own stream instead of
  * beside it on a second one: the kernel groups timed alone, bench.py's `frac_alone`).
  * The library reads its development switches (BHRT_STREAM_WAVES, BHRT_FUSED_CAMERA, BHRT_NO_SLOW_QUEUE, BHRT_DEBUG_*, BHRT_PHOTON_BALANCE_HOST,
- * BHRT_SHADOW_OVERLAP) from the environment once, at upload; the test knobs are not reachable from the environment at all. */
+ * BHRT_GATHER_COUNTING_SORT, BHRT_SHADOW_OVERLAP) from the environment once, at upload; the test knobs are not reachable from the environment at
+ * all.  tests/test_switch_paths.py holds every switch to "never its result" (DESIGN.md 5). */
 int bhrt_scene_knob(bhrt_scene *scene, const char *name, int value);
 int bhrt_device_count(int *n);
 
