@@ -44,7 +44,7 @@ class Stats(C.Structure):
                 ("seconds_photon_gather", C.c_double), ("seconds_photon_heavy", C.c_double),
                 ("photon_queries", C.c_uint64), ("photon_heavy_queries", C.c_uint64), ("photon_wave_queries", C.c_uint64),
                 ("photon_exact_queries", C.c_uint64), ("photon_nodes_visited", C.c_uint64), ("deferred_rays", C.c_uint64),
-                ("photon_lane_queries", C.c_uint64), ("photon_lane_nodes", C.c_uint64), ("photon_found", C.c_uint64), ("reserved", C.c_double * 1)]
+                ("photon_lane_queries", C.c_uint64), ("photon_lane_nodes", C.c_uint64), ("photon_found", C.c_uint64), ("launches_resolve_fused", C.c_uint64)]
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_ if n != "reserved"}
@@ -361,7 +361,7 @@ class Scene:
         return n.value
 
     def knob(self, name: str, value: int):
-        """Knobs ("frame_cap", "gather_lane_budget", "gather_stats", "shadow_overlap"): which internal path a render takes, never its result (bhrt_scene_knob)."""
+        """Knobs ("frame_cap", "gather_lane_budget", "gather_stats", "shadow_overlap", "fused_resolve"): which internal path a render takes, never its result (bhrt_scene_knob)."""
         _check(lib().bhrt_scene_knob(self._h, name.encode(), int(value)))
 
     def photon_get(self) -> np.ndarray:

@@ -105,6 +105,7 @@ struct DeviceState : DeviceQueues {
     DevBuf<uint64_t> d_fcode;                  // cap_frames
     DevBuf<float> d_ff;                        // (3*7 + 2) * cap_frames
     DevBuf<float> d_samples;                   // 3 * cap_samples
+    DevBuf<uint32_t> d_root;                   // cap_samples: sample slot -> its root Shade() frame, or kNoRootFrame (k_shade -> k_resolve_frames)
     DevBuf<uint32_t> d_order;                  // 4 * BHRT_ORDER_SHARDS * order_shard_cap (shading order, device_types.h::RayOrder)
     uint32_t order_shard_cap = 0;
     DevBuf<uint32_t> d_seg;                    // seg_start[97] + seg_count[96] + mesh_start[33] + mesh_count[33] + frame_base[96]
@@ -159,6 +160,7 @@ struct DeviceState : DeviceQueues {
         int gather_lane_budget = 0;     // knob "gather_lane_budget": photons a lane may visit before its query goes to the one-wave pass; 0 = default
         bool gather_counting_sort = false; // BHRT_GATHER_COUNTING_SORT=1: the cell order by the counting sort instead of the radix sort of pairs
         bool shadow_overlap = true;     // BHRT_SHADOW_OVERLAP=0: the any-hit kernels of a wave step on the pass's own stream, in front of the next step
+        bool fused_resolve = true;      // BHRT_FUSED_RESOLVE=0, knob "fused_resolve": a plain render resolves through the sample buffer (k_combine's root level + k_resolve)
         int gather_stats = 0;           // knob "gather_stats": the lane pass counts the photons its answers are made of (bhrt_stats.photon_found), 7 % slower
         void FromEnv()
         {
@@ -169,6 +171,7 @@ struct DeviceState : DeviceQueues {
             if (const char *e = getenv("BHRT_PHOTON_BALANCE_HOST")) balance_host = atoi(e) != 0;
             if (const char *e = getenv("BHRT_GATHER_COUNTING_SORT")) gather_counting_sort = atoi(e) != 0;
             if (const char *e = getenv("BHRT_SHADOW_OVERLAP")) shadow_overlap = atoi(e) != 0;
+            if (const char *e = getenv("BHRT_FUSED_RESOLVE")) fused_resolve = atoi(e) != 0;
         }
     } knobs;
     // a capacity overflow halves the pass (RenderPixels); later frames of the same scene and options start from the reduced size

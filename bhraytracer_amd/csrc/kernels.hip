@@ -15,6 +15,7 @@
 //   k_combine       MtlBlinn.cpp:117-137,343,431,470,511,539  folds finished frames into their parents, deepest
 //                                              wave step first (the per-level clamps forbid a running throughput)
 //   k_resolve       Main.cpp:170,220-230       in-order sample sum, /spp, gamma, Color24
+//   k_resolve_frames  (the two above)          a render of the image alone: k_combine's root level and k_resolve in one launch, no sample buffer between
 //   k_variance      (DenoiseImage's input)     per-channel variance of the pixel mean, only when a variance image is asked for
 //   k_adapt_fold    scene.h:534,570 (sampleCount)  adaptive rounds: folds a pass into each pixel's state, retires converged pixels, lists the rest
 //   k_photon_*      Main.cpp:319-386, cyPhotonMap.h   caustic photon map: emission, and the k-NN gather in three passes
@@ -189,6 +190,9 @@ __device__ inline uint32_t sample_addr(const PassInfo &P, uint32_t slot)
     fdivmod(slot, P.by_spp, px, smp);
     return smp * P.n_pixels + px;
 }
+// The other way from a sample to its radiance (DeviceState::d_root, a plain resolve with the knob "fused_resolve"): slot -> the Shade() frame its
+// camera ray opened, written by k_shade whenever it shades a ray of kind RK_CAMERA, in whichever step.  This value: the camera ray missed.
+constexpr uint32_t kNoRootFrame = 0xffffffffu;
 
 __device__ inline void put_ray(const RayQueue &q, uint32_t i, V3 o, V3 d, uint32_t frame, uint32_t meta, uint32_t ctr)
 {
@@ -943,7 +947,7 @@ __device__ inline void shade_entry(const DevScene &S, const RenderParams &R, con
 // sit in one wave: hits and misses are as uniform per workgroup in slot order as in the sorted one), frame numbers from one atomic per workgroup.
 template <bool kCamera, bool kTex, bool kFused = false>
 __device__ __forceinline__ void shade_block(const DevScene &S, const RenderParams &R, const PassInfo &P, const RayQueue &qin, const HitBuf &hb, uint32_t n, const RayQueue &qout,
-                                            const ShadowQueue &qs, const Frames &F, float *samples, Counters *cnt, const RayOrder &ord)
+                                            const ShadowQueue &qs, const Frames &F, float *samples, uint32_t *root_of, Counters *cnt, const RayOrder &ord)
 {
     static_assert(!kFused || kCamera, "only camera rays are traced in the shading kernel");
     __shared__ BlockAllocLds lds;
@@ -1024,6 +1028,7 @@ __device__ __forceinline__ void shade_block(const DevScene &S, const RenderParam
             gi = R.gi_bounces;
             bounce = R.internal_bounces;
             how = FH_ROOT;
+            if (root_of) root_of[owner] = f; // k_resolve_frames finds the sample's root frame here
         } else {
             const uint64_t pcode = F.code[owner];
             skey = F.skey[owner];
@@ -1062,8 +1067,11 @@ __device__ __forceinline__ void shade_block(const DevScene &S, const RenderParam
             // background.Sample((i/W, j/H, 0)), Main.cpp:166-167
             int pi, pj;
             uint32_t osmp;
-            slot_pixel(P, owner, pi, pj, osmp);
-            st3(samples, sample_addr(P, owner), kTex ? tc_sample(S, S.background, v3((float)pi / S.cam.width, (float)pj / S.cam.height, 0.0f)) : ld3(S.background.color));
+            if (root_of) root_of[owner] = kNoRootFrame; // k_resolve_frames forms the background value itself
+            else {
+                slot_pixel(P, owner, pi, pj, osmp);
+                st3(samples, sample_addr(P, owner), kTex ? tc_sample(S, S.background, v3((float)pi / S.cam.width, (float)pj / S.cam.height, 0.0f)) : ld3(S.background.color));
+            }
         } else if (kind == RK_GI) {
             V3 mult = ld3i(F.gi_mult, owner);
             V3 outc = v3(0, 0, 0);
@@ -1156,9 +1164,9 @@ __device__ __forceinline__ void shade_block(const DevScene &S, const RenderParam
 // ticket (release fence); the last ticket holder reads them with atomic loads behind an acquire fence.
 template <bool kCamera, bool kTex, bool kFused = false>
 __global__ void __launch_bounds__(kShadeBlock, BHRT_SHADE_WAVES) k_shade(DevScene S, RenderParams R, PassInfo P, RayQueue qin, HitBuf hb, uint32_t n, RayQueue qout,
-                                                   ShadowQueue qs, Frames F, float *samples, Counters *cnt, RayOrder ord, HostCounters *pub, uint32_t seq)
+                                                   ShadowQueue qs, Frames F, float *samples, uint32_t *root_of, Counters *cnt, RayOrder ord, HostCounters *pub, uint32_t seq)
 {
-    shade_block<kCamera, kTex, kFused>(S, R, P, qin, hb, n, qout, qs, F, samples, cnt, ord);
+    shade_block<kCamera, kTex, kFused>(S, R, P, qin, hb, n, qout, qs, F, samples, root_of, cnt, ord);
     if (!pub) return;
     __syncthreads(); // every wave is through: its queue counters were added to by returning atomics whose results it has used (block_alloc), its
     // capacity flags likewise (flag_overflow) — all acknowledged.  No agent-scope fence: only counters travel, all by atomics at agent scope; a release
@@ -1170,13 +1178,11 @@ __global__ void __launch_bounds__(kShadeBlock, BHRT_SHADE_WAVES) k_shade(DevScen
 }
 
 // ------------------------------------------------------------------------------------------------
-// Fold frames [f0, f1) (all created in one wave step) into their parents / the sample buffer.
-__global__ void __launch_bounds__(kBlock) k_combine(DevScene S, PassInfo P, Frames F, uint32_t f0, uint32_t f1, float *samples, int photon)
+// The value of Shade() frame f once its sub-terms are in (MtlBlinn.cpp:117-137): what k_combine hands to the frame's parent and what
+// k_resolve_frames sums for a root frame.  ONE copy: the two kernels owe each other the same operations in the same order.
+__device__ inline V3 frame_value(const DevScene &S, const Frames &F, uint32_t f, uint32_t info, int photon)
 {
-    const uint32_t f = f0 + blockIdx.x * blockDim.x + threadIdx.x;
-    if (f >= f1) return;
-    const uint32_t info = F.info[f];
-    const uint32_t how = info & 7u, dmode = (info >> 3) & 7u, li = (info >> 8) & 0xffu, flags = (info >> 16) & 0xfu;
+    const uint32_t dmode = (info >> 3) & 7u, li = (info >> 8) & 0xffu, flags = (info >> 16) & 0xfu;
     V3 out;
     if (flags & FF_CONST) out = ld3i(F.refr, f);
     else {
@@ -1209,6 +1215,17 @@ __global__ void __launch_bounds__(kBlock) k_combine(DevScene S, PassInfo P, Fram
             if (!done && isnan_f(out.x)) out = v3(1.0f, 0.0f, 1.0f);
         }
     }
+    return out;
+}
+
+// Fold frames [f0, f1) (all created in one wave step) into their parents / the sample buffer.
+__global__ void __launch_bounds__(kBlock) k_combine(DevScene S, PassInfo P, Frames F, uint32_t f0, uint32_t f1, float *samples, int photon)
+{
+    const uint32_t f = f0 + blockIdx.x * blockDim.x + threadIdx.x;
+    if (f >= f1) return;
+    const uint32_t info = F.info[f];
+    const uint32_t how = info & 7u;
+    const V3 out = frame_value(S, F, f, info, photon);
     const uint32_t parent = F.parent[f];
     if (how == FH_ROOT) st3(samples, sample_addr(P, parent), out);
     else if (how == FH_GI) { // MtlBlinn.cpp:406,427-432
@@ -1233,6 +1250,66 @@ __global__ void __launch_bounds__(kBlock) k_resolve(PassInfo P, const float *sam
     const size_t pix = (size_t)j * P.W + i;
     if (radiance) st3(radiance, (uint32_t)pix, out);
     if (rgb8) store_color24(rgb8, pix, out, P.gamma);
+}
+
+// The end of a pass whose only consumer is the image (RenderRange without region samples or variance, knob "fused_resolve"): the root level of
+// k_combine and k_resolve in one launch, without the sample buffer between them.  There a root frame's 12 bytes went to sample_addr — consecutive
+// frames are consecutive samples of one pixel, 12 * n_pixels bytes apart — and came straight back: 2 x 12 bytes per sample of partial lines.
+// A wave takes kResolvePixels pixels of the pass, one after the other, lanes over the samples (spp > 64: in chunks of 64, the sums carried
+// along).  Lane s looks up its sample's root frame in root_of (consecutive words; the frames themselves are neighbours too: the camera step
+// numbers them in slot order, wave by wave) and forms frame_value, or, for kNoRootFrame, the background value k_shade stores on the other path.
+// The values go to LDS and lane 3 p + c adds channel c of pixel p from zero IN SAMPLE ORDER, then divides by (float)spp: k_resolve's additions
+// and division, one chain per lane — float addition order is part of the image, so no tree and no cross-lane reduction.  Slots of edge-tile
+// pixels outside the image are never read (k_shade leaves their map entries unwritten).
+constexpr int kResolvePixels = 8;
+constexpr int kResolveStride = 64 * 3 + 3; // floats per pixel in LDS; 3 mod 32 banks: the 24 summing lanes read 24 different banks
+template <bool kTex>
+__global__ void __launch_bounds__(64) k_resolve_frames(DevScene S, PassInfo P, Frames F, const uint32_t *root_of, int photon, float *radiance, uint8_t *rgb8)
+{
+    __shared__ float s_val[kResolvePixels * kResolveStride];
+    const uint32_t lane = threadIdx.x, spp = (uint32_t)P.spp;
+    const uint32_t q0 = blockIdx.x * kResolvePixels;
+    const uint32_t n_here = min((uint32_t)kResolvePixels, P.n_pixels - q0); // the grid covers ceil(n_pixels / kResolvePixels) waves: >= 1
+    // the summing lanes: pixel sp, channel sc
+    const uint32_t sp = lane / 3u, sc = lane - 3u * sp;
+    int si = 0, sj = 0;
+    const bool summing = sp < n_here && pixel_of(P, pass_pixel(P, q0 + sp), si, sj);
+    float sum = 0.f;
+    for (uint32_t s0 = 0; s0 < spp; s0 += 64u) {
+        const uint32_t smp = s0 + lane;
+        uint32_t f[kResolvePixels], info[kResolvePixels];
+        bool live[kResolvePixels];
+        int pi[kResolvePixels], pj[kResolvePixels];
+#pragma unroll
+        for (int p = 0; p < kResolvePixels; p++) { // the lookups of all pixels are in flight together
+            pi[p] = pj[p] = 0;
+            live[p] = (uint32_t)p < n_here && pixel_of(P, pass_pixel(P, q0 + p), pi[p], pj[p]) && smp < spp; // but for the last term uniform
+            f[p] = live[p] ? root_of[(q0 + p) * spp + smp] : kNoRootFrame;
+        }
+#pragma unroll
+        for (int p = 0; p < kResolvePixels; p++) info[p] = f[p] != kNoRootFrame ? F.info[f[p]] : 0u;
+#pragma unroll
+        for (int p = 0; p < kResolvePixels; p++) {
+            if (!live[p]) continue;
+            V3 v;
+            if (f[p] != kNoRootFrame) v = frame_value(S, F, f[p], info[p], photon);
+            else v = kTex ? tc_sample(S, S.background, v3((float)pi[p] / S.cam.width, (float)pj[p] / S.cam.height, 0.0f)) : ld3(S.background.color); // Main.cpp:166-167
+            float *dst = s_val + p * kResolveStride + 3 * lane;
+            dst[0] = v.x; dst[1] = v.y; dst[2] = v.z;
+        }
+        __syncthreads();
+        if (summing) {
+            const float *src = s_val + sp * kResolveStride + sc;
+            const uint32_t n = min(64u, spp - s0);
+            for (uint32_t s = 0; s < n; s++) sum = sum + src[3 * s];
+        }
+        __syncthreads(); // the next chunk overwrites the values
+    }
+    if (!summing) return;
+    const float m = sum / (float)P.spp;
+    const size_t pix = (size_t)sj * P.W + si;
+    if (radiance) radiance[pix * 3 + sc] = m;
+    if (rgb8) rgb8[pix * 3 + sc] = color24_channel(m, P.gamma);
 }
 
 // The denoiser's noise estimate: per-channel variance of the pixel mean, same layout as the radiance image.  m is k_resolve's mean
@@ -1929,6 +2006,7 @@ static int EnsureWorkspace(DeviceState *D, uint32_t cap_samples, double frames_p
         go(D->d_hitf, cr); go(D->d_hiti, cr * 3); go(D->d_shf, cr * 7); go(D->d_shu, cr);
         go(D->d_fu, cf * 4); go(D->d_fcode, cf); go(D->d_ff, cf * 23);
         go(D->d_samples, (size_t)cap_samples * 3);
+        go(D->d_root, cap_samples);
         go(D->d_order, (size_t)4 * BHRT_ORDER_SHARDS * shard_cap);
         go(D->d_park, 3 * cr + (1u << BHRT_PARK_KEY_BITS) + kScanBlock);
         if (D->stream3) { go(D->d_shf2, cr * 7); go(D->d_shu2, cr); go(D->d_order_sh, (size_t)BHRT_ORDER_SHARDS * shard_cap); }
@@ -1938,6 +2016,8 @@ static int EnsureWorkspace(DeviceState *D, uint32_t cap_samples, double frames_p
     each([](auto &buf, size_t) { buf.Free(); return BHRT_OK; });
     D->cap_samples = 0;
     BHRT_TRY(each([](auto &buf, size_t n) { return buf.Reserve(n); }));
+    // every entry k_resolve_frames can ever meet is then kNoRootFrame or a frame number k_shade wrote, which is below cap_frames: no address outside the pool
+    HIP_CHECK(hipMemset(D->d_root, 0xff, (size_t)cap_samples * sizeof(uint32_t)));
     D->order_shard_cap = shard_cap;
     D->cap_samples = cap_samples; D->cap_rays = (uint32_t)cr; D->cap_frames = (uint32_t)cf;
     D->d_ph_frames.Free(); // sized by cap_frames: RenderPixels allocates it again when a render needs it
@@ -2283,12 +2363,14 @@ static void LaunchAnyHit(DeviceState *D, hipStream_t stream, bool meshes, const 
 
 // Renders samples [s0, s0 + spp) of n_items owned pixels of this rank: the range [0, n_items) of owned-pixel indices (d_list == nullptr) or
 // the entries of the device list d_list (an adaptive round), in passes.  Pass sizing, the halve-and-redo of a pass that overflows, the photon
-// gather per pass, the slow queue and the any-hit overlap are the same for both.  consume(P, npx) launches, on D->stream, what reads a finished
+// gather per pass, the slow queue and the any-hit overlap are the same for both.  consume(P, npx, F) launches, on D->stream, what reads a finished
 // pass's sample-major buffer D->d_samples: k_resolve / k_variance / k_copy_samples for a uniform render (RenderRange), k_adapt_fold for an
 // adaptive round (RenderAdaptive).  The caller synchronises and flushes the timers.
+// fuse_root: the consumer is k_resolve_frames, which reads the root frames themselves.  k_shade then fills the slot -> root frame map D->d_root
+// instead of storing background samples, and the root level of k_combine is not launched; d_samples holds nothing the consumer may read.
 template <class Consume>
 static int RenderPixels(bhrt_scene *scene, const bhrt_opts &o, PassInfo P, const uint32_t *d_list, uint64_t n_items, uint32_t s0, uint32_t spp, bhrt_stats *st,
-                        const Consume &consume)
+                        bool fuse_root, const Consume &consume)
 {
     DeviceState *D = scene->dev;
     const bhrt_flat_header *H = scene->flat.hdr();
@@ -2356,7 +2438,9 @@ static int RenderPixels(bhrt_scene *scene, const bhrt_opts &o, PassInfo P, const
         bool sh_pending[2] = {false, false};
         HIP_CHECK(hipMemsetAsync(D->d_cnt, 0, sizeof(Counters), D->stream));
         // d_samples needs no clearing: every slot of a valid pixel is written exactly once (k_shade: background of a camera
-        // miss; k_combine: root frame), and k_resolve never reads the slots of edge-tile pixels outside the image
+        // miss; k_combine: root frame), and k_resolve never reads the slots of edge-tile pixels outside the image.  The same holds for
+        // d_root and k_resolve_frames — also in a pass that overflowed and is redone: its k_shade launches write every entry again
+        uint32_t *const root_of = fuse_root ? D->d_root.p : nullptr;
         const uint32_t total = npx * spp;
         uint32_t n_cur = total; // first wave step: one slot per (pixel, sample); the kernels compute the camera rays themselves
         bool first_step = true;
@@ -2500,7 +2584,7 @@ static int RenderPixels(bhrt_scene *scene, const bhrt_opts &o, PassInfo P, const
                 const int par = (int)(pass_steps & 1u);
                 if (sh_wait_n) { HIP_CHECK(hipEventRecord(D->ev_shade, D->stream)); rc = launch_any_hit(D->ev_shade); if (rc) return rc; }
                 if (sh_overlap && sh_pending[par]) { HIP_CHECK(hipStreamWaitEvent(D->stream, D->ev_shadow[par], 0)); sh_pending[par] = false; } // the any-hit kernels of two steps ago still read this queue
-                hipLaunchKernelGGL(shade, sg, sb, 0, D->stream, D->S, R, P, V.Q[cur], V.HB, n_cur + n_extra, V.Q[cur ^ 1], (sh_overlap && par) ? V.SQ2 : V.SQ, F, D->d_samples, D->d_cnt, RO, D->d_pub, seq); // + n_next, n_shadow, n_frames, overflow to the host
+                hipLaunchKernelGGL(shade, sg, sb, 0, D->stream, D->S, R, P, V.Q[cur], V.HB, n_cur + n_extra, V.Q[cur ^ 1], (sh_overlap && par) ? V.SQ2 : V.SQ, F, D->d_samples, root_of, D->d_cnt, RO, D->d_pub, seq); // + n_next, n_shadow, n_frames, overflow to the host
                 t.Stop();
                 if (sh_overlap) HIP_CHECK(hipEventRecord(D->ev_shade, D->stream));
             }
@@ -2588,11 +2672,14 @@ static int RenderPixels(bhrt_scene *scene, const bhrt_opts &o, PassInfo P, const
         st->closest_rays += pass_closest;
         {
             Timer t(D, &st->seconds_other);
-            for (size_t k = frame_marks.size(); k-- > 1;) {
+            // fuse_root: the first step's frames are the root frames of the camera rays it shaded, all of them, and k_resolve_frames folds those.  A
+            // camera ray that was set aside opens its root frame in a later step, among frames of other kinds: that step's launch stays whole and
+            // stores the frame's value into d_samples, where nothing reads it — k_resolve_frames finds the frame through the map like any other
+            for (size_t k = frame_marks.size(); k-- > (fuse_root ? 2 : 1);) {
                 const uint32_t f0 = frame_marks[k - 1], f1 = frame_marks[k];
                 if (f1 > f0) hipLaunchKernelGGL(k_combine, dim3((f1 - f0 + kBlock - 1) / kBlock), dim3(kBlock), 0, D->stream, D->S, P, F, f0, f1, D->d_samples, o.photon_map);
             }
-            consume(P, npx);
+            consume(P, npx, F);
             t.Stop();
         }
         HIP_CHECK(hipGetLastError());
@@ -2613,7 +2700,16 @@ static int RenderRange(bhrt_scene *scene, const bhrt_opts &o, uint8_t *d_rgb8, f
     int rc = FramePassInfo(scene, o, P, owned_pixels);
     if (rc) return rc;
     const auto wall0 = std::chrono::steady_clock::now();
-    rc = RenderPixels(scene, o, P, nullptr, owned_pixels, 0, (uint32_t)o.spp, st, [&](const PassInfo &Pp, uint32_t npx) {
+    // nothing but the image is asked for: the root frames are resolved straight into it (k_resolve_frames); knob "fused_resolve" = 0: the two kernels below
+    const bool fuse_root = D->knobs.fused_resolve && !d_variance && !d_region_samples;
+    const bool tex = scene->flat.hdr()->n_texmaps > 0;
+    rc = RenderPixels(scene, o, P, nullptr, owned_pixels, 0, (uint32_t)o.spp, st, fuse_root, [&](const PassInfo &Pp, uint32_t npx, const Frames &F) {
+        if (fuse_root) {
+            hipLaunchKernelGGL(tex ? k_resolve_frames<true> : k_resolve_frames<false>, dim3((npx + kResolvePixels - 1) / kResolvePixels), dim3(64), 0, D->stream, D->S, Pp, F,
+                               D->d_root.p, o.photon_map, d_radiance, d_rgb8);
+            st->launches_resolve_fused++;
+            return;
+        }
         hipLaunchKernelGGL(k_resolve, dim3((npx + kBlock - 1) / kBlock), dim3(kBlock), 0, D->stream, Pp, D->d_samples, d_radiance, d_rgb8);
         if (d_variance) hipLaunchKernelGGL(k_variance, dim3((npx + kBlock - 1) / kBlock), dim3(kBlock), 0, D->stream, Pp, D->d_samples, d_variance);
         if (d_region_samples)
@@ -2653,7 +2749,7 @@ static int RenderAdaptive(bhrt_scene *scene, const bhrt_opts &o, const bhrt_adap
     for (int cur = 0; items > 0; cur ^= 1) {
         R.next = lists[cur];
         HIP_CHECK(hipMemsetAsync(R.n_next, 0, sizeof(uint32_t), D->stream));
-        rc = RenderPixels(scene, o, P, list, items, n_prev, n - n_prev, st, [&](const PassInfo &Pp, uint32_t npx) {
+        rc = RenderPixels(scene, o, P, list, items, n_prev, n - n_prev, st, false, [&](const PassInfo &Pp, uint32_t npx, const Frames &) {
             hipLaunchKernelGGL(k_adapt_fold, dim3((npx + kBlock - 1) / kBlock), dim3(kBlock), 0, D->stream, Pp, D->d_samples, A, R);
         });
         if (rc) return rc;
@@ -2760,7 +2856,8 @@ try {
 } catch (...) { return bhrt::AbiException(); }
 
 // Knobs: "shadow_overlap" — 0: the any-hit kernels of a wave step run on the pass's own stream, in front of the next step (bench.py times the kernel
-// groups alone that way; same results either way).  Test knobs (tests/): "frame_cap" — a frame pool of that many Shade() frames, so that a pass overflows and is redone in halves; "gather_lane_budget" —
+// groups alone that way; same results either way); "fused_resolve" — 0: a plain render ends in the root level of k_combine and k_resolve, through the
+// sample buffer, instead of k_resolve_frames (the A/B of tests/test_resolve_fused.py and of a profile).  Test knobs (tests/): "frame_cap" — a frame pool of that many Shade() frames, so that a pass overflows and is redone in halves; "gather_lane_budget" —
 // photons a lane of the gather's first pass may visit before its query is handed to a whole wave.  0 switches a knob off.  Neither changes a result,
 // and no environment variable sets them: a stray variable in a user's environment cannot send a render through the retry path.
 int bhrt_scene_knob(bhrt_scene *scene, const char *name, int value)
@@ -2772,6 +2869,7 @@ try {
     else if (!strcmp(name, "gather_lane_budget")) scene->dev->knobs.gather_lane_budget = value;
     else if (!strcmp(name, "gather_stats")) scene->dev->knobs.gather_stats = value;
     else if (!strcmp(name, "shadow_overlap")) scene->dev->knobs.shadow_overlap = value != 0;
+    else if (!strcmp(name, "fused_resolve")) scene->dev->knobs.fused_resolve = value != 0;
     else { SetError(std::string("knob: unknown name ") + name); return BHRT_ERR_ARG; }
     return BHRT_OK;
 } catch (...) { return bhrt::AbiException(); }

@@ -110,7 +110,7 @@ typedef struct bhrt_stats {
     /* the lane pass of the gather (k_photon_gather_fast) alone: queries it answered, kd nodes it examined, and — only with the knob "gather_stats"
      * (bhrt_scene_knob: a statistics instantiation of the kernel, 7 % slower) — the photons those answers were made of */
     uint64_t photon_lane_queries, photon_lane_nodes, photon_found;
-    double reserved[1];
+    uint64_t launches_resolve_fused; /* passes whose root frames were resolved straight into the image (k_resolve_frames, knob "fused_resolve") */
 } bhrt_stats;
 
 /* compact hit record written by the trace kernel (SoA on the device: one array per field) */
@@ -153,9 +153,10 @@ int bhrt_scene_set_lens(bhrt_scene *scene, float focaldist, float dof);
 int bhrt_scene_upload(bhrt_scene *scene, int device); /* copies the flat scene into HBM of `device`; idempotent */
 /* knobs of an uploaded scene: they steer which internal path a render takes, never its result.  Test knobs "frame_cap", "gather_lane_budget" (0 = off) and
  * "gather_stats"; "shadow_overlap" (default 1; 0 = the any-hit kernels of a wave step run in front of the next step on the pass's own stream instead of
- * beside it on a second one: the kernel groups timed alone, bench.py's `frac_alone`).
+ * beside it on a second one: the kernel groups timed alone, bench.py's `frac_alone`); "fused_resolve" (default 1; 0 = a render that asks for the image
+ * alone ends in the root level of k_combine and k_resolve, through the per-sample buffer, like every other render, instead of k_resolve_frames).
  * The library reads its development switches (BHRT_STREAM_WAVES, BHRT_FUSED_CAMERA, BHRT_NO_SLOW_QUEUE, BHRT_DEBUG_*, BHRT_PHOTON_BALANCE_HOST,
- * BHRT_GATHER_COUNTING_SORT, BHRT_SHADOW_OVERLAP) from the environment once, at upload; the test knobs are not reachable from the environment at
+ * BHRT_GATHER_COUNTING_SORT, BHRT_SHADOW_OVERLAP, BHRT_FUSED_RESOLVE) from the environment once, at upload; the test knobs are not reachable from the environment at
  * all.  tests/test_switch_paths.py holds every switch to "never its result" (DESIGN.md 5). */
 int bhrt_scene_knob(bhrt_scene *scene, const char *name, int value);
 int bhrt_device_count(int *n);
