@@ -67,7 +67,7 @@ struct DeviceQueues {
     hipEvent_t ev[2] = {nullptr, nullptr};
     hipStream_t stream2 = nullptr;             // k_trace_slow runs here, beside the pass
     std::vector<hipEvent_t> slow_events;       // one per k_trace_slow launch of a pass (its hits are in place)
-    hipStream_t stream3 = nullptr;             // any-hit work of a wave step beside the next step's closest-hit work (RenderPixels, knobs.shadow_overlap)
+    hipStream_t stream3 = nullptr;             // any-hit work of a wave step beside the next step's closest-hit work (WavePass::sh_overlap, knobs.shadow_overlap)
     hipEvent_t ev_shade = nullptr, ev_shadow[2] = {nullptr, nullptr};
     std::vector<hipEvent_t> ev_pool;           // Timer
     DeviceQueues() = default;

@@ -2029,7 +2029,7 @@ static int EnsureWorkspace(DeviceState *D, uint32_t cap_samples, double frames_p
 // queues), their hit (16 B) and shadow (32 B) slots, shading order and park lists (counted as 40 B per ray slot: 32 B of order entries — four classes of
 // 4 B, twice over for the shards' slack — and 4 B each of park_key and park_sorted; the 4 B of park_rank, which came later, are NOT counted: the
 // workspace takes 44 B, the constant decides the pass size and stays as measured, and the 15 % of headroom below covers the rest), in scenes
-// with meshes the second shadow queue and the any-hit kernels' own parked list (32 + 8 B: RenderPixels, "any-hit work beside the pass"), 12 B of
+// with meshes the second shadow queue and the any-hit kernels' own parked list (32 + 8 B: WavePass::sh_overlap, "any-hit work beside the pass"), 12 B of
 // radiance, and `frames_per_sample` Shade() frames (116 B each, + 60 B with the photon map): six by default = 1.03-1.11 KB per sample, 2^27 samples
 // = 138-149 GB.
 static uint32_t DefaultPassSamples(DeviceState *D, bool photon_map, double frames_per_sample)
@@ -2345,20 +2345,415 @@ static PassViews MakePassViews(DeviceState *D, bool sh_overlap)
     return V;
 }
 
-// The any-hit kernels of one wave step on `stream`: the first n rays of `sq` into `vis`.  n_dev != nullptr: the queue's length is read on the device and n is
-// the bound the grids cover.  With meshes the rays that enter one are parked in `order` (counted in `counters`) and finished in dense workgroups.
-static void LaunchAnyHit(DeviceState *D, hipStream_t stream, bool meshes, const ShadowQueue &sq, uint32_t n, const uint32_t *n_dev, float *vis, const RayOrder &order,
-                         Counters *counters, int path_mode, bool ls, double *seconds)
+// The traversal's path in LDS, for every mesh walk of a render: 1 = 16-bit pair indices, 2 = 32-bit (a mesh with 2^17 nodes or more), 0 = no (deeper than 32 levels)
+static int PathMode(const bhrt_scene *scene)
 {
-    Timer t(D, seconds, 1, stream);
-    const dim3 hg((n + kBlock - 1) / kBlock), hb(kBlock);
-    if (meshes) {
-        hipLaunchKernelGGL(k_trace_shadow_park, hg, hb, 0, stream, D->S, sq, n, n_dev, vis, order, counters);
-        hipLaunchKernelGGL(k_mesh_prefix, dim3(1), dim3(64), 0, stream, counters, order);
-        // (streamed like k_trace_mesh_stream the any-hit walks gain nothing: they are short, C4 +4 ms, closed room -2 ms)
-        hipLaunchKernelGGL(path_mode == 1 ? (ls ? k_shadow_mesh<1, true> : k_shadow_mesh<1>) : path_mode == 2 ? (ls ? k_shadow_mesh<2, true> : k_shadow_mesh<2>) : k_shadow_mesh<0>, dim3((hg.x + BHRT_ORDER_SHARDS) * (kBlock / kShadowBlock)), dim3(kShadowBlock), 0, stream, D->S, sq, vis, order);
-    } else hipLaunchKernelGGL(k_trace_shadow<false>, hg, hb, 0, stream, D->S, sq, n, n_dev, vis);
-    t.Stop();
+    const bhrt_flat_header *H = scene->flat.hdr();
+    const bhrt_mesh *hm = (const bhrt_mesh *)(scene->flat.blob.data() + H->off_meshes);
+    int path_mode = 1;
+    for (uint32_t k = 0; k < H->n_meshes; k++) {
+        if (hm[k].n_bvh_nodes > (1u << 17) && path_mode == 1) path_mode = 2;
+        if (hm[k].bvh_depth > 32) path_mode = 0;
+    }
+    return path_mode;
+}
+
+// The instantiation of each kernel family that a launch takes: the only places that turn PathMode and bhrt_opts::leaf_skip (ls: the walks'
+// instantiations with device_trace.h::leaf_skip compiled in) into template arguments.  Parent links (path_mode 0) never take ls.
+// The mesh walk of the parked rays; the key-sorted launches of the later steps (!cam_step) never take ls either.
+static decltype(&k_trace_mesh<true, 1>) MeshKernel(bool cam_step, int path_mode, bool ls)
+{
+    if (!cam_step) return path_mode == 1 ? k_trace_mesh<false, 1> : path_mode == 2 ? k_trace_mesh<false, 2> : k_trace_mesh<false, 0>;
+    if (path_mode == 1) return ls ? k_trace_mesh<true, 1, true> : k_trace_mesh<true, 1>;
+    if (path_mode == 2) return ls ? k_trace_mesh<true, 2, true> : k_trace_mesh<true, 2>;
+    return k_trace_mesh<true, 0>;
+}
+// The streaming walk of the later steps: path_mode 1 or 2, it does not exist for parent links.
+static decltype(&k_trace_mesh_stream<1>) StreamKernel(int path_mode, bool ls)
+{
+    if (path_mode == 1) return ls ? k_trace_mesh_stream<1, true> : k_trace_mesh_stream<1>;
+    return ls ? k_trace_mesh_stream<2, true> : k_trace_mesh_stream<2>;
+}
+// The any-hit walk of the parked shadow rays.
+static decltype(&k_shadow_mesh<1>) AnyHitMeshKernel(int path_mode, bool ls)
+{
+    if (path_mode == 1) return ls ? k_shadow_mesh<1, true> : k_shadow_mesh<1>;
+    if (path_mode == 2) return ls ? k_shadow_mesh<2, true> : k_shadow_mesh<2>;
+    return k_shadow_mesh<0>;
+}
+// fused: the camera step of a scene without meshes, k_shade traces its rays itself (shade_block's kFused).
+static decltype(&k_shade<true, true>) ShadeKernel(bool fused, bool cam_step, bool tex)
+{
+    if (fused) return tex ? k_shade<true, true, true> : k_shade<true, false, true>;
+    if (cam_step) return tex ? k_shade<true, true> : k_shade<true, false>;
+    return tex ? k_shade<false, true> : k_shade<false, false>;
+}
+// park: the rays that enter a mesh are left to the mesh walk (a wave step of a scene with meshes).  Without it the kernel walks the whole
+// scene; through meshes only as bhrt_trace_closest_dev launches it, which has no camera form.
+static decltype(&k_trace_closest<true, true>) ClosestKernel(bool park, bool cam_step, bool meshes)
+{
+    if (park) return cam_step ? k_trace_closest<true, true> : k_trace_closest<true, false>;
+    if (!meshes) return cam_step ? k_trace_closest<false, true, false> : k_trace_closest<false, false, false>;
+    return cam_step ? nullptr : k_trace_closest<false, false, true>;
+}
+
+// Host halves of -DBHRT_DEBUG_DRAIN (around a k_trace_mesh_stream launch) and -DBHRT_DEBUG_STREAM (after a completed pass)
+#ifdef BHRT_DEBUG_DRAIN
+static int DebugDrainReset()
+{
+    unsigned long long t0[4] = {~0ull, ~0ull, 0, 0};
+    HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(g_stream_t), t0, sizeof(t0)));
+    return BHRT_OK;
+}
+static int DebugDrainReport(DeviceState *D, uint32_t n_cur)
+{
+    unsigned long long t1[4];
+    HIP_CHECK(hipMemcpyFromSymbol(t1, HIP_SYMBOL(g_stream_t), sizeof(t1)));
+    static double dbg_total = 0, dbg_drain = 0;
+    if (t1[1] != ~0ull) { dbg_total += (double)(t1[2] - t1[0]) / 1e5; dbg_drain += (double)(t1[2] - t1[1]) / 1e5; }
+    if (D->knobs.debug_drain) fprintf(stderr, "mesh launch: %u rays, %.3f ms, of which %.3f ms after the list ran out (sums %.1f / %.1f ms)\n", n_cur, (double)(t1[2] - t1[0]) / 1e5, t1[1] != ~0ull ? (double)(t1[2] - t1[1]) / 1e5 : 0.0, dbg_total, dbg_drain);
+    return BHRT_OK;
+}
+#else
+static inline int DebugDrainReset() { return BHRT_OK; }
+static inline int DebugDrainReport(DeviceState *, uint32_t) { return BHRT_OK; }
+#endif
+#ifdef BHRT_DEBUG_STREAM
+static int DebugStreamReport()
+{
+    unsigned long long d[8], z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    HIP_CHECK(hipMemcpyFromSymbol(d, HIP_SYMBOL(g_stream_dbg), sizeof(d)));
+    HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(g_stream_dbg), z, sizeof(z)));
+    unsigned long long w[16], wz[16] = {};
+    HIP_CHECK(hipMemcpyFromSymbol(w, HIP_SYMBOL(g_walk_dbg), sizeof(w)));
+    HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(g_walk_dbg), wz, sizeof(wz)));
+    fprintf(stderr, "walk: descend bodies %llu (%.1f lanes), exact boxes %llu (%.1f lanes), climbs %llu (%.1f lanes), climbs after a hit %llu (%.1f lanes), triangle slots %llu (%.1f lanes), barycentric parts %llu (%.1f lanes), exact grazing quotients %llu; exact boxes %llu; box-missed leaf siblings %llu, of them left out %llu\n",
+            w[0], w[0] ? (double)w[1] / w[0] : 0., w[2], w[2] ? (double)w[3] / w[2] : 0., w[4], w[4] ? (double)w[5] / w[4] : 0., w[6], w[6] ? (double)w[7] / w[6] : 0., w[8],
+            w[8] ? (double)w[9] / w[8] : 0., w[10], w[10] ? (double)w[11] / w[10] : 0., w[12], w[13], w[14], w[15]);
+    fprintf(stderr, "stream: %llu rounds (%llu descend, %llu leaf), walking %.3f, in phase %.3f, clocks in rounds %.3g of which descend rounds %.3g, %llu refills\n", d[0], d[6],
+            d[7], d[0] ? (double)d[1] / (64.0 * d[0]) : 0.0, d[0] ? (double)d[2] / (64.0 * d[0]) : 0.0, (double)d[3], (double)d[4], d[5]);
+    return BHRT_OK;
+}
+#else
+static inline int DebugStreamReport() { return BHRT_OK; }
+#endif
+
+#ifndef BHRT_INJECT_MIN_LOG2
+#define BHRT_INJECT_MIN_LOG2 20 /* 18 / 20 / 22: C3 44.0 / 43.9 / 44.2 ms, closed room 487.6 / 486.4 / 491.1 ms */
+#endif
+constexpr uint32_t kInjectMinRays = 1u << BHRT_INJECT_MIN_LOG2; // rays of a wave step from which set-aside rays ride along with it (WavePass::MoveInSetAside)
+
+// One attempt at one pass of RenderPixels: P.n_pixels pixels, P.spp samples each, in the workspace as EnsureWorkspace left it.  Run() takes the
+// pass through its wave steps, one member function per stage of a step; a pass that `overflow`ed is redone smaller, with a new WavePass.
+struct WavePass {
+    typedef std::chrono::steady_clock::time_point TimePoint;
+    DeviceState *const D;
+    bhrt_stats *const st;
+    const RenderParams &R;
+    const PassInfo &P;
+    const TimePoint wall0;
+    const bool meshes, tex;
+    const bool ls;             // the walks' instantiations with device_trace.h::leaf_skip compiled in
+    const int path_mode;
+    const uint32_t stream_waves; // resident waves of the streaming mesh kernels (k_trace_mesh_stream): 6 per SIMD; BHRT_STREAM_WAVES=0 selects the launch-per-64-rays kernels
+    // Any-hit work beside the next step's closest-hit work (stream3): the shadow rays of step s are only needed by k_combine at the end of the pass, so their
+    // kernels go to a stream of their own as soon as k_shade has written them, with a shadow queue per step parity, and fill what the pass's stream leaves
+    // idle — above all the tail of every k_trace_mesh_stream launch (the longest walks of its last batch: 0.1-0.5 ms per wave step).
+    const bool sh_overlap;
+    const bool lens;           // thin-lens camera: the pass's camera rays come from k_lens_rays (Begin)
+    uint32_t *const root_of;   // fuse_root: k_shade's slot -> root frame map
+    const PassViews V;
+
+    // the wave step
+    int cur = 0;             // parity of the step's ray queue
+    uint32_t n_cur;          // first wave step: one slot per (pixel, sample); the kernels compute the camera rays themselves
+    bool first_step = true;
+    bool injected = false;   // this wave step shades the rays that were set aside: their hits are there, and they were counted in their own step
+    uint32_t n_extra = 0;    // slow rays that ride along with this step: slots [n_cur, n_cur + n_extra), hits in place, filed before k_shade
+    uint32_t seq = 0;        // the step's publish sequence number (WaitPublished)
+    HostCounters hc = {};    // what the step's k_shade published
+    bool overflow = false;
+    std::vector<uint32_t> frame_marks = {0};
+    // the any-hit kernels of the step whose counters the host has just read (sh_overlap): queue parity and length, and the parities still read on stream3
+    int sh_wait_par = 0; uint32_t sh_wait_n = 0;
+    bool sh_pending[2] = {false, false};
+    uint32_t slow_pending = 0, slow_traced = 0, slow_injected = 0; // set aside so far this pass / of those handed to k_trace_slow / of those moved into a wave step
+    struct SlowBatch { uint32_t end; uint32_t step; hipEvent_t done; };
+    std::vector<SlowBatch> slow_batches; // k_trace_slow launches of this pass, in order
+    size_t slow_batch_next = 0;          // first batch not yet moved in
+    uint64_t pass_closest = 0, pass_camera = 0, pass_shadow = 0, pass_deferred = 0;
+    uint32_t pass_steps = 0; // ray counters of this pass: added to *st only when the pass completes (an overflowing pass is redone)
+
+    bool CamStep() const { return first_step && !lens; } // the step's kernels form the camera rays themselves (kCamera)
+    // the camera step of a scene without meshes: k_shade traces its rays itself (shade_block's kFused); BHRT_FUSED_CAMERA=0: the two-kernel form
+    bool Fused() const { return CamStep() && !meshes && D->knobs.fused_camera; }
+    double MsSince(TimePoint t0) const { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() * 1e3; }
+
+    WavePass(bhrt_scene *scene, const bhrt_opts &o, bhrt_stats *stats, const RenderParams &Rp, const PassInfo &Pp, bool fuse_root, TimePoint render_start)
+        : D(scene->dev), st(stats), R(Rp), P(Pp), wall0(render_start), meshes(scene->flat.hdr()->n_meshes > 0), tex(scene->flat.hdr()->n_texmaps > 0), ls(o.leaf_skip != 0),
+          path_mode(PathMode(scene)), stream_waves(D->knobs.stream_waves >= 0 ? (uint32_t)D->knobs.stream_waves : D->n_cus * 4u * (uint32_t)BHRT_STREAM_OCC),
+          sh_overlap(D->knobs.shadow_overlap && D->stream3 != nullptr && D->d_shf2.p != nullptr), lens(Pp.lens_r > 0.f), root_of(fuse_root ? D->d_root.p : nullptr),
+          V(MakePassViews(D, sh_overlap)), n_cur(Pp.n_pixels * (uint32_t)Pp.spp)
+    {
+    }
+
+    // The wave steps of the pass, each a sequence of the stages below; ends early, with `overflow` set, when a step exceeds a capacity
+    int Run()
+    {
+        BHRT_TRY(Begin());
+        while (n_cur > 0 || slow_pending > slow_injected) {
+            BHRT_TRY(MoveInSetAside());
+            BHRT_TRY(TraceClosest());
+            BHRT_TRY(Shade());
+            // without sh_overlap the shadow trace of this step goes out before the host has the counters: its grid covers the upper bound
+            // (<= 1 shadow ray per shaded ray, <= the queue's capacity) and the kernels read the length on the device
+            if (!sh_overlap) LaunchAnyHit(D->stream, V.SQ, std::min<uint32_t>(n_cur + n_extra, R.cap_shadow), &D->d_cnt->n_shadow.v, V.RO, D->d_cnt);
+            BHRT_TRY(ReadCounters());
+            if (overflow) break;
+            BHRT_TRY(TraceSetAside());
+            if (sh_overlap) BHRT_TRY(QueueAnyHit());
+            n_cur = hc.n_next;
+            cur ^= 1;
+            pass_steps++;
+        }
+        if (sh_overlap) for (int k = 0; k < 2; k++) if (sh_pending[k]) HIP_CHECK(hipStreamWaitEvent(D->stream, D->ev_shadow[k], 0)); // every visibility is in its frame before the frames are read
+        return BHRT_OK;
+    }
+
+    // Clears the pass's counters, forms the lens rays, and waits out what an abandoned pass left on the side streams
+    int Begin()
+    {
+        HIP_CHECK(hipMemsetAsync(D->d_cnt, 0, sizeof(Counters), D->stream));
+        // d_samples needs no clearing: every slot of a valid pixel is written exactly once (k_shade: background of a camera
+        // miss; k_combine: root frame), and k_resolve never reads the slots of edge-tile pixels outside the image.  The same holds for
+        // d_root and k_resolve_frames — also in a pass that overflowed and is redone: its k_shade launches write every entry again
+        // Thin-lens camera: k_lens_rays writes the pass's camera rays into the queue (one per slot, dead slots included: the queue holds two rays per
+        // sample slot) and the first step runs the kernels of every later step, key sort included — lens rays of one pixel enter a mesh less
+        // coherently than pinhole rays.  Inside the pass, so a pass that overflows and is redone in halves forms its rays again.
+        if (lens) {
+            Timer t(D, &st->seconds_other);
+            hipLaunchKernelGGL(k_lens_rays, dim3((n_cur + kBlock - 1) / kBlock), dim3(kBlock), 0, D->stream, D->S, P, V.Q[0], n_cur);
+            t.Stop();
+        }
+        if (D->stream2) HIP_CHECK(hipStreamSynchronize(D->stream2)); // nothing of an abandoned pass still reads the queue
+        if (D->stream3) HIP_CHECK(hipStreamSynchronize(D->stream3));
+        return BHRT_OK;
+    }
+
+    // Set-aside rays whose hits are there come back: all of them as a wave step of their own once the queue has run empty, or, earlier, a batch
+    // behind the rays of a big step.
+    // A batch set aside by step s rides along with step s + 2 when that step is a big one (its hits, ~5 ms of walking on the second stream, are long
+    // there; the pass's stream waits for the batch's event on the device).  What is set aside late waits until the queue has run empty, as before.
+    int MoveInSetAside()
+    {
+        injected = false;
+        n_extra = 0;
+        if (n_cur == 0) {
+            const auto w0 = std::chrono::steady_clock::now();
+            HIP_CHECK(hipStreamSynchronize(D->stream2)); // the slow rays' hits
+            if (D->knobs.debug_slow)
+                fprintf(stderr, "slow rays: %u moved in after wave step %u, waited %.1f ms for their hits, pass time so far %.1f ms\n", slow_pending, pass_steps, MsSince(w0), MsSince(wall0));
+            n_cur = slow_pending - slow_injected;
+            hipLaunchKernelGGL(k_inject_slow, dim3((n_cur + kBlock - 1) / kBlock), dim3(kBlock), 0, D->stream, V.slowq.q, V.slow_hits, slow_injected, n_cur, V.Q[cur], V.HB, 0u);
+            pass_deferred += n_cur;
+            slow_injected = slow_pending;
+            slow_batch_next = slow_batches.size();
+            injected = true;
+        } else if (!first_step && n_cur >= kInjectMinRays) {
+            uint32_t upto = slow_injected;
+            size_t b = slow_batch_next;
+            while (b < slow_batches.size() && slow_batches[b].step + 2 <= pass_steps) { upto = slow_batches[b].end; b++; }
+            if (upto > slow_injected && (uint64_t)n_cur + (upto - slow_injected) <= D->cap_rays) {
+                HIP_CHECK(hipStreamWaitEvent(D->stream, slow_batches[b - 1].done, 0)); // stream2 runs its launches in order: the last one's event covers them all
+                n_extra = upto - slow_injected;
+                hipLaunchKernelGGL(k_inject_slow, dim3((n_extra + kBlock - 1) / kBlock), dim3(kBlock), 0, D->stream, V.slowq.q, V.slow_hits, slow_injected, n_extra, V.Q[cur], V.HB, n_cur);
+                if (D->knobs.debug_slow) fprintf(stderr, "slow rays: %u ride along with wave step %u (%u rays)\n", n_extra, pass_steps, n_cur);
+                pass_deferred += n_extra;
+                slow_injected = upto;
+                slow_batch_next = b;
+            }
+        }
+        return BHRT_OK;
+    }
+
+    // The closest-hit group: every ray of the step gets its hit and is filed under its shading class.  Nothing to trace in a fused camera step
+    // (k_shade does it) and in a step of moved-in rays (their hits came with them).
+    int TraceClosest()
+    {
+        const RayOrder &RO = V.RO;
+        const bool fused = Fused();
+        if (fused) {
+        } else if (injected) {
+            Timer t(D, &st->seconds_trace_closest);
+            hipLaunchKernelGGL(k_file_all, dim3((n_cur + kBlock - 1) / kBlock), dim3(kBlock), 0, D->stream, V.Q[cur], V.HB, 0u, n_cur, RO, D->d_cnt);
+            t.Stop();
+        } else {
+            Timer t(D, &st->seconds_trace_closest);
+            const SlowQueue no_slow = {V.slowq.q, 0u};
+            if (meshes) BHRT_TRY(TraceThroughMeshes());
+            else hipLaunchKernelGGL(ClosestKernel(false, CamStep(), false), dim3((n_cur + kBlock - 1) / kBlock), dim3(kBlock), 0, D->stream, D->S, P, V.Q[cur], n_cur, 0, V.HB, RO, D->d_cnt, no_slow);
+            t.Stop();
+        }
+        if (n_extra) hipLaunchKernelGGL(k_file_all, dim3(kFileAllBlocks(n_cur, n_cur + n_extra)), dim3(kBlock), 0, D->stream, V.Q[cur], V.HB, n_cur, n_cur + n_extra, RO, D->d_cnt);
+        if (!fused) {
+            st->launches_trace_closest++;
+            hipLaunchKernelGGL(k_order_prefix, dim3(1), dim3(128), 0, D->stream, D->d_cnt, RO);
+        }
+        return BHRT_OK;
+    }
+
+    // The closest-hit group of a scene with meshes: park the mesh rays, then finish them in dense workgroups
+    int TraceThroughMeshes()
+    {
+        const RayOrder &RO = V.RO;
+        const bool cam_step = CamStep();
+        const dim3 tg((n_cur + kBlock - 1) / kBlock), tb(kBlock);
+        const uint32_t n_buckets = 1u << BHRT_PARK_KEY_BITS, n_tiles = n_buckets / kScanTile;
+        if (!cam_step) HIP_CHECK(hipMemsetAsync(RO.park_bucket, 0, n_buckets * sizeof(uint32_t), D->stream)); // the trace kernel counts the keys as it parks
+        hipLaunchKernelGGL(ClosestKernel(true, cam_step, true), tg, tb, 0, D->stream, D->S, P, V.Q[cur], n_cur, 0, V.HB, RO, D->d_cnt, V.slowq);
+        hipLaunchKernelGGL(k_mesh_prefix, dim3(1), dim3(64), 0, D->stream, D->d_cnt, RO);
+        if (!cam_step) { // counting sort of the parked rays by coherence key (the camera step keeps slot order)
+            const dim3 pg(std::min<uint32_t>(tg.x + BHRT_ORDER_SHARDS, 4096u));
+            hipLaunchKernelGGL(k_scan_tiles, dim3(n_tiles), dim3(kScanBlock), 0, D->stream, RO.park_bucket, n_buckets, RO.park_bucket + n_buckets);
+            hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(kScanBlock), 0, D->stream, RO.park_bucket + n_buckets, n_tiles);
+            hipLaunchKernelGGL(k_scan_add, dim3(n_tiles), dim3(kScanBlock), 0, D->stream, RO.park_bucket, n_buckets, RO.park_bucket + n_buckets);
+            hipLaunchKernelGGL(k_park_scatter, pg, tb, 0, D->stream, RO);
+        }
+        if (sh_wait_n) { // the last step's any-hit kernels start with this step's mesh walk: they get the SIMDs its finished waves leave
+            HIP_CHECK(hipEventRecord(D->ev_shade, D->stream));
+            BHRT_TRY(LaunchQueuedAnyHit(D->ev_shade));
+        }
+        if (!cam_step && path_mode != 0 && stream_waves > 0) {
+            BHRT_TRY(DebugDrainReset());
+            hipLaunchKernelGGL(StreamKernel(path_mode, ls), dim3(std::min<uint32_t>((n_cur + 63) / 64, stream_waves)), dim3(64), 0, D->stream, D->S, V.Q[cur], V.HB, RO, D->d_cnt);
+            BHRT_TRY(DebugDrainReport(D, n_cur));
+        } else
+            hipLaunchKernelGGL(MeshKernel(cam_step, path_mode, ls), cam_step ? dim3(tg.x + BHRT_ORDER_SHARDS) /* shard segments padded to whole slices */ : dim3((n_cur + kMeshBlock - 1) / kMeshBlock),
+                               cam_step ? tb : dim3(kMeshBlock), 0, D->stream, D->S, P, V.Q[cur], V.HB, RO, D->d_cnt);
+        if (!cam_step) hipLaunchKernelGGL(k_file_parked, dim3(tg.x + BHRT_ORDER_SHARDS), tb, 0, D->stream, V.Q[cur], V.HB, RO, D->d_cnt);
+        return BHRT_OK;
+    }
+
+    // k_shade over the step's rays and those that ride along; its last workgroup publishes the step's counters under `seq`.  With sh_overlap it
+    // waits for the last readers of the shadow queue it fills.
+    int Shade()
+    {
+        const bool fused = Fused();
+        seq = ++D->pub_seq;
+        Timer t(D, &st->seconds_shade, 0);
+        const dim3 sg((n_cur + n_extra + kShadeBlock - 1) / kShadeBlock + (fused ? 0 : 3 * BHRT_ORDER_SHARDS)), sb(kShadeBlock);
+        const int par = (int)(pass_steps & 1u);
+        if (sh_wait_n) { HIP_CHECK(hipEventRecord(D->ev_shade, D->stream)); BHRT_TRY(LaunchQueuedAnyHit(D->ev_shade)); }
+        if (sh_overlap && sh_pending[par]) { HIP_CHECK(hipStreamWaitEvent(D->stream, D->ev_shadow[par], 0)); sh_pending[par] = false; } // the any-hit kernels of two steps ago still read this queue
+        hipLaunchKernelGGL(ShadeKernel(fused, CamStep(), tex), sg, sb, 0, D->stream, D->S, R, P, V.Q[cur], V.HB, n_cur + n_extra, V.Q[cur ^ 1], (sh_overlap && par) ? V.SQ2 : V.SQ, V.F, D->d_samples, root_of, D->d_cnt, V.RO, D->d_pub, seq); // + n_next, n_shadow, n_frames, overflow to the host
+        t.Stop();
+        if (sh_overlap) HIP_CHECK(hipEventRecord(D->ev_shade, D->stream));
+        return BHRT_OK;
+    }
+
+    // The any-hit kernels of one wave step on `stream`: the first n rays of `sq` into the frames' visibilities.  n_dev != nullptr: the queue's length is read on
+    // the device and n is the bound the grids cover.  With meshes the rays that enter one are parked in `order` (counted in `counters`) and finished in dense workgroups.
+    void LaunchAnyHit(hipStream_t stream, const ShadowQueue &sq, uint32_t n, const uint32_t *n_dev, const RayOrder &order, Counters *counters)
+    {
+        Timer t(D, &st->seconds_trace_shadow, 1, stream);
+        const dim3 hg((n + kBlock - 1) / kBlock), hb(kBlock);
+        if (meshes) {
+            hipLaunchKernelGGL(k_trace_shadow_park, hg, hb, 0, stream, D->S, sq, n, n_dev, V.F.vis, order, counters);
+            hipLaunchKernelGGL(k_mesh_prefix, dim3(1), dim3(64), 0, stream, counters, order);
+            // (streamed like k_trace_mesh_stream the any-hit walks gain nothing: they are short, C4 +4 ms, closed room -2 ms)
+            hipLaunchKernelGGL(AnyHitMeshKernel(path_mode, ls), dim3((hg.x + BHRT_ORDER_SHARDS) * (kBlock / kShadowBlock)), dim3(kShadowBlock), 0, stream, D->S, sq, V.F.vis, order);
+        } else hipLaunchKernelGGL(k_trace_shadow<false>, hg, hb, 0, stream, D->S, sq, n, n_dev, V.F.vis);
+        t.Stop();
+    }
+
+    // sh_overlap: the any-hit kernels of the step whose counters the host has just read (QueueAnyHit), on stream3 behind `after` (an event of the pass's stream)
+    int LaunchQueuedAnyHit(hipEvent_t after)
+    {
+        if (!sh_wait_n) return BHRT_OK;
+        const int par = sh_wait_par; const uint32_t n_sh = sh_wait_n;
+        sh_wait_n = 0;
+        HIP_CHECK(hipStreamWaitEvent(D->stream3, after, 0));
+        LaunchAnyHit(D->stream3, par ? V.SQ2 : V.SQ, n_sh, nullptr, V.RO_sh, D->d_cnt_sh);
+        HIP_CHECK(hipEventRecord(D->ev_shadow[par], D->stream3));
+        sh_pending[par] = true;
+        return BHRT_OK;
+    }
+
+    // Waits for the counters k_shade published and books the step: an overflow ends the pass, the camera step counts its valid pixels
+    int ReadCounters()
+    {
+        BHRT_TRY(WaitPublished(D, seq));
+        hc = *D->h_pub;
+        FlushTimers(D);
+        if (hc.overflow) { overflow = true; return BHRT_OK; }
+        if (first_step) { // camera step: dead rays of edge tiles are not rays
+            const uint64_t valid_px = P.list ? P.n_pixels : CountValidPixels(P, P.n_pixels); // a list holds pixels inside the image only
+            pass_closest = valid_px * (uint64_t)P.spp;
+            pass_camera = pass_closest;
+            first_step = false;
+        } else if (!injected) pass_closest += n_cur;
+        if (hc.n_shadow) { pass_shadow += hc.n_shadow; st->launches_trace_shadow++; }
+        frame_marks.push_back(hc.n_frames);
+        return BHRT_OK;
+    }
+
+    // The rays this step set aside: traced beside the pass (stream2), a batch with an event of its own
+    int TraceSetAside()
+    {
+        slow_pending = std::min<uint32_t>(hc.n_slow, kSlowCap);
+        if (slow_pending <= slow_traced) return BHRT_OK;
+        const uint32_t cnt_new = slow_pending - slow_traced;
+        hipLaunchKernelGGL(k_trace_slow, dim3(cnt_new), dim3(64), 0, D->stream2, D->S, V.slowq, slow_traced, slow_pending, V.slow_hits);
+        if (D->knobs.debug_slow) fprintf(stderr, "slow rays: %u set aside in wave step %u at %.1f ms\n", cnt_new, pass_steps, MsSince(wall0));
+        slow_traced = slow_pending;
+        const size_t bi = slow_batches.size();
+        if (bi >= D->slow_events.size()) { hipEvent_t e = nullptr; HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming)); D->slow_events.push_back(e); }
+        HIP_CHECK(hipEventRecord(D->slow_events[bi], D->stream2));
+        slow_batches.push_back({slow_pending, pass_steps, D->slow_events[bi]});
+        return BHRT_OK;
+    }
+
+    // sh_overlap: this step's shadow rays go beside the next step, with the queue's exact length
+    int QueueAnyHit()
+    {
+        if (!hc.n_shadow) return BHRT_OK;
+        sh_wait_par = (int)(pass_steps & 1u); sh_wait_n = hc.n_shadow;
+        // launched when the NEXT step's mesh walk is (TraceThroughMeshes, else Shade): behind an event of the pass's stream, so k_shade has ENDED and its rays are in memory for every XCD
+        if (hc.n_next == 0) BHRT_TRY(LaunchQueuedAnyHit(D->ev_shade)); // no next step
+        return BHRT_OK;
+    }
+};
+
+// How RenderPixels sizes its passes, and the keys the learned sizes are filed under (RenderKey)
+struct PassSizing {
+    uint32_t pass_samples;
+    double frames_per_sample;
+    bool frames_learned;
+    uint64_t frames_key, hint_key;
+};
+// Sized for 288 GB of HBM: few, large passes (every pass ends in a tail of nearly empty wavefront steps, and the big launches of a pass's
+// first steps run the denser the more rays they hold: ONE pass of 1.3e8 samples instead of two of 6.6e7 takes 7-9 % off the C3 and closed-room
+// frames).  ~1 KB of wavefront state per camera sample (1.4 KB with the photon-map frames) -> the default of 2^27 samples in flight takes
+// ~138 GB (186 GB); with less memory free the default halves until it fits.
+// Shade() frames per sample slot: six are provided for (an overflow halves the pass and redoes it).  A frame that does not fit into one pass
+// with six — C4's 2.7e8 samples per GPU — takes what the earlier passes of the same render (scene, options) have needed, + 30 %: C4 needs 1.1
+// frames per sample, and with 1.7 provided its 2^28 slots fit into 180 GB: one pass per frame instead of two.
+static PassSizing SizePasses(DeviceState *D, const bhrt_opts &o, uint64_t n_items, uint32_t spp, int world, int tile)
+{
+    PassSizing z;
+    z.frames_key = RenderKey(o, spp, world, tile);
+    z.frames_per_sample = 6.0;
+    z.frames_learned = false;
+    if (o.samples_per_pass <= 0 && D->frames_seen_key == z.frames_key && D->frames_seen > 0 && D->frames_seen < 4.0 &&
+        n_items * (uint64_t)spp > DefaultPassSamples(D, o.photon_map != 0, 6.0)) {
+        z.frames_per_sample = std::min(6.0, D->frames_seen * 1.3 + 0.25);
+        z.frames_learned = true;
+    }
+    z.pass_samples = o.samples_per_pass > 0 ? (uint32_t)o.samples_per_pass : DefaultPassSamples(D, o.photon_map != 0, z.frames_per_sample);
+    z.pass_samples = (uint32_t)std::min<uint64_t>(z.pass_samples, std::max<uint64_t>(n_items * (uint64_t)spp, 1)); // never more than this render needs
+    if (z.pass_samples < spp) z.pass_samples = spp;
+    z.hint_key = z.frames_key ^ ((uint64_t)z.pass_samples << 1);
+    return z;
 }
 
 // Renders samples [s0, s0 + spp) of n_items owned pixels of this rank: the range [0, n_items) of owned-pixel indices (d_list == nullptr) or
@@ -2373,310 +2768,66 @@ static int RenderPixels(bhrt_scene *scene, const bhrt_opts &o, PassInfo P, const
                         bool fuse_root, const Consume &consume)
 {
     DeviceState *D = scene->dev;
-    const bhrt_flat_header *H = scene->flat.hdr();
-    const int tile = P.tile, world = P.world;
     P.spp = (int32_t)spp; P.by_spp = MakeFastDiv(spp); P.s0 = s0;
-
-    // Sized for 288 GB of HBM: few, large passes (every pass ends in a tail of nearly empty wavefront steps, and the big launches of a pass's
-    // first steps run the denser the more rays they hold: ONE pass of 1.3e8 samples instead of two of 6.6e7 takes 7-9 % off the C3 and closed-room
-    // frames).  ~1 KB of wavefront state per camera sample (1.4 KB with the photon-map frames) -> the default of 2^27 samples in flight takes
-    // ~138 GB (186 GB); with less memory free the default halves until it fits.
-    // Shade() frames per sample slot: six are provided for (an overflow halves the pass and redoes it).  A frame that does not fit into one pass
-    // with six — C4's 2.7e8 samples per GPU — takes what the earlier passes of the same render (scene, options) have needed, + 30 %: C4 needs 1.1
-    // frames per sample, and with 1.7 provided its 2^28 slots fit into 180 GB: one pass per frame instead of two.
-    const uint64_t frames_key = RenderKey(o, spp, world, tile);
-    double frames_per_sample = 6.0;
-    bool frames_learned = false;
-    if (o.samples_per_pass <= 0 && D->frames_seen_key == frames_key && D->frames_seen > 0 && D->frames_seen < 4.0 &&
-        n_items * (uint64_t)spp > DefaultPassSamples(D, o.photon_map != 0, 6.0)) {
-        frames_per_sample = std::min(6.0, D->frames_seen * 1.3 + 0.25);
-        frames_learned = true;
-    }
-    uint32_t pass_samples = o.samples_per_pass > 0 ? (uint32_t)o.samples_per_pass : DefaultPassSamples(D, o.photon_map != 0, frames_per_sample);
-    pass_samples = (uint32_t)std::min<uint64_t>(pass_samples, std::max<uint64_t>(n_items * (uint64_t)spp, 1)); // never more than this render needs
-    if (pass_samples < spp) pass_samples = spp;
+    const PassSizing Z = SizePasses(D, o, n_items, spp, P.world, P.tile);
     D->timers = o.timers;
     D->photon_exact = o.photon_exact;
-    const bool ls = o.leaf_skip != 0; // the walks' instantiations with device_trace.h::leaf_skip compiled in
-    int path_mode = 1; // the traversal's path in LDS: 1 = 16-bit pair indices, 2 = 32-bit (a mesh with 2^17 nodes or more), 0 = no (deeper than 32 levels)
-    {
-        const bhrt_mesh *hm = (const bhrt_mesh *)(scene->flat.blob.data() + H->off_meshes);
-        for (uint32_t k = 0; k < H->n_meshes; k++) {
-            if (hm[k].n_bvh_nodes > (1u << 17) && path_mode == 1) path_mode = 2;
-            if (hm[k].bvh_depth > 32) path_mode = 0;
-        }
-    }
-    // resident waves of the streaming mesh kernels (k_trace_mesh_stream): 6 per SIMD; BHRT_STREAM_WAVES=0 selects the launch-per-64-rays kernels
-    const uint32_t stream_waves = D->knobs.stream_waves >= 0 ? (uint32_t)D->knobs.stream_waves : D->n_cus * 4u * (uint32_t)BHRT_STREAM_OCC;
     RenderParams R;
     R.internal_bounces = o.internal_bounces; R.gi_bounces = o.gi_bounces; R.photon = o.photon_map;
     auto wall0 = std::chrono::steady_clock::now();
 
     uint64_t q = 0;
     uint32_t pass_limit = 0; // samples actually put in flight per pass (<= buffer capacity)
-    const uint64_t hint_key = frames_key ^ ((uint64_t)pass_samples << 1);
-    if (D->pass_hint_key == hint_key && D->pass_hint) pass_limit = D->pass_hint;
+    if (D->pass_hint_key == Z.hint_key && D->pass_hint) pass_limit = D->pass_hint;
     while (q < n_items) {
-        int rc = EnsureWorkspace(D, pass_samples, frames_per_sample);
-        if (rc) return rc;
+        BHRT_TRY(EnsureWorkspace(D, Z.pass_samples, Z.frames_per_sample));
         R.cap_rays = D->cap_rays; R.cap_shadow = D->cap_rays; R.cap_frames = D->cap_frames;
         if (D->knobs.frame_cap > 0) R.cap_frames = std::min<uint32_t>(R.cap_frames, (uint32_t)D->knobs.frame_cap); // test knob: a pass that overflows
         if (o.photon_map) BHRT_TRY(D->d_ph_frames.Reserve((size_t)D->cap_frames * 15));
-        if (pass_limit == 0) pass_limit = pass_samples;
+        if (pass_limit == 0) pass_limit = Z.pass_samples;
         if (pass_limit > D->cap_samples) pass_limit = D->cap_samples;
         const uint32_t px_per_pass = pass_limit / spp;
         const uint32_t npx = (uint32_t)std::min<uint64_t>(px_per_pass, n_items - q);
         if (d_list) { P.list = d_list + q; P.q0 = 0; } else P.q0 = (uint32_t)q;
         P.n_pixels = npx;
-        // Any-hit work beside the next step's closest-hit work (stream3): the shadow rays of step s are only needed by k_combine at the end of the pass, so their
-        // kernels go to a stream of their own as soon as k_shade has written them, with a shadow queue per step parity, and fill what the pass's stream leaves
-        // idle — above all the tail of every k_trace_mesh_stream launch (the longest walks of its last batch: 0.1-0.5 ms per wave step).
-        const bool sh_overlap = D->knobs.shadow_overlap && D->stream3 != nullptr && D->d_shf2.p != nullptr;
-        const PassViews V = MakePassViews(D, sh_overlap);
-        const Frames &F = V.F;
-        const RayOrder &RO = V.RO;
-        bool sh_pending[2] = {false, false};
-        HIP_CHECK(hipMemsetAsync(D->d_cnt, 0, sizeof(Counters), D->stream));
-        // d_samples needs no clearing: every slot of a valid pixel is written exactly once (k_shade: background of a camera
-        // miss; k_combine: root frame), and k_resolve never reads the slots of edge-tile pixels outside the image.  The same holds for
-        // d_root and k_resolve_frames — also in a pass that overflowed and is redone: its k_shade launches write every entry again
-        uint32_t *const root_of = fuse_root ? D->d_root.p : nullptr;
-        const uint32_t total = npx * spp;
-        uint32_t n_cur = total; // first wave step: one slot per (pixel, sample); the kernels compute the camera rays themselves
-        bool first_step = true;
-        // Thin-lens camera: k_lens_rays writes the pass's camera rays into the queue (one per slot, dead slots included: the queue holds two rays per
-        // sample slot) and the first step runs the kernels of every later step, key sort included — lens rays of one pixel enter a mesh less
-        // coherently than pinhole rays.  Inside the pass, so a pass that overflows and is redone in halves forms its rays again.
-        const bool lens = P.lens_r > 0.f;
-        if (lens) {
-            Timer t(D, &st->seconds_other);
-            hipLaunchKernelGGL(k_lens_rays, dim3((total + kBlock - 1) / kBlock), dim3(kBlock), 0, D->stream, D->S, P, V.Q[0], total);
-            t.Stop();
-        }
-        int cur = 0;
-        std::vector<uint32_t> frame_marks = {0};
-        bool overflow = false;
-        uint64_t pass_closest = 0, pass_camera = 0, pass_shadow = 0, pass_deferred = 0;
-        uint32_t pass_steps = 0; // ray counters of this pass: added to *st only when the pass completes (an overflowing pass is redone)
-        const SlowQueue no_slow = {V.slowq.q, 0u};
-        uint32_t slow_pending = 0, slow_traced = 0, slow_injected = 0; // set aside so far this pass / of those handed to k_trace_slow / of those moved into a wave step
-        struct SlowBatch { uint32_t end; uint32_t step; hipEvent_t done; };
-        std::vector<SlowBatch> slow_batches; // k_trace_slow launches of this pass, in order
-        size_t slow_batch_next = 0;          // first batch not yet moved in
-        // A batch set aside by step s rides along with step s + 2 when that step is a big one (its hits, ~5 ms of walking on the second stream, are long
-        // there; the pass's stream waits for the batch's event on the device).  What is set aside late waits until the queue has run empty, as before.
-#ifndef BHRT_INJECT_MIN_LOG2
-#define BHRT_INJECT_MIN_LOG2 20 /* 18 / 20 / 22: C3 44.0 / 43.9 / 44.2 ms, closed room 487.6 / 486.4 / 491.1 ms */
-#endif
-        constexpr uint32_t kInjectMinRays = 1u << BHRT_INJECT_MIN_LOG2;
-        bool injected = false; // this wave step shades the rays that were set aside: their hits are there, and they were counted in their own step
-        if (D->stream2) HIP_CHECK(hipStreamSynchronize(D->stream2)); // nothing of an abandoned pass still reads the queue
-        if (D->stream3) HIP_CHECK(hipStreamSynchronize(D->stream3));
-        // the any-hit kernels of the step whose counters the host has just read, on stream3 behind `after` (an event of the pass's stream)
-        int sh_wait_par = 0; uint32_t sh_wait_n = 0;
-        auto launch_any_hit = [&](hipEvent_t after) -> int {
-            if (!sh_wait_n) return BHRT_OK;
-            const int par = sh_wait_par; const uint32_t n_sh = sh_wait_n;
-            sh_wait_n = 0;
-            HIP_CHECK(hipStreamWaitEvent(D->stream3, after, 0));
-            LaunchAnyHit(D, D->stream3, H->n_meshes > 0, par ? V.SQ2 : V.SQ, n_sh, nullptr, F.vis, V.RO_sh, D->d_cnt_sh, path_mode, ls, &st->seconds_trace_shadow);
-            HIP_CHECK(hipEventRecord(D->ev_shadow[par], D->stream3));
-            sh_pending[par] = true;
-            return BHRT_OK;
-        };
-        while (n_cur > 0 || slow_pending > slow_injected) {
-            injected = false;
-            uint32_t n_extra = 0; // slow rays that ride along with this step: slots [n_cur, n_cur + n_extra), hits in place, filed before k_shade
-            if (n_cur == 0) {
-                const auto w0 = std::chrono::steady_clock::now();
-                HIP_CHECK(hipStreamSynchronize(D->stream2)); // the slow rays' hits
-                if (D->knobs.debug_slow)
-                    fprintf(stderr, "slow rays: %u moved in after wave step %u, waited %.1f ms for their hits, pass time so far %.1f ms\n", slow_pending, pass_steps,
-                            std::chrono::duration<double>(std::chrono::steady_clock::now() - w0).count() * 1e3, std::chrono::duration<double>(std::chrono::steady_clock::now() - wall0).count() * 1e3);
-                n_cur = slow_pending - slow_injected;
-                hipLaunchKernelGGL(k_inject_slow, dim3((n_cur + kBlock - 1) / kBlock), dim3(kBlock), 0, D->stream, V.slowq.q, V.slow_hits, slow_injected, n_cur, V.Q[cur], V.HB, 0u);
-                pass_deferred += n_cur;
-                slow_injected = slow_pending;
-                slow_batch_next = slow_batches.size();
-                injected = true;
-            } else if (!first_step && n_cur >= kInjectMinRays) {
-                uint32_t upto = slow_injected;
-                size_t b = slow_batch_next;
-                while (b < slow_batches.size() && slow_batches[b].step + 2 <= pass_steps) { upto = slow_batches[b].end; b++; }
-                if (upto > slow_injected && (uint64_t)n_cur + (upto - slow_injected) <= D->cap_rays) {
-                    HIP_CHECK(hipStreamWaitEvent(D->stream, slow_batches[b - 1].done, 0)); // stream2 runs its launches in order: the last one's event covers them all
-                    n_extra = upto - slow_injected;
-                    hipLaunchKernelGGL(k_inject_slow, dim3((n_extra + kBlock - 1) / kBlock), dim3(kBlock), 0, D->stream, V.slowq.q, V.slow_hits, slow_injected, n_extra, V.Q[cur], V.HB, n_cur);
-                    if (D->knobs.debug_slow) fprintf(stderr, "slow rays: %u ride along with wave step %u (%u rays)\n", n_extra, pass_steps, n_cur);
-                    pass_deferred += n_extra;
-                    slow_injected = upto;
-                    slow_batch_next = b;
-                }
-            }
-            const SlowQueue &sq = V.slowq;
-            // the camera step of a scene without meshes: k_shade traces its rays itself (shade_block's kFused); BHRT_FUSED_CAMERA=0: the two-kernel form
-            const bool cam_step = first_step && !lens; // the step's kernels form the camera rays themselves (kCamera)
-            const bool fused = cam_step && H->n_meshes == 0 && D->knobs.fused_camera;
-            if (fused) {
-            } else if (injected) {
-                Timer t(D, &st->seconds_trace_closest);
-                hipLaunchKernelGGL(k_file_all, dim3((n_cur + kBlock - 1) / kBlock), dim3(kBlock), 0, D->stream, V.Q[cur], V.HB, 0u, n_cur, RO, D->d_cnt);
-                t.Stop();
-            } else {
-                Timer t(D, &st->seconds_trace_closest);
-                const dim3 tg((n_cur + kBlock - 1) / kBlock), tb(kBlock);
-                if (H->n_meshes > 0) { // park the mesh rays, then finish them in dense workgroups
-                    const uint32_t n_buckets = 1u << BHRT_PARK_KEY_BITS, n_tiles = n_buckets / kScanTile;
-                    if (cam_step) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_trace_closest<true, true>), tg, tb, 0, D->stream, D->S, P, V.Q[cur], n_cur, 0, V.HB, RO, D->d_cnt, sq);
-                    else {
-                        HIP_CHECK(hipMemsetAsync(RO.park_bucket, 0, n_buckets * sizeof(uint32_t), D->stream)); // the trace kernel counts the keys as it parks
-                        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_trace_closest<true, false>), tg, tb, 0, D->stream, D->S, P, V.Q[cur], n_cur, 0, V.HB, RO, D->d_cnt, sq);
-                    }
-                    hipLaunchKernelGGL(k_mesh_prefix, dim3(1), dim3(64), 0, D->stream, D->d_cnt, RO);
-                    if (!cam_step) { // counting sort of the parked rays by coherence key (the camera step keeps slot order)
-                        const dim3 pg(std::min<uint32_t>(tg.x + BHRT_ORDER_SHARDS, 4096u));
-                        hipLaunchKernelGGL(k_scan_tiles, dim3(n_tiles), dim3(kScanBlock), 0, D->stream, RO.park_bucket, n_buckets, RO.park_bucket + n_buckets);
-                        hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(kScanBlock), 0, D->stream, RO.park_bucket + n_buckets, n_tiles);
-                        hipLaunchKernelGGL(k_scan_add, dim3(n_tiles), dim3(kScanBlock), 0, D->stream, RO.park_bucket, n_buckets, RO.park_bucket + n_buckets);
-                        hipLaunchKernelGGL(k_park_scatter, pg, tb, 0, D->stream, RO);
-                    }
-                    auto mesh_kernel = cam_step ? (path_mode == 1 ? (ls ? k_trace_mesh<true, 1, true> : k_trace_mesh<true, 1>) : path_mode == 2 ? (ls ? k_trace_mesh<true, 2, true> : k_trace_mesh<true, 2>) : k_trace_mesh<true, 0>)
-                                                  : (path_mode == 1 ? k_trace_mesh<false, 1> : path_mode == 2 ? k_trace_mesh<false, 2> : k_trace_mesh<false, 0>);
-                    if (sh_wait_n) { // the last step's any-hit kernels start with this step's mesh walk: they get the SIMDs its finished waves leave
-                        HIP_CHECK(hipEventRecord(D->ev_shade, D->stream));
-                        rc = launch_any_hit(D->ev_shade); if (rc) return rc;
-                    }
-                    if (!cam_step && path_mode != 0 && stream_waves > 0)
-                    {
-#ifdef BHRT_DEBUG_DRAIN
-                        { unsigned long long t0[4] = {~0ull, ~0ull, 0, 0}; HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(g_stream_t), t0, sizeof(t0))); }
-#endif
-                        hipLaunchKernelGGL(path_mode == 1 ? (ls ? k_trace_mesh_stream<1, true> : k_trace_mesh_stream<1>) : (ls ? k_trace_mesh_stream<2, true> : k_trace_mesh_stream<2>), dim3(std::min<uint32_t>((n_cur + 63) / 64, stream_waves)), dim3(64), 0, D->stream, D->S,
-                                           V.Q[cur], V.HB, RO, D->d_cnt);
-#ifdef BHRT_DEBUG_DRAIN
-                        unsigned long long t1[4];
-                        HIP_CHECK(hipMemcpyFromSymbol(t1, HIP_SYMBOL(g_stream_t), sizeof(t1)));
-                        static double dbg_total = 0, dbg_drain = 0;
-                        if (t1[1] != ~0ull) { dbg_total += (double)(t1[2] - t1[0]) / 1e5; dbg_drain += (double)(t1[2] - t1[1]) / 1e5; }
-                        if (D->knobs.debug_drain) fprintf(stderr, "mesh launch: %u rays, %.3f ms, of which %.3f ms after the list ran out (sums %.1f / %.1f ms)\n", n_cur, (double)(t1[2] - t1[0]) / 1e5, t1[1] != ~0ull ? (double)(t1[2] - t1[1]) / 1e5 : 0.0, dbg_total, dbg_drain);
-#endif
-                    }
-                    else
-                    hipLaunchKernelGGL(mesh_kernel, cam_step ? dim3(tg.x + BHRT_ORDER_SHARDS) /* shard segments padded to whole slices */ : dim3((n_cur + kMeshBlock - 1) / kMeshBlock),
-                                       cam_step ? tb : dim3(kMeshBlock), 0, D->stream, D->S, P, V.Q[cur], V.HB, RO, D->d_cnt);
-                    if (!cam_step) hipLaunchKernelGGL(k_file_parked, dim3(tg.x + BHRT_ORDER_SHARDS), tb, 0, D->stream, V.Q[cur], V.HB, RO, D->d_cnt);
-                } else if (cam_step) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_trace_closest<false, true, false>), tg, tb, 0, D->stream, D->S, P, V.Q[cur], n_cur, 0, V.HB, RO, D->d_cnt, no_slow);
-                else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_trace_closest<false, false, false>), tg, tb, 0, D->stream, D->S, P, V.Q[cur], n_cur, 0, V.HB, RO, D->d_cnt, no_slow);
-                t.Stop();
-            }
-            if (n_extra) hipLaunchKernelGGL(k_file_all, dim3(kFileAllBlocks(n_cur, n_cur + n_extra)), dim3(kBlock), 0, D->stream, V.Q[cur], V.HB, n_cur, n_cur + n_extra, RO, D->d_cnt);
-            if (!fused) {
-                st->launches_trace_closest++;
-                hipLaunchKernelGGL(k_order_prefix, dim3(1), dim3(128), 0, D->stream, D->d_cnt, RO);
-            }
-            const uint32_t seq = ++D->pub_seq;
-            {
-                Timer t(D, &st->seconds_shade, 0);
-                const dim3 sg((n_cur + n_extra + kShadeBlock - 1) / kShadeBlock + (fused ? 0 : 3 * BHRT_ORDER_SHARDS)), sb(kShadeBlock);
-                const bool tex = H->n_texmaps > 0;
-                auto shade = fused ? (tex ? k_shade<true, true, true> : k_shade<true, false, true>)
-                                   : cam_step ? (tex ? k_shade<true, true> : k_shade<true, false>) : (tex ? k_shade<false, true> : k_shade<false, false>);
-                const int par = (int)(pass_steps & 1u);
-                if (sh_wait_n) { HIP_CHECK(hipEventRecord(D->ev_shade, D->stream)); rc = launch_any_hit(D->ev_shade); if (rc) return rc; }
-                if (sh_overlap && sh_pending[par]) { HIP_CHECK(hipStreamWaitEvent(D->stream, D->ev_shadow[par], 0)); sh_pending[par] = false; } // the any-hit kernels of two steps ago still read this queue
-                hipLaunchKernelGGL(shade, sg, sb, 0, D->stream, D->S, R, P, V.Q[cur], V.HB, n_cur + n_extra, V.Q[cur ^ 1], (sh_overlap && par) ? V.SQ2 : V.SQ, F, D->d_samples, root_of, D->d_cnt, RO, D->d_pub, seq); // + n_next, n_shadow, n_frames, overflow to the host
-                t.Stop();
-                if (sh_overlap) HIP_CHECK(hipEventRecord(D->ev_shade, D->stream));
-            }
-            if (!sh_overlap) { // the shadow trace of this step goes out before the host has the counters: its grid covers the upper bound
-              // (<= 1 shadow ray per shaded ray, <= the queue's capacity) and the kernels read the length on the device
-                LaunchAnyHit(D, D->stream, H->n_meshes > 0, V.SQ, std::min<uint32_t>(n_cur + n_extra, R.cap_shadow), &D->d_cnt->n_shadow.v, F.vis, RO, D->d_cnt, path_mode, ls,
-                             &st->seconds_trace_shadow);
-            }
-            rc = WaitPublished(D, seq);
-            if (rc) return rc;
-            const HostCounters hc = *D->h_pub;
-            FlushTimers(D);
-            if (hc.overflow) { overflow = true; break; }
-            if (first_step) { // camera step: dead rays of edge tiles are not rays
-                const uint64_t valid_px = d_list ? npx : CountValidPixels(P, npx); // a list holds pixels inside the image only
-                pass_closest = valid_px * (uint64_t)spp;
-                pass_camera = pass_closest;
-                first_step = false;
-            } else if (!injected) pass_closest += n_cur;
-            slow_pending = std::min<uint32_t>(hc.n_slow, kSlowCap);
-            if (slow_pending > slow_traced) { // the rays this step set aside: traced beside the pass
-                const uint32_t cnt_new = slow_pending - slow_traced;
-                hipLaunchKernelGGL(k_trace_slow, dim3(cnt_new), dim3(64), 0, D->stream2, D->S, V.slowq, slow_traced, slow_pending, V.slow_hits);
-                if (D->knobs.debug_slow) fprintf(stderr, "slow rays: %u set aside in wave step %u at %.1f ms\n", cnt_new, pass_steps, std::chrono::duration<double>(std::chrono::steady_clock::now() - wall0).count() * 1e3);
-                slow_traced = slow_pending;
-                const size_t bi = slow_batches.size();
-                if (bi >= D->slow_events.size()) { hipEvent_t e = nullptr; HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming)); D->slow_events.push_back(e); }
-                HIP_CHECK(hipEventRecord(D->slow_events[bi], D->stream2));
-                slow_batches.push_back({slow_pending, pass_steps, D->slow_events[bi]});
-            }
-            const uint32_t n_sh = hc.n_shadow;
-            if (n_sh) { pass_shadow += n_sh; st->launches_trace_shadow++; }
-            if (sh_overlap && n_sh) { // beside the next step, with the queue's exact length
-                sh_wait_par = (int)(pass_steps & 1u); sh_wait_n = n_sh;
-                // launched when the NEXT step's mesh walk is (below): behind an event of the pass's stream, so k_shade has ENDED and its rays are in memory for every XCD
-                if (hc.n_next == 0) { rc = launch_any_hit(D->ev_shade); if (rc) return rc; } // no next step
-            }
-            frame_marks.push_back(hc.n_frames);
-            n_cur = hc.n_next;
-            cur ^= 1;
-            pass_steps++;
-        }
-        if (sh_overlap) for (int k = 0; k < 2; k++) if (sh_pending[k]) HIP_CHECK(hipStreamWaitEvent(D->stream, D->ev_shadow[k], 0)); // every visibility is in its frame before the frames are read
-        if (overflow) {
+        WavePass pass(scene, o, st, R, P, fuse_root, wall0);
+        BHRT_TRY(pass.Run());
+        if (pass.overflow) {
             // a capacity was exceeded: redo this pass with half the pixels in the same buffers
             // (results do not depend on the pass size: every sample has its own RNG key)
             if (pass_limit <= spp) { SetError("wavefront buffers overflow even with one pixel per pass"); return BHRT_ERR_OVERFLOW; }
             pass_limit = std::max<uint32_t>(spp, pass_limit / 2);
-            D->pass_hint_key = hint_key; D->pass_hint = pass_limit;
-            if (frames_learned) D->frames_seen = 6.0; // the smaller frame pool was not enough after all: the next render of this kind provides six again
+            D->pass_hint_key = Z.hint_key; D->pass_hint = pass_limit;
+            if (Z.frames_learned) D->frames_seen = 6.0; // the smaller frame pool was not enough after all: the next render of this kind provides six again
             continue;
         }
-#ifdef BHRT_DEBUG_STREAM
-        {
-            unsigned long long d[8], z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-            HIP_CHECK(hipMemcpyFromSymbol(d, HIP_SYMBOL(g_stream_dbg), sizeof(d)));
-            HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(g_stream_dbg), z, sizeof(z)));
-            unsigned long long w[16], wz[16] = {};
-            HIP_CHECK(hipMemcpyFromSymbol(w, HIP_SYMBOL(g_walk_dbg), sizeof(w)));
-            HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(g_walk_dbg), wz, sizeof(wz)));
-            fprintf(stderr, "walk: descend bodies %llu (%.1f lanes), exact boxes %llu (%.1f lanes), climbs %llu (%.1f lanes), climbs after a hit %llu (%.1f lanes), triangle slots %llu (%.1f lanes), barycentric parts %llu (%.1f lanes), exact grazing quotients %llu; exact boxes %llu; box-missed leaf siblings %llu, of them left out %llu\n",
-                    w[0], w[0] ? (double)w[1] / w[0] : 0., w[2], w[2] ? (double)w[3] / w[2] : 0., w[4], w[4] ? (double)w[5] / w[4] : 0., w[6], w[6] ? (double)w[7] / w[6] : 0., w[8],
-                    w[8] ? (double)w[9] / w[8] : 0., w[10], w[10] ? (double)w[11] / w[10] : 0., w[12], w[13], w[14], w[15]);
-            fprintf(stderr, "stream: %llu rounds (%llu descend, %llu leaf), walking %.3f, in phase %.3f, clocks in rounds %.3g of which descend rounds %.3g, %llu refills\n", d[0], d[6],
-                    d[7], d[0] ? (double)d[1] / (64.0 * d[0]) : 0.0, d[0] ? (double)d[2] / (64.0 * d[0]) : 0.0, (double)d[3], (double)d[4], d[5]);
-        }
-#endif
-        st->camera_samples += pass_camera; st->shadow_rays += pass_shadow; st->wave_iterations += pass_steps; st->deferred_rays += pass_deferred;
+        BHRT_TRY(DebugStreamReport());
+        const Frames &F = pass.V.F;
+        const uint32_t n_frames = pass.frame_marks.back();
+        st->camera_samples += pass.pass_camera; st->shadow_rays += pass.pass_shadow; st->wave_iterations += pass.pass_steps; st->deferred_rays += pass.pass_deferred;
         { // what this pass needed of its frame pool, per sample slot
-            const double seen = (double)frame_marks.back() / (double)std::max<uint64_t>((uint64_t)npx * (uint64_t)spp, 1);
-            if (D->frames_seen_key != frames_key) { D->frames_seen_key = frames_key; D->frames_seen = 0; }
+            const double seen = (double)n_frames / (double)std::max<uint64_t>((uint64_t)npx * (uint64_t)spp, 1);
+            if (D->frames_seen_key != Z.frames_key) { D->frames_seen_key = Z.frames_key; D->frames_seen = 0; }
             D->frames_seen = std::max(D->frames_seen, seen);
         }
-        if (o.photon_map && frame_marks.back() > 0) {
+        if (o.photon_map && n_frames > 0) {
             // caustic term (MtlBlinn.cpp:329-342) of every frame of the pass in ONE gather: a gather launch lasts as long as its
             // longest query (15-80 ms for a query that fills the 1000-candidate heap), so a gather per wave step — 23 steps
             // per pass, most with a few hundred frames — spent 2 s per frame waiting for single lanes
             Timer t(D, &st->seconds_photon_gather, 0);
             const GatherToFrames sink = {F, D->S.materials};
-            int rc = RunGather(D, sink, 0, frame_marks.back(), o.photon_radius > 0.f ? o.photon_radius : 0.5f /* MAX_Area, MtlBlinn.cpp:29 */, st);
-            if (rc) return rc;
+            BHRT_TRY(RunGather(D, sink, 0, n_frames, o.photon_radius > 0.f ? o.photon_radius : 0.5f /* MAX_Area, MtlBlinn.cpp:29 */, st));
             t.Stop();
         }
         st->shade_calls += D->h_pub->n_frames;
-        st->closest_rays += pass_closest;
+        st->closest_rays += pass.pass_closest;
         {
             Timer t(D, &st->seconds_other);
             // fuse_root: the first step's frames are the root frames of the camera rays it shaded, all of them, and k_resolve_frames folds those.  A
             // camera ray that was set aside opens its root frame in a later step, among frames of other kinds: that step's launch stays whole and
             // stores the frame's value into d_samples, where nothing reads it — k_resolve_frames finds the frame through the map like any other
-            for (size_t k = frame_marks.size(); k-- > (fuse_root ? 2 : 1);) {
-                const uint32_t f0 = frame_marks[k - 1], f1 = frame_marks[k];
+            for (size_t k = pass.frame_marks.size(); k-- > (fuse_root ? 2 : 1);) {
+                const uint32_t f0 = pass.frame_marks[k - 1], f1 = pass.frame_marks[k];
                 if (f1 > f0) hipLaunchKernelGGL(k_combine, dim3((f1 - f0 + kBlock - 1) / kBlock), dim3(kBlock), 0, D->stream, D->S, P, F, f0, f1, D->d_samples, o.photon_map);
             }
             consume(P, npx, F);
@@ -3005,7 +3156,7 @@ try {
     HitBuf h; h.t = d_out.t; h.node = d_out.node; h.prim = d_out.prim; h.front = d_out.front;
     hipStream_t s = stream ? (hipStream_t)stream : scene->dev->stream;
     RayOrder no_order = {nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    auto closest_kernel = scene->flat.hdr()->n_meshes > 0 ? k_trace_closest<false, false, true> : k_trace_closest<false, false, false>;
+    auto closest_kernel = ClosestKernel(false, false, scene->flat.hdr()->n_meshes > 0);
     hipLaunchKernelGGL(closest_kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, s,
                        scene->dev->S, PassInfo(), q, (uint32_t)n, hit_side, h, no_order, (Counters *)nullptr, SlowQueue{q, 0u});
     HIP_CHECK(hipGetLastError());

@@ -26,11 +26,11 @@ from conftest import SCENES, ensure_mesh, same_bits
 
 pytestmark = pytest.mark.gpu
 
-K_SLOW_CAP = 1 << 16        # kernels.hip:314   constexpr uint32_t kSlowCap = 1u << 16 (rays set aside per pass)
-INJECT_MIN_RAYS = 1 << 20   # kernels.hip:2382  BHRT_INJECT_MIN_LOG2 20: a batch rides along only with a step of at least this many rays
-GATHER_SORT_MIN = 1 << 16   # kernels.hip:2088  the gather sorts its queries by cell only from this many queries on
-PATH16_MAX_NODES = 1 << 17  # kernels.hip:2320  16-bit path entries up to this many BVH nodes, 32-bit above
-PATH_MAX_DEPTH = 32         # kernels.hip:2321  deeper trees walk parent links (no path in LDS, leaf_skip not compiled in)
+K_SLOW_CAP = 1 << 16        # kernels.hip kSlowCap: rays set aside per pass
+INJECT_MIN_RAYS = 1 << 20   # kernels.hip kInjectMinRays (BHRT_INJECT_MIN_LOG2 20): a batch rides along only with a step of at least this many rays
+GATHER_SORT_MIN = 1 << 16   # kernels.hip RunGather: the gather sorts its queries by cell only from this many queries on
+PATH16_MAX_NODES = 1 << 17  # kernels.hip PathMode: 16-bit path entries up to this many BVH nodes, 32-bit above
+PATH_MAX_DEPTH = 32         # kernels.hip PathMode: deeper trees walk parent links (no path in LDS, leaf_skip not compiled in)
 
 SWITCHES = ("BHRT_STREAM_WAVES", "BHRT_FUSED_CAMERA", "BHRT_NO_SLOW_QUEUE", "BHRT_DEBUG_SLOW", "BHRT_GATHER_COUNTING_SORT", "BHRT_SHADOW_OVERLAP")
 
