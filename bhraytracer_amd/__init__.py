@@ -81,6 +81,7 @@ EXPORTS = [
     "bhrt_default_adaptive_opts", "bhrt_render_adaptive", "bhrt_render_adaptive_dev", "bhrt_sample_count_image", "bhrt_sample_count_image_dev",
     "bhrt_save_png_gray",
     "bhrt_scene_set_lens", "bhrt_camera_rays",
+    "bhrt_scene_set_emissive", "bhrt_scene_material_index", "bhrt_scene_set_material_emission", "bhrt_scene_get_material_emission",
 ]
 
 
@@ -207,6 +208,40 @@ class Scene:
         again, and an uploaded scene's camera is refreshed.  Opts.lens = 1 then renders through a thin lens of aperture radius dof."""
         _check(lib().bhrt_scene_set_lens(self._h, C.c_float(focaldist), C.c_float(dof)))
         self._flat = None
+
+    # ---- the emission term (DESIGN.md 12): scene state beside the flat blob, which keeps its bytes --------------------
+    def set_emissive(self, on: bool = True):
+        """bhrt_scene_set_emissive: with the term on, every Shade() frame of a Blinn material adds its <emission> (colour x optional texture) last,
+        at every bounce, in all later renders of this scene.  Off by default: the reference parses <emission> and never shades it."""
+        _check(lib().bhrt_scene_set_emissive(self._h, 1 if on else 0))
+
+    def material_index(self, name: str) -> int:
+        """bhrt_scene_material_index: the index of the XML material `name` (BhrtError, BHRT_ERR_ARG, when there is none)."""
+        i = C.c_int32(-1)
+        _check(lib().bhrt_scene_material_index(self._h, name.encode(), C.byref(i)))
+        return i.value
+
+    def set_material_emission(self, material: int, rgb):
+        """bhrt_scene_set_material_emission: a plain emission colour for material `material` (any map is dropped); refreshes an uploaded scene."""
+        c = (C.c_float * 3)(*[float(x) for x in rgb])
+        _check(lib().bhrt_scene_set_material_emission(self._h, int(material), c))
+
+    def material_emission(self, material: int):
+        """bhrt_scene_get_material_emission: ((r, g, b), texmap) — the colour and the index into the blob's texmaps[] (-1 = plain colour)."""
+        c = (C.c_float * 3)()
+        m = C.c_int32(-1)
+        _check(lib().bhrt_scene_get_material_emission(self._h, int(material), c, C.byref(m)))
+        return (c[0], c[1], c[2]), m.value
+
+    def clone(self) -> "Scene":
+        """bhrt_scene_clone: a second handle on the same loaded scene (host state only, the emission state included; no device state)."""
+        other = Scene.__new__(Scene)
+        other._h = C.c_void_p()
+        other._flat = None
+        _check(lib().bhrt_scene_clone(self._h, C.byref(other._h)))
+        other.info = Info()
+        _check(lib().bhrt_scene_info(other._h, C.byref(other.info)))
+        return other
 
     def camera_rays(self, opts: Opts, region=None):
         """Test hook (bhrt_camera_rays): the camera rays of region (x0, y0, x1, y1) — default the whole frame — as the render's first wave step forms

@@ -9,6 +9,7 @@
 //               [--denoise [--denoise-iters K]]                                  (DenoiseImage of the x64 build, Main.cpp:57-96,236-238)
 //               [--adaptive [--spp-min N] [--adaptive-threshold X] [--samples-png path]]  (RenderImage::sampleCount, scene.h:534,603-630)
 //               [--lens [--dof R] [--focaldist D]]                               (the viewport's depth of field, viewport.cpp:236-243, rendered)
+//               [--emission]                                                     (the <emission> of the materials, xmlload.cpp:344-348, shaded)
 //   bhrt info   <scene.xml>
 //
 // --gpus N: ONE process drives N GPUs of the node (the reference's one process drives 16 OpenMP threads, Main.cpp:422): the
@@ -29,6 +30,9 @@
 // --lens: bhrt_opts.lens = 1, a thin-lens camera with the scene's <dof> as aperture radius, focused at <focaldist>.  --dof R and
 // --focaldist D replace the scene's values (bhrt_scene_set_lens, before the upload) and imply --lens.  The option travels in bhrt_opts, so it
 // works with --gpus, --adaptive and --denoise; the denoiser's guides stay those of the pinhole ray.
+// --emission: bhrt_scene_set_emissive(scene, 1) before the upload and before --gpus N clones the scene: every Shade() frame of a Blinn
+// material adds its <emission> last.  Scene state, so it reaches every render the other options choose (--gpus, --rehearse, --denoise, --adaptive,
+// --lens); the denoiser's albedo guide stays the diffuse colour.  Without the flag the frame is the reference's, which never shades <emission>.
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
@@ -69,6 +73,7 @@ struct Args {
     bhrt_adaptive_opts ad;
     std::string samples_png;
     float dof = -1.f, focaldist = 0.f; // --dof / --focaldist: values for bhrt_scene_set_lens; dof < 0: not given
+    bool emission = false;             // --emission: bhrt_scene_set_emissive
 };
 
 // a finite number >= 0 (--dof) or > 0 (--focaldist), else a usage error
@@ -354,6 +359,7 @@ int main(int argc, char **argv)
         else if (s == "--adaptive-threshold") A.ad.threshold = (float)atof(next());
         else if (s == "--samples-png") A.samples_png = next();
         else if (s == "--lens") o.lens = 1;
+        else if (s == "--emission") A.emission = true;
         else if (s == "--dof") { A.dof = lens_value("--dof", next(), false); o.lens = 1; }
         else if (s == "--focaldist") { A.focaldist = lens_value("--focaldist", next(), true); o.lens = 1; }
         else { fprintf(stderr, "bhrt: unknown option %s\n", s.c_str()); return 2; }
@@ -386,6 +392,7 @@ int main(int argc, char **argv)
     printf("nodes %u, meshes %u (%u triangles, %u BVH nodes), materials %u, lights %u, textures %u, scene blob %llu bytes\n", info.n_nodes,
            info.n_meshes, info.n_triangles, info.n_bvh_nodes, info.n_materials, info.n_lights, info.n_textures, (unsigned long long)info.flat_bytes);
     if (!render) { bhrt_scene_free(scene); return 0; }
+    if (A.emission && bhrt_scene_set_emissive(scene, 1)) return fail("set emissive"); // before the upload and before --gpus N clones the scene
     if (o.lens) { // before the upload and before --gpus N clones the scene
         const bhrt_flat_header *fh = nullptr;
         uint64_t fb = 0;

@@ -92,6 +92,11 @@ struct DeviceState : DeviceQueues {
     DevBuf<uint8_t> d_blob;
     DevBuf<int32_t> d_chain;
     DevBuf<float> d_aux; // mat_r0 + light_pick (DevScene)
+    DevBuf<bhrt_texcolor> d_emission;  // FlatScene::emission, uploaded with the scene; Frames::emission points here while the term is on
+    bool emission_on = false;          // bhrt_scene_set_emissive
+    bool emission_textured = false;    // some material's emission has a map
+    bool le_on = false;                // the running render keeps Le per frame (Frames::le): term on and emission_textured
+    DevBuf<float> d_le;                // 3 * cap_frames floats, only then
     DevScene S;
     // wavefront workspace (EnsureWorkspace)
     uint32_t cap_samples = 0, cap_rays = 0, cap_frames = 0;

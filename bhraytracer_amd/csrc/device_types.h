@@ -81,6 +81,12 @@ struct Frames {
     float *caustic;    // 3: photon-map term brdf*irrad (:329-342), zero when off
     // inputs of the caustic term, only allocated when the photon map is on: hit p, hit N, vV, kd sample, ks sample
     float *ph_p, *ph_n, *ph_v, *ph_kd, *ph_ks;
+    // the emission term, read by the kEmit / kLe instantiations of the kernels only.  emission: the <emission> TexturedColor of
+    // every material (FlatScene::emission), [n_materials]; null = the term is off (bhrt_scene_set_emissive, the default).  le, 3: Le =
+    // emission.Sample(uvw, duvw) at this frame's hit, only allocated when the term is on AND some material's emission has a map; null otherwise
+    // (a plain colour needs no bytes per frame: it is read from `emission` through the material index in `info`)
+    const bhrt_texcolor *emission;
+    float *le;
 };
 
 #define BHRT_ORDER_SHARDS 32

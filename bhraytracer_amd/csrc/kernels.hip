@@ -806,7 +806,8 @@ struct ShadeOut {
 
 // kTex = false: the scene has no texture map at all (every TexturedColor is its plain colour): the texture sampling code
 // (a quarter of the kernel, 200 divisions) is not even compiled in.
-template <bool kTex>
+// kLe = true (needs kTex): the emission term is on and some emission is textured; the frame keeps its Le (Frames::le).
+template <bool kTex, bool kLe>
 __device__ inline void shade_entry(const DevScene &S, const RenderParams &R, const Frames &F, uint32_t f, uint32_t how, V3 rayP, const Attr &a, int node,
                                    int bounce, int gi, uint64_t code, uint32_t skey, ShadeOut &out)
 {
@@ -936,6 +937,12 @@ __device__ inline void shade_entry(const DevScene &S, const RenderParams &R, con
         st3(F.ph_kd, f, kd_s);
         st3(F.ph_ks, f, ks_s);
     }
+    // Le of the emission term, evaluated where the hit attributes are (frame_value adds it last).  A scene with a textured emission has a texture
+    // map, so the kTex = false kernels hold no sampling code; the kLe = false kernels hold nothing of the term
+    if (kLe) {
+        const bhrt_texcolor &e = F.emission[mi];
+        st3(F.le, f, e.map >= 0 ? tc_sample_d(S, e, a.uvw, a.du, a.dv) : ld3(e.color));
+    }
     F.info[f] = how | (dmode << 3) | (light_idx << 8) | (flags << 16) | ((uint32_t)(mi & 0xfff) << 20); // the frame's only write of info
 }
 
@@ -945,11 +952,12 @@ __device__ inline void shade_entry(const DevScene &S, const RenderParams &R, con
 // kFused (camera step of a scene without meshes): the kernel traces its camera rays itself, in slot order — no k_trace_closest in front of it (which
 // computes the same camera ray, ~300 instructions, and writes 24-byte hit records this kernel reads back), no shading order (all samples of a pixel
 // sit in one wave: hits and misses are as uniform per workgroup in slot order as in the sorted one), frame numbers from one atomic per workgroup.
-template <bool kCamera, bool kTex, bool kFused = false>
+template <bool kCamera, bool kTex, bool kFused = false, bool kLe = false>
 __device__ __forceinline__ void shade_block(const DevScene &S, const RenderParams &R, const PassInfo &P, const RayQueue &qin, const HitBuf &hb, uint32_t n, const RayQueue &qout,
                                             const ShadowQueue &qs, const Frames &F, float *samples, uint32_t *root_of, Counters *cnt, const RayOrder &ord)
 {
     static_assert(!kFused || kCamera, "only camera rays are traced in the shading kernel");
+    static_assert(!kLe || kTex, "a textured emission implies a texture map");
     __shared__ BlockAllocLds lds;
     uint32_t seg = 0, local = 0, i;
     bool active;
@@ -1057,10 +1065,11 @@ __device__ __forceinline__ void shade_block(const DevScene &S, const RenderParam
         F.code[f] = code;
         if (how == FH_REFR_OUT) st3(F.mult, f, mult); // a GI frame's multiplier stays where it is: the parent's gi_mult (k_combine)
         const int mi = S.nodes[hit.node].material;
-        const bool need_uv = kTex && mi >= 0 && (S.materials[mi].diffuse.map >= 0 || S.materials[mi].specular.map >= 0);
+        bool need_uv = kTex && mi >= 0 && (S.materials[mi].diffuse.map >= 0 || S.materials[mi].specular.map >= 0);
+        if (kLe && mi >= 0) need_uv = need_uv || F.emission[mi].map >= 0; // a textured emission reads uvw / duvw too
         Attr a;
         hit_attrs(S, o, d, hit.t, hit.node, hit.prim, need_uv, a);
-        shade_entry<kTex>(S, R, F, f, how, o, a, hit.node, bounce, gi, code, skey, so);
+        shade_entry<kTex, kLe>(S, R, F, f, how, o, a, hit.node, bounce, gi, code, skey, so);
         ray_owner = f;
     } else if (active) {
         if (kind == RK_CAMERA) {
@@ -1162,11 +1171,11 @@ __device__ __forceinline__ void shade_block(const DevScene &S, const RenderParam
 // The workgroup that finishes LAST hands the step's queue lengths to the host (what a one-lane kernel behind k_shade did: k_publish, ~6 us of
 // launch and ~5 us of gap per wave step — 2 % of a C2 frame).  Every workgroup's counter updates are atomics at agent scope and come before its
 // ticket (release fence); the last ticket holder reads them with atomic loads behind an acquire fence.
-template <bool kCamera, bool kTex, bool kFused = false>
+template <bool kCamera, bool kTex, bool kFused = false, bool kLe = false>
 __global__ void __launch_bounds__(kShadeBlock, BHRT_SHADE_WAVES) k_shade(DevScene S, RenderParams R, PassInfo P, RayQueue qin, HitBuf hb, uint32_t n, RayQueue qout,
                                                    ShadowQueue qs, Frames F, float *samples, uint32_t *root_of, Counters *cnt, RayOrder ord, HostCounters *pub, uint32_t seq)
 {
-    shade_block<kCamera, kTex, kFused>(S, R, P, qin, hb, n, qout, qs, F, samples, root_of, cnt, ord);
+    shade_block<kCamera, kTex, kFused, kLe>(S, R, P, qin, hb, n, qout, qs, F, samples, root_of, cnt, ord);
     if (!pub) return;
     __syncthreads(); // every wave is through: its queue counters were added to by returning atomics whose results it has used (block_alloc), its
     // capacity flags likewise (flag_overflow) — all acknowledged.  No agent-scope fence: only counters travel, all by atomics at agent scope; a release
@@ -1180,6 +1189,8 @@ __global__ void __launch_bounds__(kShadeBlock, BHRT_SHADE_WAVES) k_shade(DevScen
 // ------------------------------------------------------------------------------------------------
 // The value of Shade() frame f once its sub-terms are in (MtlBlinn.cpp:117-137): what k_combine hands to the frame's parent and what
 // k_resolve_frames sums for a root frame.  ONE copy: the two kernels owe each other the same operations in the same order.
+// kEmit: the emission term is on; the kEmit = false instantiations are the kernels as they were before the term existed.
+template <bool kEmit>
 __device__ inline V3 frame_value(const DevScene &S, const Frames &F, uint32_t f, uint32_t info, int photon)
 {
     const uint32_t dmode = (info >> 3) & 7u, li = (info >> 8) & 0xffu, flags = (info >> 16) & 0xfu;
@@ -1214,18 +1225,22 @@ __device__ inline V3 frame_value(const DevScene &S, const Frames &F, uint32_t f,
             done = out.x >= 1 && out.y >= 1 && out.z >= 1;
             if (!done && isnan_f(out.x)) out = v3(1.0f, 0.0f, 1.0f);
         }
+        // Shade_e = Shade_ref + Le: one float addition per channel, behind every early return, clamp and NaN replacement above;
+        // Blinn frames only (FF_CONST: a node without material or an empty MultiMtl).  F.le is wave-uniform (a kernel argument)
+        if (kEmit) out = out + (F.le ? ld3i(F.le, f) : ld3(F.emission[info >> 20].color));
     }
     return out;
 }
 
 // Fold frames [f0, f1) (all created in one wave step) into their parents / the sample buffer.
+template <bool kEmit>
 __global__ void __launch_bounds__(kBlock) k_combine(DevScene S, PassInfo P, Frames F, uint32_t f0, uint32_t f1, float *samples, int photon)
 {
     const uint32_t f = f0 + blockIdx.x * blockDim.x + threadIdx.x;
     if (f >= f1) return;
     const uint32_t info = F.info[f];
     const uint32_t how = info & 7u;
-    const V3 out = frame_value(S, F, f, info, photon);
+    const V3 out = frame_value<kEmit>(S, F, f, info, photon);
     const uint32_t parent = F.parent[f];
     if (how == FH_ROOT) st3(samples, sample_addr(P, parent), out);
     else if (how == FH_GI) { // MtlBlinn.cpp:406,427-432
@@ -1263,7 +1278,7 @@ __global__ void __launch_bounds__(kBlock) k_resolve(PassInfo P, const float *sam
 // pixels outside the image are never read (k_shade leaves their map entries unwritten).
 constexpr int kResolvePixels = 8;
 constexpr int kResolveStride = 64 * 3 + 3; // floats per pixel in LDS; 3 mod 32 banks: the 24 summing lanes read 24 different banks
-template <bool kTex>
+template <bool kTex, bool kEmit>
 __global__ void __launch_bounds__(64) k_resolve_frames(DevScene S, PassInfo P, Frames F, const uint32_t *root_of, int photon, float *radiance, uint8_t *rgb8)
 {
     __shared__ float s_val[kResolvePixels * kResolveStride];
@@ -1292,7 +1307,7 @@ __global__ void __launch_bounds__(64) k_resolve_frames(DevScene S, PassInfo P, F
         for (int p = 0; p < kResolvePixels; p++) {
             if (!live[p]) continue;
             V3 v;
-            if (f[p] != kNoRootFrame) v = frame_value(S, F, f[p], info[p], photon);
+            if (f[p] != kNoRootFrame) v = frame_value<kEmit>(S, F, f[p], info[p], photon);
             else v = kTex ? tc_sample(S, S.background, v3((float)pi[p] / S.cam.width, (float)pj[p] / S.cam.height, 0.0f)) : ld3(S.background.color); // Main.cpp:166-167
             float *dst = s_val + p * kResolveStride + 3 * lane;
             dst[0] = v.x; dst[1] = v.y; dst[2] = v.z;
@@ -1989,6 +2004,22 @@ static int EnsureUploaded(bhrt_scene *scene)
     return bhrt_scene_upload(scene, 0);
 }
 
+// The device's copy of the scene's emission state (FlatScene::emission / emissive): at upload, and again by the setters of an uploaded scene.
+// Calls on one scene do not overlap and every render synchronises its stream before it returns, so no kernel is reading the array.
+static int RefreshEmission(bhrt_scene *scene)
+{
+    DeviceState *D = scene->dev;
+    if (!D) return BHRT_OK;
+    HIP_CHECK(hipSetDevice(D->device));
+    const std::vector<bhrt_texcolor> &e = scene->flat.emission;
+    D->emission_textured = false;
+    for (const bhrt_texcolor &t : e) D->emission_textured = D->emission_textured || t.map >= 0;
+    BHRT_TRY(D->d_emission.Reserve(std::max<size_t>(e.size(), 1)));
+    if (!e.empty()) HIP_CHECK(hipMemcpy(D->d_emission, e.data(), e.size() * sizeof(bhrt_texcolor), hipMemcpyHostToDevice));
+    D->emission_on = scene->flat.emissive && !e.empty();
+    return BHRT_OK;
+}
+
 static int EnsureWorkspace(DeviceState *D, uint32_t cap_samples, double frames_per_sample)
 {
     const size_t cf_wanted = (size_t)std::ceil((double)cap_samples * frames_per_sample);
@@ -2021,6 +2052,7 @@ static int EnsureWorkspace(DeviceState *D, uint32_t cap_samples, double frames_p
     D->order_shard_cap = shard_cap;
     D->cap_samples = cap_samples; D->cap_rays = (uint32_t)cr; D->cap_frames = (uint32_t)cf;
     D->d_ph_frames.Free(); // sized by cap_frames: RenderPixels allocates it again when a render needs it
+    D->d_le.Free();        // likewise
     return BHRT_OK;
 }
 
@@ -2034,7 +2066,7 @@ static int EnsureWorkspace(DeviceState *D, uint32_t cap_samples, double frames_p
 // = 138-149 GB.
 static uint32_t DefaultPassSamples(DeviceState *D, bool photon_map, double frames_per_sample)
 {
-    const double frame_b = 116 + (photon_map ? 60 : 0);
+    const double frame_b = 116 + (photon_map ? 60 : 0) + (D->le_on ? 12 : 0); // le_on: the textured emission term of a frame (Frames::le)
     const double per_sample = 2 * (72 + 16 + 32 + 40 + (D->stream3 ? 32 + 8 : 0)) + 12 + frames_per_sample * frame_b;
     size_t free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return 1u << 26;
@@ -2056,6 +2088,8 @@ static Frames MakeFrames(DeviceState *D)
     F.rr = p; p += c; F.vis = p;
     float *q = D->d_ph_frames;
     F.ph_p = q; F.ph_n = q ? q + 3 * c : nullptr; F.ph_v = q ? q + 6 * c : nullptr; F.ph_kd = q ? q + 9 * c : nullptr; F.ph_ks = q ? q + 12 * c : nullptr;
+    F.emission = D->emission_on ? D->d_emission.p : nullptr;
+    F.le = D->le_on ? D->d_le.p : nullptr;
     return F;
 }
 
@@ -2382,8 +2416,12 @@ static decltype(&k_shadow_mesh<1>) AnyHitMeshKernel(int path_mode, bool ls)
     return k_shadow_mesh<0>;
 }
 // fused: the camera step of a scene without meshes, k_shade traces its rays itself (shade_block's kFused).
-static decltype(&k_shade<true, true>) ShadeKernel(bool fused, bool cam_step, bool tex)
+static decltype(&k_shade<true, true>) ShadeKernel(bool fused, bool cam_step, bool tex, bool le)
 {
+    if (le && tex) { // the frames keep a textured Le (DeviceState::le_on)
+        if (fused) return k_shade<true, true, true, true>;
+        return cam_step ? k_shade<true, true, false, true> : k_shade<false, true, false, true>;
+    }
     if (fused) return tex ? k_shade<true, true, true> : k_shade<true, false, true>;
     if (cam_step) return tex ? k_shade<true, true> : k_shade<true, false>;
     return tex ? k_shade<false, true> : k_shade<false, false>;
@@ -2645,7 +2683,7 @@ struct WavePass {
         const int par = (int)(pass_steps & 1u);
         if (sh_wait_n) { HIP_CHECK(hipEventRecord(D->ev_shade, D->stream)); BHRT_TRY(LaunchQueuedAnyHit(D->ev_shade)); }
         if (sh_overlap && sh_pending[par]) { HIP_CHECK(hipStreamWaitEvent(D->stream, D->ev_shadow[par], 0)); sh_pending[par] = false; } // the any-hit kernels of two steps ago still read this queue
-        hipLaunchKernelGGL(ShadeKernel(fused, CamStep(), tex), sg, sb, 0, D->stream, D->S, R, P, V.Q[cur], V.HB, n_cur + n_extra, V.Q[cur ^ 1], (sh_overlap && par) ? V.SQ2 : V.SQ, V.F, D->d_samples, root_of, D->d_cnt, V.RO, D->d_pub, seq); // + n_next, n_shadow, n_frames, overflow to the host
+        hipLaunchKernelGGL(ShadeKernel(fused, CamStep(), tex, V.F.le != nullptr), sg, sb, 0, D->stream, D->S, R, P, V.Q[cur], V.HB, n_cur + n_extra, V.Q[cur ^ 1], (sh_overlap && par) ? V.SQ2 : V.SQ, V.F, D->d_samples, root_of, D->d_cnt, V.RO, D->d_pub, seq); // + n_next, n_shadow, n_frames, overflow to the host
         t.Stop();
         if (sh_overlap) HIP_CHECK(hipEventRecord(D->ev_shade, D->stream));
         return BHRT_OK;
@@ -2769,6 +2807,7 @@ static int RenderPixels(bhrt_scene *scene, const bhrt_opts &o, PassInfo P, const
 {
     DeviceState *D = scene->dev;
     P.spp = (int32_t)spp; P.by_spp = MakeFastDiv(spp); P.s0 = s0;
+    D->le_on = D->emission_on && D->emission_textured; // before the passes are sized: DefaultPassSamples counts the term's 12 B per frame
     const PassSizing Z = SizePasses(D, o, n_items, spp, P.world, P.tile);
     D->timers = o.timers;
     D->photon_exact = o.photon_exact;
@@ -2784,6 +2823,7 @@ static int RenderPixels(bhrt_scene *scene, const bhrt_opts &o, PassInfo P, const
         R.cap_rays = D->cap_rays; R.cap_shadow = D->cap_rays; R.cap_frames = D->cap_frames;
         if (D->knobs.frame_cap > 0) R.cap_frames = std::min<uint32_t>(R.cap_frames, (uint32_t)D->knobs.frame_cap); // test knob: a pass that overflows
         if (o.photon_map) BHRT_TRY(D->d_ph_frames.Reserve((size_t)D->cap_frames * 15));
+        if (D->le_on) BHRT_TRY(D->d_le.Reserve((size_t)D->cap_frames * 3));
         if (pass_limit == 0) pass_limit = Z.pass_samples;
         if (pass_limit > D->cap_samples) pass_limit = D->cap_samples;
         const uint32_t px_per_pass = pass_limit / spp;
@@ -2828,7 +2868,7 @@ static int RenderPixels(bhrt_scene *scene, const bhrt_opts &o, PassInfo P, const
             // stores the frame's value into d_samples, where nothing reads it — k_resolve_frames finds the frame through the map like any other
             for (size_t k = pass.frame_marks.size(); k-- > (fuse_root ? 2 : 1);) {
                 const uint32_t f0 = pass.frame_marks[k - 1], f1 = pass.frame_marks[k];
-                if (f1 > f0) hipLaunchKernelGGL(k_combine, dim3((f1 - f0 + kBlock - 1) / kBlock), dim3(kBlock), 0, D->stream, D->S, P, F, f0, f1, D->d_samples, o.photon_map);
+                if (f1 > f0) hipLaunchKernelGGL(F.emission ? k_combine<true> : k_combine<false>, dim3((f1 - f0 + kBlock - 1) / kBlock), dim3(kBlock), 0, D->stream, D->S, P, F, f0, f1, D->d_samples, o.photon_map);
             }
             consume(P, npx, F);
             t.Stop();
@@ -2856,7 +2896,8 @@ static int RenderRange(bhrt_scene *scene, const bhrt_opts &o, uint8_t *d_rgb8, f
     const bool tex = scene->flat.hdr()->n_texmaps > 0;
     rc = RenderPixels(scene, o, P, nullptr, owned_pixels, 0, (uint32_t)o.spp, st, fuse_root, [&](const PassInfo &Pp, uint32_t npx, const Frames &F) {
         if (fuse_root) {
-            hipLaunchKernelGGL(tex ? k_resolve_frames<true> : k_resolve_frames<false>, dim3((npx + kResolvePixels - 1) / kResolvePixels), dim3(64), 0, D->stream, D->S, Pp, F,
+            const bool emit = F.emission != nullptr;
+            hipLaunchKernelGGL(tex ? (emit ? k_resolve_frames<true, true> : k_resolve_frames<true, false>) : (emit ? k_resolve_frames<false, true> : k_resolve_frames<false, false>), dim3((npx + kResolvePixels - 1) / kResolvePixels), dim3(64), 0, D->stream, D->S, Pp, F,
                                D->d_root.p, o.photon_map, d_radiance, d_rgb8);
             st->launches_resolve_fused++;
             return;
@@ -3122,6 +3163,7 @@ try {
         S.cam_chain = D->d_aux + H->n_materials + H->n_lights + 1;
     }
     S.cam = H->camera; S.background = H->background; S.environment = H->environment;
+    BHRT_TRY(RefreshEmission(scene));
     S.tapx[0] = S.tapy[0] = 0;
     for (int i = 1; i < 32; i++) { // scene.h:322-329 with the deterministic sin/cos (host and device agree bit for bit)
         auto halton = [](int index, int base) { float r = 0, f = 1.0f / (float)base; for (int k = index; k > 0; k /= base) { r += f * (k % base); f /= (float)base; } return r; };
@@ -3400,6 +3442,44 @@ try {
     H->camera.dof = dof;
     DeriveCameraFrame(H->camera);
     if (scene->dev) scene->dev->S.cam = H->camera;
+    return BHRT_OK;
+} catch (...) { return bhrt::AbiException(); }
+
+// ---- the emission term: scene state beside the blob.  In this translation unit because the setters refresh an uploaded scene.
+int bhrt_scene_set_emissive(bhrt_scene *scene, int on)
+try {
+    if (!scene) { SetError("bhrt_scene_set_emissive: null scene"); return BHRT_ERR_ARG; }
+    scene->flat.emissive = on ? 1 : 0;
+    return RefreshEmission(scene);
+} catch (...) { return bhrt::AbiException(); }
+
+int bhrt_scene_material_index(const bhrt_scene *scene, const char *name, int32_t *index)
+try {
+    if (!scene || !name || !index) { SetError("bhrt_scene_material_index: null argument"); return BHRT_ERR_ARG; }
+    const std::vector<std::string> &names = scene->flat.material_names;
+    for (size_t i = 0; i < names.size(); i++) // the first of that name, as the loader's own lookup (xmlload.cpp:101-107)
+        if (names[i] == name) { *index = (int32_t)i; return BHRT_OK; }
+    SetError(std::string("bhrt_scene_material_index: no material named \"") + name + "\"");
+    return BHRT_ERR_ARG;
+} catch (...) { return bhrt::AbiException(); }
+
+int bhrt_scene_set_material_emission(bhrt_scene *scene, int32_t material, const float rgb[3])
+try {
+    if (!scene || !rgb) { SetError("bhrt_scene_set_material_emission: null argument"); return BHRT_ERR_ARG; }
+    if (material < 0 || (size_t)material >= scene->flat.emission.size()) { SetError("bhrt_scene_set_material_emission: material index out of range"); return BHRT_ERR_ARG; }
+    bhrt_texcolor &e = scene->flat.emission[(size_t)material];
+    e.color[0] = rgb[0]; e.color[1] = rgb[1]; e.color[2] = rgb[2];
+    e.map = -1;
+    return RefreshEmission(scene);
+} catch (...) { return bhrt::AbiException(); }
+
+int bhrt_scene_get_material_emission(const bhrt_scene *scene, int32_t material, float rgb[3], int32_t *texmap)
+try {
+    if (!scene) { SetError("bhrt_scene_get_material_emission: null scene"); return BHRT_ERR_ARG; }
+    if (material < 0 || (size_t)material >= scene->flat.emission.size()) { SetError("bhrt_scene_get_material_emission: material index out of range"); return BHRT_ERR_ARG; }
+    const bhrt_texcolor &e = scene->flat.emission[(size_t)material];
+    if (rgb) { rgb[0] = e.color[0]; rgb[1] = e.color[1]; rgb[2] = e.color[2]; }
+    if (texmap) *texmap = e.map;
     return BHRT_OK;
 } catch (...) { return bhrt::AbiException(); }
 

@@ -185,7 +185,7 @@ struct TexColorData {
 struct MaterialData {
     std::string name;
     int kind = BHRT_MTL_BLINN;
-    TexColorData diffuse, specular, refraction;
+    TexColorData diffuse, specular, refraction, emission; // emission: (0, 0, 0), materials.h:23
     float glossiness = 20.0f;
     Col absorption = {0, 0, 0};
     float ior = 1;
@@ -340,7 +340,7 @@ struct Loader {
             if (NameIs(c, "diffuse")) { ReadColor(c, col); m.diffuse.color = col; m.diffuse.map = ReadTexture(c); }
             else if (NameIs(c, "specular")) { ReadColor(c, col); m.specular.color = col; m.specular.map = ReadTexture(c); }
             else if (NameIs(c, "glossiness")) { ReadFloat(c, f); m.glossiness = f; }
-            else if (NameIs(c, "emission")) { ReadTexture(c); /* parsed, never shaded */ }
+            else if (NameIs(c, "emission")) { ReadColor(c, col); m.emission.color = col; m.emission.map = ReadTexture(c); } // xmlload.cpp:344-348; kept beside the blob (FlatScene::emission)
             else if (NameIs(c, "reflection")) { ReadTexture(c); /* parsed, never shaded (Q8) */ }
             else if (NameIs(c, "refraction")) {
                 ReadColor(c, col);
@@ -1272,6 +1272,13 @@ int LoadSceneXml(const char *path, FlatScene &out, std::string &err, int bvh_dev
         o.ior = m.ior; o.refraction_glossiness = m.refraction_glossiness;
     }
     H.n_materials = (uint32_t)mats.size();
+    out.emission.resize(L.materials.size());
+    out.material_names.resize(L.materials.size());
+    for (size_t i = 0; i < L.materials.size(); i++) {
+        StoreTexColor(out.emission[i], L.materials[i].emission);
+        out.material_names[i] = L.materials[i].name;
+    }
+    out.emissive = 0;
     H.off_materials = W.Append(mats.data(), mats.size() * sizeof(bhrt_material));
 
     std::vector<bhrt_light> lights(L.lights.size());

@@ -12,6 +12,12 @@ namespace bhrt {
 struct FlatScene {
     std::vector<uint8_t> blob;
     std::vector<std::string> warnings; // the reference printf()s and carries on (xmlload.cpp:212-214,570-573)
+    // Scene state beside the blob: the <emission> of every material (xmlload.cpp:344-348; its map is an index into the blob's
+    // texmaps[]), the materials' XML names, and the switch of the emission term (bhrt_scene_set_emissive).  The blob holds none of it: its
+    // bytes are what they were before the term existed.
+    std::vector<bhrt_texcolor> emission;      // [n_materials]
+    std::vector<std::string> material_names;  // [n_materials]
+    int emissive = 0;
     const bhrt_flat_header *hdr() const { return reinterpret_cast<const bhrt_flat_header *>(blob.data()); }
 };
 

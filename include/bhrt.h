@@ -148,6 +148,20 @@ int bhrt_scene_flat(const bhrt_scene *scene, const void **blob, uint64_t *bytes)
  * afterwards byte-identical to the blob of the same XML with the two values written into its <camera>.  Needs no device; on an uploaded scene
  * the device's copy of the camera is refreshed (nothing else is uploaded again).  The pointer bhrt_scene_flat returned stays valid. */
 int bhrt_scene_set_lens(bhrt_scene *scene, float focaldist, float dof);
+/* The emission term.  Every Blinn material carries the <emission> of its XML (xmlload.cpp:344-348: a colour, optionally a texture
+ * map); the reference parses it and never shades it, and so does a scene here until it is switched on.  With the term on, every Shade() frame of
+ * a Blinn material evaluates to  Shade(hit) + emission.Sample(uvw, duvw)  — one float addition per channel, behind everything Shade() does, on
+ * front and back hits, at every bounce (a GI or refraction ray that lands on an emitter brings its light back).  Frames of a node without
+ * material or with an empty MultiMtl get nothing.  The state lives beside the flat blob: bhrt_scene_flat's bytes do not change, bhrt_scene_clone
+ * carries it, and bhrt_opts has no field for it.  None of these calls needs a device; on an uploaded scene they refresh the device's copy.
+ *   set_emissive           on != 0: the term is part of all later renders of this scene (bhrt_render*, _samples, _var*, _adaptive*); default 0
+ *   material_index         the index of the XML material of that name (the first, as the loader resolves node materials); unknown: BHRT_ERR_ARG
+ *   set_material_emission  a plain colour for that material, any map dropped; index out of range: BHRT_ERR_ARG
+ *   get_material_emission  the colour and the index into the blob's texmaps[] (-1 = plain colour); rgb / texmap may be NULL */
+int bhrt_scene_set_emissive(bhrt_scene *scene, int on);
+int bhrt_scene_material_index(const bhrt_scene *scene, const char *name, int32_t *index);
+int bhrt_scene_set_material_emission(bhrt_scene *scene, int32_t material, const float rgb[3]);
+int bhrt_scene_get_material_emission(const bhrt_scene *scene, int32_t material, float rgb[3], int32_t *texmap);
 
 /* ---- device residency ---------------------------------------------------------------------------- */
 int bhrt_scene_upload(bhrt_scene *scene, int device); /* copies the flat scene into HBM of `device`; idempotent */
