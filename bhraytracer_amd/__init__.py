@@ -82,6 +82,7 @@ EXPORTS = [
     "bhrt_save_png_gray",
     "bhrt_scene_set_lens", "bhrt_camera_rays",
     "bhrt_scene_set_emissive", "bhrt_scene_material_index", "bhrt_scene_set_material_emission", "bhrt_scene_get_material_emission",
+    "bhrt_scene_set_face_materials", "bhrt_scene_submaterial_count", "bhrt_scene_get_submaterial",
 ]
 
 
@@ -233,8 +234,30 @@ class Scene:
         _check(lib().bhrt_scene_get_material_emission(self._h, int(material), c, C.byref(m)))
         return (c[0], c[1], c[2]), m.value
 
+    # ---- face materials: scene state beside the flat blob, which keeps its bytes ---------------------------------------------
+    def set_face_materials(self, on: bool = True):
+        """bhrt_scene_set_face_materials: with the switch on, a hit of a node whose material is a MultiMtl (an OBJ with a .mtl) shades with the
+        sub-material of the face that was hit, in all later renders and first-hit images of this scene.  Off by default: the reference shades
+        the whole mesh with sub-material 0."""
+        _check(lib().bhrt_scene_set_face_materials(self._h, 1 if on else 0))
+
+    def submaterial_count(self, material: int) -> int:
+        """bhrt_scene_submaterial_count: the number of sub-materials of material `material`; 0 for one that is not a MultiMtl."""
+        n = C.c_int32(0)
+        _check(lib().bhrt_scene_submaterial_count(self._h, int(material), C.byref(n)))
+        return n.value
+
+    def submaterial(self, material: int, sub: int):
+        """bhrt_scene_get_submaterial: (record, face_end) — sub-material `sub` of material `material` as a flat.Material (the layout of the
+        blob's materials; bytes(record) are its bytes) and the end of its face range: faces [face_end of sub - 1, face_end) shade with it."""
+        from .flat import Material
+        m = Material()
+        e = C.c_uint32(0)
+        _check(lib().bhrt_scene_get_submaterial(self._h, int(material), int(sub), C.byref(m), C.byref(e)))
+        return m, e.value
+
     def clone(self) -> "Scene":
-        """bhrt_scene_clone: a second handle on the same loaded scene (host state only, the emission state included; no device state)."""
+        """bhrt_scene_clone: a second handle on the same loaded scene (host state only, the emission and face-material state included; no device state)."""
         other = Scene.__new__(Scene)
         other._h = C.c_void_p()
         other._flat = None

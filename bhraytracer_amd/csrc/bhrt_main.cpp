@@ -10,6 +10,7 @@
 //               [--adaptive [--spp-min N] [--adaptive-threshold X] [--samples-png path]]  (RenderImage::sampleCount, scene.h:534,603-630)
 //               [--lens [--dof R] [--focaldist D]]                               (the viewport's depth of field, viewport.cpp:236-243, rendered)
 //               [--emission]                                                     (the <emission> of the materials, xmlload.cpp:344-348, shaded)
+//               [--face-materials]                                               (the .mtl sub-material of each mesh face, viewport.cpp:581-607, rendered)
 //   bhrt info   <scene.xml>
 //
 // --gpus N: ONE process drives N GPUs of the node (the reference's one process drives 16 OpenMP threads, Main.cpp:422): the
@@ -33,6 +34,9 @@
 // --emission: bhrt_scene_set_emissive(scene, 1) before the upload and before --gpus N clones the scene: every Shade() frame of a Blinn
 // material adds its <emission> last.  Scene state, so it reaches every render the other options choose (--gpus, --rehearse, --denoise, --adaptive,
 // --lens); the denoiser's albedo guide stays the diffuse colour.  Without the flag the frame is the reference's, which never shades <emission>.
+// --face-materials: bhrt_scene_set_face_materials(scene, 1) before the upload and before --gpus N clones the scene: a mesh with a .mtl
+// shades every face with its own sub-material.  Scene state, so it reaches every render the other options choose (--gpus, --rehearse, --denoise,
+// --adaptive, --lens, --emission), the denoiser's albedo guide included.  Without the flag the frame is the reference's: sub-material 0 everywhere.
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
@@ -74,6 +78,7 @@ struct Args {
     std::string samples_png;
     float dof = -1.f, focaldist = 0.f; // --dof / --focaldist: values for bhrt_scene_set_lens; dof < 0: not given
     bool emission = false;             // --emission: bhrt_scene_set_emissive
+    bool face_materials = false;       // --face-materials: bhrt_scene_set_face_materials
 };
 
 // a finite number >= 0 (--dof) or > 0 (--focaldist), else a usage error
@@ -360,6 +365,7 @@ int main(int argc, char **argv)
         else if (s == "--samples-png") A.samples_png = next();
         else if (s == "--lens") o.lens = 1;
         else if (s == "--emission") A.emission = true;
+        else if (s == "--face-materials") A.face_materials = true;
         else if (s == "--dof") { A.dof = lens_value("--dof", next(), false); o.lens = 1; }
         else if (s == "--focaldist") { A.focaldist = lens_value("--focaldist", next(), true); o.lens = 1; }
         else { fprintf(stderr, "bhrt: unknown option %s\n", s.c_str()); return 2; }
@@ -393,6 +399,7 @@ int main(int argc, char **argv)
            info.n_meshes, info.n_triangles, info.n_bvh_nodes, info.n_materials, info.n_lights, info.n_textures, (unsigned long long)info.flat_bytes);
     if (!render) { bhrt_scene_free(scene); return 0; }
     if (A.emission && bhrt_scene_set_emissive(scene, 1)) return fail("set emissive"); // before the upload and before --gpus N clones the scene
+    if (A.face_materials && bhrt_scene_set_face_materials(scene, 1)) return fail("set face materials"); // likewise
     if (o.lens) { // before the upload and before --gpus N clones the scene
         const bhrt_flat_header *fh = nullptr;
         uint64_t fb = 0;

@@ -97,6 +97,12 @@ struct DeviceState : DeviceQueues {
     bool emission_textured = false;    // some material's emission has a map
     bool le_on = false;                // the running render keeps Le per frame (Frames::le): term on and emission_textured
     DevBuf<float> d_le;                // 3 * cap_frames floats, only then
+    // face materials, built at upload for a scene that has sub-materials: the extended material table (the blob's materials, then
+    // FlatScene::sub_materials), its Schlick R0s, and FaceMtlTable's array.  S.materials / S.mat_r0 point at them only while the switch is on
+    DevBuf<bhrt_material> d_mtl_ext;
+    DevBuf<float> d_r0_ext;
+    DevBuf<int32_t> d_fm_tab;
+    FaceMtlTable fm = {nullptr, 0}; // fm.tab != null: bhrt_scene_set_face_materials is on and the scene has sub-materials
     DevScene S;
     // wavefront workspace (EnsureWorkspace)
     uint32_t cap_samples = 0, cap_rays = 0, cap_frames = 0;

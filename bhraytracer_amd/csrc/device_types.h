@@ -63,10 +63,22 @@ struct ShadowQueue {
     float *ox, *oy, *oz, *dx, *dy, *dz, *tmax;
     uint32_t *frame;
 };
+// Face materials: which sub-material of a MultiMtl a face shades with, read by the kFm instantiations of the kernels only.
+// The kernels then see a material table that is the blob's materials followed by the sub-materials of all MultiMtls (DevScene::materials,
+// mat_r0 and Frames::emission alike).  One array (two pointers cost the camera kernels scalar registers they do not have):
+//   tab[0 .. n]               first[]: blob material m owns sub-materials [first[m], first[m + 1]) (none: Blinn, or an empty MultiMtl)
+//   tab[n + 1 ..]             face_end[]: HostMesh::mcfc of every MultiMtl, ascending within one; sub-material i's faces end at face_end[i]
+// base = n = n_materials: where the sub-materials start in the extended table.  tab == null: the switch is off
+// (bhrt_scene_set_face_materials, the default).
+struct FaceMtlTable {
+    const int32_t *tab;
+    int32_t base;
+};
+
 // One MtlBlinn::Shade invocation (MtlBlinn.cpp:89-138) awaiting its sub-terms
 struct Frames {
     uint32_t *parent;  // parent frame, or sample slot when how == FH_ROOT
-    uint32_t *info;    // how | dmode << 3 | light << 8 | flags << 16 | material << 20 (12 bits)
+    uint32_t *info;    // how | dmode << 3 | light << 8 | flags << 16 | material << 20 (12 bits; with face materials on, the index into the extended table)
     uint32_t *info2;   // (gi + 64) | bounce << 8
     uint32_t *skey;    // sample key (include/bhrt_rng.h)
     uint64_t *code;    // shade-call path code
@@ -87,6 +99,7 @@ struct Frames {
     // (a plain colour needs no bytes per frame: it is read from `emission` through the material index in `info`)
     const bhrt_texcolor *emission;
     float *le;
+    FaceMtlTable fm; // fm.tab == null: face materials are off
 };
 
 #define BHRT_ORDER_SHARDS 32

@@ -804,15 +804,39 @@ struct ShadeOut {
     V3 so, sd; float stmax;          // shadow ray
 };
 
+// Face materials: the material a hit of face `prim` of node `node` shades with, as an index into the extended table (the blob's
+// materials, then the sub-materials of all MultiMtls).  For a node whose material is a MultiMtl that is sub-material s(prim), the first i with
+// prim < face_end[i] (TriMesh::GetMaterialIndex, cyTriMesh.h:221-227), and sub-material 0 where that returns -1: a face in front of any usemtl
+// (the regrouping puts those behind the last group), a face id beyond the material's own mesh, a hit that is no triangle (prim = -1).  Any
+// other node keeps its material.  The table is wave-uniform, the face id per lane: face_end[] is ascending, so the first entry above prim is
+// found by halving [b, e) — a handful of entries, every lane's loop as long as its node's table, and none for a node without a table.  Written
+// with selects, the loop its only branch, and the table one pointer and one count indexed per lane: the camera instantiations of k_shade are
+// short of scalar registers, and two pointers (or a count read from the array) left them with scratch.
+__device__ __forceinline__ int resolve_material(const DevScene &S, const FaceMtlTable &T, int node, int prim)
+{
+    const int mi = S.nodes[node].material;
+    const int mc = mi < 0 ? 0 : mi;
+    const int b = T.tab[mc], e = mi < 0 ? b : T.tab[mc + 1]; // first[]; b == e: no material, a Blinn material or an empty MultiMtl
+    int lo = b, hi = e; // invariant: face_end[i] <= prim for i < lo, prim < face_end[i] for i >= hi; prim = -1 compares as the largest face id
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        const bool below = (uint32_t)prim < (uint32_t)T.tab[T.base + 1 + mid]; // face_end[mid]
+        hi = below ? mid : hi;
+        lo = below ? lo : mid + 1;
+    }
+    return b == e ? mi : T.base + (lo < e ? lo : b);
+}
+
 // kTex = false: the scene has no texture map at all (every TexturedColor is its plain colour): the texture sampling code
 // (a quarter of the kernel, 200 divisions) is not even compiled in.
 // kLe = true (needs kTex): the emission term is on and some emission is textured; the frame keeps its Le (Frames::le).
-template <bool kTex, bool kLe>
-__device__ inline void shade_entry(const DevScene &S, const RenderParams &R, const Frames &F, uint32_t f, uint32_t how, V3 rayP, const Attr &a, int node,
+// kFm = true: face materials are on; the caller has resolved the hit's material (mi_fm, resolve_material).  kFm = false: mi_fm is not read
+template <bool kTex, bool kLe, bool kFm>
+__device__ inline void shade_entry(const DevScene &S, const RenderParams &R, const Frames &F, uint32_t f, uint32_t how, V3 rayP, const Attr &a, int node, int mi_fm,
                                    int bounce, int gi, uint64_t code, uint32_t skey, ShadeOut &out)
 {
     out.has_refr = out.has_gi = out.has_shadow = false;
-    const int mi = S.nodes[node].material;
+    const int mi = kFm ? mi_fm : S.nodes[node].material;
     uint32_t flags = 0, dmode = DM_NONE, light_idx = 0;
     V3 zero = v3(0, 0, 0);
     // no zero-fill of the term arrays: the flags in `info` say which terms exist (k_combine reads only those)
@@ -952,12 +976,14 @@ __device__ inline void shade_entry(const DevScene &S, const RenderParams &R, con
 // kFused (camera step of a scene without meshes): the kernel traces its camera rays itself, in slot order — no k_trace_closest in front of it (which
 // computes the same camera ray, ~300 instructions, and writes 24-byte hit records this kernel reads back), no shading order (all samples of a pixel
 // sit in one wave: hits and misses are as uniform per workgroup in slot order as in the sorted one), frame numbers from one atomic per workgroup.
-template <bool kCamera, bool kTex, bool kFused = false, bool kLe = false>
+// kFm: face materials are on: the frame's material is resolve_material's.  Never with kFused (a scene with sub-materials has a mesh).
+template <bool kCamera, bool kTex, bool kFused = false, bool kLe = false, bool kFm = false>
 __device__ __forceinline__ void shade_block(const DevScene &S, const RenderParams &R, const PassInfo &P, const RayQueue &qin, const HitBuf &hb, uint32_t n, const RayQueue &qout,
                                             const ShadowQueue &qs, const Frames &F, float *samples, uint32_t *root_of, Counters *cnt, const RayOrder &ord)
 {
     static_assert(!kFused || kCamera, "only camera rays are traced in the shading kernel");
     static_assert(!kLe || kTex, "a textured emission implies a texture map");
+    static_assert(!kFm || !kFused, "sub-materials come with a mesh");
     __shared__ BlockAllocLds lds;
     uint32_t seg = 0, local = 0, i;
     bool active;
@@ -1064,12 +1090,12 @@ __device__ __forceinline__ void shade_block(const DevScene &S, const RenderParam
         F.skey[f] = skey;
         F.code[f] = code;
         if (how == FH_REFR_OUT) st3(F.mult, f, mult); // a GI frame's multiplier stays where it is: the parent's gi_mult (k_combine)
-        const int mi = S.nodes[hit.node].material;
+        const int mi = kFm ? resolve_material(S, F.fm, hit.node, hit.prim) : S.nodes[hit.node].material;
         bool need_uv = kTex && mi >= 0 && (S.materials[mi].diffuse.map >= 0 || S.materials[mi].specular.map >= 0);
         if (kLe && mi >= 0) need_uv = need_uv || F.emission[mi].map >= 0; // a textured emission reads uvw / duvw too
         Attr a;
         hit_attrs(S, o, d, hit.t, hit.node, hit.prim, need_uv, a);
-        shade_entry<kTex, kLe>(S, R, F, f, how, o, a, hit.node, bounce, gi, code, skey, so);
+        shade_entry<kTex, kLe, kFm>(S, R, F, f, how, o, a, hit.node, mi, bounce, gi, code, skey, so);
         ray_owner = f;
     } else if (active) {
         if (kind == RK_CAMERA) {
@@ -1171,11 +1197,11 @@ __device__ __forceinline__ void shade_block(const DevScene &S, const RenderParam
 // The workgroup that finishes LAST hands the step's queue lengths to the host (what a one-lane kernel behind k_shade did: k_publish, ~6 us of
 // launch and ~5 us of gap per wave step — 2 % of a C2 frame).  Every workgroup's counter updates are atomics at agent scope and come before its
 // ticket (release fence); the last ticket holder reads them with atomic loads behind an acquire fence.
-template <bool kCamera, bool kTex, bool kFused = false, bool kLe = false>
+template <bool kCamera, bool kTex, bool kFused = false, bool kLe = false, bool kFm = false>
 __global__ void __launch_bounds__(kShadeBlock, BHRT_SHADE_WAVES) k_shade(DevScene S, RenderParams R, PassInfo P, RayQueue qin, HitBuf hb, uint32_t n, RayQueue qout,
                                                    ShadowQueue qs, Frames F, float *samples, uint32_t *root_of, Counters *cnt, RayOrder ord, HostCounters *pub, uint32_t seq)
 {
-    shade_block<kCamera, kTex, kFused, kLe>(S, R, P, qin, hb, n, qout, qs, F, samples, root_of, cnt, ord);
+    shade_block<kCamera, kTex, kFused, kLe, kFm>(S, R, P, qin, hb, n, qout, qs, F, samples, root_of, cnt, ord);
     if (!pub) return;
     __syncthreads(); // every wave is through: its queue counters were added to by returning atomics whose results it has used (block_alloc), its
     // capacity flags likewise (flag_overflow) — all acknowledged.  No agent-scope fence: only counters travel, all by atomics at agent scope; a release
@@ -1466,7 +1492,9 @@ __global__ void __launch_bounds__(kBlock) k_count_image(const uint32_t *cnt, uin
 // Images beside the colour image: RenderImage's z-buffer (scene.h:532, the store commented out at
 // Main.cpp:231) and the albedo / normal inputs DenoiseImage leaves unset (Main.cpp:70-71), all from the first hit of the
 // un-jittered camera ray of every pixel (the pixel corner).  One lane per pixel, row-major.
-__global__ void __launch_bounds__(kBlock) k_first_hit(DevScene S, int W, int H, float *z, float *normal, float *albedo)
+// kFm: face materials are on; the albedo is that of the face's sub-material (T is not read otherwise).
+template <bool kFm>
+__global__ void __launch_bounds__(kBlock) k_first_hit(DevScene S, FaceMtlTable T, int W, int H, float *z, float *normal, float *albedo)
 {
     __shared__ bhrt_bvh_node nodelet[BHRT_LDS_NODES];
     const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1479,7 +1507,7 @@ __global__ void __launch_bounds__(kBlock) k_first_hit(DevScene S, int W, int H, 
     if (!active) return;
     V3 N = v3(0, 0, 0), kd = v3(0, 0, 0);
     if (hit.node >= 0 && (normal || albedo)) {
-        const int mi = S.nodes[hit.node].material;
+        const int mi = kFm ? resolve_material(S, T, hit.node, hit.prim) : S.nodes[hit.node].material;
         const bool blinn = mi >= 0 && S.materials[mi].kind == BHRT_MTL_BLINN;
         Attr a;
         hit_attrs(S, o, d, hit.t, hit.node, hit.prim, albedo && blinn && S.materials[mi].diffuse.map >= 0, a);
@@ -2011,12 +2039,64 @@ static int RefreshEmission(bhrt_scene *scene)
     DeviceState *D = scene->dev;
     if (!D) return BHRT_OK;
     HIP_CHECK(hipSetDevice(D->device));
-    const std::vector<bhrt_texcolor> &e = scene->flat.emission;
+    // as the material table the kernels see with face materials on, the array goes on behind the blob's materials: sub-material 0
+    // of a MultiMtl inherits the emission of its record, the others emit nothing.  With the switch off nothing indexes that far
+    std::vector<bhrt_texcolor> e = scene->flat.emission;
+    const std::vector<int32_t> &first = scene->flat.sub_first;
+    for (size_t m = 0; m + 1 < first.size() && m < scene->flat.emission.size(); m++)
+        for (int32_t k = first[m]; k < first[m + 1]; k++) {
+            bhrt_texcolor t;
+            memset(&t, 0, sizeof t);
+            t.map = -1;
+            e.push_back(k == first[m] ? scene->flat.emission[m] : t);
+        }
     D->emission_textured = false;
     for (const bhrt_texcolor &t : e) D->emission_textured = D->emission_textured || t.map >= 0;
     BHRT_TRY(D->d_emission.Reserve(std::max<size_t>(e.size(), 1)));
     if (!e.empty()) HIP_CHECK(hipMemcpy(D->d_emission, e.data(), e.size() * sizeof(bhrt_texcolor), hipMemcpyHostToDevice));
     D->emission_on = scene->flat.emissive && !e.empty();
+    return BHRT_OK;
+}
+
+// The device's copy of the scene's face-material state (FlatScene::sub_* / face_materials): at upload, and again by the setter of
+// an uploaded scene.  With the switch on the kernels' material table and R0s are the extended ones and DeviceState::fm selects the kFm kernels;
+// with it off everything points where it did before the switch existed.  Between renders, as RefreshEmission.
+static int RefreshFaceMaterials(bhrt_scene *scene)
+{
+    DeviceState *D = scene->dev;
+    if (!D) return BHRT_OK;
+    HIP_CHECK(hipSetDevice(D->device));
+    const bhrt_flat_header *H = scene->flat.hdr();
+    const FlatScene &fs = scene->flat;
+    const bool on = fs.face_materials && !fs.sub_materials.empty();
+    if (on && !D->d_mtl_ext.p) {
+        const bhrt_material *mats = (const bhrt_material *)(fs.blob.data() + H->off_materials);
+        std::vector<bhrt_material> ext(mats, mats + H->n_materials);
+        ext.insert(ext.end(), fs.sub_materials.begin(), fs.sub_materials.end());
+        std::vector<float> r0(ext.size());
+        for (size_t m = 0; m < ext.size(); m++) { // as DevScene::mat_r0 at upload
+            const float ior = ext[m].ior;
+            const double r0d = (double)((1 - ior) / (1 + ior));
+            r0[m] = (float)(r0d * r0d);
+        }
+        BHRT_TRY(D->d_r0_ext.Reserve(r0.size()));
+        HIP_CHECK(hipMemcpy(D->d_r0_ext, r0.data(), r0.size() * sizeof(float), hipMemcpyHostToDevice));
+        std::vector<int32_t> tab(fs.sub_first); // FaceMtlTable::tab
+        tab.insert(tab.end(), fs.sub_face_end.begin(), fs.sub_face_end.end());
+        BHRT_TRY(D->d_fm_tab.Reserve(tab.size()));
+        HIP_CHECK(hipMemcpy(D->d_fm_tab, tab.data(), tab.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+        BHRT_TRY(D->d_mtl_ext.Reserve(ext.size()));
+        HIP_CHECK(hipMemcpy(D->d_mtl_ext, ext.data(), ext.size() * sizeof(bhrt_material), hipMemcpyHostToDevice));
+    }
+    if (on) {
+        D->S.materials = D->d_mtl_ext;
+        D->S.mat_r0 = D->d_r0_ext;
+        D->fm.tab = D->d_fm_tab; D->fm.base = (int32_t)H->n_materials;
+    } else {
+        D->S.materials = (const bhrt_material *)(D->d_blob + H->off_materials);
+        D->S.mat_r0 = D->d_aux;
+        D->fm.tab = nullptr; D->fm.base = 0;
+    }
     return BHRT_OK;
 }
 
@@ -2090,6 +2170,7 @@ static Frames MakeFrames(DeviceState *D)
     F.ph_p = q; F.ph_n = q ? q + 3 * c : nullptr; F.ph_v = q ? q + 6 * c : nullptr; F.ph_kd = q ? q + 9 * c : nullptr; F.ph_ks = q ? q + 12 * c : nullptr;
     F.emission = D->emission_on ? D->d_emission.p : nullptr;
     F.le = D->le_on ? D->d_le.p : nullptr;
+    F.fm = D->fm;
     return F;
 }
 
@@ -2318,6 +2399,10 @@ static int FramePassInfo(bhrt_scene *scene, const bhrt_opts &o, PassInfo &P, uin
     if (o.spp <= 0 || o.spp > 65535) { SetError("spp must be in 1..65535"); return BHRT_ERR_ARG; }
     if (o.internal_bounces < 0 || o.internal_bounces > 255 || o.gi_bounces < -1 || o.gi_bounces > 60) { SetError("bounce counts out of range"); return BHRT_ERR_ARG; }
     if (H->n_materials > 4095 || H->n_lights > 255) { SetError("too many materials/lights for the frame record"); return BHRT_ERR_UNSUPPORTED; }
+    if (scene->flat.face_materials && H->n_materials + scene->flat.sub_materials.size() > 4095) { // the frames hold indices into the extended table
+        SetError("too many materials and sub-materials for the frame record");
+        return BHRT_ERR_UNSUPPORTED;
+    }
     P = PassInfo();
     P.W = W; P.H = Hh; P.tile = tile; P.tiles_x = (W + tile - 1) / tile; P.tiles_y = (Hh + tile - 1) / tile;
     P.rank = o.rank; P.world = world; P.spp = o.spp; P.seed = o.seed; P.jitter = o.jitter; P.gamma = o.gamma;
@@ -2416,8 +2501,14 @@ static decltype(&k_shadow_mesh<1>) AnyHitMeshKernel(int path_mode, bool ls)
     return k_shadow_mesh<0>;
 }
 // fused: the camera step of a scene without meshes, k_shade traces its rays itself (shade_block's kFused).
-static decltype(&k_shade<true, true>) ShadeKernel(bool fused, bool cam_step, bool tex, bool le)
+// fm: face materials are on (DeviceState::fm); such a scene has a mesh, so its camera step is never the fused one.
+static decltype(&k_shade<true, true>) ShadeKernel(bool fused, bool cam_step, bool tex, bool le, bool fm)
 {
+    if (fm && !fused) {
+        if (le && tex) return cam_step ? k_shade<true, true, false, true, true> : k_shade<false, true, false, true, true>;
+        if (cam_step) return tex ? k_shade<true, true, false, false, true> : k_shade<true, false, false, false, true>;
+        return tex ? k_shade<false, true, false, false, true> : k_shade<false, false, false, false, true>;
+    }
     if (le && tex) { // the frames keep a textured Le (DeviceState::le_on)
         if (fused) return k_shade<true, true, true, true>;
         return cam_step ? k_shade<true, true, false, true> : k_shade<false, true, false, true>;
@@ -2683,7 +2774,7 @@ struct WavePass {
         const int par = (int)(pass_steps & 1u);
         if (sh_wait_n) { HIP_CHECK(hipEventRecord(D->ev_shade, D->stream)); BHRT_TRY(LaunchQueuedAnyHit(D->ev_shade)); }
         if (sh_overlap && sh_pending[par]) { HIP_CHECK(hipStreamWaitEvent(D->stream, D->ev_shadow[par], 0)); sh_pending[par] = false; } // the any-hit kernels of two steps ago still read this queue
-        hipLaunchKernelGGL(ShadeKernel(fused, CamStep(), tex, V.F.le != nullptr), sg, sb, 0, D->stream, D->S, R, P, V.Q[cur], V.HB, n_cur + n_extra, V.Q[cur ^ 1], (sh_overlap && par) ? V.SQ2 : V.SQ, V.F, D->d_samples, root_of, D->d_cnt, V.RO, D->d_pub, seq); // + n_next, n_shadow, n_frames, overflow to the host
+        hipLaunchKernelGGL(ShadeKernel(fused, CamStep(), tex, V.F.le != nullptr, V.F.fm.tab != nullptr), sg, sb, 0, D->stream, D->S, R, P, V.Q[cur], V.HB, n_cur + n_extra, V.Q[cur ^ 1], (sh_overlap && par) ? V.SQ2 : V.SQ, V.F, D->d_samples, root_of, D->d_cnt, V.RO, D->d_pub, seq); // + n_next, n_shadow, n_frames, overflow to the host
         t.Stop();
         if (sh_overlap) HIP_CHECK(hipEventRecord(D->ev_shade, D->stream));
         return BHRT_OK;
@@ -3164,6 +3255,7 @@ try {
     }
     S.cam = H->camera; S.background = H->background; S.environment = H->environment;
     BHRT_TRY(RefreshEmission(scene));
+    BHRT_TRY(RefreshFaceMaterials(scene));
     S.tapx[0] = S.tapy[0] = 0;
     for (int i = 1; i < 32; i++) { // scene.h:322-329 with the deterministic sin/cos (host and device agree bit for bit)
         auto halton = [](int index, int base) { float r = 0, f = 1.0f / (float)base; for (int k = index; k > 0; k /= base) { r += f * (k % base); f /= (float)base; } return r; };
@@ -3483,6 +3575,35 @@ try {
     return BHRT_OK;
 } catch (...) { return bhrt::AbiException(); }
 
+// ---- face materials: scene state beside the blob.  The setter is in this translation unit because it refreshes an uploaded scene.
+int bhrt_scene_set_face_materials(bhrt_scene *scene, int on)
+try {
+    if (!scene) { SetError("bhrt_scene_set_face_materials: null scene"); return BHRT_ERR_ARG; }
+    scene->flat.face_materials = on ? 1 : 0;
+    return RefreshFaceMaterials(scene);
+} catch (...) { return bhrt::AbiException(); }
+
+int bhrt_scene_submaterial_count(const bhrt_scene *scene, int32_t material, int32_t *n)
+try {
+    if (!scene || !n) { SetError("bhrt_scene_submaterial_count: null argument"); return BHRT_ERR_ARG; }
+    const std::vector<int32_t> &first = scene->flat.sub_first;
+    if (material < 0 || (size_t)material + 1 >= first.size()) { SetError("bhrt_scene_submaterial_count: material index out of range"); return BHRT_ERR_ARG; }
+    *n = first[(size_t)material + 1] - first[(size_t)material];
+    return BHRT_OK;
+} catch (...) { return bhrt::AbiException(); }
+
+int bhrt_scene_get_submaterial(const bhrt_scene *scene, int32_t material, int32_t sub, struct bhrt_material *out, uint32_t *face_end)
+try {
+    if (!scene) { SetError("bhrt_scene_get_submaterial: null scene"); return BHRT_ERR_ARG; }
+    const std::vector<int32_t> &first = scene->flat.sub_first;
+    if (material < 0 || (size_t)material + 1 >= first.size()) { SetError("bhrt_scene_get_submaterial: material index out of range"); return BHRT_ERR_ARG; }
+    if (sub < 0 || sub >= first[(size_t)material + 1] - first[(size_t)material]) { SetError("bhrt_scene_get_submaterial: sub-material index out of range"); return BHRT_ERR_ARG; }
+    const size_t k = (size_t)(first[(size_t)material] + sub);
+    if (out) *out = scene->flat.sub_materials[k];
+    if (face_end) *face_end = scene->flat.sub_face_end[k];
+    return BHRT_OK;
+} catch (...) { return bhrt::AbiException(); }
+
 // ---- images beside the colour image ---------------------------------------------------------------
 int bhrt_first_hit_dev(bhrt_scene *scene, float *d_z, float *d_normal, float *d_albedo, void *stream)
 try {
@@ -3493,7 +3614,7 @@ try {
     const int W = H->camera.width, Hh = H->camera.height;
     if (!d_z && !d_normal && !d_albedo) return BHRT_OK;
     hipStream_t st = stream ? (hipStream_t)stream : D->stream;
-    hipLaunchKernelGGL(k_first_hit, dim3(((uint32_t)(W * Hh) + kBlock - 1) / kBlock), dim3(kBlock), 0, st, D->S, W, Hh, d_z, d_normal, d_albedo);
+    hipLaunchKernelGGL(D->fm.tab ? k_first_hit<true> : k_first_hit<false>, dim3(((uint32_t)(W * Hh) + kBlock - 1) / kBlock), dim3(kBlock), 0, st, D->S, D->fm, W, Hh, d_z, d_normal, d_albedo);
     HIP_CHECK(hipGetLastError());
     if (!stream) HIP_CHECK(hipStreamSynchronize(st));
     return BHRT_OK;
@@ -3571,7 +3692,7 @@ try {
         if (guides) { // the first hit of bhrt_first_hit_dev, into the scratch behind the planes, for the guides not given
             float *g = (float *)(D->d_dn.p + DenoisePlaneBytes(W, Hh));
             float *gz = d_z ? nullptr : g, *gn = d_normal ? nullptr : g + n, *ga = d_albedo ? nullptr : g + 4 * n;
-            hipLaunchKernelGGL(k_first_hit, dim3(((uint32_t)n + kBlock - 1) / kBlock), dim3(kBlock), 0, st, D->S, W, Hh, gz, gn, ga);
+            hipLaunchKernelGGL(D->fm.tab ? k_first_hit<true> : k_first_hit<false>, dim3(((uint32_t)n + kBlock - 1) / kBlock), dim3(kBlock), 0, st, D->S, D->fm, W, Hh, gz, gn, ga);
             if (gz) J.z = gz;
             if (gn) J.normal = gn;
             if (ga) J.albedo = ga;

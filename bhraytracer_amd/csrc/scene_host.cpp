@@ -190,6 +190,10 @@ struct MaterialData {
     Col absorption = {0, 0, 0};
     float ior = 1;
     float refraction_glossiness = 0;
+    // a MultiMtl's sub-materials and the cumulative face counts of their groups (HostMesh::mcfc); subs[0] holds what this record itself holds.
+    // Kept beside the blob (FlatScene::sub_materials)
+    std::vector<MaterialData> subs;
+    std::vector<int> face_end;
     MaterialData() // materials.h:23-25
     {
         diffuse.color = {0.5f, 0.5f, 0.5f};
@@ -385,35 +389,39 @@ struct Loader {
     }
 
     // MultiMtl built from a mesh's .mtl (xmlload.cpp:219-250).  Shade() dispatches on hInfo.mtlID,
-    // which triangle hits never set -> sub-material 0 is the only one ever shaded.
+    // which triangle hits never set -> sub-material 0 is the only one the reference ever shades, and the blob's record.
+    // The others are converted by the same rules and kept beside the blob for the face-material switch.
     void AppendMultiMtl(const std::string &name, const HostMesh &mesh)
     {
         MaterialData m;
         m.name = name;
         if (mesh.mtls.empty()) { m.kind = BHRT_MTL_WHITE; materials.push_back(m); return; }
-        const HostMesh::Mtl &s = mesh.mtls[0];
-        m.diffuse.color = {s.Kd[0], s.Kd[1], s.Kd[2]};
-        m.specular.color = {s.Ks[0], s.Ks[1], s.Ks[2]};
-        m.glossiness = s.Ns;
-        m.ior = s.Ni;
-        // every mesh material's textures are loaded by the reference (side effect: texture list); sub-material 0's are used
+        // every mesh material's textures are loaded by the reference (side effect: texture list), in this order
+        std::vector<MaterialData> subs(mesh.mtls.size());
         for (size_t i = 0; i < mesh.mtls.size(); i++) {
-            const HostMesh::Mtl &mi = mesh.mtls[i];
+            const HostMesh::Mtl &s = mesh.mtls[i];
+            MaterialData &d = subs[i];
+            d.name = name;
+            d.diffuse.color = {s.Kd[0], s.Kd[1], s.Kd[2]};
+            d.specular.color = {s.Ks[0], s.Ks[1], s.Ks[2]};
+            d.glossiness = s.Ns;
+            d.ior = s.Ni;
             int mapKd = -1, mapKs = -1;
-            if (!mi.map_Kd.empty()) { TexMapData t; t.texture = ReadTextureFile(mi.map_Kd.c_str()); texmaps.push_back(t); mapKd = (int)texmaps.size() - 1; }
-            if (!mi.map_Ks.empty()) { TexMapData t; t.texture = ReadTextureFile(mi.map_Ks.c_str()); texmaps.push_back(t); mapKs = (int)texmaps.size() - 1; }
-            if (i == 0) {
-                if (mapKd >= 0) m.diffuse.map = mapKd;
-                if (mapKs >= 0) m.diffuse.map = mapKs; // xmlload.cpp:230 sets the DIFFUSE texture from map_Ks (sic)
+            if (!s.map_Kd.empty()) { TexMapData t; t.texture = ReadTextureFile(s.map_Kd.c_str()); texmaps.push_back(t); mapKd = (int)texmaps.size() - 1; }
+            if (!s.map_Ks.empty()) { TexMapData t; t.texture = ReadTextureFile(s.map_Ks.c_str()); texmaps.push_back(t); mapKs = (int)texmaps.size() - 1; }
+            if (mapKd >= 0) d.diffuse.map = mapKd;
+            if (mapKs >= 0) d.diffuse.map = mapKs; // xmlload.cpp:230 sets the DIFFUSE texture from map_Ks (sic)
+            if (s.illum > 2 && s.illum <= 7) {
+                float gloss = acosf(powf(2, 1 / s.Ns));
+                if (s.illum >= 6) {
+                    d.refraction.color = {1 - s.Tf[0], 1 - s.Tf[1], 1 - s.Tf[2]};
+                    d.refraction_glossiness = gloss;
+                }
             }
         }
-        if (s.illum > 2 && s.illum <= 7) {
-            float gloss = acosf(powf(2, 1 / s.Ns));
-            if (s.illum >= 6) {
-                m.refraction.color = {1 - s.Tf[0], 1 - s.Tf[1], 1 - s.Tf[2]};
-                m.refraction_glossiness = gloss;
-            }
-        }
+        m = subs[0];
+        m.subs = std::move(subs);
+        m.face_end = mesh.mcfc;
         materials.push_back(m);
     }
 
@@ -1260,16 +1268,29 @@ int LoadSceneXml(const char *path, FlatScene &out, std::string &err, int bvh_dev
     H.n_texmaps = (uint32_t)texmaps.size();
     H.off_texmaps = W.Append(texmaps.data(), texmaps.size() * sizeof(bhrt_texmap));
 
-    std::vector<bhrt_material> mats(L.materials.size());
-    for (size_t i = 0; i < L.materials.size(); i++) {
-        bhrt_material &o = mats[i];
+    auto storeMaterial = [](bhrt_material &o, const MaterialData &m) {
         memset(&o, 0, sizeof o);
-        const MaterialData &m = L.materials[i];
         o.kind = m.kind;
         StoreTexColor(o.diffuse, m.diffuse); StoreTexColor(o.specular, m.specular); StoreTexColor(o.refraction, m.refraction);
         o.glossiness = m.glossiness;
         o.absorption[0] = m.absorption.r; o.absorption[1] = m.absorption.g; o.absorption[2] = m.absorption.b;
         o.ior = m.ior; o.refraction_glossiness = m.refraction_glossiness;
+    };
+    std::vector<bhrt_material> mats(L.materials.size());
+    out.sub_first.assign(L.materials.size() + 1, 0);
+    out.sub_materials.clear();
+    out.sub_face_end.clear();
+    out.face_materials = 0;
+    for (size_t i = 0; i < L.materials.size(); i++) {
+        const MaterialData &m = L.materials[i];
+        storeMaterial(mats[i], m);
+        for (size_t k = 0; k < m.subs.size(); k++) { // the sub-materials of a MultiMtl, beside the blob (FlatScene::sub_materials)
+            bhrt_material sm;
+            storeMaterial(sm, m.subs[k]);
+            out.sub_materials.push_back(sm);
+            out.sub_face_end.push_back((uint32_t)std::max(m.face_end[k], 0));
+        }
+        out.sub_first[i + 1] = (int32_t)out.sub_materials.size();
     }
     H.n_materials = (uint32_t)mats.size();
     out.emission.resize(L.materials.size());

@@ -18,6 +18,14 @@ struct FlatScene {
     std::vector<bhrt_texcolor> emission;      // [n_materials]
     std::vector<std::string> material_names;  // [n_materials]
     int emissive = 0;
+    // Face materials, beside the blob too: the sub-materials of every MultiMtl (one per `newmtl` of the mesh's .mtl, converted as
+    // the blob's record is from the first; xmlload.cpp:219-250) and the cumulative face counts that group the mesh's faces by them
+    // (cyTriMesh.h:461-487).  Material m owns entries [sub_first[m], sub_first[m + 1]) of the two arrays; none for a Blinn material or an empty
+    // MultiMtl.  Entry sub_first[m] repeats the blob's record of m byte for byte.  face_materials: the switch (bhrt_scene_set_face_materials).
+    std::vector<int32_t> sub_first;           // [n_materials + 1]
+    std::vector<bhrt_material> sub_materials; // [sub_first[n_materials]]
+    std::vector<uint32_t> sub_face_end;       // likewise: faces [sub_face_end[i - 1], sub_face_end[i]) of the mesh shade with sub-material i
+    int face_materials = 0;
     const bhrt_flat_header *hdr() const { return reinterpret_cast<const bhrt_flat_header *>(blob.data()); }
 };
 

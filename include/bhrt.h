@@ -162,6 +162,25 @@ int bhrt_scene_set_emissive(bhrt_scene *scene, int on);
 int bhrt_scene_material_index(const bhrt_scene *scene, const char *name, int32_t *index);
 int bhrt_scene_set_material_emission(bhrt_scene *scene, int32_t material, const float rgb[3]);
 int bhrt_scene_get_material_emission(const bhrt_scene *scene, int32_t material, float rgb[3], int32_t *texmap);
+/* Face materials.  An OBJ's .mtl becomes a MultiMtl with one Blinn sub-material per `newmtl` (xmlload.cpp:219-250) and the mesh
+ * keeps its faces grouped by them (cyTriMesh.h:461-487), but the reference's triangle hits never set the material id, so a render shades the whole
+ * mesh with sub-material 0 — and so does a scene here until it is switched on.  With the switch on, every Shade() frame opened on a hit of a node
+ * whose material is a MultiMtl uses the sub-material of the face that was hit: the first i with face < face_end[i]
+ * (TriMesh::GetMaterialIndex), and sub-material 0 where there is none (faces in front of any usemtl, a hit that is no triangle, a face id beyond
+ * the material's own mesh).  Everything behind the choice follows it at every bounce: Fresnel, the refraction chain and its absorption, the GI
+ * lobe, the caustic gather, textures; bhrt_first_hit's albedo too.  Photon emission does not (MultiMtl has no photon bounce).  The state lives
+ * beside the flat blob: bhrt_scene_flat's bytes do not change, bhrt_info.n_materials and the material indices stay the blob's, bhrt_scene_clone
+ * carries it, and bhrt_opts has no field for it.  None of these calls needs a device; on an uploaded scene the setter refreshes the device's copy.
+ * Materials plus sub-materials beyond 4095 with the switch on: the renders return BHRT_ERR_UNSUPPORTED.
+ *   set_face_materials   on != 0: all later bhrt_render*, _samples, _var*, _adaptive*, bhrt_first_hit* and the denoiser's guides; default 0
+ *   submaterial_count    the number of sub-materials of that material, 0 for one that is not a MultiMtl (or an empty one); index out of range:
+ *                        BHRT_ERR_ARG
+ *   get_submaterial      sub-material `sub` as the blob's materials are laid out (bhrt_flat.h; sub-material 0 is the blob's own record, byte for
+ *                        byte) and the end of its face range; out / face_end may be NULL; material or sub out of range: BHRT_ERR_ARG */
+struct bhrt_material;
+int bhrt_scene_set_face_materials(bhrt_scene *scene, int on);
+int bhrt_scene_submaterial_count(const bhrt_scene *scene, int32_t material, int32_t *n);
+int bhrt_scene_get_submaterial(const bhrt_scene *scene, int32_t material, int32_t sub, struct bhrt_material *out, uint32_t *face_end);
 
 /* ---- device residency ---------------------------------------------------------------------------- */
 int bhrt_scene_upload(bhrt_scene *scene, int device); /* copies the flat scene into HBM of `device`; idempotent */
