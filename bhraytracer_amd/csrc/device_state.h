@@ -86,6 +86,37 @@ struct DeviceQueues {
     }
 };
 
+// Scratch of the photon gather (GatherPass), kept from call to call.
+struct GatherWorkspace {
+    uint32_t cap = 0;             // queries the next six have room for, and what d_sort_temp is sized for (Reserve)
+    DevBuf<uint32_t> d_heavy, d_long; // queries that met 1000 photons in the lane pass; queries whose walk outlasted its lane budget
+    DevBuf<uint32_t> d_cell_of, d_gorder, d_rank_of, d_keys_out; // gather order (cell sort)
+    DevBuf<uint8_t> d_sort_temp; size_t sort_temp_bytes = 0;
+    DevBuf<uint32_t> d_cells, d_tile_sums; // the counting sort: a count per cell and one entry more, and its scan's tile sums
+    DevBuf<uint32_t> d_sel;       // candidate scratch of the selection pass's waves (grown by the pass)
+    DevBuf<unsigned long long> d_scr; uint32_t scr_lanes = 0; // candidate heaps of the exact replay: BHRT_HEAP_COLUMN x scr_lanes, element-major (grown by the replay)
+    DevBuf<GatherCounters> d_cnt;    // what the kernels count, one group per pass
+    PinnedBuf<GatherCounters> h_cnt; // its host copy: a pass reads back the group it cleared
+    // Room for a gather of cnt queries.  A failed regrow leaves cap 0, so the next call tries again.
+    int Reserve(uint32_t cnt, hipStream_t stream)
+    {
+        if (cap < cnt) {
+            cap = 0;
+            DevBuf<uint32_t> *const lists[] = {&d_heavy, &d_long, &d_cell_of, &d_gorder, &d_rank_of, &d_keys_out};
+            for (DevBuf<uint32_t> *buf : lists) buf->Free();
+            d_sort_temp.Free();
+            for (DevBuf<uint32_t> *buf : lists) BHRT_TRY(buf->Reserve(cnt));
+            if (GatherSortPairs(nullptr, nullptr, nullptr, nullptr, cnt, nullptr, &sort_temp_bytes, 28, stream) != 0) { SetError("gather sort: temp size"); return BHRT_ERR_HIP; }
+            BHRT_TRY(d_sort_temp.Reserve(std::max<size_t>(sort_temp_bytes, 16)));
+            cap = cnt;
+        }
+        BHRT_TRY(d_cnt.Reserve(1));
+        BHRT_TRY(d_cells.Reserve((size_t)BHRT_GATHER_CELLS + 1));
+        BHRT_TRY(d_tile_sums.Reserve((size_t)(BHRT_GATHER_CELLS / kScanTile + kScanBlock)));
+        return h_cnt ? BHRT_OK : h_cnt.Alloc(1);
+    }
+};
+
 struct DeviceState : DeviceQueues {
     int device = -1;
     uint32_t n_cus = 256; // compute units of the device (hipDeviceProp_t::multiProcessorCount): sizes the grids of the resident-wave kernels
@@ -135,30 +166,17 @@ struct DeviceState : DeviceQueues {
     HostCounters *d_pub = nullptr; // the device's address of h_pub
     uint32_t pub_seq = 0;
     int timers = 0;                // bhrt_opts.timers of the running call
-    int photon_exact = 0;          // bhrt_opts.photon_exact of the running call
-    uint32_t *d_knn = nullptr;     // test hook of bhrt_photon_gather_host_ex (which owns the memory): the selection pass's photon lists
-    DevBuf<uint32_t> d_sel;        // candidate scratch of the selection pass's waves
     struct PendingTimer { int e0, e1; double *acc; };
     std::vector<PendingTimer> ev_pending;
     std::vector<int> ev_free;                  // indices of ev_pool not in use
-    // caustic photon map (balanced, heap order, slot 0 unused) + gather scratch
+    // caustic photon map (balanced, heap order, slot 0 unused)
     DevBuf<DPhoton> d_photons;
     uint32_t n_photons = 0;
     std::vector<HostPhoton> h_photons; // balanced copy for bhrt_photon_export
     DevBuf<float> d_ph_frames;         // 15 * cap_frames floats (p, N, V, kd, ks per frame), only with photon_map
     DevBuf<float4> d_ph_hot, d_ph_cold, d_ph_dbox; // decoded copy the gather walks (PhotonMapDev)
     PhotonMapDev pm;
-    DevBuf<unsigned long long> d_scr; // candidate heaps of the heavy queries: (K+1) x scr_lanes, element-major
-    uint32_t scr_lanes = 0;
-    uint32_t heavy_cap = 0;       // entries of each of the next six, and what d_sort_temp is sized for
-    DevBuf<uint32_t> d_heavy;     // queries that met 1000 photons in pass 1
-    DevBuf<uint32_t> d_long;      // queries whose walk outlasted the lane budget in pass 1
-    DevBuf<uint32_t> d_cell_of, d_gorder, d_rank_of, d_keys_out; // gather order (cell sort)
-    DevBuf<uint8_t> d_sort_temp;
-    size_t sort_temp_bytes = 0;
-    DevBuf<uint32_t> d_n_heavy;   // [0] heavy, [1] long, [2..3] nodes visited (64-bit), [4] selection rounds, [5] compactions, [8..11] lane pass: found, answered
-    PinnedBuf<uint32_t> h_n_heavy;
-    DevBuf<uint32_t> d_cells, d_tile_sums;
+    GatherWorkspace gw;
     // Development switches, read from the environment ONCE, when the scene is uploaded (none changes a result), and the two test knobs, which
     // no environment variable reaches: only bhrt_scene_knob sets them.
     struct Knobs {

@@ -1,5 +1,5 @@
 // gather_sort.hip — the cell sort of the photon gather's queries as a library radix sort (round 3).
-// The gather walks its queries in Morton-cell order (kernels.hip::RunGather).  Until round 3 that order came from a counting sort over the 2^27
+// The gather walks its queries in Morton-cell order (kernels.hip::GatherPass::OrderByCell).  Until round 3 that order came from a counting sort over the 2^27
 // cells: one atomic per incoherent query into a 512 MB table, twice (41.8 ms per C5 frame), then once (33 ms).  A stable LSD radix sort of
 // (cell, query) pairs streams instead — 16.4 ms for the 5.8e8 pairs of a C5 frame on MI355X (rocPRIM behind hipCUB: a plain library sort is what
 // the guide asks for where nothing has to be fused) — and leaves the queries of a cell in index order.  Own translation unit: the header costs 10 s

@@ -1810,6 +1810,14 @@ __global__ void __launch_bounds__(kScanBlock) k_scan_add(uint32_t *data, uint32_
     const uint32_t base = blockIdx.x * kScanTile + threadIdx.x * kScanPerThread;
     for (uint32_t k = 0; k < kScanPerThread; k++) if (base + k < n) data[base + k] += add;
 }
+// The three launches: data[0, n) in place; tile_sums has room for a word per tile of kScanTile entries
+static void LaunchExclusiveScan(hipStream_t stream, uint32_t *data, uint32_t n, uint32_t *tile_sums)
+{
+    const uint32_t n_tiles = (n + kScanTile - 1) / kScanTile;
+    hipLaunchKernelGGL(k_scan_tiles, dim3(n_tiles), dim3(kScanBlock), 0, stream, data, n, tile_sums);
+    hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(kScanBlock), 0, stream, tile_sums, n_tiles);
+    hipLaunchKernelGGL(k_scan_add, dim3(n_tiles), dim3(kScanBlock), 0, stream, data, n, tile_sums);
+}
 } // namespace bhrt
 #include "device_photon_build.h"
 namespace bhrt {
@@ -1819,6 +1827,17 @@ __global__ void __launch_bounds__(kBlock) k_gather_cell_scatter(uint32_t q0, uin
     const uint32_t c = i < cnt ? cell_of[i] : BHRT_GATHER_NO_CELL;
     if (c != BHRT_GATHER_NO_CELL) order[cell_start[c] + rank_of[i]] = q0 + i;
 }
+// What the gather's kernels count for the host (GatherWorkspace::d_cnt, h_cnt).  One group per pass: a pass clears its own group with one memset and
+// the host reads that group back; no word means one thing to one pass and another to the next.
+struct GatherCounters {
+    // k_photon_gather_fast: kd-tree nodes examined; knob "gather_stats": photons the answers given here were made of, and those answers; entries of the two lists
+    struct Lane { unsigned long long visited, found, answered; uint32_t n_heavy, n_long; } lane;
+    // k_photon_gather_select: nodes; entries of the undecided list; the next query a wave takes; rounds and compactions of all waves (BHRT_DEBUG_GATHER)
+    struct Select { unsigned long long visited; uint32_t n_undecided, cursor, rounds, compactions; } select;
+    struct Replay { unsigned long long visited; } replay; // k_photon_gather_heap, per list
+    uint32_t n_ordered, pad_; // queries that take part in the cell order (k_gather_first_out; the counting sort's number lands in the host copy only)
+};
+static_assert(std::is_trivial<GatherCounters>::value && sizeof(GatherCounters) == 72 && alignof(GatherCounters) == 8, "plain data, the 64-bit sums on 8 bytes");
 // The same order from a radix sort of (cell, query) pairs (gather_sort.hip): the key of a query that takes no part is one bit above every cell, so
 // those sort to the end; the number that do take part = the position of the first such key (k_gather_first_out: one lane, a binary search).
 #define BHRT_GATHER_KEY_OUT BHRT_GATHER_CELLS
@@ -1837,11 +1856,11 @@ __global__ void __launch_bounds__(kBlock) k_gather_cell_key(Sink sink, uint32_t 
     keys[i] = c;
     vals[i] = q;
 }
-__global__ void k_gather_first_out(const uint32_t *sorted_keys, uint32_t cnt, uint32_t *out)
+__global__ void k_gather_first_out(const uint32_t *sorted_keys, uint32_t cnt, GatherCounters *counts)
 {
     uint32_t lo = 0, hi = cnt; // first index whose key is >= BHRT_GATHER_KEY_OUT
     while (lo < hi) { const uint32_t mid = lo + (hi - lo) / 2; if (sorted_keys[mid] < BHRT_GATHER_KEY_OUT) lo = mid + 1; else hi = mid; }
-    *out = lo;
+    counts->n_ordered = lo;
 }
 int GatherSortPairs(const uint32_t *keys_in, uint32_t *keys_out, const uint32_t *vals_in, uint32_t *vals_out, uint32_t n, void *temp, size_t *temp_bytes, int end_bit,
                     hipStream_t stream); // gather_sort.hip
@@ -1864,14 +1883,14 @@ __device__ inline void wave_append(bool flag, uint32_t value, uint32_t *list, ui
     if (flag) list[base + (uint32_t)__popcll(m & ((1ull << __lane_id()) - 1ull))] = value;
 }
 // kd-tree nodes examined by the gather (bhrt_stats.photon_nodes_visited): one 64-bit atomic per wave
-__device__ inline void count_visited(uint32_t visited, uint32_t *counts)
+__device__ inline void count_visited(uint32_t visited, unsigned long long *pass_visited /* the running pass's GatherCounters::*::visited */)
 {
     for (int off = 32; off > 0; off >>= 1) visited += __shfl_xor(visited, off);
-    if (__lane_id() == 0 && visited) atomicAdd((unsigned long long *)(counts + 2), (unsigned long long)visited);
+    if (__lane_id() == 0 && visited) atomicAdd(pass_visited, (unsigned long long)visited);
 }
 template <class Sink, bool kFound = false> // kFound: the statistics instantiation (knob "gather_stats")
 __global__ void __launch_bounds__(kBlock) k_photon_gather_fast(Sink sink, uint32_t q0, uint32_t cnt, const uint32_t *order, PhotonMapDev M, float radius,
-                                                               int lane_budget, uint32_t *heavy, uint32_t *longq, uint32_t *counts /* [0] heavy, [1] long, [2..3] visited, [8..9] found, [10..11] answered */)
+                                                               int lane_budget, uint32_t *heavy, uint32_t *longq, GatherCounters *counts /* lane */)
 {
     uint32_t slice;
     xcd_slice(blockIdx.x, gridDim.x, slice); // cell-sorted order: one contiguous eighth of it per XCD
@@ -1886,19 +1905,19 @@ __global__ void __launch_bounds__(kBlock) k_photon_gather_fast(Sink sink, uint32
             if (r < 2) sink.done(q, r == 1, irr, d);
         }
     }
-    wave_append(r == 2, q, heavy, &counts[0]);
-    wave_append(r == 3, q, longq, &counts[1]);
-    count_visited(visited, counts);
+    wave_append(r == 2, q, heavy, &counts->lane.n_heavy);
+    wave_append(r == 3, q, longq, &counts->lane.n_long);
+    count_visited(visited, &counts->lane.visited);
     if (kFound) { // photons the queries answered HERE were made of (the floor of the nodes a walk has to examine), and how many queries those were
         uint32_t f = r < 2 ? (uint32_t)found : 0u, nq = (i < cnt && r < 2) ? 1u : 0u;
         for (int off = 32; off > 0; off >>= 1) { f += __shfl_xor(f, off); nq += __shfl_xor(nq, off); }
-        if (__lane_id() == 0 && nq) { atomicAdd((unsigned long long *)(counts + 8), (unsigned long long)f); atomicAdd((unsigned long long *)(counts + 10), (unsigned long long)nq); }
+        if (__lane_id() == 0 && nq) { atomicAdd(&counts->lane.found, (unsigned long long)f); atomicAdd(&counts->lane.answered, (unsigned long long)nq); }
     }
 }
 // Exact replay: the queries of heavy[h0, h0+cnt) with the full candidate heap, one scratch column per lane.
 template <class Sink>
 __global__ void __launch_bounds__(kBlock) k_photon_gather_heap(Sink sink, const uint32_t *heavy, uint32_t h0, uint32_t cnt, PhotonMapDev M, float radius,
-                                                               unsigned long long *scr, size_t stride, uint32_t *counts)
+                                                               unsigned long long *scr, size_t stride, GatherCounters *counts /* replay */)
 {
     const uint32_t lane = blockIdx.x * blockDim.x + threadIdx.x;
     uint32_t visited = 0;
@@ -1908,7 +1927,7 @@ __global__ void __launch_bounds__(kBlock) k_photon_gather_heap(Sink sink, const 
         const bool found = photon_estimate_heap(M, sink.pos(q), sink.nrm(q), radius, scr + (size_t)lane * BHRT_HEAP_COLUMN, 1, irr, d, visited);
         sink.done(q, found, irr, d);
     }
-    count_visited(visited, counts);
+    count_visited(visited, &counts->replay.visited);
 }
 
 // Pass 2: one wave per query (photon_estimate_select) for what the lane pass set aside — the heavy queries (>= 1000 photons in the
@@ -1918,7 +1937,7 @@ __global__ void __launch_bounds__(kBlock) k_photon_gather_heap(Sink sink, const 
 template <class Sink>
 __global__ void __launch_bounds__(64, BHRT_SEL_WAVES_PER_CU / 4) k_photon_gather_select(Sink sink, const uint32_t *heavy, uint32_t n_heavy, const uint32_t *longq, uint32_t n_long,
                                                              PhotonMapDev M, float radius, uint32_t *undecided,
-                                                             uint32_t *counts /* [0] undecided, [1] cursor, [2..3] visited */, uint32_t *knn, uint32_t *scratch, int exact_only)
+                                                             GatherCounters *counts /* select */, uint32_t *knn, uint32_t *scratch, int exact_only)
 {
     __shared__ SelectLds lds;
     __shared__ uint32_t s_next;
@@ -1927,7 +1946,7 @@ __global__ void __launch_bounds__(64, BHRT_SEL_WAVES_PER_CU / 4) k_photon_gather
     C.d2 = scratch + (size_t)blockIdx.x * BHRT_SEL_SCRATCH_WORDS; C.idx = C.d2 + BHRT_SEL_CAP; C.sides = C.idx + BHRT_SEL_CAP;
     C.sp_node = C.sides + BHRT_SEL_CAP; C.sp_sides = C.sp_node + BHRT_SEL_SPILL; C.sp_plane = (float *)(C.sp_sides + BHRT_SEL_SPILL);
     while (true) {
-        if (threadIdx.x == 0) s_next = atomicAdd(&counts[1], 1u);
+        if (threadIdx.x == 0) s_next = atomicAdd(&counts->select.cursor, 1u);
         __syncthreads();
         const uint32_t i = s_next;
         __syncthreads();
@@ -1937,13 +1956,13 @@ __global__ void __launch_bounds__(64, BHRT_SEL_WAVES_PER_CU / 4) k_photon_gather
         const int r = photon_estimate_select(M, lds, C, sink.pos(q), sink.nrm(q), radius, irr, d, visited, knn ? knn + (size_t)q * (BHRT_PHOTON_K + 2) : nullptr, dbg,
                                              exact_only != 0);
         if (threadIdx.x == 0) {
-            if (r == 4) undecided[atomicAdd(&counts[0], 1u)] = q;
+            if (r == 4) undecided[atomicAdd(&counts->select.n_undecided, 1u)] = q;
             else sink.done(q, r == 1, irr, d);
         }
         __syncthreads();
     }
-    if (threadIdx.x == 0) { atomicAdd(&counts[4], dbg[0]); atomicAdd(&counts[5], dbg[1]); }
-    count_visited(visited, counts);
+    if (threadIdx.x == 0) { atomicAdd(&counts->select.rounds, dbg[0]); atomicAdd(&counts->select.compactions, dbg[1]); }
+    count_visited(visited, &counts->select.visited);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2257,135 +2276,138 @@ static void FlushTimers(DeviceState *D, bool final = false)
     D->ev_pending.resize(keep);
 }
 
-// Caustic gather of queries [q0, q0+cnt) of `sink`: pass 1 without candidate lists over all of them, pass 2 with the
-// candidate heap for the few that met 1000 photons (in chunks of the scratch columns).
+// Caustic gather of queries [q0, q0+cnt) of `sink`, built per call; Run() is the list of its stages: the lane pass without candidate lists over all
+// of them, the one-wave selection pass for what that set aside, the exact replay with the candidate heap for the few left over (in chunks of the
+// scratch columns).  What the call depends on is a member; what outlives it is the scratch (DeviceState::gw).
 template <class Sink>
-static int RunGather(DeviceState *D, const Sink &sink, uint32_t q0, uint32_t cnt, float radius, bhrt_stats *st)
-{
-    if (cnt == 0) return BHRT_OK;
-    if (D->heavy_cap < cnt) {
-        D->heavy_cap = 0;
-        DevBuf<uint32_t> *const lists[] = {&D->d_heavy, &D->d_long, &D->d_cell_of, &D->d_gorder, &D->d_rank_of, &D->d_keys_out};
-        for (DevBuf<uint32_t> *buf : lists) buf->Free();
-        D->d_sort_temp.Free();
-        for (DevBuf<uint32_t> *buf : lists) BHRT_TRY(buf->Reserve(cnt));
-        if (GatherSortPairs(nullptr, nullptr, nullptr, nullptr, cnt, nullptr, &D->sort_temp_bytes, 28, D->stream) != 0) { SetError("gather sort: temp size"); return BHRT_ERR_HIP; }
-        BHRT_TRY(D->d_sort_temp.Reserve(std::max<size_t>(D->sort_temp_bytes, 16)));
-        D->heavy_cap = cnt;
+struct GatherPass {
+    DeviceState *const D; const Sink &sink;
+    const uint32_t q0, cnt; const float radius;
+    const int photon_exact; // bhrt_opts.photon_exact of the call
+    uint32_t *const knn;    // test hook of bhrt_photon_gather_host_ex (which owns the memory): the selection pass's photon lists, or null
+    bhrt_stats *const st;   // or null
+    GatherWorkspace &W = D->gw;
+    const int lane_budget = D->knobs.gather_lane_budget > 0 ? D->knobs.gather_lane_budget : BHRT_GATHER_LANE_BUDGET; // test knob: a tiny budget sends every query through the selection pass
+    const uint32_t *order = nullptr; // the lane pass's queries in cell order; null: index order
+    uint32_t n_walk = cnt;           // queries of the lane pass
+    uint32_t n_heavy = 0, n_long = 0, n_undecided = 0; // entries of W.d_heavy, W.d_long and of the undecided list
+    uint32_t *undecided() const { return W.d_cell_of; } // what the selection pass could not decide (d_cell_of is free again after the cell sort)
+
+    int Run()
+    {
+        if (cnt == 0) return BHRT_OK;
+        BHRT_TRY(W.Reserve(cnt, D->stream));
+        BHRT_TRY(OrderByCell());
+        BHRT_TRY(LanePass());
+        BHRT_TRY(ReadLaneCounters());
+        if (n_heavy + n_long == 0) return BHRT_OK;
+        Timer t(D, st ? &st->seconds_photon_heavy : nullptr, 0);
+        BHRT_TRY(SelectPass());
+        BHRT_TRY(ExactReplay(undecided(), n_undecided));
+        if (photon_exact) BHRT_TRY(ExactReplay(W.d_heavy, n_heavy));
+        t.Stop();
+        return BHRT_OK;
     }
-    if (!D->d_n_heavy) {
-        BHRT_TRY(D->d_n_heavy.Reserve(12));
-        BHRT_TRY(D->h_n_heavy.Alloc(12));
-        BHRT_TRY(D->d_cells.Reserve((size_t)BHRT_GATHER_CELLS + 1));
-        BHRT_TRY(D->d_tile_sums.Reserve((size_t)(BHRT_GATHER_CELLS / kScanTile + kScanBlock)));
+    // a pass's own group of the counters: cleared in front of its kernels, read back (and waited for) behind them
+    template <class Group> int Clear(Group GatherCounters::*g) const { HIP_CHECK(hipMemsetAsync(&(W.d_cnt.p->*g), 0, sizeof(Group), D->stream)); return BHRT_OK; }
+    template <class Group> int Fetch(Group GatherCounters::*g) const
+    {
+        HIP_CHECK(hipMemcpyAsync(&(W.h_cnt.p->*g), &(W.d_cnt.p->*g), sizeof(Group), hipMemcpyDeviceToHost, D->stream));
+        HIP_CHECK(hipStreamSynchronize(D->stream));
+        return BHRT_OK;
     }
-    dim3 grid((cnt + kBlock - 1) / kBlock);
-    const dim3 block(kBlock);
-    const uint32_t *order = nullptr;
-    uint32_t n_walk = cnt; // queries of pass 1
-    if (cnt >= (1u << 16)) { // small batches are latency-bound anyway
+    // Morton-cell order of the queries that take part (order, n_walk): a wave's 64 queries then walk the same path
+    int OrderByCell()
+    {
+        if (cnt < (1u << 16)) return BHRT_OK; // small batches are latency-bound anyway
+        const dim3 grid((cnt + kBlock - 1) / kBlock), block(kBlock);
         GatherGrid G;
         for (int k = 0; k < 3; k++) {
             const float lo = D->pm.lo[k] - radius, hi = D->pm.hi[k] + radius;
-            G.lo[k] = lo;
-            G.inv_cell[k] = hi > lo ? (float)(1 << BHRT_GATHER_CELL_BITS) / (hi - lo) : 0.f;
+            G.lo[k] = lo; G.inv_cell[k] = hi > lo ? (float)(1 << BHRT_GATHER_CELL_BITS) / (hi - lo) : 0.f;
         }
         if (D->knobs.gather_counting_sort) { // the counting sort of rounds 1-3 (BHRT_GATHER_COUNTING_SORT=1: A/B and second opinion)
-            const uint32_t n_tiles = BHRT_GATHER_CELLS / kScanTile;
-            HIP_CHECK(hipMemsetAsync(D->d_cells, 0, ((size_t)BHRT_GATHER_CELLS + 1) * sizeof(uint32_t), D->stream));
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_gather_cell_count<Sink>), grid, block, 0, D->stream, sink, q0, cnt, G, D->pm, radius, D->d_cell_of, D->d_rank_of, D->d_cells);
+            HIP_CHECK(hipMemsetAsync(W.d_cells, 0, ((size_t)BHRT_GATHER_CELLS + 1) * sizeof(uint32_t), D->stream));
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_gather_cell_count<Sink>), grid, block, 0, D->stream, sink, q0, cnt, G, D->pm, radius, W.d_cell_of, W.d_rank_of, W.d_cells);
             // exclusive scan over the cells and one more entry, which ends up holding the number of queries that take part
-            hipLaunchKernelGGL(k_scan_tiles, dim3(n_tiles + 1), dim3(kScanBlock), 0, D->stream, D->d_cells, BHRT_GATHER_CELLS + 1, D->d_tile_sums);
-            hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(kScanBlock), 0, D->stream, D->d_tile_sums, n_tiles + 1);
-            hipLaunchKernelGGL(k_scan_add, dim3(n_tiles + 1), dim3(kScanBlock), 0, D->stream, D->d_cells, BHRT_GATHER_CELLS + 1, D->d_tile_sums);
-            hipLaunchKernelGGL(k_gather_cell_scatter, grid, block, 0, D->stream, q0, cnt, D->d_cell_of, D->d_rank_of, D->d_cells, D->d_gorder);
-            HIP_CHECK(hipMemcpyAsync(D->h_n_heavy, D->d_cells + BHRT_GATHER_CELLS, sizeof(uint32_t), hipMemcpyDeviceToHost, D->stream));
+            LaunchExclusiveScan(D->stream, W.d_cells, BHRT_GATHER_CELLS + 1, W.d_tile_sums);
+            hipLaunchKernelGGL(k_gather_cell_scatter, grid, block, 0, D->stream, q0, cnt, W.d_cell_of, W.d_rank_of, W.d_cells, W.d_gorder);
+            HIP_CHECK(hipMemcpyAsync(&W.h_cnt->n_ordered, W.d_cells + BHRT_GATHER_CELLS, sizeof(uint32_t), hipMemcpyDeviceToHost, D->stream));
         } else { // (cell, query) pairs through a stable radix sort: no atomics, the queries of a cell stay in index order
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_gather_cell_key<Sink>), grid, block, 0, D->stream, sink, q0, cnt, G, D->pm, radius, D->d_cell_of, D->d_rank_of);
-            size_t tb = D->sort_temp_bytes;
-            if (GatherSortPairs(D->d_cell_of, D->d_keys_out, D->d_rank_of, D->d_gorder, cnt, D->d_sort_temp, &tb, 28, D->stream) != 0) { SetError("gather sort failed"); return BHRT_ERR_HIP; }
-            hipLaunchKernelGGL(k_gather_first_out, dim3(1), dim3(1), 0, D->stream, D->d_keys_out, cnt, D->d_n_heavy + 7);
-            HIP_CHECK(hipMemcpyAsync(D->h_n_heavy, D->d_n_heavy + 7, sizeof(uint32_t), hipMemcpyDeviceToHost, D->stream));
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_gather_cell_key<Sink>), grid, block, 0, D->stream, sink, q0, cnt, G, D->pm, radius, W.d_cell_of, W.d_rank_of);
+            size_t tb = W.sort_temp_bytes;
+            if (GatherSortPairs(W.d_cell_of, W.d_keys_out, W.d_rank_of, W.d_gorder, cnt, W.d_sort_temp, &tb, 28, D->stream) != 0) { SetError("gather sort failed"); return BHRT_ERR_HIP; }
+            hipLaunchKernelGGL(k_gather_first_out, dim3(1), dim3(1), 0, D->stream, W.d_keys_out, cnt, W.d_cnt);
+            HIP_CHECK(hipMemcpyAsync(&W.h_cnt->n_ordered, &W.d_cnt->n_ordered, sizeof(uint32_t), hipMemcpyDeviceToHost, D->stream));
         }
-        order = D->d_gorder;
+        order = W.d_gorder;
         HIP_CHECK(hipStreamSynchronize(D->stream));
-        n_walk = D->h_n_heavy[0];
-        grid = dim3((n_walk + kBlock - 1) / kBlock);
+        n_walk = W.h_cnt->n_ordered;
+        return BHRT_OK;
     }
-    HIP_CHECK(hipMemsetAsync(D->d_n_heavy, 0, 12 * sizeof(uint32_t), D->stream));
-    int lane_budget = BHRT_GATHER_LANE_BUDGET;
-    if (D->knobs.gather_lane_budget > 0) lane_budget = D->knobs.gather_lane_budget; // test knob: a tiny budget sends every query through pass 2
+    // Every query that takes part, one lane each, without a candidate list; what meets 1000 photons or outlasts the budget goes to W.d_heavy / W.d_long.
     // (Streaming the queries through resident waves, lanes refilled from a cursor as in k_trace_mesh_stream, is SLOWER here — 0.69 -> 0.81-1.01 s per
     // frame for refill thresholds of 60-16 lanes: the 64 queries of a wave come from one cell and walk the tree in step, so their loads hit
     // the same lines; refilled lanes are out of step with their neighbours and every load becomes a gather.  33 of 64 lanes busy is the cheaper evil.)
-    if (n_walk > 0) {
-        if (D->knobs.gather_stats)
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_photon_gather_fast<Sink, true>), grid, block, 0, D->stream, sink, q0, n_walk, order, D->pm, radius, lane_budget, D->d_heavy,
-                               D->d_long, D->d_n_heavy);
-        else
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_photon_gather_fast<Sink>), grid, block, 0, D->stream, sink, q0, n_walk, order, D->pm, radius, lane_budget, D->d_heavy,
-                               D->d_long, D->d_n_heavy);
+    int LanePass()
+    {
+        BHRT_TRY(Clear(&GatherCounters::lane));
+        if (n_walk == 0) return BHRT_OK;
+        const auto kernel = D->knobs.gather_stats ? k_photon_gather_fast<Sink, true> : k_photon_gather_fast<Sink, false>;
+        hipLaunchKernelGGL(kernel, dim3((n_walk + kBlock - 1) / kBlock), dim3(kBlock), 0, D->stream, sink, q0, n_walk, order, D->pm, radius, lane_budget, W.d_heavy.p, W.d_long.p, W.d_cnt.p);
+        return BHRT_OK;
     }
-    HIP_CHECK(hipMemcpyAsync(D->h_n_heavy, D->d_n_heavy, 12 * sizeof(uint32_t), hipMemcpyDeviceToHost, D->stream));
-    HIP_CHECK(hipStreamSynchronize(D->stream));
-    const uint32_t n_heavy = D->h_n_heavy[0], n_long = D->h_n_heavy[1];
-    if (st) {
-        st->photon_found += (uint64_t)D->h_n_heavy[8] | ((uint64_t)D->h_n_heavy[9] << 32); // knob "gather_stats" only
+    int ReadLaneCounters()
+    {
+        BHRT_TRY(Fetch(&GatherCounters::lane));
+        const GatherCounters::Lane &c = W.h_cnt->lane;
+        n_heavy = c.n_heavy; n_long = c.n_long;
+        if (!st) return BHRT_OK;
+        st->photon_found += c.found; // knob "gather_stats" only
+        st->photon_queries += cnt; st->photon_wave_queries += n_long; st->photon_heavy_queries += n_heavy;
         st->photon_lane_queries += (uint64_t)n_walk - n_heavy - n_long;
-        st->photon_lane_nodes += (uint64_t)D->h_n_heavy[2] | ((uint64_t)D->h_n_heavy[3] << 32);
-        st->photon_queries += cnt;
-        st->photon_wave_queries += n_long;
-        st->photon_heavy_queries += n_heavy;
-        st->photon_nodes_visited += (uint64_t)D->h_n_heavy[2] | ((uint64_t)D->h_n_heavy[3] << 32);
+        st->photon_lane_nodes += c.visited; st->photon_nodes_visited += c.visited;
+        return BHRT_OK;
     }
-    if (n_heavy + n_long == 0) return BHRT_OK;
-    Timer t(D, st ? &st->seconds_photon_heavy : nullptr, 0);
-    // pass 2, one wave per query: the long walks always; the heavy queries unless the exact replay is asked for.  Undecided ones go to a list of
-    // their own (d_cell_of is free again after the cell sort)
-    const uint32_t n_sel_heavy = D->photon_exact ? 0u : n_heavy;
-    uint32_t *undecided = D->d_cell_of;
-    uint32_t n_exact = 0;
-    if (n_sel_heavy + n_long) {
-        HIP_CHECK(hipMemsetAsync(D->d_n_heavy, 0, 8 * sizeof(uint32_t), D->stream));
+    // One wave per query: the long walks always; the heavy queries unless the exact replay is asked for.  What it cannot decide goes to undecided()
+    int SelectPass()
+    {
+        const uint32_t n_sel_heavy = photon_exact ? 0u : n_heavy;
+        if (n_sel_heavy + n_long == 0) return BHRT_OK;
+        BHRT_TRY(Clear(&GatherCounters::select));
         const uint32_t sel_waves = D->n_cus * BHRT_SEL_WAVES_PER_CU; // persistent one-wave workgroups, each with its scratch (candidates 24 KB + stack spill 48 KB)
-        BHRT_TRY(D->d_sel.Reserve((size_t)sel_waves * BHRT_SEL_SCRATCH_WORDS));
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_photon_gather_select<Sink>), dim3(std::min<uint32_t>(n_sel_heavy + n_long, sel_waves)), dim3(64), 0, D->stream, sink, D->d_heavy,
-                           n_sel_heavy, D->d_long, n_long, D->pm, radius, undecided, D->d_n_heavy, D->d_knn, D->d_sel, D->photon_exact);
-        HIP_CHECK(hipMemcpyAsync(D->h_n_heavy, D->d_n_heavy, 8 * sizeof(uint32_t), hipMemcpyDeviceToHost, D->stream));
-        HIP_CHECK(hipStreamSynchronize(D->stream));
-        if (st) st->photon_nodes_visited += (uint64_t)D->h_n_heavy[2] | ((uint64_t)D->h_n_heavy[3] << 32);
+        BHRT_TRY(W.d_sel.Reserve((size_t)sel_waves * BHRT_SEL_SCRATCH_WORDS));
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_photon_gather_select<Sink>), dim3(std::min<uint32_t>(n_sel_heavy + n_long, sel_waves)), dim3(64), 0, D->stream, sink, W.d_heavy,
+                           n_sel_heavy, W.d_long, n_long, D->pm, radius, undecided(), W.d_cnt, knn, W.d_sel, photon_exact);
+        BHRT_TRY(Fetch(&GatherCounters::select));
+        const GatherCounters::Select &c = W.h_cnt->select;
+        if (st) st->photon_nodes_visited += c.visited;
         if (D->knobs.debug_gather)
-            fprintf(stderr, "select pass: %u heavy + %u long queries, %llu nodes, %u rounds, %u compactions, %u undecided\n", n_sel_heavy, n_long,
-                    (unsigned long long)((uint64_t)D->h_n_heavy[2] | ((uint64_t)D->h_n_heavy[3] << 32)), D->h_n_heavy[4], D->h_n_heavy[5], D->h_n_heavy[0]);
-        n_exact = D->h_n_heavy[0];
+            fprintf(stderr, "select pass: %u heavy + %u long queries, %llu nodes, %u rounds, %u compactions, %u undecided\n", n_sel_heavy, n_long, c.visited, c.rounds, c.compactions, c.n_undecided);
+        n_undecided = c.n_undecided;
+        return BHRT_OK;
     }
-    // the reference's candidate-heap history replayed, one lane per query: what pass 2 left undecided, and (bhrt_opts.photon_exact) every heavy query
-    for (int part = 0; part < 2; part++) {
-        const uint32_t *list = part == 0 ? undecided : D->d_heavy;
-        const uint32_t m_all = part == 0 ? n_exact : (D->photon_exact ? n_heavy : 0u);
-        if (!m_all) continue;
+    // The reference's candidate-heap history replayed for list[0, m_all), one lane per query: the undecided list and (bhrt_opts.photon_exact) the heavy one
+    int ExactReplay(const uint32_t *list, uint32_t m_all)
+    {
+        if (!m_all) return BHRT_OK;
         const uint32_t heap_lanes = 1u << 20; // as many heaps in flight as possible: the pass is a chain of dependent accesses per query (65 k lanes: 1.8x slower)
-        const int rc = D->d_scr.Reserve((size_t)std::min<uint32_t>(heap_lanes, (m_all + 4095u) & ~4095u) * BHRT_HEAP_COLUMN);
-        D->scr_lanes = (uint32_t)(D->d_scr.n / BHRT_HEAP_COLUMN);
+        const int rc = W.d_scr.Reserve((size_t)std::min<uint32_t>(heap_lanes, (m_all + 4095u) & ~4095u) * BHRT_HEAP_COLUMN);
+        W.scr_lanes = (uint32_t)(W.d_scr.n / BHRT_HEAP_COLUMN);
         if (rc) return rc;
-        HIP_CHECK(hipMemsetAsync(D->d_n_heavy + 2, 0, 2 * sizeof(uint32_t), D->stream));
-        const uint32_t chunk = std::min<uint32_t>(D->scr_lanes, heap_lanes);
+        BHRT_TRY(Clear(&GatherCounters::replay));
+        const uint32_t chunk = std::min<uint32_t>(W.scr_lanes, heap_lanes);
         for (uint32_t h0 = 0; h0 < m_all; h0 += chunk) {
             const uint32_t m = std::min<uint32_t>(chunk, m_all - h0);
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_photon_gather_heap<Sink>), dim3((m + kBlock - 1) / kBlock), dim3(kBlock), 0, D->stream, sink, list, h0, m,
-                               D->pm, radius, D->d_scr, (size_t)D->scr_lanes, D->d_n_heavy);
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_photon_gather_heap<Sink>), dim3((m + kBlock - 1) / kBlock), dim3(kBlock), 0, D->stream, sink, list, h0, m, D->pm, radius, W.d_scr, (size_t)W.scr_lanes, W.d_cnt);
         }
-        if (st) {
-            st->photon_exact_queries += m_all;
-            HIP_CHECK(hipMemcpyAsync(D->h_n_heavy + 2, D->d_n_heavy + 2, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, D->stream));
-            HIP_CHECK(hipStreamSynchronize(D->stream));
-            st->photon_nodes_visited += (uint64_t)D->h_n_heavy[2] | ((uint64_t)D->h_n_heavy[3] << 32);
-        }
+        if (!st) return BHRT_OK;
+        st->photon_exact_queries += m_all;
+        BHRT_TRY(Fetch(&GatherCounters::replay));
+        st->photon_nodes_visited += W.h_cnt->replay.visited;
+        return BHRT_OK;
     }
-    t.Stop();
-    return BHRT_OK;
-}
-
+};
 
 // The frame's constants of every pass (PassInfo without its pixels and samples) and the number of owned pixels of this rank (edge-tile
 // pixels outside the image included); checks the options.
@@ -2737,15 +2759,13 @@ struct WavePass {
         const RayOrder &RO = V.RO;
         const bool cam_step = CamStep();
         const dim3 tg((n_cur + kBlock - 1) / kBlock), tb(kBlock);
-        const uint32_t n_buckets = 1u << BHRT_PARK_KEY_BITS, n_tiles = n_buckets / kScanTile;
+        const uint32_t n_buckets = 1u << BHRT_PARK_KEY_BITS;
         if (!cam_step) HIP_CHECK(hipMemsetAsync(RO.park_bucket, 0, n_buckets * sizeof(uint32_t), D->stream)); // the trace kernel counts the keys as it parks
         hipLaunchKernelGGL(ClosestKernel(true, cam_step, true), tg, tb, 0, D->stream, D->S, P, V.Q[cur], n_cur, 0, V.HB, RO, D->d_cnt, V.slowq);
         hipLaunchKernelGGL(k_mesh_prefix, dim3(1), dim3(64), 0, D->stream, D->d_cnt, RO);
         if (!cam_step) { // counting sort of the parked rays by coherence key (the camera step keeps slot order)
             const dim3 pg(std::min<uint32_t>(tg.x + BHRT_ORDER_SHARDS, 4096u));
-            hipLaunchKernelGGL(k_scan_tiles, dim3(n_tiles), dim3(kScanBlock), 0, D->stream, RO.park_bucket, n_buckets, RO.park_bucket + n_buckets);
-            hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(kScanBlock), 0, D->stream, RO.park_bucket + n_buckets, n_tiles);
-            hipLaunchKernelGGL(k_scan_add, dim3(n_tiles), dim3(kScanBlock), 0, D->stream, RO.park_bucket, n_buckets, RO.park_bucket + n_buckets);
+            LaunchExclusiveScan(D->stream, RO.park_bucket, n_buckets, RO.park_bucket + n_buckets);
             hipLaunchKernelGGL(k_park_scatter, pg, tb, 0, D->stream, RO);
         }
         if (sh_wait_n) { // the last step's any-hit kernels start with this step's mesh walk: they get the SIMDs its finished waves leave
@@ -2901,7 +2921,6 @@ static int RenderPixels(bhrt_scene *scene, const bhrt_opts &o, PassInfo P, const
     D->le_on = D->emission_on && D->emission_textured; // before the passes are sized: DefaultPassSamples counts the term's 12 B per frame
     const PassSizing Z = SizePasses(D, o, n_items, spp, P.world, P.tile);
     D->timers = o.timers;
-    D->photon_exact = o.photon_exact;
     RenderParams R;
     R.internal_bounces = o.internal_bounces; R.gi_bounces = o.gi_bounces; R.photon = o.photon_map;
     auto wall0 = std::chrono::steady_clock::now();
@@ -2947,7 +2966,7 @@ static int RenderPixels(bhrt_scene *scene, const bhrt_opts &o, PassInfo P, const
             // per pass, most with a few hundred frames — spent 2 s per frame waiting for single lanes
             Timer t(D, &st->seconds_photon_gather, 0);
             const GatherToFrames sink = {F, D->S.materials};
-            BHRT_TRY(RunGather(D, sink, 0, n_frames, o.photon_radius > 0.f ? o.photon_radius : 0.5f /* MAX_Area, MtlBlinn.cpp:29 */, st));
+            BHRT_TRY((GatherPass<GatherToFrames>{D, sink, 0, n_frames, o.photon_radius > 0.f ? o.photon_radius : 0.5f /* MAX_Area, MtlBlinn.cpp:29 */, o.photon_exact, nullptr, st}.Run()));
             t.Stop();
         }
         st->shade_calls += D->h_pub->n_frames;
@@ -3893,63 +3912,64 @@ static int PhotonLights(const bhrt_scene *scene, std::vector<int32_t> &pl, float
     for (int32_t i : pl) sum += key(i);
     return BHRT_OK;
 }
-// emissions [e0, e0 + count) (count: a multiple of kBlock): up to `cap` photons per path into tmp, their number into counts
-static void LaunchPhotonEmit(DeviceState *D, bool global_map, uint32_t seed, uint64_t e0, uint32_t count, const int32_t *d_pl, int n_pl, float sum, DPhoton *tmp, uint32_t cap,
-                             uint32_t *counts)
-{
-    if (global_map) hipLaunchKernelGGL(k_photon_emit<true>, dim3(count / kBlock), dim3(kBlock), 0, D->stream, D->S, seed, e0, count, d_pl, n_pl, sum, tmp, cap, counts);
-    else hipLaunchKernelGGL(k_photon_emit<false>, dim3(count / kBlock), dim3(kBlock), 0, D->stream, D->S, seed, e0, count, d_pl, n_pl, sum, tmp, cap, counts);
-}
+// One batch of emissions of either map kind, and its buffers.  Emit(): emissions [e0, e0 + E) (E: a multiple of kBlock) leave up to `cap` photons
+// per path in tmp, their numbers in counts, and in offsets where each path's photons go — the exclusive prefix of the counts, taken on the device —
+// which is what k_photon_compact reads.  Per batch two words reach the host: the largest count of a path and the photons of the batch.
+struct EmitBatch {
+    DevBuf<DPhoton> tmp;
+    DevBuf<uint32_t> counts, offsets, sums, stats;
+    DevBuf<int32_t> pl; int n_pl = 0; float sum = 0; // PhotonLights
+    uint32_t cap = 8; // photons one path may store before the batch is redone with more room
+    int Init(const bhrt_scene *scene, uint32_t max_E) // batches of up to max_E emissions
+    {
+        std::vector<int32_t> lights;
+        BHRT_TRY(PhotonLights(scene, lights, sum));
+        n_pl = (int)lights.size();
+        BHRT_TRY(pl.Reserve(lights.size()));
+        HIP_CHECK(hipMemcpy(pl, lights.data(), lights.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+        BHRT_TRY(counts.Reserve(max_E)); BHRT_TRY(offsets.Reserve(max_E));
+        BHRT_TRY(sums.Reserve((max_E + kScanTile - 1) / kScanTile));
+        return stats.Reserve(2);
+    }
+    int Emit(DeviceState *D, bool global_map, uint32_t seed, uint64_t e0, uint32_t E, uint32_t *total)
+    {
+        while (true) {
+            if ((uint64_t)E * cap >= (1ull << 32)) { SetError("photon emission: a batch with room for 2^32 photons or more"); return BHRT_ERR_ARG; } // its total is a 32-bit word on the device
+            BHRT_TRY(tmp.Reserve((size_t)E * cap));
+            hipLaunchKernelGGL(global_map ? k_photon_emit<true> : k_photon_emit<false>, dim3(E / kBlock), dim3(kBlock), 0, D->stream, D->S, seed, e0, E, pl.p, n_pl, sum, tmp.p, cap, counts.p);
+            HIP_CHECK(hipMemcpyAsync(offsets, counts, E * sizeof(uint32_t), hipMemcpyDeviceToDevice, D->stream));
+            LaunchExclusiveScan(D->stream, offsets, E, sums);
+            HIP_CHECK(hipMemsetAsync(stats, 0, 2 * sizeof(uint32_t), D->stream));
+            hipLaunchKernelGGL(k_pb_batch_stats, dim3(64), dim3(256), 0, D->stream, counts.p, offsets.p, E, stats.p);
+            uint32_t h[2];
+            HIP_CHECK(hipMemcpyAsync(h, stats, sizeof h, hipMemcpyDeviceToHost, D->stream));
+            HIP_CHECK(hipStreamSynchronize(D->stream));
+            if (h[0] <= cap) { *total = h[1]; return BHRT_OK; }
+            cap = h[0]; // a path stored more than `cap` photons: redo this batch with room for all of them
+        }
+    }
+};
 
 // Emission + stable compaction + ScalePhotonPowers + balance, all in HBM: `balanced` (empty on entry) receives the balanced records (n + 1, slot 0
-// unused).  Per batch of emissions only two words reach the host (the largest count of a path, the photons of the batch).
-// global_map: BuildPhotonMap / TracePhotonRay / RandomPhotonBounce instead of the caustic variants.
+// unused).  global_map: BuildPhotonMap / TracePhotonRay / RandomPhotonBounce instead of the caustic variants.
 static int BuildPhotons(bhrt_scene *scene, const bhrt_opts *opts, uint32_t max_photons, bool global_map, DevBuf<DPhoton> &balanced, uint32_t *n_out)
 {
-    int rc = EnsureUploaded(scene);
-    if (rc) return rc;
+    BHRT_TRY(EnsureUploaded(scene));
     if (!opts || max_photons == 0 || max_photons > (1u << 28)) { SetError("bad photon budget"); return BHRT_ERR_ARG; }
     DeviceState *D = scene->dev;
-    std::vector<int32_t> pl;
-    float sum = 0;
-    BHRT_TRY(PhotonLights(scene, pl, sum));
-    DevBuf<DPhoton> d_out, d_tmp;
-    DevBuf<uint32_t> d_counts, d_offsets, d_sums, d_stats;
-    DevBuf<int32_t> d_pl;
+    const uint32_t E = global_map ? 1u << 16 : 1u << 20; // emissions per batch (nearly every emission of the global map stores photons)
+    EmitBatch b;
+    BHRT_TRY(b.Init(scene, E));
+    DevBuf<DPhoton> d_out;
     BHRT_TRY(d_out.Reserve((size_t)max_photons + 1));
     HIP_CHECK(hipMemset(d_out, 0, ((size_t)max_photons + 1) * sizeof(DPhoton)));
-    const uint32_t E = global_map ? 1u << 16 : 1u << 20; // emissions per batch (nearly every emission of the global map stores photons)
-    uint32_t cap = 8;            // photons one path may store before the batch is redone with more room
-    BHRT_TRY(d_counts.Reserve(E));
-    BHRT_TRY(d_offsets.Reserve(E));
-    BHRT_TRY(d_pl.Reserve(pl.size()));
-    HIP_CHECK(hipMemcpy(d_pl, pl.data(), pl.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-    BHRT_TRY(d_tmp.Reserve((size_t)E * cap));
-    const uint32_t n_tiles = (E + kScanTile - 1) / kScanTile;
-    BHRT_TRY(d_sums.Reserve(n_tiles));
-    BHRT_TRY(d_stats.Reserve(2));
     uint64_t e0 = 0, stored = 0;
     const uint64_t emission_budget = (uint64_t)max_photons * 4096ull + (1ull << 24);
     while (stored < max_photons && e0 < emission_budget) {
-        LaunchPhotonEmit(D, global_map, opts->seed, e0, E, d_pl, (int)pl.size(), sum, d_tmp, cap, d_counts);
-        // where every path's photons go: exclusive prefix of the counts, on the device; two words come back
-        HIP_CHECK(hipMemcpyAsync(d_offsets, d_counts, E * sizeof(uint32_t), hipMemcpyDeviceToDevice, D->stream));
-        hipLaunchKernelGGL(k_scan_tiles, dim3(n_tiles), dim3(kScanBlock), 0, D->stream, d_offsets.p, E, d_sums.p);
-        hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(kScanBlock), 0, D->stream, d_sums.p, n_tiles);
-        hipLaunchKernelGGL(k_scan_add, dim3(n_tiles), dim3(kScanBlock), 0, D->stream, d_offsets.p, E, d_sums.p);
-        HIP_CHECK(hipMemsetAsync(d_stats, 0, 2 * sizeof(uint32_t), D->stream));
-        hipLaunchKernelGGL(k_pb_batch_stats, dim3(64), dim3(256), 0, D->stream, d_counts.p, d_offsets.p, E, d_stats.p);
-        uint32_t stats[2];
-        HIP_CHECK(hipMemcpyAsync(stats, d_stats, sizeof stats, hipMemcpyDeviceToHost, D->stream));
-        HIP_CHECK(hipStreamSynchronize(D->stream));
-        if (stats[0] > cap) { // a path stored more than `cap` photons: redo this batch with room for all of them
-            cap = stats[0];
-            BHRT_TRY(d_tmp.Reserve((size_t)E * cap));
-            continue;
-        }
-        hipLaunchKernelGGL(k_photon_compact, dim3(E / kBlock), dim3(kBlock), 0, D->stream, d_tmp.p, cap, d_counts.p, d_offsets.p, (uint32_t)std::min<uint64_t>(stored, max_photons), E, max_photons, d_out.p);
-        stored += stats[1];
-        e0 += E;
+        uint32_t total = 0;
+        BHRT_TRY(b.Emit(D, global_map, opts->seed, e0, E, &total));
+        hipLaunchKernelGGL(k_photon_compact, dim3(E / kBlock), dim3(kBlock), 0, D->stream, b.tmp.p, b.cap, b.counts.p, b.offsets.p, (uint32_t)std::min<uint64_t>(stored, max_photons), E, max_photons, d_out.p);
+        stored += total; e0 += E;
     }
     const uint32_t n = (uint32_t)std::min<uint64_t>(stored, max_photons);
     if (n == 0) { SetError("photon map: no photon reached a photon surface"); return BHRT_ERR_UNSUPPORTED; }
@@ -3964,39 +3984,20 @@ static int BuildPhotons(bhrt_scene *scene, const bhrt_opts *opts, uint32_t max_p
 int bhrt_photon_emit_range(bhrt_scene *scene, const bhrt_opts *opts, int global_map, uint64_t e0, uint32_t count, void *photons_out, uint32_t capacity,
                            uint32_t *n_photons)
 try {
-    int rc = EnsureUploaded(scene);
-    if (rc) return rc;
+    BHRT_TRY(EnsureUploaded(scene));
     if (!opts || !photons_out || !n_photons || count == 0 || count % kBlock != 0 || count > (1u << 24)) { SetError("photon emit range: bad arguments (count must be a multiple of 256)"); return BHRT_ERR_ARG; }
     DeviceState *D = scene->dev;
-    std::vector<int32_t> pl;
-    float sum = 0;
-    BHRT_TRY(PhotonLights(scene, pl, sum));
-    struct { DevBuf<DPhoton> tmp, out; DevBuf<uint32_t> counts, offsets; DevBuf<int32_t> pl; } b;
-    BHRT_TRY(b.counts.Reserve(count));
-    BHRT_TRY(b.offsets.Reserve(count));
-    BHRT_TRY(b.pl.Reserve(pl.size()));
-    HIP_CHECK(hipMemcpy(b.pl, pl.data(), pl.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-    std::vector<uint32_t> counts(count), offsets(count);
-    uint32_t cap = 8;
-    uint64_t total = 0;
-    for (int attempt = 0; attempt < 2; attempt++) {
-        BHRT_TRY(b.tmp.Reserve((size_t)count * cap));
-        LaunchPhotonEmit(D, global_map != 0, opts->seed, e0, count, b.pl, (int)pl.size(), sum, b.tmp, cap, b.counts);
-        HIP_CHECK(hipMemcpyAsync(counts.data(), b.counts, count * sizeof(uint32_t), hipMemcpyDeviceToHost, D->stream));
-        HIP_CHECK(hipStreamSynchronize(D->stream));
-        uint32_t maxc = 0;
-        for (uint32_t i = 0; i < count; i++) maxc = std::max(maxc, counts[i]);
-        if (maxc <= cap) break;
-        cap = maxc; // a path stored more photons than there was room for: once more with room for all
-    }
-    for (uint32_t i = 0; i < count; i++) { offsets[i] = (uint32_t)std::min<uint64_t>(total, capacity); total += counts[i]; }
-    *n_photons = (uint32_t)std::min<uint64_t>(total, 0xffffffffull);
+    EmitBatch b;
+    BHRT_TRY(b.Init(scene, count));
+    uint32_t total = 0;
+    BHRT_TRY(b.Emit(D, global_map != 0, opts->seed, e0, count, &total));
+    *n_photons = total;
     if (total > capacity) { SetError("photon emit range: photons_out too small"); return BHRT_ERR_ARG; }
     if (total == 0) return BHRT_OK;
-    BHRT_TRY(b.out.Reserve((size_t)total + 1));
-    HIP_CHECK(hipMemcpyAsync(b.offsets, offsets.data(), count * sizeof(uint32_t), hipMemcpyHostToDevice, D->stream));
-    hipLaunchKernelGGL(k_photon_compact, dim3(count / kBlock), dim3(kBlock), 0, D->stream, b.tmp.p, cap, b.counts.p, b.offsets.p, 0u, count, (uint32_t)total, b.out.p);
-    HIP_CHECK(hipMemcpyAsync(photons_out, b.out + 1, (size_t)total * sizeof(DPhoton), hipMemcpyDefault, D->stream)); // host or device destination
+    DevBuf<DPhoton> out;
+    BHRT_TRY(out.Reserve((size_t)total + 1));
+    hipLaunchKernelGGL(k_photon_compact, dim3(count / kBlock), dim3(kBlock), 0, D->stream, b.tmp.p, b.cap, b.counts.p, b.offsets.p, 0u, count, total, out.p);
+    HIP_CHECK(hipMemcpyAsync(photons_out, out + 1, (size_t)total * sizeof(DPhoton), hipMemcpyDefault, D->stream)); // host or device destination
     HIP_CHECK(hipStreamSynchronize(D->stream));
     return BHRT_OK;
 } catch (...) { return bhrt::AbiException(); }
@@ -4062,33 +4063,29 @@ try {
     if (rc) return rc;
     DeviceState *D = scene->dev;
     D->timers = 0;
-    D->photon_exact = photon_exact;
     if (!D->d_photons) { SetError("photon map: call bhrt_photon_build first"); return BHRT_ERR_ARG; }
     if (!p || !nrm || !irrad || !dir) { SetError("null buffer"); return BHRT_ERR_ARG; }
     if (cnt == 0) return BHRT_OK;
     const uint32_t chunk = (knn || knn_count || d2max) ? 1u << 14 : 1u << 20;
-    struct Hook { DeviceState *D; DevBuf<uint32_t> knn; ~Hook() { D->d_knn = nullptr; } } b = {D, {}}; // the test hook never outlives its memory
+    DevBuf<uint32_t> d_knn; // the test hook's photon lists
     DevBuf<float> d_f;
     BHRT_TRY(d_f.Reserve((size_t)chunk * 12));
     float *d_buf = d_f;
     const size_t kw = BHRT_PHOTON_K + 2;
     std::vector<uint32_t> h_knn;
-    if (knn || knn_count || d2max) { BHRT_TRY(b.knn.Reserve((size_t)chunk * kw)); h_knn.resize((size_t)chunk * kw); }
+    if (knn || knn_count || d2max) { BHRT_TRY(d_knn.Reserve((size_t)chunk * kw)); h_knn.resize((size_t)chunk * kw); }
     for (size_t c0 = 0; c0 < cnt; c0 += chunk) {
         const uint32_t m = (uint32_t)std::min<size_t>(chunk, cnt - c0);
         HIP_CHECK(hipMemcpy(d_buf, p + c0 * 3, (size_t)m * 3 * sizeof(float), hipMemcpyHostToDevice));
         HIP_CHECK(hipMemcpy(d_buf + (size_t)chunk * 3, nrm + c0 * 3, (size_t)m * 3 * sizeof(float), hipMemcpyHostToDevice));
-        if (b.knn) HIP_CHECK(hipMemset(b.knn, 0, (size_t)m * kw * sizeof(uint32_t)));
-        D->d_knn = b.knn;
+        if (d_knn) HIP_CHECK(hipMemset(d_knn, 0, (size_t)m * kw * sizeof(uint32_t)));
         const GatherToArrays sink = {d_buf, d_buf + (size_t)chunk * 3, d_buf + (size_t)chunk * 6, d_buf + (size_t)chunk * 9};
-        rc = RunGather(D, sink, 0, m, radius, nullptr);
-        D->d_knn = nullptr;
-        if (rc) return rc;
+        BHRT_TRY((GatherPass<GatherToArrays>{D, sink, 0, m, radius, photon_exact, d_knn, nullptr}.Run()));
         HIP_CHECK(hipStreamSynchronize(D->stream));
         HIP_CHECK(hipMemcpy(irrad + c0 * 3, d_buf + (size_t)chunk * 6, (size_t)m * 3 * sizeof(float), hipMemcpyDeviceToHost));
         HIP_CHECK(hipMemcpy(dir + c0 * 3, d_buf + (size_t)chunk * 9, (size_t)m * 3 * sizeof(float), hipMemcpyDeviceToHost));
-        if (b.knn) {
-            HIP_CHECK(hipMemcpy(h_knn.data(), b.knn, (size_t)m * kw * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        if (d_knn) {
+            HIP_CHECK(hipMemcpy(h_knn.data(), d_knn, (size_t)m * kw * sizeof(uint32_t), hipMemcpyDeviceToHost));
             for (uint32_t i = 0; i < m; i++) {
                 const uint32_t *row = &h_knn[(size_t)i * kw];
                 if (knn_count) knn_count[c0 + i] = row[0];

@@ -306,6 +306,29 @@ def test_gpu_sharded_photon_build_equals_single_build(B, load_scene):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("global_map", [False, True])
+def test_gpu_emission_batch_does_not_depend_on_its_size(global_map, B, load_scene):
+    """The emission batch bhrt_photon_build and bhrt_photon_emit_range share (kernels.hip EmitBatch) takes the place of every path's photons from
+    a scan of 8192-entry tiles on the device: emissions [0, 16896) in one call give the bytes of the calls of 256 (less than a tile), 8192 (one
+    tile exactly) and 8448 (a tile and a part of one) emissions strung together.  And a buffer that is too small: nothing written, the needed
+    size reported.  In global mode every one of these calls is redone with more room (paths of this scene store up to 22 photons, the first
+    attempt has room for 8); in caustic mode none is."""
+    sc = load_scene("c5_caustics")
+    opts = B.default_opts(seed=7)
+    whole = sc.photon_emit_range(opts, 0, 16896, global_map=global_map)
+    parts, e0 = [], 0
+    for count in (256, 8192, 8448):
+        parts.append(sc.photon_emit_range(opts, e0, count, global_map=global_map))
+        e0 += count
+    assert e0 == 16896 and len(whole) > 0 and all(len(p) > 0 for p in parts)
+    assert np.concatenate(parts).tobytes() == whole.tobytes()
+    need = len(parts[0])
+    small = np.full((need, 24), 0xA5, np.uint8)
+    n, ok = sc.photon_emit_range_into(opts, 0, 256, small.ctypes.data, need - 1, global_map=global_map)
+    assert not ok and n == need and (small == 0xA5).all()
+
+
+@pytest.mark.gpu
 def test_gpu_photon_records_stay_on_the_device(B, load_scene):
     """The multi-GPU build with device-resident exchange buffers (what dist.photon_build_sharded does under RCCL): emission writes
     its records to a device pointer, they are strung together on the device and installed from a device pointer — and a buffer

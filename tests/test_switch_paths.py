@@ -28,7 +28,7 @@ pytestmark = pytest.mark.gpu
 
 K_SLOW_CAP = 1 << 16        # kernels.hip kSlowCap: rays set aside per pass
 INJECT_MIN_RAYS = 1 << 20   # kernels.hip kInjectMinRays (BHRT_INJECT_MIN_LOG2 20): a batch rides along only with a step of at least this many rays
-GATHER_SORT_MIN = 1 << 16   # kernels.hip RunGather: the gather sorts its queries by cell only from this many queries on
+GATHER_SORT_MIN = 1 << 16   # kernels.hip GatherPass::OrderByCell: the gather sorts its queries by cell only from this many queries on
 PATH16_MAX_NODES = 1 << 17  # kernels.hip PathMode: 16-bit path entries up to this many BVH nodes, 32-bit above
 PATH_MAX_DEPTH = 32         # kernels.hip PathMode: deeper trees walk parent links (no path in LDS, leaf_skip not compiled in)
 
