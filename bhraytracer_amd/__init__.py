@@ -44,7 +44,8 @@ class Stats(C.Structure):
                 ("seconds_photon_gather", C.c_double), ("seconds_photon_heavy", C.c_double),
                 ("photon_queries", C.c_uint64), ("photon_heavy_queries", C.c_uint64), ("photon_wave_queries", C.c_uint64),
                 ("photon_exact_queries", C.c_uint64), ("photon_nodes_visited", C.c_uint64), ("deferred_rays", C.c_uint64),
-                ("photon_lane_queries", C.c_uint64), ("photon_lane_nodes", C.c_uint64), ("photon_found", C.c_uint64), ("launches_resolve_fused", C.c_uint64)]
+                ("photon_lane_queries", C.c_uint64), ("photon_lane_nodes", C.c_uint64), ("photon_found", C.c_uint64), ("launches_resolve_fused", C.c_uint64),
+                ("global_gather_queries", C.c_uint64), ("global_gather_heavy_queries", C.c_uint64), ("seconds_global_gather", C.c_double)]
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_ if n != "reserved"}
@@ -83,6 +84,7 @@ EXPORTS = [
     "bhrt_scene_set_lens", "bhrt_camera_rays",
     "bhrt_scene_set_emissive", "bhrt_scene_material_index", "bhrt_scene_set_material_emission", "bhrt_scene_get_material_emission",
     "bhrt_scene_set_face_materials", "bhrt_scene_submaterial_count", "bhrt_scene_get_submaterial",
+    "bhrt_scene_set_global_gather", "bhrt_global_map_build", "bhrt_global_map_set", "bhrt_global_map_get", "bhrt_global_gather_host",
 ]
 
 
@@ -256,8 +258,48 @@ class Scene:
         _check(lib().bhrt_scene_get_submaterial(self._h, int(material), int(sub), C.byref(m), C.byref(e)))
         return m, e.value
 
+    # ---- the global gather: switch and radius beside the flat blob, the map in a device slot of its own ----------------------
+    def set_global_gather(self, on: bool = True, radius: float = 0.0):
+        """bhrt_scene_set_global_gather: with the switch on, a Shade() frame whose GI term is cut by gi < 0 gathers it from the installed global
+        map instead (diffuse x EstimateIrradiance<1000>), in all later renders of this scene.  radius 0 = the reference's 0.5.  The renders
+        raise (BHRT_ERR_ARG) while the switch is on and no global map is installed."""
+        _check(lib().bhrt_scene_set_global_gather(self._h, 1 if on else 0, C.c_float(radius)))
+
+    def global_map_build(self, opts: Opts, max_photons: int) -> int:
+        """bhrt_global_map_build: BuildPhotonMap on the device, balanced and left installed for the global gather; returns the photons stored."""
+        n = C.c_uint32(0)
+        _check(lib().bhrt_global_map_build(self._h, C.byref(opts), int(max_photons), C.byref(n)))
+        return n.value
+
+    def global_map_set(self, records) -> int:
+        """bhrt_global_map_set: installs balanced (n, 24) uint8 records as they are (photon_build_global's or global_map_get's); none removes the map."""
+        r = np.ascontiguousarray(records if records is not None else np.zeros((0, 24)), np.uint8).reshape(-1, 24)
+        _check(lib().bhrt_global_map_set(self._h, _ptr(r) if len(r) else None, len(r)))
+        return len(r)
+
+    def global_map_set_ptr(self, ptr: int, n: int):
+        """Same from `ptr` (host or device memory holding n balanced records)."""
+        _check(lib().bhrt_global_map_set(self._h, C.c_void_p(ptr), int(n)))
+
+    def global_map_get(self) -> np.ndarray:
+        """bhrt_global_map_get: the installed global map, balanced (n, 24) uint8 records."""
+        n = C.c_uint32(0)
+        _check(lib().bhrt_global_map_get(self._h, None, 0, C.byref(n)))
+        out = np.zeros((n.value, 24), np.uint8)
+        _check(lib().bhrt_global_map_get(self._h, _ptr(out), n.value, C.byref(n)))
+        return out
+
+    def global_gather(self, p, nrm, radius=0.5, exact=False):
+        """bhrt_global_gather_host: EstimateIrradiance<1000> on the global map for n points; returns (irradiance, direction), each (n, 3)."""
+        p = np.ascontiguousarray(p, np.float32)
+        nrm = np.ascontiguousarray(nrm, np.float32)
+        irr, d = np.zeros_like(p), np.zeros_like(p)
+        _check(lib().bhrt_global_gather_host(self._h, _ptr(p), _ptr(nrm), C.c_size_t(p.shape[0]), C.c_float(radius), 1 if exact else 0, _ptr(irr), _ptr(d)))
+        return irr, d
+
     def clone(self) -> "Scene":
-        """bhrt_scene_clone: a second handle on the same loaded scene (host state only, the emission and face-material state included; no device state)."""
+        """bhrt_scene_clone: a second handle on the same loaded scene (host state only: the emission, face-material and global-gather state included;
+        no device state, so no photon map)."""
         other = Scene.__new__(Scene)
         other._h = C.c_void_p()
         other._flat = None

@@ -11,6 +11,7 @@
 //               [--lens [--dof R] [--focaldist D]]                               (the viewport's depth of field, viewport.cpp:236-243, rendered)
 //               [--emission]                                                     (the <emission> of the materials, xmlload.cpp:344-348, shaded)
 //               [--face-materials]                                               (the .mtl sub-material of each mesh face, viewport.cpp:581-607, rendered)
+//               [--global-map N [--global-radius R]]                             (BuildPhotonMap, Main.cpp:196,251-317, gathered where the GI recursion ends)
 //   bhrt info   <scene.xml>
 //
 // --gpus N: ONE process drives N GPUs of the node (the reference's one process drives 16 OpenMP threads, Main.cpp:422): the
@@ -37,6 +38,10 @@
 // --face-materials: bhrt_scene_set_face_materials(scene, 1) before the upload and before --gpus N clones the scene: a mesh with a .mtl
 // shades every face with its own sub-material.  Scene state, so it reaches every render the other options choose (--gpus, --rehearse, --denoise,
 // --adaptive, --lens, --emission), the denoiser's albedo guide included.  Without the flag the frame is the reference's: sub-material 0 everywhere.
+// --global-map N: bhrt_scene_set_global_gather(scene, 1, R) before --gpus N clones the scene, and bhrt_global_map_build with the render's seed on every
+// device once its scene is uploaded: a Shade() frame whose GI term is cut by the bounce budget gathers it from the global photon
+// map (radius R, default the reference's 0.5).  With --gpus K every rank builds the whole map itself: the emission is keyed, so the bytes are
+// the same on every rank.  Independent of --photons; --photon-exact selects the heavy-query path of both gathers.
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
@@ -79,6 +84,8 @@ struct Args {
     float dof = -1.f, focaldist = 0.f; // --dof / --focaldist: values for bhrt_scene_set_lens; dof < 0: not given
     bool emission = false;             // --emission: bhrt_scene_set_emissive
     bool face_materials = false;       // --face-materials: bhrt_scene_set_face_materials
+    uint32_t global_map = 0;           // --global-map N: photons of the global map (bhrt_global_map_build); switches the global gather on
+    float global_radius = 0.f;         // --global-radius R; 0 = the reference's 0.5
 };
 
 // a finite number >= 0 (--dof) or > 0 (--focaldist), else a usage error
@@ -207,6 +214,7 @@ static int render_multi(bhrt_scene *first, const Args &A, const bhrt_info &info,
             hipStream_t s = nullptr;
             auto setup = [&]() {
                 HOST_CHECK(bhrt_scene_upload(scenes[r], devs[r]), "upload");
+                if (A.global_map) HOST_CHECK(bhrt_global_map_build(scenes[r], &A.o, A.global_map, nullptr), "global map build"); // the whole map on every rank: keyed emission, identical bytes
                 HOST_CHECK(hipSetDevice(devs[r]), "hipSetDevice");
                 HOST_CHECK(hipStreamCreate(&s), "stream");
                 HOST_CHECK(hipMalloc(&d_rgb, npx * 3), "hipMalloc");
@@ -366,6 +374,8 @@ int main(int argc, char **argv)
         else if (s == "--lens") o.lens = 1;
         else if (s == "--emission") A.emission = true;
         else if (s == "--face-materials") A.face_materials = true;
+        else if (s == "--global-map") A.global_map = (uint32_t)strtoul(next(), nullptr, 10);
+        else if (s == "--global-radius") A.global_radius = lens_value("--global-radius", next(), true);
         else if (s == "--dof") { A.dof = lens_value("--dof", next(), false); o.lens = 1; }
         else if (s == "--focaldist") { A.focaldist = lens_value("--focaldist", next(), true); o.lens = 1; }
         else { fprintf(stderr, "bhrt: unknown option %s\n", s.c_str()); return 2; }
@@ -385,6 +395,7 @@ int main(int argc, char **argv)
         fprintf(stderr, "bhrt: usage: --adaptive needs 2 <= --spp-min <= --spp <= 65535 and a number for --adaptive-threshold\n");
         return 2;
     }
+    if (A.global_radius > 0.f && !A.global_map) { fprintf(stderr, "bhrt: usage: --global-radius needs --global-map N\n"); return 2; }
     A.dn.gamma = o.gamma;
     bhrt_scene *scene = nullptr;
     if (bhrt_scene_load_xml(A.scene.c_str(), &scene)) return fail("LoadScene");
@@ -400,6 +411,7 @@ int main(int argc, char **argv)
     if (!render) { bhrt_scene_free(scene); return 0; }
     if (A.emission && bhrt_scene_set_emissive(scene, 1)) return fail("set emissive"); // before the upload and before --gpus N clones the scene
     if (A.face_materials && bhrt_scene_set_face_materials(scene, 1)) return fail("set face materials"); // likewise
+    if (A.global_map && bhrt_scene_set_global_gather(scene, 1, A.global_radius)) return fail("set global gather"); // likewise; the map is built after the upload
     if (o.lens) { // before the upload and before --gpus N clones the scene
         const bhrt_flat_header *fh = nullptr;
         uint64_t fb = 0;
@@ -432,6 +444,11 @@ int main(int argc, char **argv)
         printf("%d GPU(s): frame %.3f s on the slowest GPU, %s tile gather %.4f s, %.3f s wall incl. set-up\n", A.gpus, slowest, A.rehearse ? "rehearsed (device-to-device)" : "RCCL", gather_s, wall);
     } else {
         if (bhrt_scene_upload(scene, A.device)) return fail("upload");
+        if (A.global_map) { // BuildPhotonMap, Main.cpp:196
+            uint32_t stored = 0;
+            if (bhrt_global_map_build(scene, &o, A.global_map, &stored)) return fail("BuildPhotonMap");
+            printf("global photon map: %u photons, gather radius %g\n", stored, A.global_radius > 0.f ? A.global_radius : 0.5f);
+        }
         if (!A.photon_file.empty()) { // a cached photon pass
             if (bhrt_photon_import(scene, A.photon_file.c_str(), 0)) return fail("photon import");
             o.photon_map = 1;

@@ -117,6 +117,17 @@ struct GatherWorkspace {
     }
 };
 
+// An installed photon map: the balanced 24-byte records (heap order, slot 0 unused), the decoded copy the gather walks, and the host copy a
+// getter fetches on demand.  InstallPhotonMapDev fills one.
+struct PhotonSlot {
+    DevBuf<DPhoton> d_photons;
+    uint32_t n_photons = 0;
+    std::vector<HostPhoton> h_photons; // balanced copy for bhrt_photon_get / _export, bhrt_global_map_get
+    DevBuf<float4> d_ph_hot, d_ph_cold, d_ph_dbox; // decoded copy the gather walks (PhotonMapDev)
+    PhotonMapDev pm = {};
+    void Clear() { d_photons.Free(); d_ph_hot.Free(); d_ph_cold.Free(); d_ph_dbox.Free(); n_photons = 0; h_photons.clear(); pm = PhotonMapDev{}; }
+};
+
 struct DeviceState : DeviceQueues {
     int device = -1;
     uint32_t n_cus = 256; // compute units of the device (hipDeviceProp_t::multiProcessorCount): sizes the grids of the resident-wave kernels
@@ -169,13 +180,9 @@ struct DeviceState : DeviceQueues {
     struct PendingTimer { int e0, e1; double *acc; };
     std::vector<PendingTimer> ev_pending;
     std::vector<int> ev_free;                  // indices of ev_pool not in use
-    // caustic photon map (balanced, heap order, slot 0 unused)
-    DevBuf<DPhoton> d_photons;
-    uint32_t n_photons = 0;
-    std::vector<HostPhoton> h_photons; // balanced copy for bhrt_photon_export
-    DevBuf<float> d_ph_frames;         // 15 * cap_frames floats (p, N, V, kd, ks per frame), only with photon_map
-    DevBuf<float4> d_ph_hot, d_ph_cold, d_ph_dbox; // decoded copy the gather walks (PhotonMapDev)
-    PhotonMapDev pm;
+    // the caustic photon map (bhrt_photon_build / _install / _import) and the global one (bhrt_global_map_build / _set): independent slots
+    PhotonSlot cmap, gmap;
+    DevBuf<float> d_ph_frames;         // 15 * cap_frames floats (p, N, V, kd, ks per frame), only with photon_map or the global gather
     GatherWorkspace gw;
     // Development switches, read from the environment ONCE, when the scene is uploaded (none changes a result), and the two test knobs, which
     // no environment variable reaches: only bhrt_scene_knob sets them.

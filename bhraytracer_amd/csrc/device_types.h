@@ -46,7 +46,10 @@ enum : uint32_t { FH_ROOT = 0, FH_GI = 1, FH_REFR_FRONT = 2, FH_REFR_OUT = 3 };
 // direct-light term state of a frame
 enum : uint32_t { DM_NONE = 0, DM_AMBIENT = 1, DM_DIRECT = 2, DM_POINT = 3, DM_POINT_ZERO = 4 };
 // frame flags
-enum : uint32_t { FF_CONST = 1u /* value in refr */, FF_HAS_REFR = 2u /* a refraction ray was emitted: refr + refr_color valid */, FF_HAS_GI = 4u };
+enum : uint32_t { FF_CONST = 1u /* value in refr */, FF_HAS_REFR = 2u /* a refraction ray was emitted: refr + refr_color valid */, FF_HAS_GI = 4u,
+                  // the GI term was cut by gi < 0 (MtlBlinn.cpp:386) and the global gather is on: `gi` holds G, zero until
+                  // GlobalGatherToFrames finds photons.  Set by the kGg instantiations of k_shade only; never together with FF_HAS_GI
+                  FF_GI_CUT = 8u };
 
 // Closest-hit ray queue (SoA, one array per field -> coalesced)
 struct RayQueue {
@@ -84,14 +87,15 @@ struct Frames {
     uint64_t *code;    // shade-call path code
     float *mult;       // 3: factor applied when delivering to the parent (GI: kd/ks sample; REFR_OUT: refraction*absorption)
     float *refr;       // 3: refraction term (MtlBlinn.cpp:117)
-    float *gi;         // 3: GI term (:124)
+    float *gi;         // 3: GI term (:124); on a frame marked FF_GI_CUT the global map's estimate G in its place
     float *gi_mult;    // 3: (useSpecular ? specular : diffuse).Sample at this frame's hit (:406,417)
     float *brdf;       // 3: brdfXCosTheta (:325)
     float *refr_color; // 3: (1-F)*refraction (:117)
     float *rr;         // squared distance to the point light (PointLight.cpp:10-11)
     float *vis;        // Shadow() result (GenLight.cpp:10-13)
     float *caustic;    // 3: photon-map term brdf*irrad (:329-342), zero when off
-    // inputs of the caustic term, only allocated when the photon map is on: hit p, hit N, vV, kd sample, ks sample
+    // inputs of the caustic term, only allocated when the photon map or the global gather is on: hit p, hit N, vV, kd sample, ks sample
+    // (the global gather reads p, N and kd of the frames it marked; without the caustic term only those are written)
     float *ph_p, *ph_n, *ph_v, *ph_kd, *ph_ks;
     // the emission term, read by the kEmit / kLe instantiations of the kernels only.  emission: the <emission> TexturedColor of
     // every material (FlatScene::emission), [n_materials]; null = the term is off (bhrt_scene_set_emissive, the default).  le, 3: Le =

@@ -831,7 +831,9 @@ __device__ __forceinline__ int resolve_material(const DevScene &S, const FaceMtl
 // (a quarter of the kernel, 200 divisions) is not even compiled in.
 // kLe = true (needs kTex): the emission term is on and some emission is textured; the frame keeps its Le (Frames::le).
 // kFm = true: face materials are on; the caller has resolved the hit's material (mi_fm, resolve_material).  kFm = false: mi_fm is not read
-template <bool kTex, bool kLe, bool kFm>
+// kGg = true: the global gather is on: a frame whose GI term is cut by gi < 0 is marked FF_GI_CUT, its G starts at zero and it
+// keeps the gather's inputs.  kGg = false: the kernels as they were before the gather existed
+template <bool kTex, bool kLe, bool kFm, bool kGg>
 __device__ inline void shade_entry(const DevScene &S, const RenderParams &R, const Frames &F, uint32_t f, uint32_t how, V3 rayP, const Attr &a, int node, int mi_fm,
                                    int bounce, int gi, uint64_t code, uint32_t skey, ShadeOut &out)
 {
@@ -917,6 +919,10 @@ __device__ inline void shade_entry(const DevScene &S, const RenderParams &R, con
         flags |= FF_HAS_GI;
         const bhrt_texcolor &tcs = useSpecular ? newSpecular : m.diffuse;
         st3(F.gi_mult, f, useSpecular ? ks_s : kd_s);
+    } else if (kGg) { // MtlBlinn.cpp:386 returns black here; with the gather on, G of the global map (GlobalGatherToFrames::done)
+        flags |= FF_GI_CUT;
+        st3(F.gi, f, zero);
+        if (!R.photon) { st3(F.ph_p, f, a.p); st3(F.ph_n, f, a.N); st3(F.ph_kd, f, kd_s); } // with the caustic term on every frame keeps them, below
     }
     // ---- direct light, PathTracing_DiffuseNSpecular (MtlBlinn.cpp:304-351)
     if (S.n_lights > 0) {
@@ -977,7 +983,8 @@ __device__ inline void shade_entry(const DevScene &S, const RenderParams &R, con
 // computes the same camera ray, ~300 instructions, and writes 24-byte hit records this kernel reads back), no shading order (all samples of a pixel
 // sit in one wave: hits and misses are as uniform per workgroup in slot order as in the sorted one), frame numbers from one atomic per workgroup.
 // kFm: face materials are on: the frame's material is resolve_material's.  Never with kFused (a scene with sub-materials has a mesh).
-template <bool kCamera, bool kTex, bool kFused = false, bool kLe = false, bool kFm = false>
+// kGg: the global gather is on: shade_entry marks the frames whose GI term is cut.
+template <bool kCamera, bool kTex, bool kFused = false, bool kLe = false, bool kFm = false, bool kGg = false>
 __device__ __forceinline__ void shade_block(const DevScene &S, const RenderParams &R, const PassInfo &P, const RayQueue &qin, const HitBuf &hb, uint32_t n, const RayQueue &qout,
                                             const ShadowQueue &qs, const Frames &F, float *samples, uint32_t *root_of, Counters *cnt, const RayOrder &ord)
 {
@@ -1095,7 +1102,7 @@ __device__ __forceinline__ void shade_block(const DevScene &S, const RenderParam
         if (kLe && mi >= 0) need_uv = need_uv || F.emission[mi].map >= 0; // a textured emission reads uvw / duvw too
         Attr a;
         hit_attrs(S, o, d, hit.t, hit.node, hit.prim, need_uv, a);
-        shade_entry<kTex, kLe, kFm>(S, R, F, f, how, o, a, hit.node, mi, bounce, gi, code, skey, so);
+        shade_entry<kTex, kLe, kFm, kGg>(S, R, F, f, how, o, a, hit.node, mi, bounce, gi, code, skey, so);
         ray_owner = f;
     } else if (active) {
         if (kind == RK_CAMERA) {
@@ -1197,11 +1204,11 @@ __device__ __forceinline__ void shade_block(const DevScene &S, const RenderParam
 // The workgroup that finishes LAST hands the step's queue lengths to the host (what a one-lane kernel behind k_shade did: k_publish, ~6 us of
 // launch and ~5 us of gap per wave step — 2 % of a C2 frame).  Every workgroup's counter updates are atomics at agent scope and come before its
 // ticket (release fence); the last ticket holder reads them with atomic loads behind an acquire fence.
-template <bool kCamera, bool kTex, bool kFused = false, bool kLe = false, bool kFm = false>
+template <bool kCamera, bool kTex, bool kFused = false, bool kLe = false, bool kFm = false, bool kGg = false>
 __global__ void __launch_bounds__(kShadeBlock, BHRT_SHADE_WAVES) k_shade(DevScene S, RenderParams R, PassInfo P, RayQueue qin, HitBuf hb, uint32_t n, RayQueue qout,
                                                    ShadowQueue qs, Frames F, float *samples, uint32_t *root_of, Counters *cnt, RayOrder ord, HostCounters *pub, uint32_t seq)
 {
-    shade_block<kCamera, kTex, kFused, kLe, kFm>(S, R, P, qin, hb, n, qout, qs, F, samples, root_of, cnt, ord);
+    shade_block<kCamera, kTex, kFused, kLe, kFm, kGg>(S, R, P, qin, hb, n, qout, qs, F, samples, root_of, cnt, ord);
     if (!pub) return;
     __syncthreads(); // every wave is through: its queue counters were added to by returning atomics whose results it has used (block_alloc), its
     // capacity flags likewise (flag_overflow) — all acknowledged.  No agent-scope fence: only counters travel, all by atomics at agent scope; a release
@@ -1228,7 +1235,7 @@ __device__ inline V3 frame_value(const DevScene &S, const Frames &F, uint32_t f,
         if (flags & FF_HAS_REFR) out = out + ld3i(F.refr, f); // else PathTracing_Refraction returned black
         bool done = out.x >= 1 && out.y >= 1 && out.z >= 1;
         if (!done) {
-            if (flags & FF_HAS_GI) out = out + ld3i(F.gi, f);  // else gi < 0: black (MtlBlinn.cpp:386)
+            if (flags & (FF_HAS_GI | FF_GI_CUT)) out = out + ld3i(F.gi, f);  // FF_GI_CUT: gi < 0 with the global gather on, G; neither: gi < 0, black (MtlBlinn.cpp:386)
             done = out.x >= 1 && out.y >= 1 && out.z >= 1;
         }
         if (!done) {
@@ -1685,6 +1692,23 @@ struct GatherToFrames { // the caustic term of Shade(), MtlBlinn.cpp:329-342
         }
     }
 };
+struct GlobalGatherToFrames { // G of the frames whose GI term was cut by gi < 0 (FF_GI_CUT), from the global map; PathTracing_GlobalIllumination, MtlBlinn.cpp:386
+    Frames F;
+    __device__ bool skip(uint32_t f) const { return ((F.info[f] >> 16) & (FF_CONST | FF_GI_CUT)) != FF_GI_CUT; }
+    __device__ V3 pos(uint32_t f) const { return ld3i(F.ph_p, f); }
+    __device__ V3 nrm(uint32_t f) const { return ld3i(F.ph_n, f); }
+    __device__ void done(uint32_t f, bool found, V3 irr, V3 vL) const
+    {
+        if (!found) return; // as the caustic sink: no photon, no contribution (F.gi stays the zero k_shade wrote)
+        const V3 vN = normalized(ld3i(F.ph_n, f));
+        const float cosTheta = -dot(vL, vN);
+        if (cosTheta > 0) {
+            V3 g = clamp_white(v3(0, 0, 0) + ld3i(F.ph_kd, f) * irr); // diffuse.Sample(uvw, duvw) * E: the diffuse lobe alone
+            if (isnan_f(g.x)) g = v3(0, 0, 0);
+            st3(F.gi, f, g);
+        }
+    }
+};
 struct GatherToArrays { // bhrt_photon_gather_host
     const float *p, *n;
     float *irrad, *dir;
@@ -1835,7 +1859,8 @@ struct GatherCounters {
     // k_photon_gather_select: nodes; entries of the undecided list; the next query a wave takes; rounds and compactions of all waves (BHRT_DEBUG_GATHER)
     struct Select { unsigned long long visited; uint32_t n_undecided, cursor, rounds, compactions; } select;
     struct Replay { unsigned long long visited; } replay; // k_photon_gather_heap, per list
-    uint32_t n_ordered, pad_; // queries that take part in the cell order (k_gather_first_out; the counting sort's number lands in the host copy only)
+    uint32_t n_ordered; // queries that take part in the cell order (k_gather_first_out; the counting sort's number lands in the host copy only)
+    uint32_t n_asking;  // k_gather_count_asking: queries the sink does not skip (the global gather's bhrt_stats::global_gather_queries)
 };
 static_assert(std::is_trivial<GatherCounters>::value && sizeof(GatherCounters) == 72 && alignof(GatherCounters) == 8, "plain data, the 64-bit sums on 8 bytes");
 // The same order from a radix sort of (cell, query) pairs (gather_sort.hip): the key of a query that takes no part is one bit above every cell, so
@@ -1855,6 +1880,14 @@ __global__ void __launch_bounds__(kBlock) k_gather_cell_key(Sink sink, uint32_t 
     }
     keys[i] = c;
     vals[i] = q;
+}
+// the queries of [q0, q0 + cnt) the sink does not skip: one atomic per wave
+template <class Sink>
+__global__ void __launch_bounds__(kBlock) k_gather_count_asking(Sink sink, uint32_t q0, uint32_t cnt, GatherCounters *counts)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint64_t m = __ballot(i < cnt && !sink.skip(q0 + i));
+    if (__lane_id() == 0 && m) atomicAdd(&counts->n_asking, (uint32_t)__popcll(m));
 }
 __global__ void k_gather_first_out(const uint32_t *sorted_keys, uint32_t cnt, GatherCounters *counts)
 {
@@ -2163,7 +2196,7 @@ static int EnsureWorkspace(DeviceState *D, uint32_t cap_samples, double frames_p
 // with meshes the second shadow queue and the any-hit kernels' own parked list (32 + 8 B: WavePass::sh_overlap, "any-hit work beside the pass"), 12 B of
 // radiance, and `frames_per_sample` Shade() frames (116 B each, + 60 B with the photon map): six by default = 1.03-1.11 KB per sample, 2^27 samples
 // = 138-149 GB.
-static uint32_t DefaultPassSamples(DeviceState *D, bool photon_map, double frames_per_sample)
+static uint32_t DefaultPassSamples(DeviceState *D, bool photon_map /* caustic term or global gather: the frames keep the gather's inputs */, double frames_per_sample)
 {
     const double frame_b = 116 + (photon_map ? 60 : 0) + (D->le_on ? 12 : 0); // le_on: the textured emission term of a frame (Frames::le)
     const double per_sample = 2 * (72 + 16 + 32 + 40 + (D->stream3 ? 32 + 8 : 0)) + 12 + frames_per_sample * frame_b;
@@ -2286,6 +2319,8 @@ struct GatherPass {
     const int photon_exact; // bhrt_opts.photon_exact of the call
     uint32_t *const knn;    // test hook of bhrt_photon_gather_host_ex (which owns the memory): the selection pass's photon lists, or null
     bhrt_stats *const st;   // or null
+    const PhotonMapDev &M;  // the map the queries walk: the caustic slot's or the global slot's (DeviceState::cmap, gmap)
+    const bool global;      // the statistics are the global gather's (bhrt_stats::global_gather_*), not the caustic term's
     GatherWorkspace &W = D->gw;
     const int lane_budget = D->knobs.gather_lane_budget > 0 ? D->knobs.gather_lane_budget : BHRT_GATHER_LANE_BUDGET; // test knob: a tiny budget sends every query through the selection pass
     const uint32_t *order = nullptr; // the lane pass's queries in cell order; null: index order
@@ -2297,11 +2332,12 @@ struct GatherPass {
     {
         if (cnt == 0) return BHRT_OK;
         BHRT_TRY(W.Reserve(cnt, D->stream));
+        if (global && st) BHRT_TRY(CountAsking());
         BHRT_TRY(OrderByCell());
         BHRT_TRY(LanePass());
         BHRT_TRY(ReadLaneCounters());
         if (n_heavy + n_long == 0) return BHRT_OK;
-        Timer t(D, st ? &st->seconds_photon_heavy : nullptr, 0);
+        Timer t(D, st && !global ? &st->seconds_photon_heavy : nullptr, 0);
         BHRT_TRY(SelectPass());
         BHRT_TRY(ExactReplay(undecided(), n_undecided));
         if (photon_exact) BHRT_TRY(ExactReplay(W.d_heavy, n_heavy));
@@ -2316,6 +2352,16 @@ struct GatherPass {
         HIP_CHECK(hipStreamSynchronize(D->stream));
         return BHRT_OK;
     }
+    // The global gather's query count: the frames of [q0, q0 + cnt) the sink does not skip (the caustic term books every frame, as it always has)
+    int CountAsking()
+    {
+        HIP_CHECK(hipMemsetAsync(&W.d_cnt->n_asking, 0, sizeof(uint32_t), D->stream));
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_gather_count_asking<Sink>), dim3((cnt + kBlock - 1) / kBlock), dim3(kBlock), 0, D->stream, sink, q0, cnt, W.d_cnt.p);
+        HIP_CHECK(hipMemcpyAsync(&W.h_cnt->n_asking, &W.d_cnt->n_asking, sizeof(uint32_t), hipMemcpyDeviceToHost, D->stream));
+        HIP_CHECK(hipStreamSynchronize(D->stream));
+        st->global_gather_queries += W.h_cnt->n_asking;
+        return BHRT_OK;
+    }
     // Morton-cell order of the queries that take part (order, n_walk): a wave's 64 queries then walk the same path
     int OrderByCell()
     {
@@ -2323,18 +2369,18 @@ struct GatherPass {
         const dim3 grid((cnt + kBlock - 1) / kBlock), block(kBlock);
         GatherGrid G;
         for (int k = 0; k < 3; k++) {
-            const float lo = D->pm.lo[k] - radius, hi = D->pm.hi[k] + radius;
+            const float lo = M.lo[k] - radius, hi = M.hi[k] + radius;
             G.lo[k] = lo; G.inv_cell[k] = hi > lo ? (float)(1 << BHRT_GATHER_CELL_BITS) / (hi - lo) : 0.f;
         }
         if (D->knobs.gather_counting_sort) { // the counting sort of rounds 1-3 (BHRT_GATHER_COUNTING_SORT=1: A/B and second opinion)
             HIP_CHECK(hipMemsetAsync(W.d_cells, 0, ((size_t)BHRT_GATHER_CELLS + 1) * sizeof(uint32_t), D->stream));
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_gather_cell_count<Sink>), grid, block, 0, D->stream, sink, q0, cnt, G, D->pm, radius, W.d_cell_of, W.d_rank_of, W.d_cells);
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_gather_cell_count<Sink>), grid, block, 0, D->stream, sink, q0, cnt, G, M, radius, W.d_cell_of, W.d_rank_of, W.d_cells);
             // exclusive scan over the cells and one more entry, which ends up holding the number of queries that take part
             LaunchExclusiveScan(D->stream, W.d_cells, BHRT_GATHER_CELLS + 1, W.d_tile_sums);
             hipLaunchKernelGGL(k_gather_cell_scatter, grid, block, 0, D->stream, q0, cnt, W.d_cell_of, W.d_rank_of, W.d_cells, W.d_gorder);
             HIP_CHECK(hipMemcpyAsync(&W.h_cnt->n_ordered, W.d_cells + BHRT_GATHER_CELLS, sizeof(uint32_t), hipMemcpyDeviceToHost, D->stream));
         } else { // (cell, query) pairs through a stable radix sort: no atomics, the queries of a cell stay in index order
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_gather_cell_key<Sink>), grid, block, 0, D->stream, sink, q0, cnt, G, D->pm, radius, W.d_cell_of, W.d_rank_of);
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_gather_cell_key<Sink>), grid, block, 0, D->stream, sink, q0, cnt, G, M, radius, W.d_cell_of, W.d_rank_of);
             size_t tb = W.sort_temp_bytes;
             if (GatherSortPairs(W.d_cell_of, W.d_keys_out, W.d_rank_of, W.d_gorder, cnt, W.d_sort_temp, &tb, 28, D->stream) != 0) { SetError("gather sort failed"); return BHRT_ERR_HIP; }
             hipLaunchKernelGGL(k_gather_first_out, dim3(1), dim3(1), 0, D->stream, W.d_keys_out, cnt, W.d_cnt);
@@ -2354,7 +2400,7 @@ struct GatherPass {
         BHRT_TRY(Clear(&GatherCounters::lane));
         if (n_walk == 0) return BHRT_OK;
         const auto kernel = D->knobs.gather_stats ? k_photon_gather_fast<Sink, true> : k_photon_gather_fast<Sink, false>;
-        hipLaunchKernelGGL(kernel, dim3((n_walk + kBlock - 1) / kBlock), dim3(kBlock), 0, D->stream, sink, q0, n_walk, order, D->pm, radius, lane_budget, W.d_heavy.p, W.d_long.p, W.d_cnt.p);
+        hipLaunchKernelGGL(kernel, dim3((n_walk + kBlock - 1) / kBlock), dim3(kBlock), 0, D->stream, sink, q0, n_walk, order, M, radius, lane_budget, W.d_heavy.p, W.d_long.p, W.d_cnt.p);
         return BHRT_OK;
     }
     int ReadLaneCounters()
@@ -2363,6 +2409,7 @@ struct GatherPass {
         const GatherCounters::Lane &c = W.h_cnt->lane;
         n_heavy = c.n_heavy; n_long = c.n_long;
         if (!st) return BHRT_OK;
+        if (global) { st->global_gather_heavy_queries += n_heavy; return BHRT_OK; }
         st->photon_found += c.found; // knob "gather_stats" only
         st->photon_queries += cnt; st->photon_wave_queries += n_long; st->photon_heavy_queries += n_heavy;
         st->photon_lane_queries += (uint64_t)n_walk - n_heavy - n_long;
@@ -2378,10 +2425,10 @@ struct GatherPass {
         const uint32_t sel_waves = D->n_cus * BHRT_SEL_WAVES_PER_CU; // persistent one-wave workgroups, each with its scratch (candidates 24 KB + stack spill 48 KB)
         BHRT_TRY(W.d_sel.Reserve((size_t)sel_waves * BHRT_SEL_SCRATCH_WORDS));
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_photon_gather_select<Sink>), dim3(std::min<uint32_t>(n_sel_heavy + n_long, sel_waves)), dim3(64), 0, D->stream, sink, W.d_heavy,
-                           n_sel_heavy, W.d_long, n_long, D->pm, radius, undecided(), W.d_cnt, knn, W.d_sel, photon_exact);
+                           n_sel_heavy, W.d_long, n_long, M, radius, undecided(), W.d_cnt, knn, W.d_sel, photon_exact);
         BHRT_TRY(Fetch(&GatherCounters::select));
         const GatherCounters::Select &c = W.h_cnt->select;
-        if (st) st->photon_nodes_visited += c.visited;
+        if (st && !global) st->photon_nodes_visited += c.visited;
         if (D->knobs.debug_gather)
             fprintf(stderr, "select pass: %u heavy + %u long queries, %llu nodes, %u rounds, %u compactions, %u undecided\n", n_sel_heavy, n_long, c.visited, c.rounds, c.compactions, c.n_undecided);
         n_undecided = c.n_undecided;
@@ -2399,9 +2446,9 @@ struct GatherPass {
         const uint32_t chunk = std::min<uint32_t>(W.scr_lanes, heap_lanes);
         for (uint32_t h0 = 0; h0 < m_all; h0 += chunk) {
             const uint32_t m = std::min<uint32_t>(chunk, m_all - h0);
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_photon_gather_heap<Sink>), dim3((m + kBlock - 1) / kBlock), dim3(kBlock), 0, D->stream, sink, list, h0, m, D->pm, radius, W.d_scr, (size_t)W.scr_lanes, W.d_cnt);
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_photon_gather_heap<Sink>), dim3((m + kBlock - 1) / kBlock), dim3(kBlock), 0, D->stream, sink, list, h0, m, M, radius, W.d_scr, (size_t)W.scr_lanes, W.d_cnt);
         }
-        if (!st) return BHRT_OK;
+        if (!st || global) return BHRT_OK;
         st->photon_exact_queries += m_all;
         BHRT_TRY(Fetch(&GatherCounters::replay));
         st->photon_nodes_visited += W.h_cnt->replay.visited;
@@ -2524,20 +2571,27 @@ static decltype(&k_shadow_mesh<1>) AnyHitMeshKernel(int path_mode, bool ls)
 }
 // fused: the camera step of a scene without meshes, k_shade traces its rays itself (shade_block's kFused).
 // fm: face materials are on (DeviceState::fm); such a scene has a mesh, so its camera step is never the fused one.
-static decltype(&k_shade<true, true>) ShadeKernel(bool fused, bool cam_step, bool tex, bool le, bool fm)
+// kGg: the global gather is on.  kGg = false names exactly the instantiations there were before the gather existed.
+template <bool kGg>
+static decltype(&k_shade<true, true>) ShadeKernelOf(bool fused, bool cam_step, bool tex, bool le, bool fm)
 {
     if (fm && !fused) {
-        if (le && tex) return cam_step ? k_shade<true, true, false, true, true> : k_shade<false, true, false, true, true>;
-        if (cam_step) return tex ? k_shade<true, true, false, false, true> : k_shade<true, false, false, false, true>;
-        return tex ? k_shade<false, true, false, false, true> : k_shade<false, false, false, false, true>;
+        if (le && tex) return cam_step ? k_shade<true, true, false, true, true, kGg> : k_shade<false, true, false, true, true, kGg>;
+        if (cam_step) return tex ? k_shade<true, true, false, false, true, kGg> : k_shade<true, false, false, false, true, kGg>;
+        return tex ? k_shade<false, true, false, false, true, kGg> : k_shade<false, false, false, false, true, kGg>;
     }
     if (le && tex) { // the frames keep a textured Le (DeviceState::le_on)
-        if (fused) return k_shade<true, true, true, true>;
-        return cam_step ? k_shade<true, true, false, true> : k_shade<false, true, false, true>;
+        if (fused) return k_shade<true, true, true, true, false, kGg>;
+        return cam_step ? k_shade<true, true, false, true, false, kGg> : k_shade<false, true, false, true, false, kGg>;
     }
-    if (fused) return tex ? k_shade<true, true, true> : k_shade<true, false, true>;
-    if (cam_step) return tex ? k_shade<true, true> : k_shade<true, false>;
-    return tex ? k_shade<false, true> : k_shade<false, false>;
+    if (fused) return tex ? k_shade<true, true, true, false, false, kGg> : k_shade<true, false, true, false, false, kGg>;
+    if (cam_step) return tex ? k_shade<true, true, false, false, false, kGg> : k_shade<true, false, false, false, false, kGg>;
+    return tex ? k_shade<false, true, false, false, false, kGg> : k_shade<false, false, false, false, false, kGg>;
+}
+// gg: the render gathers from the global map (WavePass::gg)
+static decltype(&k_shade<true, true>) ShadeKernel(bool fused, bool cam_step, bool tex, bool le, bool fm, bool gg)
+{
+    return gg ? ShadeKernelOf<true>(fused, cam_step, tex, le, fm) : ShadeKernelOf<false>(fused, cam_step, tex, le, fm);
 }
 // park: the rays that enter a mesh are left to the mesh walk (a wave step of a scene with meshes).  Without it the kernel walks the whole
 // scene; through meshes only as bhrt_trace_closest_dev launches it, which has no camera form.
@@ -2612,6 +2666,8 @@ struct WavePass {
     // idle — above all the tail of every k_trace_mesh_stream launch (the longest walks of its last batch: 0.1-0.5 ms per wave step).
     const bool sh_overlap;
     const bool lens;           // thin-lens camera: the pass's camera rays come from k_lens_rays (Begin)
+    const bool gg;             // the global gather is on and its map installed: the kGg instantiations of k_shade mark the frames gi < 0 cuts.
+                               // Not a field of RenderParams: a longer kernel argument costs the switch-off camera kernels 20-36 B of scratch per lane
     uint32_t *const root_of;   // fuse_root: k_shade's slot -> root frame map
     const PassViews V;
 
@@ -2643,7 +2699,7 @@ struct WavePass {
     WavePass(bhrt_scene *scene, const bhrt_opts &o, bhrt_stats *stats, const RenderParams &Rp, const PassInfo &Pp, bool fuse_root, TimePoint render_start)
         : D(scene->dev), st(stats), R(Rp), P(Pp), wall0(render_start), meshes(scene->flat.hdr()->n_meshes > 0), tex(scene->flat.hdr()->n_texmaps > 0), ls(o.leaf_skip != 0),
           path_mode(PathMode(scene)), stream_waves(D->knobs.stream_waves >= 0 ? (uint32_t)D->knobs.stream_waves : D->n_cus * 4u * (uint32_t)BHRT_STREAM_OCC),
-          sh_overlap(D->knobs.shadow_overlap && D->stream3 != nullptr && D->d_shf2.p != nullptr), lens(Pp.lens_r > 0.f), root_of(fuse_root ? D->d_root.p : nullptr),
+          sh_overlap(D->knobs.shadow_overlap && D->stream3 != nullptr && D->d_shf2.p != nullptr), lens(Pp.lens_r > 0.f), gg(scene->flat.global_gather != 0 && D->gmap.n_photons > 0), root_of(fuse_root ? D->d_root.p : nullptr),
           V(MakePassViews(D, sh_overlap)), n_cur(Pp.n_pixels * (uint32_t)Pp.spp)
     {
     }
@@ -2794,7 +2850,7 @@ struct WavePass {
         const int par = (int)(pass_steps & 1u);
         if (sh_wait_n) { HIP_CHECK(hipEventRecord(D->ev_shade, D->stream)); BHRT_TRY(LaunchQueuedAnyHit(D->ev_shade)); }
         if (sh_overlap && sh_pending[par]) { HIP_CHECK(hipStreamWaitEvent(D->stream, D->ev_shadow[par], 0)); sh_pending[par] = false; } // the any-hit kernels of two steps ago still read this queue
-        hipLaunchKernelGGL(ShadeKernel(fused, CamStep(), tex, V.F.le != nullptr, V.F.fm.tab != nullptr), sg, sb, 0, D->stream, D->S, R, P, V.Q[cur], V.HB, n_cur + n_extra, V.Q[cur ^ 1], (sh_overlap && par) ? V.SQ2 : V.SQ, V.F, D->d_samples, root_of, D->d_cnt, V.RO, D->d_pub, seq); // + n_next, n_shadow, n_frames, overflow to the host
+        hipLaunchKernelGGL(ShadeKernel(fused, CamStep(), tex, V.F.le != nullptr, V.F.fm.tab != nullptr, gg), sg, sb, 0, D->stream, D->S, R, P, V.Q[cur], V.HB, n_cur + n_extra, V.Q[cur ^ 1], (sh_overlap && par) ? V.SQ2 : V.SQ, V.F, D->d_samples, root_of, D->d_cnt, V.RO, D->d_pub, seq); // + n_next, n_shadow, n_frames, overflow to the host
         t.Stop();
         if (sh_overlap) HIP_CHECK(hipEventRecord(D->ev_shade, D->stream));
         return BHRT_OK;
@@ -2887,18 +2943,18 @@ struct PassSizing {
 // Shade() frames per sample slot: six are provided for (an overflow halves the pass and redoes it).  A frame that does not fit into one pass
 // with six — C4's 2.7e8 samples per GPU — takes what the earlier passes of the same render (scene, options) have needed, + 30 %: C4 needs 1.1
 // frames per sample, and with 1.7 provided its 2^28 slots fit into 180 GB: one pass per frame instead of two.
-static PassSizing SizePasses(DeviceState *D, const bhrt_opts &o, uint64_t n_items, uint32_t spp, int world, int tile)
+static PassSizing SizePasses(DeviceState *D, const bhrt_opts &o, bool ph_frames, uint64_t n_items, uint32_t spp, int world, int tile)
 {
     PassSizing z;
     z.frames_key = RenderKey(o, spp, world, tile);
     z.frames_per_sample = 6.0;
     z.frames_learned = false;
     if (o.samples_per_pass <= 0 && D->frames_seen_key == z.frames_key && D->frames_seen > 0 && D->frames_seen < 4.0 &&
-        n_items * (uint64_t)spp > DefaultPassSamples(D, o.photon_map != 0, 6.0)) {
+        n_items * (uint64_t)spp > DefaultPassSamples(D, ph_frames, 6.0)) {
         z.frames_per_sample = std::min(6.0, D->frames_seen * 1.3 + 0.25);
         z.frames_learned = true;
     }
-    z.pass_samples = o.samples_per_pass > 0 ? (uint32_t)o.samples_per_pass : DefaultPassSamples(D, o.photon_map != 0, z.frames_per_sample);
+    z.pass_samples = o.samples_per_pass > 0 ? (uint32_t)o.samples_per_pass : DefaultPassSamples(D, ph_frames, z.frames_per_sample);
     z.pass_samples = (uint32_t)std::min<uint64_t>(z.pass_samples, std::max<uint64_t>(n_items * (uint64_t)spp, 1)); // never more than this render needs
     if (z.pass_samples < spp) z.pass_samples = spp;
     z.hint_key = z.frames_key ^ ((uint64_t)z.pass_samples << 1);
@@ -2919,7 +2975,10 @@ static int RenderPixels(bhrt_scene *scene, const bhrt_opts &o, PassInfo P, const
     DeviceState *D = scene->dev;
     P.spp = (int32_t)spp; P.by_spp = MakeFastDiv(spp); P.s0 = s0;
     D->le_on = D->emission_on && D->emission_textured; // before the passes are sized: DefaultPassSamples counts the term's 12 B per frame
-    const PassSizing Z = SizePasses(D, o, n_items, spp, P.world, P.tile);
+    // the global gather: the scene's switch, with the map the entry point has checked for (BHRT_CHECK_GLOBAL)
+    const bool gg = scene->flat.global_gather != 0 && D->gmap.n_photons > 0;
+    const bool ph_frames = o.photon_map != 0 || gg; // the frames keep the inputs of a gather (Frames::ph_*)
+    const PassSizing Z = SizePasses(D, o, ph_frames, n_items, spp, P.world, P.tile);
     D->timers = o.timers;
     RenderParams R;
     R.internal_bounces = o.internal_bounces; R.gi_bounces = o.gi_bounces; R.photon = o.photon_map;
@@ -2932,7 +2991,7 @@ static int RenderPixels(bhrt_scene *scene, const bhrt_opts &o, PassInfo P, const
         BHRT_TRY(EnsureWorkspace(D, Z.pass_samples, Z.frames_per_sample));
         R.cap_rays = D->cap_rays; R.cap_shadow = D->cap_rays; R.cap_frames = D->cap_frames;
         if (D->knobs.frame_cap > 0) R.cap_frames = std::min<uint32_t>(R.cap_frames, (uint32_t)D->knobs.frame_cap); // test knob: a pass that overflows
-        if (o.photon_map) BHRT_TRY(D->d_ph_frames.Reserve((size_t)D->cap_frames * 15));
+        if (ph_frames) BHRT_TRY(D->d_ph_frames.Reserve((size_t)D->cap_frames * 15));
         if (D->le_on) BHRT_TRY(D->d_le.Reserve((size_t)D->cap_frames * 3));
         if (pass_limit == 0) pass_limit = Z.pass_samples;
         if (pass_limit > D->cap_samples) pass_limit = D->cap_samples;
@@ -2966,7 +3025,13 @@ static int RenderPixels(bhrt_scene *scene, const bhrt_opts &o, PassInfo P, const
             // per pass, most with a few hundred frames — spent 2 s per frame waiting for single lanes
             Timer t(D, &st->seconds_photon_gather, 0);
             const GatherToFrames sink = {F, D->S.materials};
-            BHRT_TRY((GatherPass<GatherToFrames>{D, sink, 0, n_frames, o.photon_radius > 0.f ? o.photon_radius : 0.5f /* MAX_Area, MtlBlinn.cpp:29 */, o.photon_exact, nullptr, st}.Run()));
+            BHRT_TRY((GatherPass<GatherToFrames>{D, sink, 0, n_frames, o.photon_radius > 0.f ? o.photon_radius : 0.5f /* MAX_Area, MtlBlinn.cpp:29 */, o.photon_exact, nullptr, st, D->cmap.pm, false}.Run()));
+            t.Stop();
+        }
+        if (gg && n_frames > 0) { // G of the frames whose GI term gi < 0 cut (FF_GI_CUT), likewise in one gather per pass, from the global map
+            Timer t(D, &st->seconds_global_gather, 0);
+            const GlobalGatherToFrames sink = {F};
+            BHRT_TRY((GatherPass<GlobalGatherToFrames>{D, sink, 0, n_frames, scene->flat.global_radius, o.photon_exact, nullptr, st, D->gmap.pm, true}.Run()));
             t.Stop();
         }
         st->shade_calls += D->h_pub->n_frames;
@@ -3085,12 +3150,21 @@ static const char *LensArgsError(const bhrt_scene *scene, const bhrt_opts *o)
         if (*bad_) { SetError(bad_); return BHRT_ERR_ARG; }                                                    \
     } while (0)
 
+// The global gather's switch against the installed map, checked before any device is touched and before any kernel is launched
+#define BHRT_CHECK_GLOBAL(scene)                                                                                                                    \
+    do {                                                                                                                                            \
+        if ((scene) && (scene)->flat.global_gather && !((scene)->dev && (scene)->dev->gmap.n_photons)) {                                          \
+            SetError("the global gather is on (bhrt_scene_set_global_gather) but no global map is installed: bhrt_global_map_build or _set first"); \
+            return BHRT_ERR_ARG;                                                                                                                    \
+        }                                                                                                                                           \
+    } while (0)
+
 // What the render entry points share: the photon map that photon_map = 1 needs, and statistics that start at zero and reach the caller also when
 // the render fails.  render(bhrt_stats *) does the work.
 template <class Render>
 static int RenderWithStats(bhrt_scene *scene, const bhrt_opts *opts, bhrt_stats *stats, const Render &render)
 {
-    if (opts->photon_map && !scene->dev->d_photons) { SetError("photon_map = 1 needs bhrt_photon_build first"); return BHRT_ERR_ARG; }
+    if (opts->photon_map && !scene->dev->cmap.d_photons) { SetError("photon_map = 1 needs bhrt_photon_build first"); return BHRT_ERR_ARG; }
     bhrt_stats local;
     memset(&local, 0, sizeof local);
     const int rc = render(&local);
@@ -3376,6 +3450,7 @@ int bhrt_render_var_dev(bhrt_scene *scene, const bhrt_opts *opts, uint8_t *d_rgb
 try {
     (void)stream; // the render pipeline synchronises its own stream per wave step
     BHRT_CHECK_LENS(scene, opts);
+    BHRT_CHECK_GLOBAL(scene);
     int rc = EnsureUploaded(scene);
     if (rc) return rc;
     if (!opts) { SetError("null opts"); return BHRT_ERR_ARG; }
@@ -3395,6 +3470,7 @@ int bhrt_render(bhrt_scene *scene, const bhrt_opts *opts, uint8_t *rgb8, float *
 int bhrt_render_var(bhrt_scene *scene, const bhrt_opts *opts, uint8_t *rgb8, float *radiance, float *variance, bhrt_stats *stats)
 try {
     BHRT_CHECK_LENS(scene, opts);
+    BHRT_CHECK_GLOBAL(scene);
     int rc = EnsureUploaded(scene);
     if (rc) return rc;
     if (!opts) { SetError("null opts"); return BHRT_ERR_ARG; }
@@ -3425,6 +3501,7 @@ try {
     const char *bad = AdaptiveArgsError(opts, aopts);
     if (*bad) { SetError(bad); return BHRT_ERR_ARG; }
     BHRT_CHECK_LENS(scene, opts);
+    BHRT_CHECK_GLOBAL(scene);
     int rc = EnsureUploaded(scene);
     if (rc) return rc;
     return RenderWithStats(scene, opts, stats, [&](bhrt_stats *st) { return RenderAdaptive(scene, *opts, *aopts, d_rgb8, d_radiance, d_variance, d_count, st); });
@@ -3436,6 +3513,7 @@ try {
     const char *bad = AdaptiveArgsError(opts, aopts);
     if (*bad) { SetError(bad); return BHRT_ERR_ARG; }
     BHRT_CHECK_LENS(scene, opts);
+    BHRT_CHECK_GLOBAL(scene);
     int rc = EnsureUploaded(scene);
     if (rc) return rc;
     FrameStage fs = {rgb8, radiance, variance, count};
@@ -3497,6 +3575,7 @@ void bhrt_host_free(void *ptr)
 int bhrt_render_samples(bhrt_scene *scene, const bhrt_opts *opts, int x0, int y0, int x1, int y1, float *samples, bhrt_stats *stats)
 try {
     BHRT_CHECK_LENS(scene, opts);
+    BHRT_CHECK_GLOBAL(scene);
     int rc = EnsureUploaded(scene);
     if (rc) return rc;
     if (!opts || !samples) { SetError("null argument"); return BHRT_ERR_ARG; }
@@ -3841,11 +3920,11 @@ static int BalanceOnDevice(DeviceState *D, const DPhoton *d_in, uint32_t n, DevB
 // them from here on), the decoded hot / cold copy the gather walks (PhotonMapDev), the direction bounds of the top levels and the bounds of the
 // positions are formed on the device.  The map that was installed before stays in place until all of that is there.  The host copy
 // (bhrt_photon_get / _export) is fetched when somebody asks for it.
-static int InstallPhotonMapDev(DeviceState *D, DevBuf<DPhoton> balanced, uint32_t n)
+static int InstallPhotonMapDev(DeviceState *D, PhotonSlot &slot /* D->cmap or D->gmap */, DevBuf<DPhoton> balanced, uint32_t n)
 {
     DevBuf<float4> hot, cold, dbox;
     DevBuf<float> lo, hi, d_b6;
-    PhotonMapDev pm = D->pm;
+    PhotonMapDev pm = slot.pm;
     BHRT_TRY(hot.Reserve((size_t)n + 1));
     BHRT_TRY(cold.Reserve(((size_t)n + 1) * 2));
     hipLaunchKernelGGL(k_photon_expand, dim3((n + 1 + kBlock - 1) / kBlock), dim3(kBlock), 0, D->stream, balanced.p, n, hot.p, cold.p);
@@ -3870,19 +3949,20 @@ static int InstallPhotonMapDev(DeviceState *D, DevBuf<DPhoton> balanced, uint32_
     HIP_CHECK(hipStreamSynchronize(D->stream));
     for (int k = 0; k < 3; k++) { pm.lo[k] = b6[k]; pm.hi[k] = b6[3 + k]; }
     // all of it is there: the new map takes the place of the old one
-    D->d_photons = std::move(balanced); D->d_ph_hot = std::move(hot); D->d_ph_cold = std::move(cold); D->d_ph_dbox = std::move(dbox);
-    D->n_photons = n;
-    D->pm = pm;
-    D->h_photons.clear();
+    slot.d_photons = std::move(balanced); slot.d_ph_hot = std::move(hot); slot.d_ph_cold = std::move(cold); slot.d_ph_dbox = std::move(dbox);
+    slot.n_photons = n;
+    slot.pm = pm;
+    slot.h_photons.clear();
     return BHRT_OK;
 }
-// host copy of the installed map, fetched on demand (bhrt_photon_get / bhrt_photon_export)
-static int EnsureHostPhotons(DeviceState *D)
+// host copy of an installed map, fetched on demand (bhrt_photon_get / bhrt_photon_export / bhrt_global_map_get)
+static int EnsureHostPhotons(DeviceState *D, PhotonSlot &slot)
 {
-    if (!D->h_photons.empty() || !D->d_photons || !D->n_photons) return BHRT_OK;
-    D->h_photons.assign((size_t)D->n_photons + 1, HostPhoton());
-    HIP_CHECK(hipMemcpy(D->h_photons.data(), D->d_photons, ((size_t)D->n_photons + 1) * sizeof(DPhoton), hipMemcpyDeviceToHost));
-    memset(&D->h_photons[0], 0, sizeof(HostPhoton));
+    if (!slot.h_photons.empty() || !slot.d_photons || !slot.n_photons) return BHRT_OK;
+    HIP_CHECK(hipSetDevice(D->device));
+    slot.h_photons.assign((size_t)slot.n_photons + 1, HostPhoton());
+    HIP_CHECK(hipMemcpy(slot.h_photons.data(), slot.d_photons, ((size_t)slot.n_photons + 1) * sizeof(DPhoton), hipMemcpyDeviceToHost));
+    memset(&slot.h_photons[0], 0, sizeof(HostPhoton));
     return BHRT_OK;
 }
 // the balance of n + 1 emission-order records in HBM: on the device, or (BHRT_PHOTON_BALANCE_HOST=1: the tests' second opinion) by photon_host.cpp
@@ -4016,7 +4096,7 @@ try {
     hipLaunchKernelGGL(k_photon_scale, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, D->stream, d.p, n, 1.f / (float)(int)n);
     BHRT_TRY(BalanceRecords(D, d, n, bal)); // the records stay in HBM from the caller's buffer to the installed map
     d.Free();
-    return InstallPhotonMapDev(D, std::move(bal), n);
+    return InstallPhotonMapDev(D, D->cmap, std::move(bal), n);
 } catch (...) { return bhrt::AbiException(); }
 
 int bhrt_photon_build(bhrt_scene *scene, const bhrt_opts *opts, uint32_t max_photons, uint32_t *n_stored)
@@ -4025,8 +4105,8 @@ try {
     DevBuf<DPhoton> bal;
     uint32_t n = 0;
     BHRT_TRY(BuildPhotons(scene, opts, max_photons, false, bal, &n));
-    BHRT_TRY(InstallPhotonMapDev(scene->dev, std::move(bal), n));
-    if (n_stored) *n_stored = scene->dev->n_photons;
+    BHRT_TRY(InstallPhotonMapDev(scene->dev, scene->dev->cmap, std::move(bal), n));
+    if (n_stored) *n_stored = scene->dev->cmap.n_photons;
     return BHRT_OK;
 } catch (...) { return bhrt::AbiException(); }
 
@@ -4056,14 +4136,18 @@ try {
 } catch (...) { return bhrt::AbiException(); }
 
 
-int bhrt_photon_gather_host_ex(bhrt_scene *scene, const float *p, const float *nrm, size_t cnt, float radius, int photon_exact, float *irrad, float *dir,
-                               uint32_t *knn, uint32_t *knn_count, float *d2max)
-try {
+} // extern "C"
+
+// EstimateIrradiance<1000> for cnt host points on the caustic slot (bhrt_photon_gather_host_ex) or the global one (bhrt_global_gather_host)
+static int GatherHost(bhrt_scene *scene, bool global, const float *p, const float *nrm, size_t cnt, float radius, int photon_exact, float *irrad, float *dir,
+                      uint32_t *knn, uint32_t *knn_count, float *d2max)
+{
     int rc = EnsureUploaded(scene);
     if (rc) return rc;
     DeviceState *D = scene->dev;
     D->timers = 0;
-    if (!D->d_photons) { SetError("photon map: call bhrt_photon_build first"); return BHRT_ERR_ARG; }
+    const PhotonSlot &slot = global ? D->gmap : D->cmap;
+    if (!slot.d_photons) { SetError(global ? "global map: call bhrt_global_map_build or bhrt_global_map_set first" : "photon map: call bhrt_photon_build first"); return BHRT_ERR_ARG; }
     if (!p || !nrm || !irrad || !dir) { SetError("null buffer"); return BHRT_ERR_ARG; }
     if (cnt == 0) return BHRT_OK;
     const uint32_t chunk = (knn || knn_count || d2max) ? 1u << 14 : 1u << 20;
@@ -4080,7 +4164,7 @@ try {
         HIP_CHECK(hipMemcpy(d_buf + (size_t)chunk * 3, nrm + c0 * 3, (size_t)m * 3 * sizeof(float), hipMemcpyHostToDevice));
         if (d_knn) HIP_CHECK(hipMemset(d_knn, 0, (size_t)m * kw * sizeof(uint32_t)));
         const GatherToArrays sink = {d_buf, d_buf + (size_t)chunk * 3, d_buf + (size_t)chunk * 6, d_buf + (size_t)chunk * 9};
-        BHRT_TRY((GatherPass<GatherToArrays>{D, sink, 0, m, radius, photon_exact, d_knn, nullptr}.Run()));
+        BHRT_TRY((GatherPass<GatherToArrays>{D, sink, 0, m, radius, photon_exact, d_knn, nullptr, slot.pm, false}.Run()));
         HIP_CHECK(hipStreamSynchronize(D->stream));
         HIP_CHECK(hipMemcpy(irrad + c0 * 3, d_buf + (size_t)chunk * 6, (size_t)m * 3 * sizeof(float), hipMemcpyDeviceToHost));
         HIP_CHECK(hipMemcpy(dir + c0 * 3, d_buf + (size_t)chunk * 9, (size_t)m * 3 * sizeof(float), hipMemcpyDeviceToHost));
@@ -4095,6 +4179,29 @@ try {
         }
     }
     return BHRT_OK;
+}
+// bhrt_photon_get / bhrt_global_map_get
+static int GetPhotons(const bhrt_scene *scene, bool global, void *photons_out, uint32_t capacity, uint32_t *n)
+{
+    if (!scene || !scene->dev || !(global ? scene->dev->gmap : scene->dev->cmap).n_photons) { SetError(global ? "global map: nothing installed" : "photon map: nothing built"); return BHRT_ERR_ARG; }
+    PhotonSlot &slot = global ? scene->dev->gmap : scene->dev->cmap;
+    const int hrc = EnsureHostPhotons(scene->dev, slot);
+    if (hrc) return hrc;
+    const uint32_t have = slot.n_photons;
+    if (n) *n = have;
+    if (photons_out) {
+        if (capacity < have) { SetError("photon buffer too small"); return BHRT_ERR_ARG; }
+        memcpy(photons_out, &slot.h_photons[1], (size_t)have * sizeof(HostPhoton));
+    }
+    return BHRT_OK;
+}
+
+extern "C" {
+
+int bhrt_photon_gather_host_ex(bhrt_scene *scene, const float *p, const float *nrm, size_t cnt, float radius, int photon_exact, float *irrad, float *dir,
+                               uint32_t *knn, uint32_t *knn_count, float *d2max)
+try {
+    return GatherHost(scene, false, p, nrm, cnt, radius, photon_exact, irrad, dir, knn, knn_count, d2max);
 } catch (...) { return bhrt::AbiException(); }
 
 int bhrt_photon_gather_host(bhrt_scene *scene, const float *p, const float *nrm, size_t cnt, float radius, float *irrad, float *dir)
@@ -4104,27 +4211,18 @@ int bhrt_photon_gather_host(bhrt_scene *scene, const float *p, const float *nrm,
 
 int bhrt_photon_get(const bhrt_scene *scene, void *photons_out, uint32_t capacity, uint32_t *n)
 try {
-    if (!scene || !scene->dev || !scene->dev->n_photons) { SetError("photon map: nothing built"); return BHRT_ERR_ARG; }
-    const int hrc = EnsureHostPhotons(scene->dev);
-    if (hrc) return hrc;
-    const uint32_t have = scene->dev->n_photons;
-    if (n) *n = have;
-    if (photons_out) {
-        if (capacity < have) { SetError("photon buffer too small"); return BHRT_ERR_ARG; }
-        memcpy(photons_out, &scene->dev->h_photons[1], (size_t)have * sizeof(HostPhoton));
-    }
-    return BHRT_OK;
+    return GetPhotons(scene, false, photons_out, capacity, n);
 } catch (...) { return bhrt::AbiException(); }
 
 int bhrt_photon_export(const bhrt_scene *scene, const char *dat_path)
 try {
-    if (!scene || !scene->dev || !scene->dev->n_photons || !dat_path) { SetError("photon map: nothing to export"); return BHRT_ERR_ARG; }
-    const int hrc = EnsureHostPhotons(scene->dev);
+    if (!scene || !scene->dev || !scene->dev->cmap.n_photons || !dat_path) { SetError("photon map: nothing to export"); return BHRT_ERR_ARG; }
+    const int hrc = EnsureHostPhotons(scene->dev, scene->dev->cmap);
     if (hrc) return hrc;
     FILE *fp = fopen(dat_path, "wb"); // fwrite(GetPhotons(), sizeof(Photon), NumPhotons(), fp), Main.cpp:383-385
     if (!fp) { SetError(std::string("cannot write ") + dat_path); return BHRT_ERR_IO; }
-    const size_t n = scene->dev->n_photons;
-    const bool ok = fwrite(&scene->dev->h_photons[1], sizeof(HostPhoton), n, fp) == n;
+    const size_t n = scene->dev->cmap.n_photons;
+    const bool ok = fwrite(&scene->dev->cmap.h_photons[1], sizeof(HostPhoton), n, fp) == n;
     fclose(fp);
     if (!ok) { SetError("short write"); return BHRT_ERR_IO; }
     return BHRT_OK;
@@ -4157,11 +4255,59 @@ try {
     if (rebalance) { // InitializePhotonMapByFile runs PrepareForIrradianceEstimation again (cyPhotonMap.h:409-417): on the device like the build's
         BHRT_TRY(BalanceRecords(D, d, (uint32_t)n, bal));
         d.Free();
-        return InstallPhotonMapDev(D, std::move(bal), (uint32_t)n); // the host copy is fetched again when somebody asks for it
+        return InstallPhotonMapDev(D, D->cmap, std::move(bal), (uint32_t)n); // the host copy is fetched again when somebody asks for it
     }
-    BHRT_TRY(InstallPhotonMapDev(D, std::move(d), (uint32_t)n));
-    D->h_photons.swap(h); // the map is installed: its host copy is already there
+    BHRT_TRY(InstallPhotonMapDev(D, D->cmap, std::move(d), (uint32_t)n));
+    D->cmap.h_photons.swap(h); // the map is installed: its host copy is already there
     return BHRT_OK;
+} catch (...) { return bhrt::AbiException(); }
+
+// ---- the global gather: the switch and radius are scene state beside the blob, the map a device slot of its own -------------------
+int bhrt_scene_set_global_gather(bhrt_scene *scene, int on, float radius)
+try {
+    if (!scene) { SetError("bhrt_scene_set_global_gather: null scene"); return BHRT_ERR_ARG; }
+    if (!(radius >= 0.f && radius <= 3.402823466e38f)) { SetError("bhrt_scene_set_global_gather: radius must be finite and >= 0"); return BHRT_ERR_ARG; }
+    scene->flat.global_gather = on ? 1 : 0;
+    scene->flat.global_radius = radius > 0.f ? radius : 0.5f; // MAX_Area, MtlBlinn.cpp:29
+    return BHRT_OK; // nothing to refresh on the device: RenderPixels reads the two per render
+} catch (...) { return bhrt::AbiException(); }
+
+int bhrt_global_map_build(bhrt_scene *scene, const bhrt_opts *opts, uint32_t max_photons, uint32_t *n_stored)
+try {
+    if (!scene) { SetError("null scene"); return BHRT_ERR_ARG; }
+    DevBuf<DPhoton> bal;
+    uint32_t n = 0;
+    BHRT_TRY(BuildPhotons(scene, opts, max_photons, true, bal, &n));
+    BHRT_TRY(InstallPhotonMapDev(scene->dev, scene->dev->gmap, std::move(bal), n));
+    if (n_stored) *n_stored = scene->dev->gmap.n_photons;
+    return BHRT_OK;
+} catch (...) { return bhrt::AbiException(); }
+
+int bhrt_global_map_set(bhrt_scene *scene, const void *balanced_records, uint32_t n)
+try {
+    if (!scene) { SetError("null scene"); return BHRT_ERR_ARG; }
+    if (n == 0) { // removes the map
+        if (scene->dev) { HIP_CHECK(hipSetDevice(scene->dev->device)); scene->dev->gmap.Clear(); }
+        return BHRT_OK;
+    }
+    if (!balanced_records || n > (1u << 28)) { SetError("global map set: bad arguments"); return BHRT_ERR_ARG; }
+    BHRT_TRY(EnsureUploaded(scene));
+    DeviceState *D = scene->dev;
+    DevBuf<DPhoton> d;
+    BHRT_TRY(d.Reserve((size_t)n + 1));
+    HIP_CHECK(hipMemset(d, 0, sizeof(DPhoton))); // slot 0 unused and zero
+    HIP_CHECK(hipMemcpy(d + 1, balanced_records, (size_t)n * sizeof(DPhoton), hipMemcpyDefault)); // host or device source
+    return InstallPhotonMapDev(D, D->gmap, std::move(d), n); // the records are balanced already: used in the order given
+} catch (...) { return bhrt::AbiException(); }
+
+int bhrt_global_map_get(const bhrt_scene *scene, void *photons_out, uint32_t capacity, uint32_t *n)
+try {
+    return GetPhotons(scene, true, photons_out, capacity, n);
+} catch (...) { return bhrt::AbiException(); }
+
+int bhrt_global_gather_host(bhrt_scene *scene, const float *p, const float *nrm, size_t cnt, float radius, int photon_exact, float *irrad, float *dir)
+try {
+    return GatherHost(scene, true, p, nrm, cnt, radius, photon_exact, irrad, dir, nullptr, nullptr, nullptr);
 } catch (...) { return bhrt::AbiException(); }
 
 } // extern "C"

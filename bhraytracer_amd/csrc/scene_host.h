@@ -26,6 +26,10 @@ struct FlatScene {
     std::vector<bhrt_material> sub_materials; // [sub_first[n_materials]]
     std::vector<uint32_t> sub_face_end;       // likewise: faces [sub_face_end[i - 1], sub_face_end[i]) of the mesh shade with sub-material i
     int face_materials = 0;
+    // The global gather, beside the blob too: the switch and the gather radius (bhrt_scene_set_global_gather).  The map itself
+    // is device state (DeviceState::gmap): a clone carries these two and no map.
+    int global_gather = 0;
+    float global_radius = 0.5f; // MAX_Area, MtlBlinn.cpp:29
     const bhrt_flat_header *hdr() const { return reinterpret_cast<const bhrt_flat_header *>(blob.data()); }
 };
 

@@ -65,7 +65,7 @@ typedef struct bhrt_opts {
     /* tile partition: this process renders tiles t with t % world_size == rank */
     int32_t rank, world_size;
     int32_t tile_size;        /* square tile edge in pixels, default 32 */
-    int32_t samples_per_pass; /* upper bound on camera samples in flight per wavefront pass.  Device memory per sample: ~1 KB (1.4 KB with the photon map)
+    int32_t samples_per_pass; /* upper bound on camera samples in flight per wavefront pass.  Device memory per sample: ~1 KB (1.4 KB with the photon map or the global gather)
                                  when six Shade() frames are provided per sample slot.  0 = choose: what the frame needs, at most 2^28 slots, halved until
                                  the workspace fits into 85 % of the free memory — with six frames per slot that is 2^27 (~138 GB / 186 GB); a frame too
                                  large for one such pass (config 4: 2.65e8 samples per GPU) provides the frames per slot its earlier passes needed + 30 %
@@ -111,6 +111,10 @@ typedef struct bhrt_stats {
      * (bhrt_scene_knob: a statistics instantiation of the kernel, 7 % slower) — the photons those answers were made of */
     uint64_t photon_lane_queries, photon_lane_nodes, photon_found;
     uint64_t launches_resolve_fused; /* passes whose root frames were resolved straight into the image (k_resolve_frames, knob "fused_resolve") */
+    /* the global gather (bhrt_scene_set_global_gather): EstimateIrradiance<1000> on the global map where gi < 0 cuts the GI term */
+    uint64_t global_gather_queries;       /* Shade() frames that asked for the global term */
+    uint64_t global_gather_heavy_queries; /* queries that met 1000 photons */
+    double seconds_global_gather;         /* wall clock of the gather of every pass, HIP events */
 } bhrt_stats;
 
 /* compact hit record written by the trace kernel (SoA on the device: one array per field) */
@@ -179,6 +183,19 @@ int bhrt_scene_get_material_emission(const bhrt_scene *scene, int32_t material, 
  *                        byte) and the end of its face range; out / face_end may be NULL; material or sub out of range: BHRT_ERR_ARG */
 struct bhrt_material;
 int bhrt_scene_set_face_materials(bhrt_scene *scene, int on);
+/* The global gather: indirect light from the global photon map where the GI recursion ends.  PathTracing_GlobalIllumination returns
+ * black when its bounce budget is spent (i_GIbounceCount < 0, MtlBlinn.cpp:386); with the switch on and a global map installed it returns there
+ *     (E, vL) = EstimateIrradiance<1000>(radius, hInfo.p, &hInfo.N) on the global map          (cyPhotonMap.h:332-382)
+ *     G       = -vL . vN > 0 ? clamp(Color::Black() + diffuse.Sample(uvw, duvw) * E) : black;   black where G.r is NaN or no photon is found
+ * and Shade() goes on as it does behind any GI term: outColor += G, the early return at white, the direct and caustic terms, the clamp, the NaN
+ * replacement, Le.  Frames that open a GI child (gi >= 0) are unchanged, so gi_bounces = 0 adds multi-bounce indirect light behind one GI ray per
+ * sample, and gi_bounces = -1 shows the map at the first hit.  Frames of a node without material or with an empty MultiMtl get nothing; with face
+ * materials on, diffuse is the hit face's sub-material.  The caustic map (bhrt_opts.photon_map) is independent; bhrt_opts.photon_exact selects the
+ * heavy-query path of both gathers.  The switch and radius live beside the flat blob: bhrt_scene_flat's bytes do not change, bhrt_scene_clone
+ * carries them (not the map, which is device state), and bhrt_opts has no field for them.  Needs no device.
+ *   on != 0: all later bhrt_render*, _samples, _var*, _adaptive* of this scene; they return BHRT_ERR_ARG, before any kernel is launched, while no
+ *   global map is installed.  radius: 0 = the reference's MAX_Area, 0.5 (MtlBlinn.cpp:29); negative or not finite: BHRT_ERR_ARG.  Default: off */
+int bhrt_scene_set_global_gather(bhrt_scene *scene, int on, float radius);
 int bhrt_scene_submaterial_count(const bhrt_scene *scene, int32_t material, int32_t *n);
 int bhrt_scene_get_submaterial(const bhrt_scene *scene, int32_t material, int32_t sub, struct bhrt_material *out, uint32_t *face_end);
 
@@ -236,11 +253,23 @@ int bhrt_photon_emit_range(bhrt_scene *scene, const bhrt_opts *opts, int global_
                            uint32_t *n_photons);
 int bhrt_photon_install(bhrt_scene *scene, const void *records_emission_order /* host or device pointer */, uint32_t n);
 /* The reference's second map, BuildPhotonMap (Main.cpp:251-295; TracePhotonRay Main.cpp:296-317, RandomPhotonBounce
- * MtlBlinn.cpp:140-202): photons that survive diffuse and specular bounces.  Its only call is commented out in the reference
- * (Main.cpp:196) and nothing gathers from it, so it is built on request and handed back: balanced 24-byte records into
- * photons_out (capacity records; may be NULL) and / or written like Resource/photonmap.dat (dat_path, may be NULL). */
+ * MtlBlinn.cpp:140-202): photons that survive diffuse and specular bounces, stored from the second hit on (indirect light only).
+ * Its only call is commented out in the reference (Main.cpp:196) and the reference never gathers from it.  This call builds it
+ * on request and hands it back, installing nothing: balanced 24-byte records into photons_out (capacity records; may be NULL)
+ * and / or written like Resource/photonmap.dat (dat_path, may be NULL).  The global gather (bhrt_scene_set_global_gather) reads
+ * the map that bhrt_global_map_build / _set install. */
 int bhrt_photon_build_global(bhrt_scene *scene, const bhrt_opts *opts, uint32_t max_photons, void *photons_out, uint32_t capacity, uint32_t *n_stored,
                              const char *dat_path);
+/* The global map's own device slot; the caustic map of bhrt_photon_build / _install / _import is not touched by any of these.
+ *   build        BuildPhotonMap as bhrt_photon_build_global runs it (same records), balanced and left installed; *n_stored may be NULL
+ *   set          installs n balanced 24-byte records as they are (what bhrt_photon_build_global or bhrt_global_map_get returned); host or device
+ *                pointer; n = 0 removes the map
+ *   get          mirrors bhrt_photon_get
+ *   gather_host  bhrt_photon_gather_host_ex on this slot: the estimate alone (test hook) */
+int bhrt_global_map_build(bhrt_scene *scene, const bhrt_opts *opts, uint32_t max_photons, uint32_t *n_stored);
+int bhrt_global_map_set(bhrt_scene *scene, const void *balanced_records, uint32_t n);
+int bhrt_global_map_get(const bhrt_scene *scene, void *photons_out /* 24 B records, balanced order */, uint32_t capacity, uint32_t *n);
+int bhrt_global_gather_host(bhrt_scene *scene, const float *p, const float *n, size_t cnt, float radius, int photon_exact, float *irrad, float *dir);
 int bhrt_photon_gather_host(bhrt_scene *scene, const float *p, const float *n, size_t cnt, float radius, float *irrad, float *dir);
 /* same with the choice of bhrt_opts.photon_exact, and (test hook, any pointer may be NULL) the photons the estimate used: knn = cnt x 1000
  * indices into the balanced map (1-based, unsorted, unused slots 0), knn_count = how many, d2max = np.dist2[0] at the end of LocatePhotons.
