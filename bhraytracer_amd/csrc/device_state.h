@@ -197,6 +197,7 @@ struct DeviceState : DeviceQueues {
         bool gather_counting_sort = false; // BHRT_GATHER_COUNTING_SORT=1: the cell order by the counting sort instead of the radix sort of pairs
         bool shadow_overlap = true;     // BHRT_SHADOW_OVERLAP=0: the any-hit kernels of a wave step on the pass's own stream, in front of the next step
         bool fused_resolve = true;      // BHRT_FUSED_RESOLVE=0, knob "fused_resolve": a plain render resolves through the sample buffer (k_combine's root level + k_resolve)
+        bool finish_misses = true;      // BHRT_FINISH_MISSES=0, knob "finish_misses": k_trace_closest files the rays that left the scene for k_shade like every other ray
         int gather_stats = 0;           // knob "gather_stats": the lane pass counts the photons its answers are made of (bhrt_stats.photon_found), 7 % slower
         void FromEnv()
         {
@@ -208,6 +209,7 @@ struct DeviceState : DeviceQueues {
             if (const char *e = getenv("BHRT_GATHER_COUNTING_SORT")) gather_counting_sort = atoi(e) != 0;
             if (const char *e = getenv("BHRT_SHADOW_OVERLAP")) shadow_overlap = atoi(e) != 0;
             if (const char *e = getenv("BHRT_FUSED_RESOLVE")) fused_resolve = atoi(e) != 0;
+            if (const char *e = getenv("BHRT_FINISH_MISSES")) finish_misses = atoi(e) != 0;
         }
     } knobs;
     // a capacity overflow halves the pass (RenderPixels); later frames of the same scene and options start from the reduced size

@@ -302,6 +302,24 @@ __device__ inline uint32_t shading_class(uint32_t meta, const Hit &hit)
     }
     return heavy ? RC_HEAVY : ((kind == RK_REFR_IN && is_hit) ? RC_MEDIUM : RC_LIGHT);
 }
+// The GI term of frame `owner` whose GI ray (direction d) left the scene: environment * the frame's GI multiplier, PathTracing_GlobalIllumination
+// (MtlBlinn.cpp:408-433).  ONE copy: k_shade and k_trace_closest, which finishes such a ray where it is traced, owe each other the same operations
+// in the same order.  kTex = false: the environment is a plain colour (the only form k_trace_closest is launched for).
+template <bool kTex>
+__device__ inline void gi_miss(const DevScene &S, const float *gi_mult, float *gi, uint32_t owner, V3 d)
+{
+    const V3 mult = ld3i(gi_mult, owner);
+    V3 outc = v3(0, 0, 0);
+    if (d.x == d.y && d.x == 0) {
+        outc = outc + v3(1.0f, 0.0f, 1.0f); // MtlBlinn.cpp:411-415
+    } else {
+        V3 env = (kTex ? sample_environment(S, S.environment, d) : ld3(S.environment.color)) * mult;
+        if (!(isnan_f(env.x) || isnan_f(env.y) || isnan_f(env.z))) outc = outc + env;
+    }
+    if (isnan_f(outc.x)) outc = v3(1.0f, 0.0f, 1.0f);
+    else outc = clamp_white(outc);
+    st3(gi, owner, outc);
+}
 
 // Closest hit of every queued ray.  meta == nullptr: every ray uses `uniform_side` (public bhrt_trace_closest_*).
 // kPark (scenes with meshes, render path): rays that reach a mesh whose root box they hit are parked on list RC_MESH
@@ -316,10 +334,20 @@ struct SlowQueue {
     uint32_t cap;
 };
 constexpr uint32_t kSlowCap = 1u << 16; // per pass; rays beyond it are simply traced in their own wave step
+// Misses finished here (the render path, DESIGN.md 4 "Finish misses"; uniform per launch, all three pointers null = every ray is filed): a ray that
+// was walked to the end in this kernel — not parked, not set aside — and hit nothing needs no hit record, no order entry and no place in k_shade:
+//   RK_GI      fin_gi[owner] = gi_miss (owner = the ray's frame), what k_shade stores for it.  The host only asks for it when the environment is a plain colour.
+//   RK_CAMERA  fin_root[slot] = kNoRootFrame (fin_root = the slot -> root frame map of a pass that has one; k_resolve_frames forms the background value).
+// Refraction rays that miss, GI hits within the bias, parked rays whose walk misses later and set-aside rays go the way they went.  Three pointers, not
+// the Frames struct: longer argument lists have cost kernels scratch.
+// Waves per SIMD: the parking instantiations sat at exactly the 100 scalar registers that eight waves allow, by the allocator's luck and not by any bound; with
+// the three pointers it took 102 and the kernel fell to seven.  Bounded to 7..8 it takes 94 (the camera form keeps one 64-bit mask in a vector register's
+// lanes; no scratch).  The other instantiations get the target's whole range, 1..8 (gfx950 holds at most eight waves per SIMD), and keep their code.
 template <bool kPark, bool kCamera, bool kMeshes = true>
-__global__ void __launch_bounds__(kBlock) k_trace_closest(DevScene S, PassInfo P, RayQueue q, uint32_t n, int uniform_side, HitBuf h, RayOrder ord, Counters *cnt,
-                                                          SlowQueue slow /* cap 0: nothing is set aside */)
+__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kPark ? 7 : 1, 8))) k_trace_closest(DevScene S, PassInfo P, RayQueue q, uint32_t n, int uniform_side, HitBuf h, RayOrder ord, Counters *cnt,
+                                                          SlowQueue slow /* cap 0: nothing is set aside */, const float *fin_gi_mult, float *fin_gi, uint32_t *fin_root)
 {
+    constexpr bool kFinish = kPark || !kMeshes; // the instantiations of a wave step; <false, false, true> only serves the public trace API
     __shared__ bhrt_bvh_node nodelet[(kPark || !kMeshes) ? 1 : BHRT_LDS_NODES]; // top BVH levels of the mesh being traversed (device_trace.h)
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     bool active = i < n;
@@ -343,6 +371,20 @@ __global__ void __launch_bounds__(kBlock) k_trace_closest(DevScene S, PassInfo P
             slow.q.rng_ctr[k] = (kCamera || (meta & 15u) == RK_GI) ? 0u : q.rng_ctr[i];
             active = false; // not a ray of this wave step any more: neither finished nor filed for shading
             parked = -1;
+        }
+    }
+    if (kFinish && active && !dead && parked < 0 && hit.node < 0) {
+        const uint32_t kind = meta & 15u;
+        if (!kCamera && kind == RK_GI && fin_gi) {
+            // gi_mult[owner] was written by the previous step's k_shade, which has ended before this launch starts on the same stream; the any-hit
+            // kernels beside this one (stream3) touch the frames' visibilities only
+            gi_miss<false>(S, fin_gi_mult, fin_gi, q.frame[i], d);
+            active = false; // finished: no hit record, no order entry
+        } else if (kind == RK_CAMERA && fin_root) {
+            uint32_t slot = i;
+            if (!kCamera) slot = q.frame[i]; // a lens ray from the queue
+            fin_root[slot] = kNoRootFrame;
+            active = false;
         }
     }
     if (active) { h.t[i] = hit.t; h.node[i] = hit.node; h.prim[i] = hit.prim; h.front[i] = hit.front | ((parked + 1) << 8); }
@@ -1115,19 +1157,12 @@ __device__ __forceinline__ void shade_block(const DevScene &S, const RenderParam
                 st3(samples, sample_addr(P, owner), kTex ? tc_sample(S, S.background, v3((float)pi / S.cam.width, (float)pj / S.cam.height, 0.0f)) : ld3(S.background.color));
             }
         } else if (kind == RK_GI) {
-            V3 mult = ld3i(F.gi_mult, owner);
-            V3 outc = v3(0, 0, 0);
             if (is_hit) {
-                outc = outc + v3(0, 0, 0) * mult; // |z| <= Bias: indirect stays black (MtlBlinn.cpp:398-406)
-            } else if (d.x == d.y && d.x == 0) {
-                outc = outc + v3(1.0f, 0.0f, 1.0f); // MtlBlinn.cpp:411-415
-            } else {
-                V3 env = (kTex ? sample_environment(S, S.environment, d) : ld3(S.environment.color)) * mult;
-                if (!(isnan_f(env.x) || isnan_f(env.y) || isnan_f(env.z))) outc = outc + env;
-            }
-            if (isnan_f(outc.x)) outc = v3(1.0f, 0.0f, 1.0f);
-            else outc = clamp_white(outc);
-            st3(F.gi, owner, outc);
+                V3 outc = v3(0, 0, 0) + v3(0, 0, 0) * ld3i(F.gi_mult, owner); // |z| <= Bias: indirect stays black (MtlBlinn.cpp:398-406)
+                if (isnan_f(outc.x)) outc = v3(1.0f, 0.0f, 1.0f);
+                else outc = clamp_white(outc);
+                st3(F.gi, owner, outc);
+            } else gi_miss<kTex>(S, F.gi_mult, F.gi, owner, d); // the misses k_trace_closest did not finish itself: parked, set aside, or a textured environment
         } else if (kind == RK_REFR_IN) {
             if (!is_hit) {
                 st3(F.refr, owner, v3(1.0f, 0.0f, 1.0f)); // RefractionRecusive returns NANPurple (MtlBlinn.cpp:517)
@@ -1208,12 +1243,19 @@ template <bool kCamera, bool kTex, bool kFused = false, bool kLe = false, bool k
 __global__ void __launch_bounds__(kShadeBlock, BHRT_SHADE_WAVES) k_shade(DevScene S, RenderParams R, PassInfo P, RayQueue qin, HitBuf hb, uint32_t n, RayQueue qout,
                                                    ShadowQueue qs, Frames F, float *samples, uint32_t *root_of, Counters *cnt, RayOrder ord, HostCounters *pub, uint32_t seq)
 {
+    // The grid is sized on the host from the step's queue length; the shading order may hold far fewer rays (k_trace_closest finishes the misses itself).  The
+    // workgroups beyond its last segment leave at once and take no ticket — with the segment lookup, the barrier and a ticket on the one counter line an empty
+    // workgroup cost what a workgroup of misses had cost (measured: profiles/r07/README.md) — and the last of the others publishes.  Nothing filed at all:
+    // workgroup 0 alone.
+    constexpr uint32_t kSegs = 3 * BHRT_ORDER_SHARDS;
+    if (!kFused && blockIdx.x >= max(1u, ord.seg_start[kSegs])) return; // uniform per workgroup
     shade_block<kCamera, kTex, kFused, kLe, kFm, kGg>(S, R, P, qin, hb, n, qout, qs, F, samples, root_of, cnt, ord);
     if (!pub) return;
     __syncthreads(); // every wave is through: its queue counters were added to by returning atomics whose results it has used (block_alloc), its
     // capacity flags likewise (flag_overflow) — all acknowledged.  No agent-scope fence: only counters travel, all by atomics at agent scope; a release
     // fence here writes the XCD's whole L2 back, per workgroup (measured: C2 frame 4.9 -> 9.8 ms).
-    if (threadIdx.x == 0 && atomicAdd(&cnt->shade_done.v, 1u) == gridDim.x - 1u) {
+    const uint32_t n_wg = kFused ? gridDim.x : max(1u, min(gridDim.x, ord.seg_start[kSegs])); // the workgroups that take a ticket
+    if (threadIdx.x == 0 && atomicAdd(&cnt->shade_done.v, 1u) == n_wg - 1u) {
         __hip_atomic_store(&cnt->shade_done.v, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); // for the next step's launch
         publish_counters(cnt, pub, seq);
     }
@@ -2669,6 +2711,9 @@ struct WavePass {
     const bool gg;             // the global gather is on and its map installed: the kGg instantiations of k_shade mark the frames gi < 0 cuts.
                                // Not a field of RenderParams: a longer kernel argument costs the switch-off camera kernels 20-36 B of scratch per lane
     uint32_t *const root_of;   // fuse_root: k_shade's slot -> root frame map
+    // k_trace_closest finishes the unparked GI and camera misses itself (knob "finish_misses"), for a whole render or not at all: the value of a GI miss must
+    // not need texture code in that kernel, so only with a plain-colour <environment>.  (The background is not evaluated there: k_resolve_frames forms it.)
+    const bool finish;
     const PassViews V;
 
     // the wave step
@@ -2700,7 +2745,7 @@ struct WavePass {
         : D(scene->dev), st(stats), R(Rp), P(Pp), wall0(render_start), meshes(scene->flat.hdr()->n_meshes > 0), tex(scene->flat.hdr()->n_texmaps > 0), ls(o.leaf_skip != 0),
           path_mode(PathMode(scene)), stream_waves(D->knobs.stream_waves >= 0 ? (uint32_t)D->knobs.stream_waves : D->n_cus * 4u * (uint32_t)BHRT_STREAM_OCC),
           sh_overlap(D->knobs.shadow_overlap && D->stream3 != nullptr && D->d_shf2.p != nullptr), lens(Pp.lens_r > 0.f), gg(scene->flat.global_gather != 0 && D->gmap.n_photons > 0), root_of(fuse_root ? D->d_root.p : nullptr),
-          V(MakePassViews(D, sh_overlap)), n_cur(Pp.n_pixels * (uint32_t)Pp.spp)
+          finish(D->knobs.finish_misses && scene->flat.hdr()->environment.map < 0), V(MakePassViews(D, sh_overlap)), n_cur(Pp.n_pixels * (uint32_t)Pp.spp)
     {
     }
 
@@ -2733,7 +2778,8 @@ struct WavePass {
         HIP_CHECK(hipMemsetAsync(D->d_cnt, 0, sizeof(Counters), D->stream));
         // d_samples needs no clearing: every slot of a valid pixel is written exactly once (k_shade: background of a camera
         // miss; k_combine: root frame), and k_resolve never reads the slots of edge-tile pixels outside the image.  The same holds for
-        // d_root and k_resolve_frames — also in a pass that overflowed and is redone: its k_shade launches write every entry again
+        // d_root (k_shade, and k_trace_closest for the misses it finishes itself) and k_resolve_frames — also in a pass that overflowed and is redone: its
+        // launches of both kernels write every entry again
         // Thin-lens camera: k_lens_rays writes the pass's camera rays into the queue (one per slot, dead slots included: the queue holds two rays per
         // sample slot) and the first step runs the kernels of every later step, key sort included — lens rays of one pixel enter a mesh less
         // coherently than pinhole rays.  Inside the pass, so a pass that overflows and is redone in halves forms its rays again.
@@ -2798,7 +2844,7 @@ struct WavePass {
             Timer t(D, &st->seconds_trace_closest);
             const SlowQueue no_slow = {V.slowq.q, 0u};
             if (meshes) BHRT_TRY(TraceThroughMeshes());
-            else hipLaunchKernelGGL(ClosestKernel(false, CamStep(), false), dim3((n_cur + kBlock - 1) / kBlock), dim3(kBlock), 0, D->stream, D->S, P, V.Q[cur], n_cur, 0, V.HB, RO, D->d_cnt, no_slow);
+            else hipLaunchKernelGGL(ClosestKernel(false, CamStep(), false), dim3((n_cur + kBlock - 1) / kBlock), dim3(kBlock), 0, D->stream, D->S, P, V.Q[cur], n_cur, 0, V.HB, RO, D->d_cnt, no_slow, finish ? V.F.gi_mult : nullptr, finish ? V.F.gi : nullptr, finish ? root_of : nullptr);
             t.Stop();
         }
         if (n_extra) hipLaunchKernelGGL(k_file_all, dim3(kFileAllBlocks(n_cur, n_cur + n_extra)), dim3(kBlock), 0, D->stream, V.Q[cur], V.HB, n_cur, n_cur + n_extra, RO, D->d_cnt);
@@ -2817,7 +2863,7 @@ struct WavePass {
         const dim3 tg((n_cur + kBlock - 1) / kBlock), tb(kBlock);
         const uint32_t n_buckets = 1u << BHRT_PARK_KEY_BITS;
         if (!cam_step) HIP_CHECK(hipMemsetAsync(RO.park_bucket, 0, n_buckets * sizeof(uint32_t), D->stream)); // the trace kernel counts the keys as it parks
-        hipLaunchKernelGGL(ClosestKernel(true, cam_step, true), tg, tb, 0, D->stream, D->S, P, V.Q[cur], n_cur, 0, V.HB, RO, D->d_cnt, V.slowq);
+        hipLaunchKernelGGL(ClosestKernel(true, cam_step, true), tg, tb, 0, D->stream, D->S, P, V.Q[cur], n_cur, 0, V.HB, RO, D->d_cnt, V.slowq, finish ? V.F.gi_mult : nullptr, finish ? V.F.gi : nullptr, finish ? root_of : nullptr);
         hipLaunchKernelGGL(k_mesh_prefix, dim3(1), dim3(64), 0, D->stream, D->d_cnt, RO);
         if (!cam_step) { // counting sort of the parked rays by coherence key (the camera step keeps slot order)
             const dim3 pg(std::min<uint32_t>(tg.x + BHRT_ORDER_SHARDS, 4096u));
@@ -3233,7 +3279,8 @@ try {
 
 // Knobs: "shadow_overlap" — 0: the any-hit kernels of a wave step run on the pass's own stream, in front of the next step (bench.py times the kernel
 // groups alone that way; same results either way); "fused_resolve" — 0: a plain render ends in the root level of k_combine and k_resolve, through the
-// sample buffer, instead of k_resolve_frames (the A/B of tests/test_resolve_fused.py and of a profile).  Test knobs (tests/): "frame_cap" — a frame pool of that many Shade() frames, so that a pass overflows and is redone in halves; "gather_lane_budget" —
+// sample buffer, instead of k_resolve_frames (the A/B of tests/test_resolve_fused.py and of a profile); "finish_misses" — 0: k_trace_closest files every ray for
+// k_shade, the rays that left the scene included, instead of finishing those itself (the A/B of tests/test_finish_misses.py and of a profile).  Test knobs (tests/): "frame_cap" — a frame pool of that many Shade() frames, so that a pass overflows and is redone in halves; "gather_lane_budget" —
 // photons a lane of the gather's first pass may visit before its query is handed to a whole wave.  0 switches a knob off.  Neither changes a result,
 // and no environment variable sets them: a stray variable in a user's environment cannot send a render through the retry path.
 int bhrt_scene_knob(bhrt_scene *scene, const char *name, int value)
@@ -3246,6 +3293,7 @@ try {
     else if (!strcmp(name, "gather_stats")) scene->dev->knobs.gather_stats = value;
     else if (!strcmp(name, "shadow_overlap")) scene->dev->knobs.shadow_overlap = value != 0;
     else if (!strcmp(name, "fused_resolve")) scene->dev->knobs.fused_resolve = value != 0;
+    else if (!strcmp(name, "finish_misses")) scene->dev->knobs.finish_misses = value != 0;
     else { SetError(std::string("knob: unknown name ") + name); return BHRT_ERR_ARG; }
     return BHRT_OK;
 } catch (...) { return bhrt::AbiException(); }
@@ -3385,7 +3433,7 @@ try {
     RayOrder no_order = {nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     auto closest_kernel = ClosestKernel(false, false, scene->flat.hdr()->n_meshes > 0);
     hipLaunchKernelGGL(closest_kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, s,
-                       scene->dev->S, PassInfo(), q, (uint32_t)n, hit_side, h, no_order, (Counters *)nullptr, SlowQueue{q, 0u});
+                       scene->dev->S, PassInfo(), q, (uint32_t)n, hit_side, h, no_order, (Counters *)nullptr, SlowQueue{q, 0u}, (const float *)nullptr, (float *)nullptr, (uint32_t *)nullptr);
     HIP_CHECK(hipGetLastError());
     if (!stream) HIP_CHECK(hipStreamSynchronize(s));
     return BHRT_OK;

@@ -204,9 +204,11 @@ int bhrt_scene_upload(bhrt_scene *scene, int device); /* copies the flat scene i
 /* knobs of an uploaded scene: they steer which internal path a render takes, never its result.  Test knobs "frame_cap", "gather_lane_budget" (0 = off) and
  * "gather_stats"; "shadow_overlap" (default 1; 0 = the any-hit kernels of a wave step run in front of the next step on the pass's own stream instead of
  * beside it on a second one: the kernel groups timed alone, bench.py's `frac_alone`); "fused_resolve" (default 1; 0 = a render that asks for the image
- * alone ends in the root level of k_combine and k_resolve, through the per-sample buffer, like every other render, instead of k_resolve_frames).
+ * alone ends in the root level of k_combine and k_resolve, through the per-sample buffer, like every other render, instead of k_resolve_frames);
+ * "finish_misses" (default 1; 0 = the closest-hit kernel files the rays that left the scene for the shading kernel, like every other ray, instead of
+ * storing their value itself).
  * The library reads its development switches (BHRT_STREAM_WAVES, BHRT_FUSED_CAMERA, BHRT_NO_SLOW_QUEUE, BHRT_DEBUG_*, BHRT_PHOTON_BALANCE_HOST,
- * BHRT_GATHER_COUNTING_SORT, BHRT_SHADOW_OVERLAP, BHRT_FUSED_RESOLVE) from the environment once, at upload; the test knobs are not reachable from the environment at
+ * BHRT_GATHER_COUNTING_SORT, BHRT_SHADOW_OVERLAP, BHRT_FUSED_RESOLVE, BHRT_FINISH_MISSES) from the environment once, at upload; the test knobs are not reachable from the environment at
  * all.  tests/test_switch_paths.py holds every switch to "never its result" (DESIGN.md 5). */
 int bhrt_scene_knob(bhrt_scene *scene, const char *name, int value);
 int bhrt_device_count(int *n);
