@@ -62,6 +62,12 @@ class AdaptiveOpts(C.Structure):
     _fields_ = [("min_spp", C.c_int32), ("threshold", C.c_float), ("floor", C.c_float), ("reserved", C.c_int32 * 5)]
 
 
+class Progress(C.Structure):
+    """bhrt_progress: where a progressive session stands (bhrt_progressive_status)."""
+    _fields_ = [("steps", C.c_uint32), ("spp_min", C.c_uint32), ("spp_max", C.c_uint32), ("active_pixels", C.c_uint64),
+                ("camera_samples", C.c_uint64), ("finished", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
 class Hits(C.Structure):
     _fields_ = [("t", C.c_void_p), ("node", C.c_void_p), ("prim", C.c_void_p), ("front", C.c_void_p)]
 
@@ -85,6 +91,8 @@ EXPORTS = [
     "bhrt_scene_set_emissive", "bhrt_scene_material_index", "bhrt_scene_set_material_emission", "bhrt_scene_get_material_emission",
     "bhrt_scene_set_face_materials", "bhrt_scene_submaterial_count", "bhrt_scene_get_submaterial",
     "bhrt_scene_set_global_gather", "bhrt_global_map_build", "bhrt_global_map_set", "bhrt_global_map_get", "bhrt_global_gather_host",
+    "bhrt_progressive_begin", "bhrt_progressive_step", "bhrt_progressive_frame", "bhrt_progressive_frame_dev", "bhrt_progressive_status",
+    "bhrt_progressive_end",
 ]
 
 
@@ -167,6 +175,7 @@ class Scene:
         self._flat = None
 
     def close(self):
+        """bhrt_scene_free: the scene, its device state and an open progressive session with it."""
         if self._h:
             lib().bhrt_scene_free(self._h)
             self._h = C.c_void_p()
@@ -395,6 +404,48 @@ class Scene:
         _check(lib().bhrt_render_adaptive_dev(self._h, C.byref(opts), C.byref(aopts), v(d_rgb8_ptr), v(d_radiance_ptr), v(d_variance_ptr), v(d_count_ptr),
                                               C.byref(st), None))
         return st
+
+    # ---- progressive rendering: the frame as a session that steps advance and that can be read at any point ----------------
+    def progressive_begin(self, opts: Opts, aopts: AdaptiveOpts = None):
+        """bhrt_progressive_begin: opens the scene's session; opts.spp is the per-pixel maximum, aopts (None = uniform) the retirement test."""
+        _check(lib().bhrt_progressive_begin(self._h, C.byref(opts), C.byref(aopts) if aopts is not None else None))
+
+    def progressive_step(self, n: int) -> Stats:
+        """bhrt_progressive_step: n more samples for every active pixel (up to the maximum); returns that step's Stats."""
+        st = Stats()
+        _check(lib().bhrt_progressive_step(self._h, int(n), C.byref(st)))
+        return st
+
+    def progressive_frame(self, variance=True, count=True):
+        """bhrt_progressive_frame: the session's frame now, (rgb8 (H, W, 3) uint8, radiance (H, W, 3), variance (H, W, 3) float32 or None,
+        count (H, W) uint32 or None); pixels of other ranks' tiles stay 0."""
+        W, H = self.width, self.height
+        rgb = np.zeros((H, W, 3), np.uint8)
+        rad = np.zeros((H, W, 3), np.float32)
+        var = np.zeros((H, W, 3), np.float32) if variance else None
+        cnt = np.zeros((H, W), np.uint32) if count else None
+        _check(lib().bhrt_progressive_frame(self._h, _ptr(rgb), _ptr(rad), _ptr(var) if variance else None, _ptr(cnt) if count else None))
+        return rgb, rad, var, cnt
+
+    def progressive_frame_into(self, rgb=None, rad=None, var=None, cnt=None):
+        """bhrt_progressive_frame into the caller's host arrays (None = not wanted): pixels of other ranks' tiles keep what the arrays hold."""
+        p = lambda x: _ptr(x) if x is not None else None  # noqa: E731
+        _check(lib().bhrt_progressive_frame(self._h, p(rgb), p(rad), p(var), p(cnt)))
+
+    def progressive_frame_dev(self, d_rgb8_ptr: int = 0, d_radiance_ptr: int = 0, d_variance_ptr: int = 0, d_count_ptr: int = 0, stream: int = 0):
+        """bhrt_progressive_frame_dev on raw device pointers (0 = not wanted); with a stream the call does not synchronise."""
+        v = lambda x: C.c_void_p(x or None)  # noqa: E731
+        _check(lib().bhrt_progressive_frame_dev(self._h, v(d_rgb8_ptr), v(d_radiance_ptr), v(d_variance_ptr), v(d_count_ptr), v(stream)))
+
+    def progressive_status(self) -> Progress:
+        """bhrt_progressive_status: steps, smallest / largest count, active pixels, samples so far, finished."""
+        p = Progress()
+        _check(lib().bhrt_progressive_status(self._h, C.byref(p)))
+        return p
+
+    def progressive_end(self):
+        """bhrt_progressive_end (the seam's StopRender): closes the session and frees its state; fine when none is open."""
+        _check(lib().bhrt_progressive_end(self._h))
 
     def sample_count_image(self, count):
         """RenderImage::ComputeSampleCountImage (scene.h:603-626, bhrt_sample_count_image) of a count image: returns (img uint8 shaped like

@@ -12,6 +12,7 @@
 //               [--emission]                                                     (the <emission> of the materials, xmlload.cpp:344-348, shaded)
 //               [--face-materials]                                               (the .mtl sub-material of each mesh face, viewport.cpp:581-607, rendered)
 //               [--global-map N [--global-radius R]]                             (BuildPhotonMap, Main.cpp:196,251-317, gathered where the GI recursion ends)
+//               [--progressive N [--time-limit SECONDS] [--live-png path]]       (BeginRender .. StopRender, Main.cpp:178,243: the frame in steps)
 //   bhrt info   <scene.xml>
 //
 // --gpus N: ONE process drives N GPUs of the node (the reference's one process drives 16 OpenMP threads, Main.cpp:422): the
@@ -42,6 +43,12 @@
 // device once its scene is uploaded: a Shade() frame whose GI term is cut by the bounce budget gathers it from the global photon
 // map (radius R, default the reference's 0.5).  With --gpus K every rank builds the whole map itself: the emission is keyed, so the bytes are
 // the same on every rank.  Independent of --photons; --photon-exact selects the heavy-query path of both gathers.
+// --progressive N: the frame as a session (bhrt_progressive_*): steps of N samples per pixel up to --spp, one line per step
+// (step, samples per pixel min / max, active pixels, seconds since the first step began).  --live-png is written whole after each step (a
+// temporary file beside it, renamed over it): what a viewport would show.  --time-limit stops after the first step that ends beyond the
+// limit; at least one step always runs; the final PNG is the frame at that moment.  --adaptive becomes the session's retirement test
+// (--samples-png works), --denoise filters the final frame once, and the scene options (--lens, --emission, --face-materials, --global-map,
+// --photons) apply as they do to a blocking render.  One device: with --gpus N > 1 a usage error (no tile exchange per step yet).
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
@@ -86,10 +93,14 @@ struct Args {
     bool face_materials = false;       // --face-materials: bhrt_scene_set_face_materials
     uint32_t global_map = 0;           // --global-map N: photons of the global map (bhrt_global_map_build); switches the global gather on
     float global_radius = 0.f;         // --global-radius R; 0 = the reference's 0.5
+    int progressive = 0;               // --progressive N: samples per pixel and step of a bhrt_progressive_* session; 0 = one blocking render
+    bool progressive_given = false;
+    double time_limit = -1.0;          // --time-limit SECONDS; < 0: not given
+    std::string live_png;              // --live-png PATH
 };
 
-// a finite number >= 0 (--dof) or > 0 (--focaldist), else a usage error
-static float lens_value(const char *opt, const char *text, bool positive)
+// a finite number >= 0 (--dof, --time-limit) or > 0 (--focaldist, --global-radius), else a usage error
+static float number_value(const char *opt, const char *text, bool positive)
 {
     char *end = nullptr;
     const float v = strtof(text, &end);
@@ -100,8 +111,9 @@ static float lens_value(const char *opt, const char *text, bool positive)
     return v;
 }
 
-// the adaptive frame's round count (doubling from min_spp up to the largest count) and the spp statistics of its rendered pixels (count > 0)
-static void print_adaptive(const std::vector<uint32_t> &cnt, const bhrt_opts &o, const bhrt_adaptive_opts &ad)
+// the adaptive frame's round count (doubling from min_spp up to the largest count) and the spp statistics of its rendered pixels (count > 0);
+// rounds = false (--progressive: the steps are the caller's, and their lines say what ran): the statistics alone
+static void print_adaptive(const std::vector<uint32_t> &cnt, const bhrt_opts &o, const bhrt_adaptive_opts &ad, bool rounds_known = true)
 {
     uint64_t total = 0, px = 0;
     uint32_t cmin = 0xffffffffu, cmax = 0;
@@ -109,8 +121,45 @@ static void print_adaptive(const std::vector<uint32_t> &cnt, const bhrt_opts &o,
         if (c) { total += c; px++; cmin = std::min(cmin, c); cmax = std::max(cmax, c); }
     int rounds = px ? 1 : 0;
     for (uint32_t n = (uint32_t)ad.min_spp; px && n < cmax; rounds++) n = std::min<uint32_t>((uint32_t)o.spp, 2 * n);
+    if (!rounds_known) {
+        printf("adaptive: spp mean %.3f min %u max %u, %llu samples\n", px ? (double)total / (double)px : 0.0, px ? cmin : 0, cmax, (unsigned long long)total);
+        return;
+    }
     printf("adaptive: %d round(s), spp mean %.3f min %u max %u, %llu samples\n", rounds, px ? (double)total / (double)px : 0.0, px ? cmin : 0, cmax,
            (unsigned long long)total);
+}
+
+// --progressive: BeginRender as a session stepped until every pixel has retired or the time limit has passed, then StopRender.  rgb / rad / var /
+// cnt: the frame at that moment (rad, var and cnt may be empty); st: the sums over the steps.
+static int render_progressive(bhrt_scene *scene, const Args &A, const bhrt_info &info, std::vector<uint8_t> &rgb, std::vector<float> &rad, std::vector<float> &var,
+                              std::vector<uint32_t> &cnt, bhrt_stats &st)
+{
+    if (bhrt_progressive_begin(scene, &A.o, A.adaptive ? &A.ad : nullptr)) return fail("BeginRender (progressive)");
+    const std::string tmp = A.live_png.empty() ? std::string() : A.live_png + ".tmp";
+    const auto t0 = std::chrono::steady_clock::now();
+    bhrt_progress pg;
+    memset(&pg, 0, sizeof pg);
+    for (;;) {
+        bhrt_stats one;
+        if (bhrt_progressive_step(scene, A.progressive, &one)) return fail("progressive step");
+        st.closest_rays += one.closest_rays; st.shadow_rays += one.shadow_rays; st.shade_calls += one.shade_calls; st.camera_samples += one.camera_samples;
+        st.passes += one.passes; st.wave_iterations += one.wave_iterations; st.seconds_total += one.seconds_total;
+        if (bhrt_progressive_status(scene, &pg)) return fail("progressive status");
+        const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        printf("step %u: spp min %u max %u, %llu active pixel(s), %.3f s\n", pg.steps, pg.spp_min, pg.spp_max, (unsigned long long)pg.active_pixels, secs);
+        fflush(stdout);
+        if (!A.live_png.empty()) { // the viewport's refresh: a whole file at every moment
+            if (bhrt_progressive_frame(scene, rgb.data(), nullptr, nullptr, nullptr)) return fail("progressive frame");
+            if (bhrt_save_png(tmp.c_str(), rgb.data(), info.width, info.height)) return fail("SaveImage (live)");
+            if (rename(tmp.c_str(), A.live_png.c_str())) { fprintf(stderr, "bhrt: cannot rename %s to %s\n", tmp.c_str(), A.live_png.c_str()); return 1; }
+        }
+        if (pg.finished || (A.time_limit >= 0.0 && secs > A.time_limit)) break;
+    }
+    if (bhrt_progressive_frame(scene, rgb.data(), rad.empty() ? nullptr : rad.data(), var.empty() ? nullptr : var.data(), cnt.empty() ? nullptr : cnt.data()))
+        return fail("progressive frame");
+    if (bhrt_progressive_end(scene)) return fail("StopRender");
+    printf("progressive: %u step(s) of %d, %s\n", pg.steps, A.progressive, pg.finished ? "finished" : "stopped by --time-limit");
+    return 0;
 }
 
 // Everything render_multi owns besides the caller's scene: released on every way out (the early returns included).
@@ -375,9 +424,12 @@ int main(int argc, char **argv)
         else if (s == "--emission") A.emission = true;
         else if (s == "--face-materials") A.face_materials = true;
         else if (s == "--global-map") A.global_map = (uint32_t)strtoul(next(), nullptr, 10);
-        else if (s == "--global-radius") A.global_radius = lens_value("--global-radius", next(), true);
-        else if (s == "--dof") { A.dof = lens_value("--dof", next(), false); o.lens = 1; }
-        else if (s == "--focaldist") { A.focaldist = lens_value("--focaldist", next(), true); o.lens = 1; }
+        else if (s == "--global-radius") A.global_radius = number_value("--global-radius", next(), true);
+        else if (s == "--progressive") { A.progressive = atoi(next()); A.progressive_given = true; }
+        else if (s == "--time-limit") A.time_limit = number_value("--time-limit", next(), false);
+        else if (s == "--live-png") A.live_png = next();
+        else if (s == "--dof") { A.dof = number_value("--dof", next(), false); o.lens = 1; }
+        else if (s == "--focaldist") { A.focaldist = number_value("--focaldist", next(), true); o.lens = 1; }
         else { fprintf(stderr, "bhrt: unknown option %s\n", s.c_str()); return 2; }
     }
     if (A.gpus < 0 || A.gpus > 64 || (A.gpus > 0 && (o.rank != 0 || o.world_size != 1))) { fprintf(stderr, "bhrt: --gpus N drives all N ranks itself (no --rank / --world)\n"); return 2; }
@@ -396,6 +448,13 @@ int main(int argc, char **argv)
         return 2;
     }
     if (A.global_radius > 0.f && !A.global_map) { fprintf(stderr, "bhrt: usage: --global-radius needs --global-map N\n"); return 2; }
+    if (!A.progressive_given && (A.time_limit >= 0.0 || !A.live_png.empty())) { fprintf(stderr, "bhrt: usage: --time-limit and --live-png need --progressive N\n"); return 2; }
+    if (A.progressive_given && A.progressive < 1) { fprintf(stderr, "bhrt: usage: --progressive needs a step of at least 1 sample per pixel\n"); return 2; }
+    if (A.progressive_given && A.gpus > 1) { // before any device is touched
+        fprintf(stderr, "bhrt: usage: --progressive runs on one device; --gpus %d would need a tile exchange per step\n", A.gpus);
+        return 2;
+    }
+    if (A.progressive_given && A.gpus == 1) A.gpus = 0; // one device: the session needs no communicator
     A.dn.gamma = o.gamma;
     bhrt_scene *scene = nullptr;
     if (bhrt_scene_load_xml(A.scene.c_str(), &scene)) return fail("LoadScene");
@@ -459,7 +518,11 @@ int main(int argc, char **argv)
             o.photon_map = 1;
         }
         if (o.photon_map && !A.photon_out.empty() && bhrt_photon_export(scene, A.photon_out.c_str())) return fail("photon export");
-        if (A.adaptive) {
+        if (A.progressive_given) {
+            std::vector<float> var(A.denoise ? rad.size() : 0, 0.f);
+            if (render_progressive(scene, A, info, rgb, rad, var, cnt, st)) return 1;
+            if (A.denoise && bhrt_denoise(scene, &A.dn, rad.data(), var.data(), nullptr, nullptr, nullptr, nullptr, rgb.data())) return fail("DenoiseImage");
+        } else if (A.adaptive) {
             std::vector<float> var(A.denoise ? rad.size() : 0, 0.f);
             if (bhrt_render_adaptive(scene, &o, &A.ad, rgb.data(), rad.empty() ? nullptr : rad.data(), var.empty() ? nullptr : var.data(), cnt.data(), &st))
                 return fail("BeginRender (adaptive)");
@@ -474,7 +537,7 @@ int main(int argc, char **argv)
     printf("rendered %llu camera samples, %.0f rays (%llu closest + %llu shadow), %u wave steps in %u pass(es): %.3f s, %.1f Mrays/s\n",
            (unsigned long long)st.camera_samples, rays, (unsigned long long)st.closest_rays, (unsigned long long)st.shadow_rays, st.wave_iterations,
            st.passes, st.seconds_total, rays / st.seconds_total / 1e6);
-    if (A.adaptive) print_adaptive(cnt, o, A.ad);
+    if (A.adaptive) print_adaptive(cnt, o, A.ad, !A.progressive_given);
     if (bhrt_save_png(A.out.c_str(), rgb.data(), info.width, info.height)) return fail("SaveImage");
     if (!A.samples_png.empty()) { // ComputeSampleCountImage + SaveSampleCountImage (scene.h:603-630)
         std::vector<uint8_t> img(cnt.size());

@@ -225,6 +225,10 @@ struct DeviceState : DeviceQueues {
     // bhrt_render_adaptive_dev: the per-pixel state of the rounds (AdaptState: 36 B per owned pixel), two lists of owned-pixel indices (4 B each)
     // and the next list's length; grown on demand
     DevBuf<uint8_t> d_ad;
+    // bhrt_progressive_*: the session's per-pixel state (ProgState: 40 B per owned pixel), two lists of owned-pixel indices (4 B each) and the next
+    // list's length.  No render entry point touches it; freed by bhrt_progressive_end
+    DevBuf<uint8_t> d_prog;
+    uint64_t prog_session = 0; // ProgressiveSession::id of the session whose state d_prog holds (allocated and zeroed for it); 0 = none
     // bhrt_denoise_dev: the filter's planes (DenoisePlaneBytes), then the first-hit guides it computes itself; grown on demand
     DevBuf<uint8_t> d_dn;
     // scratch for the public trace API (EnsureApiScratch)

@@ -18,6 +18,8 @@
 //   k_resolve_frames  (the two above)          a render of the image alone: k_combine's root level and k_resolve in one launch, no sample buffer between
 //   k_variance      (DenoiseImage's input)     per-channel variance of the pixel mean, only when a variance image is asked for
 //   k_adapt_fold    scene.h:534,570 (sampleCount)  adaptive rounds: folds a pass into each pixel's state, retires converged pixels, lists the rest
+//   k_prog_fold     Main.cpp:178,243 (BeginRender .. StopRender)  progressive session: folds a step's pass into each pixel's kept state, lists the pixels still active
+//   k_prog_frame    (the viewport's refresh)   progressive session: resolves the kept state into radiance, RGB8, variance and count images
 //   k_photon_*      Main.cpp:319-386, cyPhotonMap.h   caustic photon map: emission, and the k-NN gather in three passes
 //   k_tiles_*       (no counterpart)           multi-GPU framebuffer exchange: pack / unpack of a rank's tiles
 // The recursion of the reference becomes: ray kinds (continuations) + a tree of shading frames.
@@ -1503,6 +1505,103 @@ __global__ void __launch_bounds__(kBlock) k_adapt_fold(PassInfo P, const float *
     }
     __syncthreads();
     if (keep) R.next[s_base[kBlock / 64] + s_base[wave] + (uint32_t)__popcll(mk & ((1ull << lane) - 1ull))] = q;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Progressive session (bhrt_progressive_*): the adaptive rounds turned inside out.  The caller chooses how many samples a step
+// adds, and the frame can be read between any two steps, so EVERY pixel keeps its state, retired or not, indexed by its owned-pixel index q, 40 B:
+//   a[q] = (S.x, S.y, S.z, mu.x), b[q] = (mu.y, mu.z, M2.x, M2.y), c[q] = (M2.z, count as bits)
+// Every active pixel stands at the same count, the step's s0, so the fold does not read the count (36 B in, 40 B out).
+struct ProgState {
+    float4 *a, *b;
+    float2 *c;
+};
+struct ProgParams {
+    uint32_t n_max;        // bhrt_opts.spp
+    uint32_t n_min;        // bhrt_adaptive_opts.min_spp; 0xffffffff = a uniform session: only n_max retires a pixel
+    float threshold, floor;
+    uint32_t *next, *n_next; // the next step's list and its length (zeroed by the host before the step)
+};
+
+// One lane per pixel of the pass (P.list, or the first step's range).  k_adapt_fold's recurrence, operation for operation, over samples
+// k = s0 + 1 .. n, and its retirement test where the session has one (n >= n_min).  The state and the count n are stored either way; a pixel
+// that does not retire is appended to the next step's list (wave ballot + prefix popcount, one atomic per workgroup).  The first step
+// (s0 == 0) reads no state, and drops the edge-tile pixels outside the image.
+__global__ void __launch_bounds__(kBlock) k_prog_fold(PassInfo P, const float *samples, ProgState A, ProgParams R)
+{
+    __shared__ uint32_t s_base[kBlock / 64 + 1];
+    const uint32_t ql = blockIdx.x * blockDim.x + threadIdx.x;
+    uint32_t q = 0;
+    int i = 0, j = 0;
+    bool keep = false;
+    if (ql < P.n_pixels) {
+        q = pass_pixel(P, ql);
+        if (pixel_of(P, q, i, j)) {
+            V3 S = v3(0, 0, 0), mu = v3(0, 0, 0), M2 = v3(0, 0, 0);
+            if (P.s0) {
+                const float4 a = A.a[q], b = A.b[q];
+                S = v3(a.x, a.y, a.z); mu = v3(a.w, b.x, b.y); M2 = v3(b.z, b.w, A.c[q].x);
+            }
+            uint32_t k = P.s0;
+            for (int s = 0; s < P.spp; s++) {
+                const V3 x = ld3i(samples, (uint32_t)s * P.n_pixels + ql);
+                S = S + x;
+                k++;
+                const V3 d = x - mu;
+                mu = mu + d / (float)k;
+                M2 = M2 + d * (x - mu);
+            }
+            const uint32_t n = k;
+            keep = n < R.n_max;
+            if (keep && n >= R.n_min) {
+                const V3 m = S / (float)n;
+                const V3 v = (M2 / (float)(n - 1)) / (float)n;
+                const float L = (0.2126f * m.x + 0.7152f * m.y) + 0.0722f * m.z;
+                const float vL = ((0.2126f * 0.2126f) * v.x + (0.7152f * 0.7152f) * v.y) + (0.0722f * 0.0722f) * v.z;
+                keep = !(sqrtf(vL) <= R.threshold * fmaxf(L, R.floor));
+            }
+            A.a[q] = make_float4(S.x, S.y, S.z, mu.x);
+            A.b[q] = make_float4(mu.y, mu.z, M2.x, M2.y);
+            A.c[q] = make_float2(M2.z, __uint_as_float(n));
+        }
+    }
+    const uint32_t lane = __lane_id(), wave = threadIdx.x >> 6;
+    const uint64_t mk = __ballot(keep);
+    if (lane == 0) s_base[wave] = (uint32_t)__popcll(mk);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t sum = 0;
+        for (int w = 0; w < kBlock / 64; w++) { const uint32_t t = s_base[w]; s_base[w] = sum; sum += t; }
+        s_base[kBlock / 64] = sum ? atomicAdd(R.n_next, sum) : 0u;
+    }
+    __syncthreads();
+    if (keep) R.next[s_base[kBlock / 64] + s_base[wave] + (uint32_t)__popcll(mk & ((1ull << lane) - 1ull))] = q;
+}
+
+// The session's frame, on demand: one lane per owned pixel (P.q0 = 0, P.n_pixels = all of them, no list), 40 B in, up to 31 B out.
+//   radiance = S / (float)c   (k_resolve's division)     rgb8 = store_color24 of it (k_resolve's gamma rule)
+//   variance = (M2 / (float)(c - 1)) / (float)c, 0 at c == 1   (k_adapt_fold's)      count = c
+// A pixel at count 0 (no step yet) is written as zeros.  Pixels of other ranks' tiles are not touched.
+__global__ void __launch_bounds__(kBlock) k_prog_frame(PassInfo P, ProgState A, float *radiance, uint8_t *rgb8, float *variance, uint32_t *count)
+{
+    const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= P.n_pixels) return;
+    int i, j;
+    if (!pixel_of(P, q, i, j)) return;
+    const float4 a = A.a[q], b = A.b[q];
+    const float2 c = A.c[q];
+    const uint32_t n = __float_as_uint(c.y);
+    const size_t pix = (size_t)j * P.W + i;
+    V3 m = v3(0, 0, 0), v = v3(0, 0, 0);
+    if (n) m = v3(a.x, a.y, a.z) / (float)n;
+    if (n > 1) v = (v3(b.z, b.w, c.x) / (float)(n - 1)) / (float)n;
+    if (radiance) st3(radiance, (uint32_t)pix, m);
+    if (rgb8) {
+        if (n) store_color24(rgb8, pix, m, P.gamma);
+        else { rgb8[pix * 3] = 0; rgb8[pix * 3 + 1] = 0; rgb8[pix * 3 + 2] = 0; }
+    }
+    if (variance) st3(variance, (uint32_t)pix, v);
+    if (count) count[pix] = n;
 }
 
 // RenderImage::ComputeSampleCountImage (scene.h:603-626): min / max of the counts (exact in any order; one workgroup strides over the
@@ -3181,6 +3280,72 @@ static int RenderAdaptive(bhrt_scene *scene, const bhrt_opts &o, const bhrt_adap
     return BHRT_OK;
 }
 
+// ---- progressive session -------------------------------------------------------------------------------------------------
+// The session's device state: d_prog = a[N] b[N] c[N] list0[N] list1[N] n_next.  Allocated and zeroed (count 0 everywhere: a frame before the
+// first step) when the session first needs the device.
+struct ProgViews {
+    ProgState A;
+    uint32_t *lists[2], *n_next;
+};
+static int EnsureProgState(bhrt_scene *scene, ProgViews &V)
+{
+    DeviceState *D = scene->dev;
+    ProgressiveSession &G = scene->prog;
+    const size_t N = (size_t)G.owned;
+    if (D->prog_session != G.id) { // this device state holds nothing of the session
+        // bhrt_scene_upload refuses to drop a device state that holds a session's, so this is not reached through the public calls
+        if (G.c) { SetError("progressive session: its state is not on this device (session state lost): bhrt_progressive_end and begin again"); return BHRT_ERR_ARG; }
+        D->prog_session = 0;
+        BHRT_TRY(D->d_prog.Reserve(N * 48 + 16));
+        HIP_CHECK(hipMemsetAsync(D->d_prog.p, 0, N * 40, D->stream));
+        HIP_CHECK(hipStreamSynchronize(D->stream)); // bhrt_progressive_frame_dev may read it on the caller's stream
+        D->prog_session = G.id;
+    }
+    V.A.a = (float4 *)D->d_prog.p; V.A.b = V.A.a + N; V.A.c = (float2 *)(V.A.b + N);
+    V.lists[0] = (uint32_t *)(V.A.c + N); V.lists[1] = V.lists[0] + N;
+    V.n_next = V.lists[1] + N;
+    return BHRT_OK;
+}
+
+// One step: samples [c, c1) of every active pixel through RenderPixels, each pass folded by k_prog_fold.  The host reads the next list's
+// length once (4 bytes); what bhrt_progressive_status reports follows from it (ProgressiveSession).
+static int ProgressiveStep(bhrt_scene *scene, uint32_t n_samples, bhrt_stats *st)
+{
+    DeviceState *D = scene->dev;
+    ProgressiveSession &G = scene->prog;
+    const bhrt_opts &o = G.o;
+    PassInfo P;
+    uint64_t owned_pixels = 0;
+    BHRT_TRY(FramePassInfo(scene, o, P, owned_pixels)); // every step: bhrt_scene_set_lens between two steps applies to this one's samples
+    ProgViews V;
+    BHRT_TRY(EnsureProgState(scene, V));
+    const uint32_t c1 = (uint32_t)std::min<uint64_t>((uint64_t)o.spp, (uint64_t)G.c + n_samples);
+    ProgParams R;
+    R.n_max = (uint32_t)o.spp; R.n_min = G.adaptive ? (uint32_t)G.a.min_spp : 0xffffffffu;
+    R.threshold = G.a.threshold; R.floor = G.a.floor;
+    R.next = V.lists[G.cur ^ 1]; R.n_next = V.n_next;
+    const auto wall0 = std::chrono::steady_clock::now();
+    HIP_CHECK(hipMemsetAsync(R.n_next, 0, sizeof(uint32_t), D->stream));
+    const ProgState A = V.A;
+    // the first step takes the range of owned pixels (and drops those outside the image); later ones the list the step before left
+    const int rc = RenderPixels(scene, o, P, G.c ? V.lists[G.cur] : nullptr, G.c ? G.active : G.owned, G.c, c1 - G.c, st, false,
+                                [&](const PassInfo &Pp, uint32_t npx, const Frames &) {
+                                    hipLaunchKernelGGL(k_prog_fold, dim3((npx + kBlock - 1) / kBlock), dim3(kBlock), 0, D->stream, Pp, D->d_samples, A, R);
+                                });
+    if (rc) return rc; // a pass may have been folded: bhrt_progressive_step marks the session failed
+    uint32_t active = 0;
+    HIP_CHECK(hipMemcpyAsync(&active, R.n_next, sizeof active, hipMemcpyDeviceToHost, D->stream));
+    HIP_CHECK(hipStreamSynchronize(D->stream));
+    FlushTimers(D, true);
+    if (active > G.active || (c1 >= (uint32_t)o.spp && active)) { SetError("progressive step: pixels active after their last sample"); return BHRT_ERR_HIP; }
+    const uint64_t retired = G.active - active;
+    if (retired && !G.first_retired) G.first_retired = c1;
+    G.retired_samples += retired * c1;
+    G.active = active; G.c = c1; G.cur ^= 1; G.steps++;
+    st->seconds_total += std::chrono::duration<double>(std::chrono::steady_clock::now() - wall0).count();
+    return BHRT_OK;
+}
+
 // bhrt_opts.lens against the scene's camera, checked before any device is touched; "" = valid
 static const char *LensArgsError(const bhrt_scene *scene, const bhrt_opts *o)
 {
@@ -3302,6 +3467,10 @@ int bhrt_scene_upload(bhrt_scene *scene, int device)
 try {
     if (!scene) { SetError("null scene"); return BHRT_ERR_ARG; }
     if (scene->dev && scene->dev->device == device) { HIP_CHECK(hipSetDevice(device)); return BHRT_OK; }
+    if (scene->dev && scene->prog.open && scene->dev->prog_session == scene->prog.id) { // the move would drop the device state, the session's with it
+        SetError("bhrt_scene_upload: a progressive session of this scene holds its state on device " + std::to_string(scene->dev->device) + ": bhrt_progressive_end first");
+        return BHRT_ERR_ARG;
+    }
     int count = 0;
     if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) { SetError("no HIP device available (this path has no CPU fallback)"); return BHRT_ERR_NO_DEVICE; }
     if (device < 0 || device >= count) { SetError("device index out of range"); return BHRT_ERR_ARG; }
@@ -3569,6 +3738,131 @@ try {
     if (opts->world_size > 1) BHRT_TRY(fs.Upload(scene->dev->stream));
     BHRT_TRY(bhrt_render_adaptive_dev(scene, opts, aopts, fs.d_rgb8, fs.d_radiance, fs.d_variance, fs.d_count, stats, nullptr));
     return fs.Download(scene->dev->stream);
+} catch (...) { return bhrt::AbiException(); }
+
+// ---- progressive session (ProgressiveStep) ------------------------------------------------------------------
+#define BHRT_CHECK_SESSION(scene, what)                                                                        \
+    do {                                                                                                       \
+        if (!(scene)) { SetError("null scene"); return BHRT_ERR_ARG; }                                         \
+        if (!(scene)->prog.open) { SetError(what ": no progressive session is open on this scene (bhrt_progressive_begin)"); return BHRT_ERR_ARG; } \
+    } while (0)
+// a step that failed part-way leaves state that c and the lists do not describe: nothing but end (and status) is served afterwards
+#define BHRT_CHECK_SESSION_USABLE(scene, what)                                                                 \
+    do {                                                                                                       \
+        BHRT_CHECK_SESSION(scene, what);                                                                       \
+        if ((scene)->prog.failed) { SetError(what ": a step of this session failed; its state is not usable: bhrt_progressive_end"); return BHRT_ERR_ARG; } \
+    } while (0)
+// photon_map = 1 against the installed caustic map; a scene that was never uploaded has none
+#define BHRT_CHECK_CAUSTIC(scene, opts)                                                                        \
+    do {                                                                                                       \
+        if ((opts)->photon_map && !((scene)->dev && (scene)->dev->cmap.d_photons)) { SetError("photon_map = 1 needs bhrt_photon_build first"); return BHRT_ERR_ARG; } \
+    } while (0)
+
+int bhrt_progressive_begin(bhrt_scene *scene, const bhrt_opts *opts, const bhrt_adaptive_opts *aopts)
+try {
+    if (!scene || !opts) { SetError("bhrt_progressive_begin: null argument"); return BHRT_ERR_ARG; }
+    if (scene->prog.open) { SetError("bhrt_progressive_begin: a session is already open on this scene (bhrt_progressive_end first)"); return BHRT_ERR_ARG; }
+    if (aopts) {
+        const char *bad = AdaptiveArgsError(opts, aopts);
+        if (*bad) { SetError(bad); return BHRT_ERR_ARG; }
+    }
+    BHRT_CHECK_LENS(scene, opts);
+    BHRT_CHECK_GLOBAL(scene);
+    BHRT_CHECK_CAUSTIC(scene, opts);
+    PassInfo P;
+    uint64_t owned_pixels = 0;
+    BHRT_TRY(FramePassInfo(scene, *opts, P, owned_pixels)); // spp in 1..65535, rank, bounce counts: host arithmetic only
+    if (owned_pixels > 0xffffffffull) { SetError("progressive session: more than 2^32 owned pixels"); return BHRT_ERR_ARG; }
+    static uint64_t next_id = 0; // calls on different scenes may overlap
+    ProgressiveSession G;
+    G.id = __atomic_add_fetch(&next_id, 1, __ATOMIC_RELAXED);
+    G.open = true; G.adaptive = aopts != nullptr;
+    G.o = *opts;
+    if (aopts) G.a = *aopts;
+    G.owned = owned_pixels;
+    P.q0 = 0;
+    G.active = CountValidPixels(P, (uint32_t)owned_pixels);
+    scene->prog = G;
+    return BHRT_OK;
+} catch (...) { return bhrt::AbiException(); }
+
+int bhrt_progressive_step(bhrt_scene *scene, int32_t n_samples, bhrt_stats *stats)
+try {
+    BHRT_CHECK_SESSION_USABLE(scene, "bhrt_progressive_step");
+    if (n_samples <= 0) { SetError("bhrt_progressive_step: n_samples must be >= 1"); return BHRT_ERR_ARG; }
+    const bhrt_opts *opts = &scene->prog.o;
+    BHRT_CHECK_LENS(scene, opts); // the setters may have run since begin
+    BHRT_CHECK_GLOBAL(scene);
+    BHRT_CHECK_CAUSTIC(scene, opts);
+    if (scene->prog.active == 0) { // finished: nothing to render
+        if (stats) memset(stats, 0, sizeof *stats);
+        return BHRT_OK;
+    }
+    int rc = EnsureUploaded(scene);
+    if (rc) return rc;
+    rc = RenderWithStats(scene, opts, stats, [&](bhrt_stats *st) { return ProgressiveStep(scene, (uint32_t)n_samples, st); });
+    if (rc) scene->prog.failed = true;
+    return rc;
+} catch (...) { return bhrt::AbiException(); }
+
+int bhrt_progressive_frame_dev(bhrt_scene *scene, uint8_t *d_rgb8, float *d_radiance, float *d_variance, uint32_t *d_count, void *stream)
+try {
+    BHRT_CHECK_SESSION_USABLE(scene, "bhrt_progressive_frame");
+    int rc = EnsureUploaded(scene);
+    if (rc) return rc;
+    DeviceState *D = scene->dev;
+    ProgressiveSession &G = scene->prog;
+    PassInfo P;
+    uint64_t owned_pixels = 0;
+    BHRT_TRY(FramePassInfo(scene, G.o, P, owned_pixels));
+    ProgViews V;
+    BHRT_TRY(EnsureProgState(scene, V));
+    if (G.owned == 0) return BHRT_OK;
+    P.q0 = 0; P.n_pixels = (uint32_t)G.owned;
+    hipStream_t st = stream ? (hipStream_t)stream : D->stream;
+    hipLaunchKernelGGL(k_prog_frame, dim3((P.n_pixels + kBlock - 1) / kBlock), dim3(kBlock), 0, st, P, V.A, d_radiance, d_rgb8, d_variance, d_count);
+    HIP_CHECK(hipGetLastError());
+    if (!stream) HIP_CHECK(hipStreamSynchronize(st));
+    return BHRT_OK;
+} catch (...) { return bhrt::AbiException(); }
+
+int bhrt_progressive_frame(bhrt_scene *scene, uint8_t *rgb8, float *radiance, float *variance, uint32_t *count)
+try {
+    BHRT_CHECK_SESSION_USABLE(scene, "bhrt_progressive_frame");
+    int rc = EnsureUploaded(scene);
+    if (rc) return rc;
+    FrameStage fs = {rgb8, radiance, variance, count};
+    BHRT_TRY(fs.Reserve(scene));
+    if (scene->prog.o.world_size > 1) BHRT_TRY(fs.Upload(scene->dev->stream));
+    BHRT_TRY(bhrt_progressive_frame_dev(scene, fs.d_rgb8, fs.d_radiance, fs.d_variance, fs.d_count, nullptr));
+    return fs.Download(scene->dev->stream);
+} catch (...) { return bhrt::AbiException(); }
+
+int bhrt_progressive_status(const bhrt_scene *scene, bhrt_progress *progress)
+try {
+    BHRT_CHECK_SESSION(scene, "bhrt_progressive_status");
+    if (!progress) { SetError("bhrt_progressive_status: null argument"); return BHRT_ERR_ARG; }
+    const ProgressiveSession &G = scene->prog;
+    memset(progress, 0, sizeof *progress);
+    progress->steps = G.steps;
+    progress->spp_min = G.first_retired ? G.first_retired : G.c; // pixels only ever retire at the count all active ones stand at
+    progress->spp_max = G.c;
+    progress->active_pixels = G.active;
+    progress->camera_samples = G.retired_samples + G.active * (uint64_t)G.c;
+    progress->finished = G.active == 0;
+    return BHRT_OK;
+} catch (...) { return bhrt::AbiException(); }
+
+int bhrt_progressive_end(bhrt_scene *scene)
+try {
+    if (!scene) { SetError("null scene"); return BHRT_ERR_ARG; }
+    if (scene->dev && scene->dev->d_prog.p) {
+        HIP_CHECK(hipSetDevice(scene->dev->device));
+        scene->dev->d_prog.Free(); // hipFree waits for the device: a frame kernel on the caller's stream included
+    }
+    if (scene->dev) scene->dev->prog_session = 0;
+    scene->prog = ProgressiveSession();
+    return BHRT_OK;
 } catch (...) { return bhrt::AbiException(); }
 
 int bhrt_sample_count_image_dev(bhrt_scene *scene, const uint32_t *d_count, size_t n, uint8_t *d_img, uint32_t *smax, void *stream)

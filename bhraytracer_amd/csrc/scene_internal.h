@@ -14,10 +14,29 @@ void SetError(const std::string &msg);
 // (std::bad_alloc from a file-sized allocation, std::length_error, ...): sets bhrt_last_error() and returns an error code.
 int AbiException();
 void DestroyDeviceState(DeviceState *d); // defined in the HIP TU
+
+// The host side of a progressive session (bhrt_progressive_*): the options it was begun with and what the steps so far have left.
+// Everything bhrt_progressive_status reports is kept here: a step reads back one word (the next list's length), and every pixel that left
+// the list in a step retired at that step's count.  The per-pixel state is device memory (DeviceState::d_prog), allocated by the first step or frame.
+struct ProgressiveSession {
+    bool open = false, adaptive = false;
+    bool failed = false;         // a step failed part-way: passes may be folded that c and the lists do not know of; only end is left
+    uint64_t id = 0;             // names the session; DeviceState::prog_session says whose state d_prog holds, so the state's validity lives with the buffer
+    bhrt_opts o = {};
+    bhrt_adaptive_opts a = {};
+    uint32_t c = 0;              // the count every active pixel stands at
+    uint32_t steps = 0;
+    uint32_t first_retired = 0;  // the count of the first pixels that retired; 0 = none has
+    uint64_t owned = 0;          // owned-pixel indices of this rank (edge-tile pixels outside the image included)
+    uint64_t active = 0;         // active pixels inside the image
+    uint64_t retired_samples = 0; // sum of the counts of the retired pixels
+    int cur = 0;                 // which of the two device lists holds the active pixels (c > 0; the first step takes the range [0, owned))
+};
 } // namespace bhrt
 
 struct bhrt_scene {
     bhrt::FlatScene flat;
     uint32_t n_triangles = 0, n_bvh_nodes = 0, max_bvh_depth = 0;
     bhrt::DeviceState *dev = nullptr;
+    bhrt::ProgressiveSession prog; // not carried by bhrt_scene_clone
 };

@@ -5,7 +5,7 @@
  * renderer (all paths relative to /root/reference/BHRayTracer):
  *     int  LoadScene(char const *filename);   Main.cpp:43, xmlload.cpp:65
  *     void BeginRender();                     Main.cpp:178   (called from viewport.cpp:425-449)
- *     void StopRender();                      Main.cpp:243
+ *     void StopRender();                      Main.cpp:243   (here: bhrt_progressive_end, the end of a resumable frame)
  *     globals rootNode, camera, renderImage, lights, materials, ...   Main.cpp:17-37
  * and, one level down, the plugin virtuals of Scenes/scene.h (Object::IntersectRay :256,
  * Light::Illuminate :268, Material::Shade :291, Texture::Sample :314) reached through
@@ -200,7 +200,8 @@ int bhrt_scene_submaterial_count(const bhrt_scene *scene, int32_t material, int3
 int bhrt_scene_get_submaterial(const bhrt_scene *scene, int32_t material, int32_t sub, struct bhrt_material *out, uint32_t *face_end);
 
 /* ---- device residency ---------------------------------------------------------------------------- */
-int bhrt_scene_upload(bhrt_scene *scene, int device); /* copies the flat scene into HBM of `device`; idempotent */
+int bhrt_scene_upload(bhrt_scene *scene, int device); /* copies the flat scene into HBM of `device`; idempotent.  To another device: the device state of the
+                                                        * old one is dropped; BHRT_ERR_ARG while a progressive session holds state there */
 /* knobs of an uploaded scene: they steer which internal path a render takes, never its result.  Test knobs "frame_cap", "gather_lane_budget" (0 = off) and
  * "gather_stats"; "shadow_overlap" (default 1; 0 = the any-hit kernels of a wave step run in front of the next step on the pass's own stream instead of
  * beside it on a second one: the kernel groups timed alone, bench.py's `frac_alone`); "fused_resolve" (default 1; 0 = a render that asks for the image
@@ -374,6 +375,52 @@ int bhrt_sample_count_image_dev(bhrt_scene *scene, const uint32_t *d_count, size
 int bhrt_sample_count_image(bhrt_scene *scene, const uint32_t *count, size_t n, uint8_t *img, uint32_t *smax);
 /* RenderImage::SaveSampleCountImage (scene.h:630): an 8-bit one-channel PNG of w x h bytes */
 int bhrt_save_png_gray(const char *path, const uint8_t *gray, int width, int height);
+
+/* ---- progressive rendering: the frame as a state that a call advances by a few samples per pixel and that can be read at any point
+ * (DESIGN.md 15).  BeginRender() starts a frame the viewport shows filling in, and StopRender() (Main.cpp:243) ends it whenever the user
+ * likes: begin / step / frame / end.  A session belongs to a scene; at most one is open per scene.
+ * Every active pixel of the session stands at the same count c.  bhrt_progressive_step(n) renders samples [c, min(spp, c + n)) of every
+ * active pixel, each with the RNG key of bhrt_render's (seed, pixel, sample index), and folds them into the pixel's state in float32 and in
+ * sample order with the operations of the adaptive rounds above (S += x; d = x - mu; mu += d / k; M2 += d * (x - mu)).  A pixel at its new
+ * count c' then retires when c' == spp, or, with adaptive options, when c' >= min_spp and sqrt(vL) <= threshold * max(L, floor) (L, vL as
+ * above).  Without adaptive options only the maximum retires a pixel.  So a uniform session's frame at count c is bhrt_render's at spp = c bit
+ * for bit, and a session stepped min_spp, min_spp, 2 min_spp, ... is bhrt_render_adaptive's.  A retired pixel keeps its state: the frame keeps
+ * returning the value it retired with.
+ * The state (40 B per owned pixel: S, mu, M2, count; plus two lists of 4 B) lives in a buffer of its own that belongs to the scene; it is
+ * allocated by the first step or frame, on the device the scene is uploaded to, and freed by bhrt_progressive_end and bhrt_scene_free.  While a
+ * session holds state there, bhrt_scene_upload to another device returns BHRT_ERR_ARG and changes nothing (end the session first); to the same
+ * device it stays the no-op it is.  bhrt_render*, bhrt_render_adaptive*,
+ * bhrt_first_hit* and bhrt_denoise* on the same scene between two steps do not disturb the session.  The scene setters (bhrt_scene_set_lens,
+ * _set_emissive, _set_material_emission, _set_face_materials, _set_global_gather, the photon and global maps) between two steps apply to
+ * the samples rendered afterwards: the frame then mixes samples of both states. */
+typedef struct bhrt_progress {
+    uint32_t steps;            /* bhrt_progressive_step calls that rendered something */
+    uint32_t spp_min, spp_max; /* smallest / largest count over this rank's pixels inside the image */
+    uint64_t active_pixels;    /* pixels that the next step would still sample */
+    uint64_t camera_samples;   /* sum of the counts */
+    int32_t finished;          /* 1 = no active pixel is left */
+    int32_t reserved[3];
+} bhrt_progress;
+/* begin: copies the options.  bhrt_opts.spp is the per-pixel maximum, 1 <= spp <= 65535; rank, world_size, tile_size and samples_per_pass mean
+ * what they mean for bhrt_render; aopts = NULL: a uniform session.  Checked before any device is touched, BHRT_ERR_ARG otherwise: the options as
+ * bhrt_render_adaptive checks its own (lens, the global gather without a map, photon_map without a map), with aopts 2 <= min_spp <= spp,
+ * floor > 0 and threshold not NaN, and that no session is open on the scene.  Needs no device.
+ * step: n_samples <= 0 or no open session: BHRT_ERR_ARG.  *stats (may be NULL) is that step's alone.  A step on a finished session returns
+ * BHRT_OK, renders nothing and does not count in bhrt_progress.steps.  A step that fails once it has started rendering (BHRT_ERR_HIP,
+ * BHRT_ERR_OVERFLOW, ...) may have folded some of its passes: the session is marked failed, bhrt_progressive_step and _frame* return BHRT_ERR_ARG
+ * from then on, bhrt_progressive_status reports the last complete step, and bhrt_progressive_end is the way out.
+ * frame: resolves the state into the caller's images for this rank's pixels inside the image, at any time in an open session, any number of
+ * times: radiance = S / (float)c, rgb8 = gamma + Color24 of it (the session's bhrt_opts.gamma), variance = (M2 / (float)(c - 1)) / (float)c
+ * (0 at c == 1), count = c; pixels at count 0 (before the first step) are written as zeros, pixels of other ranks' tiles are left untouched.
+ * Layouts as bhrt_render_adaptive's; any pointer may be NULL.  _dev: device pointers; with a stream the kernel is enqueued there and the call
+ * does not synchronise (the caller does, before the next call on this scene); stream = NULL: the scene's own stream, synchronised.
+ * end: the StopRender of the seam: closes the session and frees its state; BHRT_OK when no session is open. */
+int bhrt_progressive_begin(bhrt_scene *scene, const bhrt_opts *opts, const bhrt_adaptive_opts *aopts /* NULL = uniform */);
+int bhrt_progressive_step(bhrt_scene *scene, int32_t n_samples, bhrt_stats *stats);
+int bhrt_progressive_frame(bhrt_scene *scene, uint8_t *rgb8, float *radiance, float *variance, uint32_t *count);
+int bhrt_progressive_frame_dev(bhrt_scene *scene, uint8_t *d_rgb8, float *d_radiance, float *d_variance, uint32_t *d_count, void *stream);
+int bhrt_progressive_status(const bhrt_scene *scene, bhrt_progress *progress);
+int bhrt_progressive_end(bhrt_scene *scene);
 
 /* ---- test hook: csrc/bhrt_detmath.h evaluated on the device, to prove host and device produce the same bits.
  * fn: 0 sin 1 cos 2 tan 3 acos 4 asin 5 atan2(a,b) 6 pow(a,b) 7 rand_to_unit(bits of a) 8 a/b 9 sqrt(a); host pointers */
