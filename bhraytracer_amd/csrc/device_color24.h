@@ -1,5 +1,5 @@
 // device_color24.h — the tail of every 8-bit image of the render path: gamma (USE_GamaCorrection, Main.cpp:220-226) and Color24
-// (cyColor.h:271-272).  k_resolve, k_resolve_frames, k_adapt_fold (kernels.hip) and the denoiser's last iteration (denoise.hip) all call it, so a frame that
+// (cyColor.h:271-272).  k_resolve, k_resolve_frames, k_fold_frame (kernels.hip) and the denoiser's last iteration (denoise.hip) all call it, so a frame that
 // the denoiser leaves alone (K = 0) gets the render's own bytes.
 #pragma once
 #include <stddef.h>

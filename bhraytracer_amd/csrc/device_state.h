@@ -222,11 +222,11 @@ struct DeviceState : DeviceQueues {
     DevBuf<uint8_t> d_frame_rgb;
     DevBuf<float> d_frame_rad, d_frame_var;
     DevBuf<uint32_t> d_frame_cnt;
-    // bhrt_render_adaptive_dev: the per-pixel state of the rounds (AdaptState: 36 B per owned pixel), two lists of owned-pixel indices (4 B each)
-    // and the next list's length; grown on demand
+    // The estimator's state (FoldViews, kernels.hip): FoldState, 40 B per owned pixel, two lists of owned-pixel indices (4 B each) and the next
+    // list's length: 48 B per owned pixel + 16.  Two buffers of that layout:
+    // bhrt_render_adaptive_dev: the state of the rounds; grown on demand, never zeroed (round 0 writes what the frame kernel reads)
     DevBuf<uint8_t> d_ad;
-    // bhrt_progressive_*: the session's per-pixel state (ProgState: 40 B per owned pixel), two lists of owned-pixel indices (4 B each) and the next
-    // list's length.  No render entry point touches it; freed by bhrt_progressive_end
+    // bhrt_progressive_*: the session's state.  No render entry point touches it; freed by bhrt_progressive_end
     DevBuf<uint8_t> d_prog;
     uint64_t prog_session = 0; // ProgressiveSession::id of the session whose state d_prog holds (allocated and zeroed for it); 0 = none
     // bhrt_denoise_dev: the filter's planes (DenoisePlaneBytes), then the first-hit guides it computes itself; grown on demand

@@ -17,9 +17,9 @@
 //   k_resolve       Main.cpp:170,220-230       in-order sample sum, /spp, gamma, Color24
 //   k_resolve_frames  (the two above)          a render of the image alone: k_combine's root level and k_resolve in one launch, no sample buffer between
 //   k_variance      (DenoiseImage's input)     per-channel variance of the pixel mean, only when a variance image is asked for
-//   k_adapt_fold    scene.h:534,570 (sampleCount)  adaptive rounds: folds a pass into each pixel's state, retires converged pixels, lists the rest
-//   k_prog_fold     Main.cpp:178,243 (BeginRender .. StopRender)  progressive session: folds a step's pass into each pixel's kept state, lists the pixels still active
-//   k_prog_frame    (the viewport's refresh)   progressive session: resolves the kept state into radiance, RGB8, variance and count images
+//   k_fold          scene.h:534,570 (sampleCount); Main.cpp:178,243 (BeginRender .. StopRender)  adaptive rounds and progressive steps: folds a
+//                                              pass into each pixel's kept state, lists the pixels still active
+//   k_fold_frame    (the viewport's refresh)   resolves the kept state into radiance, RGB8, variance and count images
 //   k_photon_*      Main.cpp:319-386, cyPhotonMap.h   caustic photon map: emission, and the k-NN gather in three passes
 //   k_tiles_*       (no counterpart)           multi-GPU framebuffer exchange: pack / unpack of a rank's tiles
 // The recursion of the reference becomes: ray kinds (continuations) + a tree of shading frames.
@@ -1427,107 +1427,33 @@ __global__ void __launch_bounds__(kBlock) k_variance(PassInfo P, const float *sa
 }
 
 // ------------------------------------------------------------------------------------------------
-// Adaptive sampling.  Round 0 gives every owned pixel samples [0, min_spp); round r >= 1 gives every pixel still active samples
-// [n_{r-1}, n_r), n_r = min(max_spp, 2 n_{r-1}).  The state a pixel carries between its rounds, indexed by its owned-pixel index q, 36 B:
-//   a[q] = (S.x, S.y, S.z, mu.x), b[q] = (mu.y, mu.z, M2.x, M2.y), c[q] = M2.z      (n is the round's s0: every active pixel has the same)
-struct AdaptState {
-    float4 *a, *b;
-    float *c;
-};
-struct AdaptParams {
-    uint32_t n_max;        // bhrt_opts.spp
-    float threshold, floor;
-    float *radiance, *variance; // W*H*3 each (may be NULL)
-    uint8_t *rgb8;              // W*H*3 (may be NULL)
-    uint32_t *count;            // W*H (may be NULL)
-    uint32_t *next, *n_next;    // the next round's list and its length (zeroed by the host before the round)
-};
-
-// One lane per pixel of the pass (P.list, or round 0's range).  In float32, in sample order, for k = s0 + 1 .. n (x = sample k - 1):
-//   S += x;   d = x - mu;   mu += d / (float)k;   M2 += d * (x - mu)                  (no contraction: -ffp-contract=off)
-// then   m = S / (float)n                                   (k_resolve's mean: the same additions from 0 in the same order, the same division)
-//        v = (M2 / (float)(n - 1)) / (float)n                (per-channel variance of the mean)
-//        L = (0.2126 m.r + 0.7152 m.g) + 0.0722 m.b,   vL = (0.2126^2 v.r + 0.7152^2 v.g) + 0.0722^2 v.b   (the denoiser's luminance)
-// The pixel retires when n == n_max or sqrtf(vL) <= threshold * fmaxf(L, floor): it writes radiance m, rgb8 (store_color24, k_resolve's
-// gamma rule), variance v and count n, once.  Otherwise it stores its state and is appended to the next round's list (wave ballot + prefix
-// popcount, one atomic per workgroup).  Round 0 reads no state, and drops the edge-tile pixels outside the image.
-__global__ void __launch_bounds__(kBlock) k_adapt_fold(PassInfo P, const float *samples, AdaptState A, AdaptParams R)
-{
-    __shared__ uint32_t s_base[kBlock / 64 + 1];
-    const uint32_t ql = blockIdx.x * blockDim.x + threadIdx.x;
-    uint32_t q = 0;
-    int i = 0, j = 0;
-    bool keep = false;
-    if (ql < P.n_pixels) {
-        q = pass_pixel(P, ql);
-        if (pixel_of(P, q, i, j)) {
-            V3 S = v3(0, 0, 0), mu = v3(0, 0, 0), M2 = v3(0, 0, 0);
-            if (P.s0) {
-                const float4 a = A.a[q], b = A.b[q];
-                S = v3(a.x, a.y, a.z); mu = v3(a.w, b.x, b.y); M2 = v3(b.z, b.w, A.c[q]);
-            }
-            uint32_t k = P.s0;
-            for (int s = 0; s < P.spp; s++) {
-                const V3 x = ld3i(samples, (uint32_t)s * P.n_pixels + ql);
-                S = S + x;
-                k++;
-                const V3 d = x - mu;
-                mu = mu + d / (float)k;
-                M2 = M2 + d * (x - mu);
-            }
-            const uint32_t n = k;
-            const V3 m = S / (float)n;
-            const V3 v = (M2 / (float)(n - 1)) / (float)n;
-            const float L = (0.2126f * m.x + 0.7152f * m.y) + 0.0722f * m.z;
-            const float vL = ((0.2126f * 0.2126f) * v.x + (0.7152f * 0.7152f) * v.y) + (0.0722f * 0.0722f) * v.z;
-            if (n >= R.n_max || sqrtf(vL) <= R.threshold * fmaxf(L, R.floor)) {
-                const size_t pix = (size_t)j * P.W + i;
-                if (R.radiance) st3(R.radiance, (uint32_t)pix, m);
-                if (R.rgb8) store_color24(R.rgb8, pix, m, P.gamma);
-                if (R.variance) st3(R.variance, (uint32_t)pix, v);
-                if (R.count) R.count[pix] = n;
-            } else {
-                A.a[q] = make_float4(S.x, S.y, S.z, mu.x);
-                A.b[q] = make_float4(mu.y, mu.z, M2.x, M2.y);
-                A.c[q] = M2.z;
-                keep = true;
-            }
-        }
-    }
-    const uint32_t lane = __lane_id(), wave = threadIdx.x >> 6;
-    const uint64_t mk = __ballot(keep);
-    if (lane == 0) s_base[wave] = (uint32_t)__popcll(mk);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t sum = 0;
-        for (int w = 0; w < kBlock / 64; w++) { const uint32_t t = s_base[w]; s_base[w] = sum; sum += t; }
-        s_base[kBlock / 64] = sum ? atomicAdd(R.n_next, sum) : 0u;
-    }
-    __syncthreads();
-    if (keep) R.next[s_base[kBlock / 64] + s_base[wave] + (uint32_t)__popcll(mk & ((1ull << lane) - 1ull))] = q;
-}
-
-// ------------------------------------------------------------------------------------------------
-// Progressive session (bhrt_progressive_*): the adaptive rounds turned inside out.  The caller chooses how many samples a step
-// adds, and the frame can be read between any two steps, so EVERY pixel keeps its state, retired or not, indexed by its owned-pixel index q, 40 B:
+// The per-pixel estimator of the adaptive render (bhrt_render_adaptive*) and of the progressive session (bhrt_progressive_*,
+// DESIGN.md 15).  A step gives every pixel still active samples [s0, n); the adaptive render is the schedule n_0 = min_spp,
+// n_r = min(max_spp, 2 n_{r-1}) of such steps with the frame resolved once at the end, a session lets the caller choose each step's size
+// and reads the frame between any two.  EVERY pixel keeps its state, retired or not, indexed by its owned-pixel index q, 40 B:
 //   a[q] = (S.x, S.y, S.z, mu.x), b[q] = (mu.y, mu.z, M2.x, M2.y), c[q] = (M2.z, count as bits)
 // Every active pixel stands at the same count, the step's s0, so the fold does not read the count (36 B in, 40 B out).
-struct ProgState {
+struct FoldState {
     float4 *a, *b;
     float2 *c;
 };
-struct ProgParams {
+struct FoldParams {
     uint32_t n_max;        // bhrt_opts.spp
     uint32_t n_min;        // bhrt_adaptive_opts.min_spp; 0xffffffff = a uniform session: only n_max retires a pixel
     float threshold, floor;
     uint32_t *next, *n_next; // the next step's list and its length (zeroed by the host before the step)
 };
 
-// One lane per pixel of the pass (P.list, or the first step's range).  k_adapt_fold's recurrence, operation for operation, over samples
-// k = s0 + 1 .. n, and its retirement test where the session has one (n >= n_min).  The state and the count n are stored either way; a pixel
-// that does not retire is appended to the next step's list (wave ballot + prefix popcount, one atomic per workgroup).  The first step
-// (s0 == 0) reads no state, and drops the edge-tile pixels outside the image.
-__global__ void __launch_bounds__(kBlock) k_prog_fold(PassInfo P, const float *samples, ProgState A, ProgParams R)
+// One lane per pixel of the pass (P.list, or the first step's range).  In float32, in sample order, for k = s0 + 1 .. n (x = sample k - 1):
+//   S += x;   d = x - mu;   mu += d / (float)k;   M2 += d * (x - mu)                  (no contraction: -ffp-contract=off)
+// The state and the count n are stored, whatever follows.  The pixel retires when n >= n_max, or, where n >= n_min, when
+//   sqrtf(vL) <= threshold * fmaxf(L, floor)      with
+//        m = S / (float)n                                   (k_resolve's mean: the same additions from 0 in the same order, the same division)
+//        v = (M2 / (float)(n - 1)) / (float)n                (per-channel variance of the mean)
+//        L = (0.2126 m.r + 0.7152 m.g) + 0.0722 m.b,   vL = (0.2126^2 v.r + 0.7152^2 v.g) + 0.0722^2 v.b   (the denoiser's luminance)
+// A pixel that does not retire is appended to the next step's list (wave ballot + prefix popcount, one atomic per workgroup).  No image is
+// written: k_fold_frame does that.  The first step (s0 == 0) reads no state, and drops the edge-tile pixels outside the image.
+__global__ void __launch_bounds__(kBlock) k_fold(PassInfo P, const float *samples, FoldState A, FoldParams R)
 {
     __shared__ uint32_t s_base[kBlock / 64 + 1];
     const uint32_t ql = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1578,11 +1504,12 @@ __global__ void __launch_bounds__(kBlock) k_prog_fold(PassInfo P, const float *s
     if (keep) R.next[s_base[kBlock / 64] + s_base[wave] + (uint32_t)__popcll(mk & ((1ull << lane) - 1ull))] = q;
 }
 
-// The session's frame, on demand: one lane per owned pixel (P.q0 = 0, P.n_pixels = all of them, no list), 40 B in, up to 31 B out.
+// The frame of the kept state: one lane per owned pixel (P.q0 = 0, P.n_pixels = all of them, no list), 40 B in, up to 31 B out.  A session
+// asks for it on demand; the adaptive render runs it once, after its last round.
 //   radiance = S / (float)c   (k_resolve's division)     rgb8 = store_color24 of it (k_resolve's gamma rule)
-//   variance = (M2 / (float)(c - 1)) / (float)c, 0 at c == 1   (k_adapt_fold's)      count = c
-// A pixel at count 0 (no step yet) is written as zeros.  Pixels of other ranks' tiles are not touched.
-__global__ void __launch_bounds__(kBlock) k_prog_frame(PassInfo P, ProgState A, float *radiance, uint8_t *rgb8, float *variance, uint32_t *count)
+//   variance = (M2 / (float)(c - 1)) / (float)c, 0 at c == 1   (k_fold's v)           count = c
+// A pixel at count 0 (no step yet) is written as zeros.  Pixels of other ranks' tiles and edge-tile pixels outside the image are not touched.
+__global__ void __launch_bounds__(kBlock) k_fold_frame(PassInfo P, FoldState A, float *radiance, uint8_t *rgb8, float *variance, uint32_t *count)
 {
     const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
     if (q >= P.n_pixels) return;
@@ -3107,10 +3034,10 @@ static PassSizing SizePasses(DeviceState *D, const bhrt_opts &o, bool ph_frames,
 }
 
 // Renders samples [s0, s0 + spp) of n_items owned pixels of this rank: the range [0, n_items) of owned-pixel indices (d_list == nullptr) or
-// the entries of the device list d_list (an adaptive round), in passes.  Pass sizing, the halve-and-redo of a pass that overflows, the photon
+// the entries of the device list d_list (an adaptive round, a progressive step), in passes.  Pass sizing, the halve-and-redo of a pass that overflows, the photon
 // gather per pass, the slow queue and the any-hit overlap are the same for both.  consume(P, npx, F) launches, on D->stream, what reads a finished
-// pass's sample-major buffer D->d_samples: k_resolve / k_variance / k_copy_samples for a uniform render (RenderRange), k_adapt_fold for an
-// adaptive round (RenderAdaptive).  The caller synchronises and flushes the timers.
+// pass's sample-major buffer D->d_samples: k_resolve / k_variance / k_copy_samples for a uniform render (RenderRange), k_fold for an
+// adaptive round or a progressive step (FoldStep).  The caller synchronises and flushes the timers.
 // fuse_root: the consumer is k_resolve_frames, which reads the root frames themselves.  k_shade then fills the slot -> root frame map D->d_root
 // instead of storing background samples, and the root level of k_combine is not launched; d_samples holds nothing the consumer may read.
 template <class Consume>
@@ -3234,45 +3161,83 @@ static int RenderRange(bhrt_scene *scene, const bhrt_opts &o, uint8_t *d_rgb8, f
     return BHRT_OK;
 }
 
-// The adaptive render: rounds of RenderPixels over the pixels still active, each pass folded by k_adapt_fold.  The host reads
-// the next list's length once per round (4 bytes).  Options checked by the caller (AdaptiveArgsError).
+// ---- adaptive render and progressive session ---------------------------------------------------------------------------
+// The estimator's device state for N owned pixels, in one buffer: a[N] b[N] c[N] list0[N] list1[N] n_next, 48 N + 16 bytes.
+struct FoldViews {
+    FoldState A;
+    uint32_t *lists[2], *n_next;
+};
+static int ReserveFoldState(DevBuf<uint8_t> &buf, size_t N, FoldViews &V)
+{
+    BHRT_TRY(buf.Reserve(N * 48 + 16));
+    V.A.a = (float4 *)buf.p; V.A.b = V.A.a + N; V.A.c = (float2 *)(V.A.b + N);
+    V.lists[0] = (uint32_t *)(V.A.c + N); V.lists[1] = V.lists[0] + N;
+    V.n_next = V.lists[1] + N;
+    return BHRT_OK;
+}
+// FramePassInfo for a render that lists owned-pixel indices in 32 bits; `what` opens the message
+static int FoldPassInfo(bhrt_scene *scene, const bhrt_opts &o, const char *what, PassInfo &P, uint64_t &owned_pixels)
+{
+    BHRT_TRY(FramePassInfo(scene, o, P, owned_pixels));
+    if (owned_pixels > 0xffffffffull) { SetError(std::string(what) + ": more than 2^32 owned pixels"); return BHRT_ERR_ARG; }
+    return BHRT_OK;
+}
+
+// One step: samples [s0, s0 + spp) of the `items` active pixels through RenderPixels, each pass folded by k_fold.  The first step (s0 == 0) takes
+// the range of owned pixels (and drops those outside the image), a later one the list V.lists[cur] that the step before left; the survivors go
+// to V.lists[cur ^ 1].  R: n_max, n_min, threshold, floor.  The host reads the next list's length, `active`, once (4 bytes), and synchronises.
+static int FoldStep(bhrt_scene *scene, const bhrt_opts &o, const PassInfo &P, const FoldViews &V, int cur, uint64_t items, uint32_t s0, uint32_t spp,
+                    FoldParams R, bhrt_stats *st, uint32_t &active)
+{
+    DeviceState *D = scene->dev;
+    const FoldState A = V.A;
+    R.next = V.lists[cur ^ 1]; R.n_next = V.n_next;
+    HIP_CHECK(hipMemsetAsync(R.n_next, 0, sizeof(uint32_t), D->stream));
+    BHRT_TRY(RenderPixels(scene, o, P, s0 ? V.lists[cur] : nullptr, items, s0, spp, st, false, [&](const PassInfo &Pp, uint32_t npx, const Frames &) {
+        hipLaunchKernelGGL(k_fold, dim3((npx + kBlock - 1) / kBlock), dim3(kBlock), 0, D->stream, Pp, D->d_samples, A, R);
+    }));
+    HIP_CHECK(hipMemcpyAsync(&active, R.n_next, sizeof active, hipMemcpyDeviceToHost, D->stream));
+    HIP_CHECK(hipStreamSynchronize(D->stream));
+    return BHRT_OK;
+}
+// The frame of the state in V on stream s, into the caller's images (any may be NULL).  A zero-sized grid is a launch error: nothing is launched for no pixels.
+static int FoldFrame(PassInfo P, const FoldViews &V, uint64_t owned_pixels, uint8_t *d_rgb8, float *d_radiance, float *d_variance, uint32_t *d_count, hipStream_t s)
+{
+    if (owned_pixels == 0) return BHRT_OK;
+    P.q0 = 0; P.n_pixels = (uint32_t)owned_pixels;
+    hipLaunchKernelGGL(k_fold_frame, dim3((P.n_pixels + kBlock - 1) / kBlock), dim3(kBlock), 0, s, P, V.A, d_radiance, d_rgb8, d_variance, d_count);
+    HIP_CHECK(hipGetLastError());
+    return BHRT_OK;
+}
+
+// The adaptive render: the doubling schedule over FoldStep, then the frame, once.  Its state (DeviceState::d_ad) is not zeroed:
+// round 0 reads none and writes that of every pixel the frame kernel later reads.  Options checked by the caller (AdaptiveArgsError).
 static int RenderAdaptive(bhrt_scene *scene, const bhrt_opts &o, const bhrt_adaptive_opts &ao, uint8_t *d_rgb8, float *d_radiance, float *d_variance,
                           uint32_t *d_count, bhrt_stats *st)
 {
     DeviceState *D = scene->dev;
     PassInfo P;
     uint64_t owned_pixels = 0;
-    int rc = FramePassInfo(scene, o, P, owned_pixels);
-    if (rc) return rc;
-    if (owned_pixels > 0xffffffffull) { SetError("adaptive render: more than 2^32 owned pixels"); return BHRT_ERR_ARG; }
-    BHRT_TRY(D->d_ad.Reserve((size_t)owned_pixels * 44 + 16));
-    const size_t N = (D->d_ad.n - 16) / 44; // the pixels the buffer was sized for
-    AdaptState A;
-    A.a = (float4 *)D->d_ad.p; A.b = A.a + N; A.c = (float *)(A.b + N);
-    uint32_t *lists[2] = {(uint32_t *)(A.c + N), (uint32_t *)(A.c + N) + N};
-    AdaptParams R;
-    R.n_max = (uint32_t)o.spp; R.threshold = ao.threshold; R.floor = ao.floor;
-    R.radiance = d_radiance; R.variance = d_variance; R.rgb8 = d_rgb8; R.count = d_count;
-    R.n_next = lists[1] + N;
+    BHRT_TRY(FoldPassInfo(scene, o, "adaptive render", P, owned_pixels));
+    FoldViews V;
+    BHRT_TRY(ReserveFoldState(D->d_ad, (size_t)owned_pixels, V));
+    FoldParams R = {};
+    R.n_max = (uint32_t)o.spp; R.n_min = (uint32_t)ao.min_spp; R.threshold = ao.threshold; R.floor = ao.floor;
     const auto wall0 = std::chrono::steady_clock::now();
     uint32_t n_prev = 0, n = (uint32_t)ao.min_spp;
     uint64_t items = owned_pixels;
-    const uint32_t *list = nullptr; // round 0: the contiguous range
     for (int cur = 0; items > 0; cur ^= 1) {
-        R.next = lists[cur];
-        HIP_CHECK(hipMemsetAsync(R.n_next, 0, sizeof(uint32_t), D->stream));
-        rc = RenderPixels(scene, o, P, list, items, n_prev, n - n_prev, st, false, [&](const PassInfo &Pp, uint32_t npx, const Frames &) {
-            hipLaunchKernelGGL(k_adapt_fold, dim3((npx + kBlock - 1) / kBlock), dim3(kBlock), 0, D->stream, Pp, D->d_samples, A, R);
-        });
-        if (rc) return rc;
         uint32_t active = 0;
-        HIP_CHECK(hipMemcpyAsync(&active, R.n_next, sizeof active, hipMemcpyDeviceToHost, D->stream));
-        HIP_CHECK(hipStreamSynchronize(D->stream));
+        BHRT_TRY(FoldStep(scene, o, P, V, cur, items, n_prev, n - n_prev, R, st, active));
         if (n >= (uint32_t)o.spp && active) { SetError("adaptive render: pixels active after the last round"); return BHRT_ERR_HIP; }
         items = active;
-        list = lists[cur];
         n_prev = n;
         n = (uint32_t)std::min<uint64_t>((uint64_t)o.spp, 2ull * n);
+    }
+    {
+        Timer t(D, &st->seconds_other);
+        BHRT_TRY(FoldFrame(P, V, owned_pixels, d_rgb8, d_radiance, d_variance, d_count, D->stream));
+        t.Stop();
     }
     HIP_CHECK(hipStreamSynchronize(D->stream));
     FlushTimers(D, true);
@@ -3280,35 +3245,30 @@ static int RenderAdaptive(bhrt_scene *scene, const bhrt_opts &o, const bhrt_adap
     return BHRT_OK;
 }
 
-// ---- progressive session -------------------------------------------------------------------------------------------------
-// The session's device state: d_prog = a[N] b[N] c[N] list0[N] list1[N] n_next.  Allocated and zeroed (count 0 everywhere: a frame before the
-// first step) when the session first needs the device.
-struct ProgViews {
-    ProgState A;
-    uint32_t *lists[2], *n_next;
-};
-static int EnsureProgState(bhrt_scene *scene, ProgViews &V)
+// The session's device state, DeviceState::d_prog.  Allocated and zeroed (count 0 everywhere: a frame before the first step) when the session
+// first needs the device.
+static int EnsureProgState(bhrt_scene *scene, FoldViews &V)
 {
     DeviceState *D = scene->dev;
     ProgressiveSession &G = scene->prog;
     const size_t N = (size_t)G.owned;
-    if (D->prog_session != G.id) { // this device state holds nothing of the session
+    const bool fresh = D->prog_session != G.id; // this device state holds nothing of the session
+    if (fresh) {
         // bhrt_scene_upload refuses to drop a device state that holds a session's, so this is not reached through the public calls
         if (G.c) { SetError("progressive session: its state is not on this device (session state lost): bhrt_progressive_end and begin again"); return BHRT_ERR_ARG; }
         D->prog_session = 0;
-        BHRT_TRY(D->d_prog.Reserve(N * 48 + 16));
+    }
+    BHRT_TRY(ReserveFoldState(D->d_prog, N, V)); // the session's own buffer already holds N pixels: a view of it
+    if (fresh) {
         HIP_CHECK(hipMemsetAsync(D->d_prog.p, 0, N * 40, D->stream));
         HIP_CHECK(hipStreamSynchronize(D->stream)); // bhrt_progressive_frame_dev may read it on the caller's stream
         D->prog_session = G.id;
     }
-    V.A.a = (float4 *)D->d_prog.p; V.A.b = V.A.a + N; V.A.c = (float2 *)(V.A.b + N);
-    V.lists[0] = (uint32_t *)(V.A.c + N); V.lists[1] = V.lists[0] + N;
-    V.n_next = V.lists[1] + N;
     return BHRT_OK;
 }
 
-// One step: samples [c, c1) of every active pixel through RenderPixels, each pass folded by k_prog_fold.  The host reads the next list's
-// length once (4 bytes); what bhrt_progressive_status reports follows from it (ProgressiveSession).
+// One step of the session: FoldStep over samples [c, c1) of every active pixel; what bhrt_progressive_status reports follows from the count
+// it returns (ProgressiveSession).
 static int ProgressiveStep(bhrt_scene *scene, uint32_t n_samples, bhrt_stats *st)
 {
     DeviceState *D = scene->dev;
@@ -3317,25 +3277,15 @@ static int ProgressiveStep(bhrt_scene *scene, uint32_t n_samples, bhrt_stats *st
     PassInfo P;
     uint64_t owned_pixels = 0;
     BHRT_TRY(FramePassInfo(scene, o, P, owned_pixels)); // every step: bhrt_scene_set_lens between two steps applies to this one's samples
-    ProgViews V;
+    FoldViews V;
     BHRT_TRY(EnsureProgState(scene, V));
     const uint32_t c1 = (uint32_t)std::min<uint64_t>((uint64_t)o.spp, (uint64_t)G.c + n_samples);
-    ProgParams R;
+    FoldParams R = {};
     R.n_max = (uint32_t)o.spp; R.n_min = G.adaptive ? (uint32_t)G.a.min_spp : 0xffffffffu;
     R.threshold = G.a.threshold; R.floor = G.a.floor;
-    R.next = V.lists[G.cur ^ 1]; R.n_next = V.n_next;
     const auto wall0 = std::chrono::steady_clock::now();
-    HIP_CHECK(hipMemsetAsync(R.n_next, 0, sizeof(uint32_t), D->stream));
-    const ProgState A = V.A;
-    // the first step takes the range of owned pixels (and drops those outside the image); later ones the list the step before left
-    const int rc = RenderPixels(scene, o, P, G.c ? V.lists[G.cur] : nullptr, G.c ? G.active : G.owned, G.c, c1 - G.c, st, false,
-                                [&](const PassInfo &Pp, uint32_t npx, const Frames &) {
-                                    hipLaunchKernelGGL(k_prog_fold, dim3((npx + kBlock - 1) / kBlock), dim3(kBlock), 0, D->stream, Pp, D->d_samples, A, R);
-                                });
-    if (rc) return rc; // a pass may have been folded: bhrt_progressive_step marks the session failed
     uint32_t active = 0;
-    HIP_CHECK(hipMemcpyAsync(&active, R.n_next, sizeof active, hipMemcpyDeviceToHost, D->stream));
-    HIP_CHECK(hipStreamSynchronize(D->stream));
+    BHRT_TRY(FoldStep(scene, o, P, V, G.cur, G.c ? G.active : G.owned, G.c, c1 - G.c, R, st, active)); // a pass may have been folded: bhrt_progressive_step marks the session failed
     FlushTimers(D, true);
     if (active > G.active || (c1 >= (uint32_t)o.spp && active)) { SetError("progressive step: pixels active after their last sample"); return BHRT_ERR_HIP; }
     const uint64_t retired = G.active - active;
@@ -3771,8 +3721,7 @@ try {
     BHRT_CHECK_CAUSTIC(scene, opts);
     PassInfo P;
     uint64_t owned_pixels = 0;
-    BHRT_TRY(FramePassInfo(scene, *opts, P, owned_pixels)); // spp in 1..65535, rank, bounce counts: host arithmetic only
-    if (owned_pixels > 0xffffffffull) { SetError("progressive session: more than 2^32 owned pixels"); return BHRT_ERR_ARG; }
+    BHRT_TRY(FoldPassInfo(scene, *opts, "progressive session", P, owned_pixels)); // spp in 1..65535, rank, bounce counts: host arithmetic only
     static uint64_t next_id = 0; // calls on different scenes may overlap
     ProgressiveSession G;
     G.id = __atomic_add_fetch(&next_id, 1, __ATOMIC_RELAXED);
@@ -3815,13 +3764,10 @@ try {
     PassInfo P;
     uint64_t owned_pixels = 0;
     BHRT_TRY(FramePassInfo(scene, G.o, P, owned_pixels));
-    ProgViews V;
+    FoldViews V;
     BHRT_TRY(EnsureProgState(scene, V));
-    if (G.owned == 0) return BHRT_OK;
-    P.q0 = 0; P.n_pixels = (uint32_t)G.owned;
     hipStream_t st = stream ? (hipStream_t)stream : D->stream;
-    hipLaunchKernelGGL(k_prog_frame, dim3((P.n_pixels + kBlock - 1) / kBlock), dim3(kBlock), 0, st, P, V.A, d_radiance, d_rgb8, d_variance, d_count);
-    HIP_CHECK(hipGetLastError());
+    BHRT_TRY(FoldFrame(P, V, G.owned, d_rgb8, d_radiance, d_variance, d_count, st));
     if (!stream) HIP_CHECK(hipStreamSynchronize(st));
     return BHRT_OK;
 } catch (...) { return bhrt::AbiException(); }

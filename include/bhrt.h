@@ -349,9 +349,9 @@ int bhrt_denoise(bhrt_scene *scene, const bhrt_denoise_opts *opts, const float *
  *   v_c = (M2_c / (n - 1)) / n      (variance of the mean, per channel)
  *   L   = (0.2126 m_r + 0.7152 m_g) + 0.0722 m_b,   vL = (0.2126^2 v_r + 0.7152^2 v_g) + 0.0722^2 v_b
  *   the pixel retires when n == max_spp or sqrt(vL) <= threshold * max(L, floor).
- * The test reads the pixel's own samples only: results do not depend on rank, world size, tile size or pass size.  A retiring pixel
- * writes its radiance, RGB8 bytes (bhrt_opts.gamma as bhrt_render), variance (laid out like bhrt_render_var's) and count n once;
- * pixels of other ranks' tiles are left untouched.  Ranks may finish unevenly: adaptive work is not rebalanced between them. */
+ * The test reads the pixel's own samples only: results do not depend on rank, world size, tile size or pass size.  After the last
+ * round every owned pixel's radiance, RGB8 bytes (bhrt_opts.gamma as bhrt_render), variance (laid out like bhrt_render_var's) and count n are
+ * written, once; pixels of other ranks' tiles are left untouched.  What the images hold after a call that returned an error is unspecified.  Ranks may finish unevenly: adaptive work is not rebalanced between them. */
 typedef struct bhrt_adaptive_opts {
     int32_t min_spp;  /* samples of round 0, >= 2; bhrt_opts.spp is the per-pixel maximum (<= 65535); default 16 */
     float threshold;  /* relative standard error of the mean's luminance; < 0 = never retire early (every pixel reaches spp), +inf = every
@@ -363,7 +363,7 @@ void bhrt_default_adaptive_opts(bhrt_adaptive_opts *a);
 /* The arguments are checked before any device is touched: 2 <= min_spp <= spp <= 65535, floor > 0, threshold not NaN, else BHRT_ERR_ARG.
  * rgb8 / radiance / variance: as bhrt_render_var's (each may be NULL); count: W*H uint32 samples per pixel (may be NULL).
  * stats->camera_samples = the sum of the counts of the owned pixels inside the image.  _dev: device pointers (the render synchronises its
- * own stream); the state of the rounds (44 B per owned pixel) belongs to the scene. */
+ * own stream); the state of the rounds (48 B per owned pixel) belongs to the scene. */
 int bhrt_render_adaptive_dev(bhrt_scene *scene, const bhrt_opts *opts, const bhrt_adaptive_opts *aopts, uint8_t *d_rgb8, float *d_radiance, float *d_variance,
                              uint32_t *d_count, bhrt_stats *stats, void *stream);
 int bhrt_render_adaptive(bhrt_scene *scene, const bhrt_opts *opts, const bhrt_adaptive_opts *aopts, uint8_t *rgb8, float *radiance, float *variance,

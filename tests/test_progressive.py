@@ -250,8 +250,9 @@ def test_off_the_schedule(B, scene):
     assert set(levels) <= {6, 9, 12, 15, 16} and len(levels) >= 2
     for n in levels:
         sel = cnt == n
-        urgb, urad, _ = sc.render(B.default_opts(spp=n, gi_bounces=3, seed=11))
+        urgb, urad, uvar = sc.render_var(B.default_opts(spp=n, gi_bounces=3, seed=11))
         assert np.array_equal(rgb[sel], urgb[sel]) and same_bits(rad[sel], urad[sel]), n
+        assert np.all(np.abs(var[sel] - uvar[sel]) <= 1e-4 * np.abs(uvar[sel]) + 1e-12), n  # the two-pass variance: the session's anchor outside the fold
     assert int(cnt.sum(dtype=np.uint64)) == sum(st.camera_samples for _, st, _ in run)
 
 

@@ -5,7 +5,8 @@ frames (min 16, max 256) over a grid of thresholds and floors; each line gives t
 render's wall time (bhrt_stats.seconds_total, scene resident, outputs in HBM; the best of --reps renders after a warm-up render).  Prints one
 JSON line per frame, then a summary line per scene: the cheapest adaptive setting whose MSE is at most uniform-64's, and its time over
 uniform-64's.  --once: one uniform (64 spp) and one adaptive frame (the defaults) of the first scene, for a profiler run
-(`rocprofv3 --kernel-trace --stats -- python tools/adaptive_quality.py --once`)."""
+(`rocprofv3 --kernel-trace --stats -- python tools/adaptive_quality.py --once`).  --time-only: per scene, only the wall times of 1 + --reps adaptive
+frames (min 16, max 256, the first threshold and floor), one JSON line; with BHRT_LIB set, of that build: run it in turns to compare two builds."""
 import argparse
 import json
 import os
@@ -26,6 +27,7 @@ def main():
     ap.add_argument("--floors", default="0.05,0.1")
     ap.add_argument("--reps", type=int, default=2)
     ap.add_argument("--once", action="store_true")
+    ap.add_argument("--time-only", action="store_true")
     a = ap.parse_args()
     import torch
     import bhraytracer_amd as B
@@ -55,6 +57,12 @@ def main():
             adaptive(B.default_adaptive_opts())
             print(json.dumps({"scene": name, "once": True}))
             return
+        if a.time_only:
+            ao = B.default_adaptive_opts(min_spp=16, threshold=float(a.thresholds.split(",")[0]), floor=float(a.floors.split(",")[0]))
+            sts = [sc.render_adaptive_dev(B.default_opts(spp=256, seed=1), ao, rgb.data_ptr(), rad.data_ptr(), 0, cnt.data_ptr()) for _ in range(1 + a.reps)]
+            print(json.dumps({"scene": name, "lib": B.LIB_PATH, "warmup_s": sts[0].seconds_total, "seconds": [s.seconds_total for s in sts[1:]],
+                              "samples": sts[-1].camera_samples, "passes": sts[-1].passes}), flush=True)
+            continue
         ref, _, _ = uniform(a.ref_spp, seed=1000, reps=0)
         rows = []
         for spp in (32, 64, 128):
