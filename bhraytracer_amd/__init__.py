@@ -93,6 +93,7 @@ EXPORTS = [
     "bhrt_scene_set_global_gather", "bhrt_global_map_build", "bhrt_global_map_set", "bhrt_global_map_get", "bhrt_global_gather_host",
     "bhrt_progressive_begin", "bhrt_progressive_step", "bhrt_progressive_frame", "bhrt_progressive_frame_dev", "bhrt_progressive_status",
     "bhrt_progressive_end",
+    "bhrt_guides", "bhrt_guides_dev",
 ]
 
 
@@ -495,6 +496,28 @@ class Scene:
     def first_hit_dev(self, d_z: int = 0, d_normal: int = 0, d_albedo: int = 0, stream: int = 0):
         _check(lib().bhrt_first_hit_dev(self._h, C.c_void_p(d_z or None), C.c_void_p(d_normal or None), C.c_void_p(d_albedo or None),
                                         C.c_void_p(stream or None)))
+
+    def guides(self, opts: Opts, want=("z", "normal", "albedo", "coverage"), into=None):
+        """Sampled guide images (bhrt_guides): z (H, W), normal (H, W, 3), albedo (H, W, 3) and coverage (H, W), formed by the
+        camera samples of a render with these options (spp, seed, jitter, lens, rank / world_size / tile_size, samples_per_pass) and averaged
+        per pixel.  Returns a dict of the images named in `want` (the others are passed as NULL); `into`: a dict of host arrays to write into
+        instead of fresh zeros (pixels of other ranks' tiles keep what they hold)."""
+        H, W = self.height, self.width
+        shapes = {"z": (H, W), "normal": (H, W, 3), "albedo": (H, W, 3), "coverage": (H, W)}
+        out = {}
+        for k in want:
+            a = into[k] if into is not None and k in into else np.zeros(shapes[k], np.float32)
+            if a.dtype != np.float32 or a.shape != shapes[k] or not a.flags["C_CONTIGUOUS"]:
+                raise ValueError(f"{k}: expected a contiguous float32 array of shape {shapes[k]}")
+            out[k] = a
+        p = lambda k: _ptr(out[k]) if k in out else None  # noqa: E731
+        _check(lib().bhrt_guides(self._h, C.byref(opts), p("z"), p("normal"), p("albedo"), p("coverage")))
+        return out
+
+    def guides_dev(self, opts: Opts, d_z: int = 0, d_normal: int = 0, d_albedo: int = 0, d_coverage: int = 0, stream: int = 0):
+        """bhrt_guides_dev on raw device pointers (0 = NULL); with a stream the call does not synchronise."""
+        v = lambda x: C.c_void_p(x or None)  # noqa: E731
+        _check(lib().bhrt_guides_dev(self._h, C.byref(opts), v(d_z), v(d_normal), v(d_albedo), v(d_coverage), v(stream)))
 
     def zbuffer_image_dev(self, d_z: int, n: int, d_img: int, stream: int = 0):
         """RenderImage::ComputeZBufferImage (scene.h:578-600) on device buffers."""

@@ -6,7 +6,7 @@
 //   bhrt render <scene.xml> [-o out.png] [--spp N] [--gi N] [--bounces N] [--seed S] [--no-jitter] [--no-gamma]
 //               [--device D | --gpus N [--rehearse]] [--rank R --world N] [--tile T] [--radiance out.f32] [--leaf-skip] [--photon-exact]
 //               [--photons N] [--photon-file map.dat] [--photon-out map.dat]     (USE_PhotonMap, Main.cpp:51,53,194,383)
-//               [--denoise [--denoise-iters K]]                                  (DenoiseImage of the x64 build, Main.cpp:57-96,236-238)
+//               [--denoise [--denoise-iters K] [--guide-spp N]]                  (DenoiseImage of the x64 build, Main.cpp:57-96,236-238)
 //               [--adaptive [--spp-min N] [--adaptive-threshold X] [--samples-png path]]  (RenderImage::sampleCount, scene.h:534,603-630)
 //               [--lens [--dof R] [--focaldist D]]                               (the viewport's depth of field, viewport.cpp:236-243, rendered)
 //               [--emission]                                                     (the <emission> of the materials, xmlload.cpp:344-348, shaded)
@@ -27,12 +27,16 @@
 // --denoise: the PNG is the denoised frame (bhrt_denoise, as the reference's 64-bit build saves it); --radiance stays the render's own
 // radiance.  With --gpus N the ranks' variance tiles travel in a second block beside the first and GPU 0 denoises the gathered frame; a
 // partial frame (--world > 1) cannot be denoised.
+// --guide-spp N (needs --denoise; without it a usage error): the filter's guides (depth, normal, albedo) are bhrt_guides' at N samples per pixel with
+// the render's seed, jitter and lens: averaged over the pixel footprint the colour image is averaged over.  0, the default: the
+// guides the denoiser computes itself, the pinhole ray through the pixel corner.  With --gpus N the guides are computed where the denoiser runs,
+// on GPU 0 for the whole frame.
 // --adaptive: bhrt_render_adaptive; --spp is the per-pixel maximum, --spp-min round 0's samples.  --samples-png writes the
 // sample-count image as SaveSampleCountImage does (scene.h:630); its normalisation needs the whole frame, so --world > 1 refuses it.  With
 // --gpus N the counts travel as the float section of a further block (exact below 2^24); with --denoise the adaptive variance is the filter's.
 // --lens: bhrt_opts.lens = 1, a thin-lens camera with the scene's <dof> as aperture radius, focused at <focaldist>.  --dof R and
 // --focaldist D replace the scene's values (bhrt_scene_set_lens, before the upload) and imply --lens.  The option travels in bhrt_opts, so it
-// works with --gpus, --adaptive and --denoise; the denoiser's guides stay those of the pinhole ray.
+// works with --gpus, --adaptive and --denoise; the denoiser's guides stay those of the pinhole ray unless --guide-spp asks for sampled ones.
 // --emission: bhrt_scene_set_emissive(scene, 1) before the upload and before --gpus N clones the scene: every Shade() frame of a Blinn
 // material adds its <emission> last.  Scene state, so it reaches every render the other options choose (--gpus, --rehearse, --denoise, --adaptive,
 // --lens); the denoiser's albedo guide stays the diffuse colour.  Without the flag the frame is the reference's, which never shades <emission>.
@@ -85,6 +89,8 @@ struct Args {
     bool rehearse = false; // --rehearse: the N ranks of --gpus N all on device 0, the all-gather as N device-to-device copies (no RCCL)
     bool denoise = false;
     bhrt_denoise_opts dn;
+    int guide_spp = 0;                 // --guide-spp N: the denoiser's guides from bhrt_guides at N samples per pixel; 0 = the denoiser's own first hit
+    bool guide_spp_given = false;
     bool adaptive = false;
     bhrt_adaptive_opts ad;
     std::string samples_png;
@@ -160,6 +166,25 @@ static int render_progressive(bhrt_scene *scene, const Args &A, const bhrt_info 
     if (bhrt_progressive_end(scene)) return fail("StopRender");
     printf("progressive: %u step(s) of %d, %s\n", pg.steps, A.progressive, pg.finished ? "finished" : "stopped by --time-limit");
     return 0;
+}
+
+// The options of the guide images --guide-spp asks for: the render's seed, jitter and lens, the whole frame
+static bhrt_opts guide_opts(const Args &A)
+{
+    bhrt_opts g = A.o;
+    g.spp = A.guide_spp; g.rank = 0; g.world_size = 1;
+    return g;
+}
+
+// DenoiseImage on host images (Main.cpp:236-238), with sampled guides when --guide-spp asks for them; rgb receives the filter's bytes
+static int denoise_frame(bhrt_scene *scene, const Args &A, const bhrt_info &info, const float *rad, const float *var, uint8_t *rgb)
+{
+    if (A.guide_spp <= 0) return bhrt_denoise(scene, &A.dn, rad, var, nullptr, nullptr, nullptr, nullptr, rgb) ? fail("DenoiseImage") : 0;
+    const size_t npx = (size_t)info.width * info.height;
+    std::vector<float> z(npx), nrm(npx * 3), alb(npx * 3);
+    const bhrt_opts g = guide_opts(A);
+    if (bhrt_guides(scene, &g, z.data(), nrm.data(), alb.data(), nullptr)) return fail("guide images");
+    return bhrt_denoise(scene, &A.dn, rad, var, z.data(), nrm.data(), alb.data(), nullptr, rgb) ? fail("DenoiseImage") : 0;
 }
 
 // Everything render_multi owns besides the caller's scene: released on every way out (the early returns included).
@@ -258,7 +283,7 @@ static int render_multi(bhrt_scene *first, const Args &A, const bhrt_info &info,
     for (int r = 0; r < N; r++)
         th.emplace_back([&, r]() {
             uint8_t *d_rgb = nullptr, *d_mine = nullptr, *d_all = nullptr, *d_mine_v = nullptr, *d_all_v = nullptr, *d_mine_c = nullptr, *d_all_c = nullptr;
-            float *d_rad = nullptr, *d_var = nullptr, *d_cntf = nullptr;
+            float *d_rad = nullptr, *d_var = nullptr, *d_cntf = nullptr, *d_guide = nullptr;
             uint32_t *d_cnt = nullptr;
             hipStream_t s = nullptr;
             auto setup = [&]() {
@@ -277,6 +302,7 @@ static int render_multi(bhrt_scene *first, const Args &A, const bhrt_info &info,
                     HOST_CHECK(hipMalloc(&d_mine_v, bb), "hipMalloc");
                     HOST_CHECK(hipMalloc(&d_all_v, bb * N), "hipMalloc");
                     HOST_CHECK(hipMemsetAsync(d_var, 0, npx * 3 * sizeof(float), s), "memset");
+                    if (r == 0 && A.guide_spp > 0) HOST_CHECK(hipMalloc(&d_guide, npx * 7 * sizeof(float)), "hipMalloc"); // z, normal, albedo
                 }
                 if (A.adaptive) { // the counts: a further block whose float section holds them (channel 0 of a W x H x 3 float image)
                     HOST_CHECK(hipMalloc(&d_cnt, npx * sizeof(uint32_t)), "hipMalloc");
@@ -290,7 +316,7 @@ static int render_multi(bhrt_scene *first, const Args &A, const bhrt_info &info,
             setup();
             auto release = [&]() {
                 (void)hipFree(d_rgb); (void)hipFree(d_rad); (void)hipFree(d_mine); (void)hipFree(d_all);
-                (void)hipFree(d_var); (void)hipFree(d_mine_v); (void)hipFree(d_all_v);
+                (void)hipFree(d_var); (void)hipFree(d_mine_v); (void)hipFree(d_all_v); (void)hipFree(d_guide);
                 (void)hipFree(d_cnt); (void)hipFree(d_cntf); (void)hipFree(d_mine_c); (void)hipFree(d_all_c);
                 if (s) (void)hipStreamDestroy(s);
             };
@@ -355,7 +381,12 @@ static int render_multi(bhrt_scene *first, const Args &A, const bhrt_info &info,
                 HOST_CHECK(hipStreamSynchronize(s), "sync");
                 gather_s[r] = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
                 if (r == 0 && A.denoise) { // DenoiseImage on the gathered frame (Main.cpp:236-238): the PNG bytes become the filter's
-                    HOST_CHECK(bhrt_denoise_dev(scenes[0], &A.dn, d_rad, d_var, nullptr, nullptr, nullptr, nullptr, d_rgb, s), "denoise");
+                    if (d_guide) { // --guide-spp: the whole frame's guides, here where the filter runs
+                        const bhrt_opts g = guide_opts(A);
+                        HOST_CHECK(bhrt_guides_dev(scenes[0], &g, d_guide, d_guide + npx, d_guide + 4 * npx, nullptr, s), "guide images");
+                    }
+                    HOST_CHECK(bhrt_denoise_dev(scenes[0], &A.dn, d_rad, d_var, d_guide, d_guide ? d_guide + npx : nullptr, d_guide ? d_guide + 4 * npx : nullptr, nullptr, d_rgb, s),
+                               "denoise");
                     HOST_CHECK(hipStreamSynchronize(s), "sync");
                 }
                 if (r == 0) {
@@ -416,6 +447,7 @@ int main(int argc, char **argv)
         else if (s == "--photon-out") A.photon_out = next();
         else if (s == "--denoise") A.denoise = true;
         else if (s == "--denoise-iters") A.dn.iterations = atoi(next());
+        else if (s == "--guide-spp") { A.guide_spp = atoi(next()); A.guide_spp_given = true; }
         else if (s == "--adaptive") A.adaptive = true;
         else if (s == "--spp-min") A.ad.min_spp = atoi(next());
         else if (s == "--adaptive-threshold") A.ad.threshold = (float)atof(next());
@@ -438,6 +470,8 @@ int main(int argc, char **argv)
         return 2;
     }
     if (A.denoise && (A.dn.iterations < 0 || A.dn.iterations > 16)) { fprintf(stderr, "bhrt: usage: --denoise-iters must be in 0..16\n"); return 2; }
+    if (A.guide_spp_given && !A.denoise) { fprintf(stderr, "bhrt: usage: --guide-spp needs --denoise (the guide images steer the denoiser)\n"); return 2; }
+    if (A.guide_spp < 0 || A.guide_spp > 65535) { fprintf(stderr, "bhrt: usage: --guide-spp must be in 0..65535 (0 = the denoiser's own first-hit guides)\n"); return 2; }
     if (!A.adaptive && !A.samples_png.empty()) { fprintf(stderr, "bhrt: usage: --samples-png needs --adaptive\n"); return 2; }
     if (A.adaptive && !A.samples_png.empty() && o.world_size > 1) { // before any device is touched
         fprintf(stderr, "bhrt: usage: --samples-png normalises over the whole frame; a rank of --world %d renders part of it (use --gpus N)\n", o.world_size);
@@ -478,8 +512,9 @@ int main(int argc, char **argv)
         if ((A.dof >= 0.f || A.focaldist > 0.f) && bhrt_scene_set_lens(scene, A.focaldist, A.dof >= 0.f ? A.dof : fh->camera.dof)) return fail("set lens");
         if (!(fh->camera.dof >= 0.f && fh->camera.dof <= 3.402823466e38f)) { fprintf(stderr, "bhrt: usage: --lens: the scene's <dof> must be a finite number >= 0 (or give --dof)\n"); return 2; }
         printf("lens: focal distance %g, aperture radius %g%s\n", fh->camera.focaldist, fh->camera.dof, fh->camera.dof > 0.f ? "" : " (pinhole)");
-        if (A.denoise) printf("note: --denoise guides (depth, normal, albedo) are those of the pinhole ray; lens-averaged guides are not implemented\n");
+        if (A.denoise && A.guide_spp <= 0) printf("note: --denoise guides (depth, normal, albedo) are those of the pinhole ray; --guide-spp N forms them from the lens rays\n");
     }
+    if (A.denoise && A.guide_spp > 0) printf("denoise guides: %d sample(s) per pixel%s\n", A.guide_spp, o.lens ? ", through the lens" : "");
     std::vector<uint8_t> rgb((size_t)info.width * info.height * 3, 0);
     std::vector<float> rad(A.radiance_out.empty() && !A.denoise ? 0 : (size_t)info.width * info.height * 3, 0.f);
     std::vector<uint32_t> cnt(A.adaptive ? (size_t)info.width * info.height : 0, 0u);
@@ -521,16 +556,16 @@ int main(int argc, char **argv)
         if (A.progressive_given) {
             std::vector<float> var(A.denoise ? rad.size() : 0, 0.f);
             if (render_progressive(scene, A, info, rgb, rad, var, cnt, st)) return 1;
-            if (A.denoise && bhrt_denoise(scene, &A.dn, rad.data(), var.data(), nullptr, nullptr, nullptr, nullptr, rgb.data())) return fail("DenoiseImage");
+            if (A.denoise && denoise_frame(scene, A, info, rad.data(), var.data(), rgb.data())) return 1;
         } else if (A.adaptive) {
             std::vector<float> var(A.denoise ? rad.size() : 0, 0.f);
             if (bhrt_render_adaptive(scene, &o, &A.ad, rgb.data(), rad.empty() ? nullptr : rad.data(), var.empty() ? nullptr : var.data(), cnt.data(), &st))
                 return fail("BeginRender (adaptive)");
-            if (A.denoise && bhrt_denoise(scene, &A.dn, rad.data(), var.data(), nullptr, nullptr, nullptr, nullptr, rgb.data())) return fail("DenoiseImage");
+            if (A.denoise && denoise_frame(scene, A, info, rad.data(), var.data(), rgb.data())) return 1;
         } else if (A.denoise) {
             std::vector<float> var(rad.size(), 0.f);
             if (bhrt_render_var(scene, &o, rgb.data(), rad.data(), var.data(), &st)) return fail("BeginRender");
-            if (bhrt_denoise(scene, &A.dn, rad.data(), var.data(), nullptr, nullptr, nullptr, nullptr, rgb.data())) return fail("DenoiseImage");
+            if (denoise_frame(scene, A, info, rad.data(), var.data(), rgb.data())) return 1;
         } else if (bhrt_render(scene, &o, rgb.data(), rad.empty() ? nullptr : rad.data(), &st)) return fail("BeginRender");
     }
     const double rays = (double)st.closest_rays + (double)st.shadow_rays;

@@ -231,6 +231,8 @@ struct DeviceState : DeviceQueues {
     uint64_t prog_session = 0; // ProgressiveSession::id of the session whose state d_prog holds (allocated and zeroed for it); 0 = none
     // bhrt_denoise_dev: the filter's planes (DenoisePlaneBytes), then the first-hit guides it computes itself; grown on demand
     DevBuf<uint8_t> d_dn;
+    // bhrt_guides_dev: the running sums between the sample chunks of a call (k_guides), 32 B per pixel of a pass; only when spp exceeds one chunk
+    DevBuf<float4> d_guides;
     // scratch for the public trace API (EnsureApiScratch)
     size_t api_cap = 0; // rays
     DevBuf<float> d_api_f;   // 9 * api_cap

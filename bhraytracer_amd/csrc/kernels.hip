@@ -1595,6 +1595,81 @@ __global__ void __launch_bounds__(kBlock) k_first_hit(DevScene S, FaceMtlTable T
     if (albedo) st3(albedo, q, kd);
 }
 
+// The sampled guide images (bhrt_guides*): k_first_hit's three values and a hit flag for every camera sample of a pixel — the
+// render's own ray of (seed, pixel, sample): camera_ray, jitter and lens included — summed per pixel in float32, in sample order.
+// A launch covers samples [P.s0, P.s0 + P.spp) (a chunk of at most kBlock) of the pass's pixels.  A workgroup holds ppb = kBlock / P.spp
+// pixels, the samples of a pixel in consecutive lanes: they walk the same BVH path, and a pixel never straddles two workgroups.  Each lane
+// traces one sample and leaves t, N, kd and the flag in LDS; behind the barrier the lane of the chunk's first sample folds its pixel's entries
+// in ascending order.  The sum starts as the first hit's values (no 0 + x: spp = 1 keeps k_first_hit's bits, the sign of a zero included).
+// first / last: the chunk is the call's first / last one.  Between chunks the running sums live in acc, two float4 per pixel of the pass:
+// (sum t, sum N), (sum kd, the hit count's bits); a call of one chunk reads and writes none.  The last chunk divides and stores:
+//   coverage = k / n, z = k ? sum t / k : BIGFLOAT, normal = sum N / n, albedo = sum kd / n      (n = n_total, the call's spp)
+template <bool kFm>
+__global__ void __launch_bounds__(kBlock) k_guides(DevScene S, FaceMtlTable T, PassInfo P, uint32_t ppb, uint32_t n_total, int first, int last, float4 *acc,
+                                                   float *z, float *normal, float *albedo, float *coverage)
+{
+    __shared__ bhrt_bvh_node nodelet[BHRT_LDS_NODES];
+    __shared__ float s_v[7][kBlock];
+    __shared__ uint32_t s_hit[kBlock];
+    const uint32_t lane = threadIdx.x, c = (uint32_t)P.spp;
+    uint32_t pl, s;
+    fdivmod(lane, P.by_spp, pl, s);
+    const uint32_t q_local = blockIdx.x * ppb + pl;
+    V3 o = v3(0, 0, 0), d = v3(0, 0, 1);
+    bool active = false;
+    if (pl < ppb && q_local < P.n_pixels) {
+        const uint32_t slot = q_local * c + s;
+        active = P.lens_r > 0.f ? camera_ray<true>(S, P, slot, o, d) : camera_ray(S, P, slot, o, d); // a kernel argument: uniform
+    }
+    Hit hit;
+    trace_closest(S, o, d, BHRT_HIT_FRONT, hit, active, nodelet); // uniform call: the block stages nodelets together
+    const bool got = active && hit.node >= 0;
+    V3 N = v3(0, 0, 0), kd = v3(0, 0, 0);
+    if (got && (normal || albedo)) { // as k_first_hit
+        const int mi = kFm ? resolve_material(S, T, hit.node, hit.prim) : S.nodes[hit.node].material;
+        const bool blinn = mi >= 0 && S.materials[mi].kind == BHRT_MTL_BLINN;
+        Attr a;
+        hit_attrs(S, o, d, hit.t, hit.node, hit.prim, albedo && blinn && S.materials[mi].diffuse.map >= 0, a);
+        N = a.N;
+        if (blinn) kd = tc_sample_d(S, S.materials[mi].diffuse, a.uvw, a.du, a.dv);
+        else if (mi >= 0 && S.materials[mi].kind == BHRT_MTL_WHITE) kd = v3(1, 1, 1);
+    }
+    s_v[0][lane] = hit.t;
+    s_v[1][lane] = N.x; s_v[2][lane] = N.y; s_v[3][lane] = N.z;
+    s_v[4][lane] = kd.x; s_v[5][lane] = kd.y; s_v[6][lane] = kd.z;
+    s_hit[lane] = got ? 1u : 0u;
+    __syncthreads();
+    if (!active || s != 0) return; // one lane per pixel inside the image folds; lane + c <= kBlock because pl < ppb
+    float st = 0.f;
+    V3 sN = v3(0, 0, 0), sk = v3(0, 0, 0);
+    uint32_t k = 0;
+    if (!first) {
+        const float4 a = acc[2 * (size_t)q_local], b = acc[2 * (size_t)q_local + 1];
+        st = a.x; sN = v3(a.y, a.z, a.w); sk = v3(b.x, b.y, b.z); k = __float_as_uint(b.w);
+    }
+    for (uint32_t e = lane; e < lane + c; e++) {
+        if (!s_hit[e]) continue;
+        const float t = s_v[0][e];
+        const V3 Ne = v3(s_v[1][e], s_v[2][e], s_v[3][e]), ke = v3(s_v[4][e], s_v[5][e], s_v[6][e]);
+        if (k == 0) { st = t; sN = Ne; sk = ke; }
+        else { st += t; sN = sN + Ne; sk = sk + ke; }
+        k++;
+    }
+    if (!last) {
+        acc[2 * (size_t)q_local] = make_float4(st, sN.x, sN.y, sN.z);
+        acc[2 * (size_t)q_local + 1] = make_float4(sk.x, sk.y, sk.z, __uint_as_float(k));
+        return;
+    }
+    int i, j;
+    if (!pixel_of(P, pass_pixel(P, q_local), i, j)) return;
+    const uint32_t pix = (uint32_t)j * (uint32_t)P.W + (uint32_t)i;
+    const float n = (float)n_total;
+    if (coverage) coverage[pix] = (float)k / n;
+    if (z) z[pix] = k ? st / (float)k : BHRT_BIGFLOAT;
+    if (normal) st3(normal, pix, sN / n);
+    if (albedo) st3(albedo, pix, sk / n);
+}
+
 // RenderImage::ComputeZBufferImage (scene.h:578-600): min / max over the hits, then (zmax - z) / (zmax - zmin) * 255 truncated.
 // Min and max are exact in any order; one workgroup strides over the image.
 __global__ void __launch_bounds__(1024) k_z_range(const float *z, uint32_t n, float *range)
@@ -4018,6 +4093,77 @@ try {
     if (z) HIP_CHECK(hipMemcpy(z, d, n * sizeof(float), hipMemcpyDeviceToHost));
     if (normal) HIP_CHECK(hipMemcpy(normal, d + n, 3 * n * sizeof(float), hipMemcpyDeviceToHost));
     if (albedo) HIP_CHECK(hipMemcpy(albedo, d + 4 * n, 3 * n * sizeof(float), hipMemcpyDeviceToHost));
+    return BHRT_OK;
+} catch (...) { return bhrt::AbiException(); }
+
+// ---- sampled guide images (k_guides) -------------------------------------------------------
+// The options of bhrt_guides*, checked before any device is touched (host arithmetic only): lens and dof as the renders check them, spp in
+// 1..65535 and rank inside world_size through FramePassInfo.  The bounce counts are not read by this call and are not checked.
+static int GuidesPassInfo(bhrt_scene *scene, const bhrt_opts *opts, PassInfo &P, uint64_t &owned_pixels)
+{
+    if (!scene || !opts) { SetError("bhrt_guides: null scene or opts"); return BHRT_ERR_ARG; }
+    BHRT_CHECK_LENS(scene, opts);
+    bhrt_opts o = *opts;
+    o.gi_bounces = 0; o.internal_bounces = 0;
+    BHRT_TRY(FramePassInfo(scene, o, P, owned_pixels));
+    if (owned_pixels > 0x7fffffffull) { SetError("bhrt_guides: more than 2^31 owned pixels"); return BHRT_ERR_ARG; }
+    return BHRT_OK;
+}
+
+int bhrt_guides_dev(bhrt_scene *scene, const bhrt_opts *opts, float *d_z, float *d_normal, float *d_albedo, float *d_coverage, void *stream)
+try {
+    PassInfo P;
+    uint64_t owned_pixels = 0;
+    BHRT_TRY(GuidesPassInfo(scene, opts, P, owned_pixels));
+    int rc = EnsureUploaded(scene);
+    if (rc) return rc;
+    if ((!d_z && !d_normal && !d_albedo && !d_coverage) || owned_pixels == 0) return BHRT_OK;
+    DeviceState *D = scene->dev;
+    hipStream_t st = stream ? (hipStream_t)stream : D->stream;
+    // Chunks of c samples, at most a workgroup's; samples_per_pass bounds the samples in flight, so it bounds the chunk and the pixels of a
+    // pass as well.  The sums are sequential in the sample index whatever the chunks are: the result depends on neither.
+    const uint32_t n = (uint32_t)opts->spp, cap = opts->samples_per_pass > 0 ? (uint32_t)opts->samples_per_pass : 0xffffffffu;
+    const uint32_t c = std::min(std::min(n, (uint32_t)kBlock), cap), n_chunks = (n + c - 1) / c;
+    const uint64_t pass_px = std::min<uint64_t>(std::min<uint64_t>(owned_pixels, std::max<uint32_t>(cap / c, 1u)), (1u << 30) / c); // slots of a pass fit 32 bits
+    if (n_chunks > 1) BHRT_TRY(D->d_guides.Reserve((size_t)pass_px * 2));
+    auto kernel = D->fm.tab ? k_guides<true> : k_guides<false>;
+    for (uint64_t q = 0; q < owned_pixels; q += pass_px) {
+        const uint32_t npx = (uint32_t)std::min<uint64_t>(pass_px, owned_pixels - q);
+        for (uint32_t k = 0; k < n_chunks; k++) {
+            PassInfo Pp = P;
+            Pp.q0 = (uint32_t)q; Pp.n_pixels = npx;
+            Pp.s0 = k * c; Pp.spp = (int32_t)std::min(c, n - k * c);
+            Pp.by_spp = MakeFastDiv((uint32_t)Pp.spp);
+            const uint32_t ppb = (uint32_t)kBlock / (uint32_t)Pp.spp;
+            hipLaunchKernelGGL(kernel, dim3((npx + ppb - 1) / ppb), dim3(kBlock), 0, st, D->S, D->fm, Pp, ppb, n, k == 0, k + 1 == n_chunks, D->d_guides.p, d_z, d_normal,
+                               d_albedo, d_coverage);
+        }
+    }
+    HIP_CHECK(hipGetLastError());
+    if (!stream) HIP_CHECK(hipStreamSynchronize(st));
+    return BHRT_OK;
+} catch (...) { return bhrt::AbiException(); }
+
+int bhrt_guides(bhrt_scene *scene, const bhrt_opts *opts, float *z, float *normal, float *albedo, float *coverage)
+try {
+    PassInfo P;
+    uint64_t owned_pixels = 0;
+    BHRT_TRY(GuidesPassInfo(scene, opts, P, owned_pixels));
+    int rc = EnsureUploaded(scene);
+    if (rc) return rc;
+    const bhrt_flat_header *H = scene->flat.hdr();
+    const size_t n = (size_t)H->camera.width * H->camera.height;
+    DevBuf<float> d; // z, normal, albedo, coverage
+    BHRT_TRY(d.Reserve(n * 8));
+    float *const host[4] = {z, normal, albedo, coverage};
+    float *const dev[4] = {d.p, d.p + n, d.p + 4 * n, d.p + 7 * n};
+    const size_t floats[4] = {n, 3 * n, 3 * n, n};
+    if (opts->world_size > 1) // pixels of other ranks' tiles keep the caller's values
+        for (int k = 0; k < 4; k++)
+            if (host[k]) HIP_CHECK(hipMemcpy(dev[k], host[k], floats[k] * sizeof(float), hipMemcpyHostToDevice));
+    BHRT_TRY(bhrt_guides_dev(scene, opts, z ? dev[0] : nullptr, normal ? dev[1] : nullptr, albedo ? dev[2] : nullptr, coverage ? dev[3] : nullptr, nullptr));
+    for (int k = 0; k < 4; k++)
+        if (host[k]) HIP_CHECK(hipMemcpy(host[k], dev[k], floats[k] * sizeof(float), hipMemcpyDeviceToHost));
     return BHRT_OK;
 } catch (...) { return bhrt::AbiException(); }
 

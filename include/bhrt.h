@@ -85,7 +85,8 @@ typedef struct bhrt_opts {
                                * ray of a sample starts on the disc of radius dof around the eye, in the camera's x/y plane, and goes through the sample's point on
                                * the image plane, which lies at <focaldist> (Main.cpp:181-189): the viewport's preview (viewport.cpp:236-243) as a render.  With
                                * dof == 0 the render is the pinhole one, bit for bit.  Any other value, or 1 with a negative / non-finite dof: BHRT_ERR_ARG,
-                               * before a device is touched.  The images beside the colour image (bhrt_first_hit*) and the denoiser's guides stay the pinhole ray's */
+                               * before a device is touched.  The images beside the colour image (bhrt_first_hit*) and the guides the denoiser computes itself stay the pinhole ray's;
+                               * bhrt_guides* forms guide images from the lens rays */
 } bhrt_opts;
 
 typedef struct bhrt_stats {
@@ -305,6 +306,25 @@ int bhrt_tiles_unpack_dev(const void *d_blocks /* world blocks, rank-major */, i
  * Any pointer may be NULL. */
 int bhrt_first_hit_dev(bhrt_scene *scene, float *d_z, float *d_normal, float *d_albedo, void *stream);
 int bhrt_first_hit(bhrt_scene *scene, float *z, float *normal, float *albedo);
+/* Sampled guide images: the same three images, and the coverage, formed by the render's own camera samples, so that they are
+ * averaged over the pixel footprint the colour image is averaged over: jitter and, with bhrt_opts.lens, the aperture.  For an owned pixel inside
+ * the image and n = spp, sample s = 0 .. n-1 has the camera ray the render forms for (seed, pixel, s) (what bhrt_camera_rays returns), its first
+ * hit with BHRT_SIDE_FRONT, and on a hit the values of the first-hit images for that ray: t_s, N_s (HitInfo::N, world space) and kd_s (a Blinn material:
+ * diffuse.Sample(uvw, duvw); white: (1, 1, 1); else 0).  With k the number of samples that hit and every sum taken over those samples alone, in
+ * float32, in ascending sample order, starting from the first one's value:
+ *   coverage  W*H floats    (float)k / (float)n
+ *   z         W*H floats    k ? (sum t_s) / (float)k : BIGFLOAT
+ *   normal    W*H*3 floats  (sum N_s) / (float)n        not renormalised: a pixel on an edge, or one that partly misses, carries a shorter normal
+ *   albedo    W*H*3 floats  (sum kd_s) / (float)n
+ * With spp = 1, jitter = 0 and lens = 0 (or dof = 0) z, normal and albedo are the first-hit images bit for bit.  Row-major; any pointer may be NULL.
+ * Uses spp (1 .. 65535), seed, jitter, lens, rank, world_size, tile_size and samples_per_pass (the most samples in flight; 0 = no bound) of the
+ * options; the result depends on neither the pass size nor the partition, and pixels of other ranks' tiles are left untouched.  Bad options
+ * (spp, lens, lens = 1 with a bad dof, rank outside world_size): BHRT_ERR_ARG, before any device is touched.  The face-material switch of the
+ * scene applies to the albedo as it does to the first-hit images.  _dev: device pointers; with a stream the call does not synchronise.  The running
+ * sums of a call whose spp exceeds one workgroup's 256 samples (or samples_per_pass) are scratch of the scene, 32 B per pixel of a pass: calls on
+ * one scene must not overlap. */
+int bhrt_guides_dev(bhrt_scene *scene, const bhrt_opts *opts, float *d_z, float *d_normal, float *d_albedo, float *d_coverage, void *stream);
+int bhrt_guides(bhrt_scene *scene, const bhrt_opts *opts, float *z, float *normal, float *albedo, float *coverage);
 /* RenderImage::ComputeZBufferImage (scene.h:578-600): 8-bit depth image, 0 where nothing is hit.  Device pointers. */
 int bhrt_zbuffer_image_dev(bhrt_scene *scene, const float *d_z, size_t n, uint8_t *d_img, void *stream);
 /* colorArray of BeginRender (Main.cpp:202,219-229): pow(colour, 1/2.2f) as floats — the "color" image DenoiseImage is given
