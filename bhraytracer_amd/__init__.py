@@ -94,7 +94,11 @@ EXPORTS = [
     "bhrt_progressive_begin", "bhrt_progressive_step", "bhrt_progressive_frame", "bhrt_progressive_frame_dev", "bhrt_progressive_status",
     "bhrt_progressive_end",
     "bhrt_guides", "bhrt_guides_dev",
+    "bhrt_denoise_sampled", "bhrt_denoise_sampled_dev",
 ]
+
+# BHRT_DENOISE_SIGMA_COVERAGE of include/bhrt.h: the default coverage tolerance of the denoiser for sampled guides
+DENOISE_SIGMA_COVERAGE = 0.5
 
 
 def lib():
@@ -484,6 +488,34 @@ class Scene:
         v = lambda x: C.c_void_p(x or None)  # noqa: E731
         _check(lib().bhrt_denoise_dev(self._h, C.byref(opts), v(d_radiance), v(d_variance), v(d_z), v(d_normal), v(d_albedo), v(d_out), v(d_rgb8),
                                       v(stream)))
+
+    def denoise_sampled(self, opts: DenoiseOpts, radiance, variance, z, normal, albedo, coverage, sigma_coverage: float = DENOISE_SIGMA_COVERAGE):
+        """The denoiser for sampled guides (bhrt_denoise_sampled) on host arrays: radiance and variance as for denoise(); z, normal,
+        albedo and coverage are the four images of guides() with the render's seed, jitter and lens (None is passed as NULL: an error unless
+        opts.iterations == 0).  Returns (out (H, W, 3) float32 linear, rgb8 (H, W, 3) uint8)."""
+        W, H = self.width, self.height
+
+        def arr(a, shape):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, np.float32)
+            if a.size != int(np.prod(shape)):
+                raise ValueError(f"expected {shape} floats, got {a.shape}")
+            return a
+        c = arr(radiance, (H, W, 3))
+        v, zz, n, a, cov = arr(variance, (H, W, 3)), arr(z, (H, W)), arr(normal, (H, W, 3)), arr(albedo, (H, W, 3)), arr(coverage, (H, W))
+        out = np.zeros((H, W, 3), np.float32)
+        rgb = np.zeros((H, W, 3), np.uint8)
+        p = lambda x: _ptr(x) if x is not None else None  # noqa: E731
+        _check(lib().bhrt_denoise_sampled(self._h, C.byref(opts), C.c_float(sigma_coverage), _ptr(c), p(v), p(zz), p(n), p(a), p(cov), _ptr(out), _ptr(rgb)))
+        return out, rgb
+
+    def denoise_sampled_dev(self, opts: DenoiseOpts, sigma_coverage: float, d_radiance: int, d_variance: int = 0, d_z: int = 0, d_normal: int = 0,
+                            d_albedo: int = 0, d_coverage: int = 0, d_out: int = 0, d_rgb8: int = 0, stream: int = 0):
+        """bhrt_denoise_sampled_dev on raw device pointers (0 = NULL); with a stream the call does not synchronise."""
+        v = lambda x: C.c_void_p(x or None)  # noqa: E731
+        _check(lib().bhrt_denoise_sampled_dev(self._h, C.byref(opts), C.c_float(sigma_coverage), v(d_radiance), v(d_variance), v(d_z), v(d_normal),
+                                              v(d_albedo), v(d_coverage), v(d_out), v(d_rgb8), v(stream)))
 
     # ---- images beside the colour image (RenderImage z-buffer, DenoiseImage inputs) ------------
     def first_hit(self):

@@ -6,7 +6,7 @@
 //   bhrt render <scene.xml> [-o out.png] [--spp N] [--gi N] [--bounces N] [--seed S] [--no-jitter] [--no-gamma]
 //               [--device D | --gpus N [--rehearse]] [--rank R --world N] [--tile T] [--radiance out.f32] [--leaf-skip] [--photon-exact]
 //               [--photons N] [--photon-file map.dat] [--photon-out map.dat]     (USE_PhotonMap, Main.cpp:51,53,194,383)
-//               [--denoise [--denoise-iters K] [--guide-spp N]]                  (DenoiseImage of the x64 build, Main.cpp:57-96,236-238)
+//               [--denoise [--denoise-iters K] [--guide-spp N [--coverage-filter [--sigma-coverage X]]]]  (DenoiseImage of the x64 build, Main.cpp:57-96,236-238)
 //               [--adaptive [--spp-min N] [--adaptive-threshold X] [--samples-png path]]  (RenderImage::sampleCount, scene.h:534,603-630)
 //               [--lens [--dof R] [--focaldist D]]                               (the viewport's depth of field, viewport.cpp:236-243, rendered)
 //               [--emission]                                                     (the <emission> of the materials, xmlload.cpp:344-348, shaded)
@@ -31,6 +31,10 @@
 // the render's seed, jitter and lens: averaged over the pixel footprint the colour image is averaged over.  0, the default: the
 // guides the denoiser computes itself, the pinhole ray through the pixel corner.  With --gpus N the guides are computed where the denoiser runs,
 // on GPU 0 for the whole frame.
+// --coverage-filter (needs --denoise and --guide-spp N > 0; without them a usage error): the filter is bhrt_denoise_sampled, which
+// also takes bhrt_guides' coverage image: demodulation by albedo + (1 - coverage), normals compared by direction, coverage as a weight of its own.
+// --sigma-coverage X (finite, >= 0; needs --coverage-filter): its coverage tolerance, default BHRT_DENOISE_SIGMA_COVERAGE.  With --gpus N on GPU 0,
+// as --guide-spp.  Without the flag --guide-spp hands its three images to bhrt_denoise as before.
 // --adaptive: bhrt_render_adaptive; --spp is the per-pixel maximum, --spp-min round 0's samples.  --samples-png writes the
 // sample-count image as SaveSampleCountImage does (scene.h:630); its normalisation needs the whole frame, so --world > 1 refuses it.  With
 // --gpus N the counts travel as the float section of a further block (exact below 2^24); with --denoise the adaptive variance is the filter's.
@@ -91,6 +95,9 @@ struct Args {
     bhrt_denoise_opts dn;
     int guide_spp = 0;                 // --guide-spp N: the denoiser's guides from bhrt_guides at N samples per pixel; 0 = the denoiser's own first hit
     bool guide_spp_given = false;
+    bool coverage_filter = false;      // --coverage-filter: bhrt_denoise_sampled with bhrt_guides' four images instead of bhrt_denoise with three
+    float sigma_coverage = BHRT_DENOISE_SIGMA_COVERAGE; // --sigma-coverage X
+    bool sigma_coverage_given = false;
     bool adaptive = false;
     bhrt_adaptive_opts ad;
     std::string samples_png;
@@ -183,6 +190,11 @@ static int denoise_frame(bhrt_scene *scene, const Args &A, const bhrt_info &info
     const size_t npx = (size_t)info.width * info.height;
     std::vector<float> z(npx), nrm(npx * 3), alb(npx * 3);
     const bhrt_opts g = guide_opts(A);
+    if (A.coverage_filter) {
+        std::vector<float> cov(npx);
+        if (bhrt_guides(scene, &g, z.data(), nrm.data(), alb.data(), cov.data())) return fail("guide images");
+        return bhrt_denoise_sampled(scene, &A.dn, A.sigma_coverage, rad, var, z.data(), nrm.data(), alb.data(), cov.data(), nullptr, rgb) ? fail("DenoiseImage (sampled guides)") : 0;
+    }
     if (bhrt_guides(scene, &g, z.data(), nrm.data(), alb.data(), nullptr)) return fail("guide images");
     return bhrt_denoise(scene, &A.dn, rad, var, z.data(), nrm.data(), alb.data(), nullptr, rgb) ? fail("DenoiseImage") : 0;
 }
@@ -302,7 +314,7 @@ static int render_multi(bhrt_scene *first, const Args &A, const bhrt_info &info,
                     HOST_CHECK(hipMalloc(&d_mine_v, bb), "hipMalloc");
                     HOST_CHECK(hipMalloc(&d_all_v, bb * N), "hipMalloc");
                     HOST_CHECK(hipMemsetAsync(d_var, 0, npx * 3 * sizeof(float), s), "memset");
-                    if (r == 0 && A.guide_spp > 0) HOST_CHECK(hipMalloc(&d_guide, npx * 7 * sizeof(float)), "hipMalloc"); // z, normal, albedo
+                    if (r == 0 && A.guide_spp > 0) HOST_CHECK(hipMalloc(&d_guide, npx * 8 * sizeof(float)), "hipMalloc"); // z, normal, albedo, coverage
                 }
                 if (A.adaptive) { // the counts: a further block whose float section holds them (channel 0 of a W x H x 3 float image)
                     HOST_CHECK(hipMalloc(&d_cnt, npx * sizeof(uint32_t)), "hipMalloc");
@@ -383,10 +395,14 @@ static int render_multi(bhrt_scene *first, const Args &A, const bhrt_info &info,
                 if (r == 0 && A.denoise) { // DenoiseImage on the gathered frame (Main.cpp:236-238): the PNG bytes become the filter's
                     if (d_guide) { // --guide-spp: the whole frame's guides, here where the filter runs
                         const bhrt_opts g = guide_opts(A);
-                        HOST_CHECK(bhrt_guides_dev(scenes[0], &g, d_guide, d_guide + npx, d_guide + 4 * npx, nullptr, s), "guide images");
+                        HOST_CHECK(bhrt_guides_dev(scenes[0], &g, d_guide, d_guide + npx, d_guide + 4 * npx, A.coverage_filter ? d_guide + 7 * npx : nullptr, s), "guide images");
                     }
-                    HOST_CHECK(bhrt_denoise_dev(scenes[0], &A.dn, d_rad, d_var, d_guide, d_guide ? d_guide + npx : nullptr, d_guide ? d_guide + 4 * npx : nullptr, nullptr, d_rgb, s),
-                               "denoise");
+                    if (A.coverage_filter)
+                        HOST_CHECK(bhrt_denoise_sampled_dev(scenes[0], &A.dn, A.sigma_coverage, d_rad, d_var, d_guide, d_guide + npx, d_guide + 4 * npx, d_guide + 7 * npx, nullptr, d_rgb, s),
+                                   "denoise (sampled guides)");
+                    else
+                        HOST_CHECK(bhrt_denoise_dev(scenes[0], &A.dn, d_rad, d_var, d_guide, d_guide ? d_guide + npx : nullptr, d_guide ? d_guide + 4 * npx : nullptr, nullptr, d_rgb, s),
+                                   "denoise");
                     HOST_CHECK(hipStreamSynchronize(s), "sync");
                 }
                 if (r == 0) {
@@ -448,6 +464,8 @@ int main(int argc, char **argv)
         else if (s == "--denoise") A.denoise = true;
         else if (s == "--denoise-iters") A.dn.iterations = atoi(next());
         else if (s == "--guide-spp") { A.guide_spp = atoi(next()); A.guide_spp_given = true; }
+        else if (s == "--coverage-filter") A.coverage_filter = true;
+        else if (s == "--sigma-coverage") { A.sigma_coverage = number_value("--sigma-coverage", next(), false); A.sigma_coverage_given = true; }
         else if (s == "--adaptive") A.adaptive = true;
         else if (s == "--spp-min") A.ad.min_spp = atoi(next());
         else if (s == "--adaptive-threshold") A.ad.threshold = (float)atof(next());
@@ -472,6 +490,11 @@ int main(int argc, char **argv)
     if (A.denoise && (A.dn.iterations < 0 || A.dn.iterations > 16)) { fprintf(stderr, "bhrt: usage: --denoise-iters must be in 0..16\n"); return 2; }
     if (A.guide_spp_given && !A.denoise) { fprintf(stderr, "bhrt: usage: --guide-spp needs --denoise (the guide images steer the denoiser)\n"); return 2; }
     if (A.guide_spp < 0 || A.guide_spp > 65535) { fprintf(stderr, "bhrt: usage: --guide-spp must be in 0..65535 (0 = the denoiser's own first-hit guides)\n"); return 2; }
+    if (A.coverage_filter && (!A.denoise || A.guide_spp <= 0)) {
+        fprintf(stderr, "bhrt: usage: --coverage-filter needs --denoise and --guide-spp N with N > 0 (the filter reads the sampled guides' coverage)\n");
+        return 2;
+    }
+    if (A.sigma_coverage_given && !A.coverage_filter) { fprintf(stderr, "bhrt: usage: --sigma-coverage needs --coverage-filter\n"); return 2; }
     if (!A.adaptive && !A.samples_png.empty()) { fprintf(stderr, "bhrt: usage: --samples-png needs --adaptive\n"); return 2; }
     if (A.adaptive && !A.samples_png.empty() && o.world_size > 1) { // before any device is touched
         fprintf(stderr, "bhrt: usage: --samples-png normalises over the whole frame; a rank of --world %d renders part of it (use --gpus N)\n", o.world_size);
@@ -515,6 +538,7 @@ int main(int argc, char **argv)
         if (A.denoise && A.guide_spp <= 0) printf("note: --denoise guides (depth, normal, albedo) are those of the pinhole ray; --guide-spp N forms them from the lens rays\n");
     }
     if (A.denoise && A.guide_spp > 0) printf("denoise guides: %d sample(s) per pixel%s\n", A.guide_spp, o.lens ? ", through the lens" : "");
+    if (A.coverage_filter) printf("denoise filter: for sampled guides, coverage tolerance %g\n", A.sigma_coverage);
     std::vector<uint8_t> rgb((size_t)info.width * info.height * 3, 0);
     std::vector<float> rad(A.radiance_out.empty() && !A.denoise ? 0 : (size_t)info.width * info.height * 3, 0.f);
     std::vector<uint32_t> cnt(A.adaptive ? (size_t)info.width * info.height : 0, 0u);

@@ -28,4 +28,10 @@ const char *DenoiseOptsError(const bhrt_denoise_opts &o);
 // enqueues the whole filter on `s`; returns the launch status
 hipError_t DenoiseLaunch(const DenoiseJob &J, hipStream_t s);
 
+// The filter for sampled guides (bhrt_denoise_sampled*): J's z, normal and albedo are bhrt_guides' images and `coverage` (W*H) its coverage
+// image; all four are read when J.o.iterations > 0.  The planes are DenoiseJob::planes as above: the coverage is read in place.
+// "" when sigma_coverage is usable (finite, >= 0), else what is wrong with it
+const char *DenoiseSigmaCoverageError(float sigma_coverage);
+hipError_t DenoiseSampledLaunch(const DenoiseJob &J, const float *coverage, float sigma_coverage, hipStream_t s);
+
 } // namespace bhrt

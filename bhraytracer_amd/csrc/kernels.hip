@@ -4266,6 +4266,76 @@ try {
     return BHRT_OK;
 } catch (...) { return bhrt::AbiException(); }
 
+// The filter for sampled guides (denoise.hip): the options of both entry points, checked alike
+static int DenoiseSampledArgs(const bhrt_denoise_opts *opts, float sigma_coverage, const float *radiance, const float *z, const float *normal, const float *albedo,
+                              const float *coverage)
+{
+    if (!opts || !radiance) { SetError("denoise: null opts or radiance"); return BHRT_ERR_ARG; }
+    const char *bad = DenoiseOptsError(*opts);
+    if (!*bad) bad = DenoiseSigmaCoverageError(sigma_coverage);
+    if (*bad) { SetError(bad); return BHRT_ERR_ARG; }
+    if (opts->iterations > 0 && (!z || !normal || !albedo || !coverage)) { // K = 0 reads no guide
+        SetError("denoise: the filter for sampled guides needs z, normal, albedo and coverage");
+        return BHRT_ERR_ARG;
+    }
+    return BHRT_OK;
+}
+
+int bhrt_denoise_sampled_dev(bhrt_scene *scene, const bhrt_denoise_opts *opts, float sigma_coverage, const float *d_radiance, const float *d_variance, const float *d_z,
+                             const float *d_normal, const float *d_albedo, const float *d_coverage, float *d_out, uint8_t *d_rgb8, void *stream)
+try {
+    int rc = EnsureUploaded(scene);
+    if (rc) return rc;
+    BHRT_TRY(DenoiseSampledArgs(opts, sigma_coverage, d_radiance, d_z, d_normal, d_albedo, d_coverage));
+    if (!d_out && !d_rgb8) return BHRT_OK;
+    DeviceState *D = scene->dev;
+    const bhrt_flat_header *H = scene->flat.hdr();
+    const int W = H->camera.width, Hh = H->camera.height;
+    const size_t n = (size_t)W * Hh;
+    if (n == 0 || n > 0x7fffffffull) { SetError("denoise: frame size out of range"); return BHRT_ERR_ARG; }
+    hipStream_t st = stream ? (hipStream_t)stream : D->stream;
+    DenoiseJob J;
+    J.W = W; J.H = Hh; J.o = *opts;
+    J.radiance = d_radiance; J.variance = d_variance; J.z = d_z; J.normal = d_normal; J.albedo = d_albedo; J.out = d_out; J.rgb8 = d_rgb8;
+    J.planes = nullptr;
+    if (opts->iterations > 0) {
+        BHRT_TRY(D->d_dn.Reserve(DenoisePlaneBytes(W, Hh)));
+        J.planes = (float4 *)D->d_dn.p;
+    }
+    HIP_CHECK(DenoiseSampledLaunch(J, d_coverage, sigma_coverage, st));
+    if (!stream) HIP_CHECK(hipStreamSynchronize(st));
+    return BHRT_OK;
+} catch (...) { return bhrt::AbiException(); }
+
+int bhrt_denoise_sampled(bhrt_scene *scene, const bhrt_denoise_opts *opts, float sigma_coverage, const float *radiance, const float *variance, const float *z,
+                         const float *normal, const float *albedo, const float *coverage, float *out, uint8_t *rgb8)
+try {
+    int rc = EnsureUploaded(scene);
+    if (rc) return rc;
+    BHRT_TRY(DenoiseSampledArgs(opts, sigma_coverage, radiance, z, normal, albedo, coverage));
+    if (!out && !rgb8) return BHRT_OK;
+    DeviceState *D = scene->dev;
+    const bhrt_flat_header *H = scene->flat.hdr();
+    const size_t n = (size_t)H->camera.width * H->camera.height;
+    // device copies, back to back: radiance, variance, normal, albedo, out (3n floats each), z, coverage (n each), rgb8 (3n bytes)
+    DevBuf<uint8_t> d;
+    BHRT_TRY(d.Reserve(n * 71));
+    float *f = (float *)d.p;
+    float *d_c = f, *d_v = f + 3 * n, *d_n = f + 6 * n, *d_a = f + 9 * n, *d_o = f + 12 * n, *d_z = f + 15 * n, *d_cov = f + 16 * n;
+    uint8_t *d_rgb = d.p + n * 68;
+    HIP_CHECK(hipMemcpyAsync(d_c, radiance, n * 12, hipMemcpyHostToDevice, D->stream));
+    if (variance) HIP_CHECK(hipMemcpyAsync(d_v, variance, n * 12, hipMemcpyHostToDevice, D->stream));
+    if (normal) HIP_CHECK(hipMemcpyAsync(d_n, normal, n * 12, hipMemcpyHostToDevice, D->stream));
+    if (albedo) HIP_CHECK(hipMemcpyAsync(d_a, albedo, n * 12, hipMemcpyHostToDevice, D->stream));
+    if (z) HIP_CHECK(hipMemcpyAsync(d_z, z, n * 4, hipMemcpyHostToDevice, D->stream));
+    if (coverage) HIP_CHECK(hipMemcpyAsync(d_cov, coverage, n * 4, hipMemcpyHostToDevice, D->stream));
+    BHRT_TRY(bhrt_denoise_sampled_dev(scene, opts, sigma_coverage, d_c, variance ? d_v : nullptr, z ? d_z : nullptr, normal ? d_n : nullptr, albedo ? d_a : nullptr,
+                                      coverage ? d_cov : nullptr, out ? d_o : nullptr, rgb8 ? d_rgb : nullptr, nullptr));
+    if (out) HIP_CHECK(hipMemcpy(out, d_o, n * 12, hipMemcpyDeviceToHost));
+    if (rgb8) HIP_CHECK(hipMemcpy(rgb8, d_rgb, n * 3, hipMemcpyDeviceToHost));
+    return BHRT_OK;
+} catch (...) { return bhrt::AbiException(); }
+
 static bool TileArgsOk(int W, int H, int tile, int rank, int world)
 {
     if (W <= 0 || H <= 0 || tile <= 0 || world <= 0 || rank < 0 || rank >= world) { SetError("bad tile partition"); return false; }

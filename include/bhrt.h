@@ -358,6 +358,20 @@ int bhrt_denoise_dev(bhrt_scene *scene, const bhrt_denoise_opts *opts, const flo
                      const float *d_albedo, float *d_out, uint8_t *d_rgb8, void *stream);
 int bhrt_denoise(bhrt_scene *scene, const bhrt_denoise_opts *opts, const float *radiance, const float *variance, const float *z, const float *normal,
                  const float *albedo, float *out, uint8_t *rgb8);
+/* The denoiser for sampled guides: the same filter with a demodulation, a normal weight and a further weight that read the
+ * coverage image, stated exactly in csrc/denoise.hip beside the other.  z, normal, albedo and coverage are the four images of one
+ * bhrt_guides* call with the render's seed, jitter and lens: a partly covered pixel is divided by albedo + (1 - coverage), the share of the
+ * background included, its shortened normal is compared by direction, and pixels of unlike coverage mix less
+ * (exp(-|coverage difference| / sigma_coverage)).  Fed one un-jittered pinhole sample's guides it is bhrt_denoise* to rounding.
+ * radiance, variance (may be NULL), out, rgb8 and the options: as for bhrt_denoise*.  sigma_coverage: finite and >= 0, else BHRT_ERR_ARG;
+ * BHRT_DENOISE_SIGMA_COVERAGE is the measured default.  With iterations > 0 all four guide images are required (a NULL one: BHRT_ERR_ARG);
+ * iterations = 0 reads none.  _dev: device pointers; with a stream the call does not synchronise.  Scratch (48 B per pixel; the coverage is read
+ * in place) is the scene's, shared with bhrt_denoise*: calls on one scene must not overlap, a call on another stream included. */
+#define BHRT_DENOISE_SIGMA_COVERAGE 0.5f
+int bhrt_denoise_sampled_dev(bhrt_scene *scene, const bhrt_denoise_opts *opts, float sigma_coverage, const float *d_radiance, const float *d_variance, const float *d_z,
+                             const float *d_normal, const float *d_albedo, const float *d_coverage, float *d_out, uint8_t *d_rgb8, void *stream);
+int bhrt_denoise_sampled(bhrt_scene *scene, const bhrt_denoise_opts *opts, float sigma_coverage, const float *radiance, const float *variance, const float *z,
+                         const float *normal, const float *albedo, const float *coverage, float *out, uint8_t *rgb8);
 
 /* ---- adaptive sampling: RenderImage's per-pixel sample counts (Scenes/scene.h:534,570), which BeginRender only ever sets to 0
  * (Main.cpp:214), filled by a render that stops sampling a pixel once its mean is good enough ------------------------

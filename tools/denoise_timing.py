@@ -4,7 +4,9 @@ image.  Wall time per call from HIP events; for kernel times run it under `rocpr
 with the algorithmic bytes of each kernel group:
     variance  2 x 12 B per sample (the samples are read twice: mean, then squared deviations) + 12 B per pixel written
     filter    prepare: 12 B radiance + 12 B variance + 4 + 12 + 12 B guides read, 32 B of planes written per pixel;
-              step: 32 B read (centre (e, v_L) and (n, z)), 16 B written per pixel; last step: + 12 B albedo, 12 B out + 3 B rgb8 instead"""
+              step: 32 B read (centre (e, v_L) and (n, z)), 16 B written per pixel; last step: + 12 B albedo, 12 B out + 3 B rgb8 instead
+--sampled times the filter for sampled guides as well (bhrt_denoise_sampled_dev: k_dns_prepare + K x k_dns_step) on the same frames
+with a band of partial coverage; it reads 4 B of coverage more per pixel in prepare and in every step (the last step 4 B more again)."""
 import argparse
 import json
 import os
@@ -22,6 +24,7 @@ def main():
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--iterations", type=int, default=5)
     ap.add_argument("--no-variance-kernel", action="store_true")
+    ap.add_argument("--sampled", action="store_true", help="also time bhrt_denoise_sampled_dev (the filter for sampled guides)")
     a = ap.parse_args()
     import torch
     import bhraytracer_amd as B
@@ -73,6 +76,24 @@ def main():
             nbytes = px * (40 + (12 if vp else 0) + 32) + (a.iterations - 1) * px * 48 + px * (32 + 12 + 12 + 3)
             ms = ev0.elapsed_time(ev1) / a.reps
             res[f"denoise_{W}x{H}_{name}"] = {"ms_per_call": ms, "bytes": nbytes, "GBps": nbytes / ms / 1e6}
+            if not a.sampled:
+                continue
+            # the filter for sampled guides: a ramp of partial coverage over the middle tenth of the columns, n and albedo scaled by it
+            cov = torch.clamp((torch.arange(W, device=dev, dtype=torch.float32) - 0.45 * W) / (0.1 * W), 0, 1).repeat(H, 1).contiguous()
+            cov = torch.where(z >= 1e30, torch.zeros_like(cov), cov)
+            n_s, al_s = (n * cov[..., None]).contiguous(), (al * cov[..., None]).contiguous()
+            z_s = torch.where(cov > 0, z, torch.full_like(z, 1e30))
+            args = (c.data_ptr(), vp, z_s.data_ptr(), n_s.data_ptr(), al_s.data_ptr(), cov.data_ptr(), out.data_ptr(), rgb.data_ptr(), s.cuda_stream)
+            sc.denoise_sampled_dev(o, B.DENOISE_SIGMA_COVERAGE, *args)
+            torch.cuda.synchronize()
+            ev0.record(s)
+            for _ in range(a.reps):
+                sc.denoise_sampled_dev(o, B.DENOISE_SIGMA_COVERAGE, *args)
+            ev1.record(s)
+            torch.cuda.synchronize()
+            nbytes += px * 4 * (a.iterations + 2)
+            ms = ev0.elapsed_time(ev1) / a.reps
+            res[f"denoise_sampled_{W}x{H}_{name}"] = {"ms_per_call": ms, "bytes": nbytes, "GBps": nbytes / ms / 1e6}
     print(json.dumps(res))
 
 
