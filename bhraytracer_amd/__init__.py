@@ -95,6 +95,7 @@ EXPORTS = [
     "bhrt_progressive_end",
     "bhrt_guides", "bhrt_guides_dev",
     "bhrt_denoise_sampled", "bhrt_denoise_sampled_dev",
+    "bhrt_scene_set_camera", "bhrt_scene_set_shutter", "bhrt_scene_get_shutter",
 ]
 
 # BHRT_DENOISE_SIGMA_COVERAGE of include/bhrt.h: the default coverage tolerance of the denoiser for sampled guides
@@ -226,6 +227,28 @@ class Scene:
         _check(lib().bhrt_scene_set_lens(self._h, C.c_float(focaldist), C.c_float(dof)))
         self._flat = None
 
+    # ---- the camera and its shutter ---------------------------------------------------------------------------------------
+    def set_camera(self, pos, target, up, fov: float = 0.0):
+        """bhrt_scene_set_camera: the camera's <position>, <target>, <up> and <fov> (<= 0 keeps the current one) of the loaded scene, through
+        the loader's own operations; the blob becomes that of the edited scene file, and an uploaded scene's camera is refreshed."""
+        v = [None if a is None else (C.c_float * 3)(*[float(x) for x in a]) for a in (pos, target, up)]
+        _check(lib().bhrt_scene_set_camera(self._h, v[0], v[1], v[2], C.c_float(fov)))
+        self._flat = None
+
+    def set_shutter(self, on: bool = True, pos1=None, target1=None, up1=None):
+        """bhrt_scene_set_shutter: camera motion blur between the scene's camera (pose 0) and (pos1, target1, up1), the camera at the end of the
+        exposure; every camera sample draws its own time in [0, 1).  on = False clears the state.  The blob keeps its bytes."""
+        v = [None if a is None else (C.c_float * 3)(*[float(x) for x in a]) for a in (pos1, target1, up1)]
+        _check(lib().bhrt_scene_set_shutter(self._h, 1 if on else 0, v[0], v[1], v[2]))
+
+    def shutter(self):
+        """bhrt_scene_get_shutter: (on, pose1 (3, 3) float32 = pos1, target1, up1 as given, frame1 (4, 3) float32 = pos1, top_left1, dd_x1,
+        dd_y1 as derived)."""
+        on = C.c_int(0)
+        pose, frame = np.zeros((3, 3), np.float32), np.zeros((4, 3), np.float32)
+        _check(lib().bhrt_scene_get_shutter(self._h, C.byref(on), _ptr(pose), _ptr(frame)))
+        return bool(on.value), pose, frame
+
     # ---- the emission term (DESIGN.md 12): scene state beside the flat blob, which keeps its bytes --------------------
     def set_emissive(self, on: bool = True):
         """bhrt_scene_set_emissive: with the term on, every Shade() frame of a Blinn material adds its <emission> (colour x optional texture) last,
@@ -312,7 +335,7 @@ class Scene:
         return irr, d
 
     def clone(self) -> "Scene":
-        """bhrt_scene_clone: a second handle on the same loaded scene (host state only: the emission, face-material and global-gather state included;
+        """bhrt_scene_clone: a second handle on the same loaded scene (host state only: the emission, face-material, global-gather and shutter state included;
         no device state, so no photon map)."""
         other = Scene.__new__(Scene)
         other._h = C.c_void_p()

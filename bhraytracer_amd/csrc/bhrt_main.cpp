@@ -13,6 +13,8 @@
 //               [--face-materials]                                               (the .mtl sub-material of each mesh face, viewport.cpp:581-607, rendered)
 //               [--global-map N [--global-radius R]]                             (BuildPhotonMap, Main.cpp:196,251-317, gathered where the GI recursion ends)
 //               [--progressive N [--time-limit SECONDS] [--live-png path]]       (BeginRender .. StopRender, Main.cpp:178,243: the frame in steps)
+//               [--camera-pos X,Y,Z] [--camera-target X,Y,Z] [--camera-up X,Y,Z] [--fov F]   (the <camera> tags, xmlload.cpp:109-127, replaced)
+//               [--shutter-pos X,Y,Z] [--shutter-target X,Y,Z] [--shutter-up X,Y,Z]           (camera motion blur: the camera at the end of the exposure)
 //   bhrt info   <scene.xml>
 //
 // --gpus N: ONE process drives N GPUs of the node (the reference's one process drives 16 OpenMP threads, Main.cpp:422): the
@@ -57,6 +59,13 @@
 // limit; at least one step always runs; the final PNG is the frame at that moment.  --adaptive becomes the session's retirement test
 // (--samples-png works), --denoise filters the final frame once, and the scene options (--lens, --emission, --face-materials, --global-map,
 // --photons) apply as they do to a blocking render.  One device: with --gpus N > 1 a usage error (no tile exchange per step yet).
+// --camera-pos / --camera-target / --camera-up / --fov: bhrt_scene_set_camera before the upload and before --gpus N clones the scene.
+// Each is optional; a missing one is read from the scene: its position, the point it looks at on the plane of focus (pos + dir * focaldist), its
+// up vector, its fov.  --shutter-pos / --shutter-target / --shutter-up: any of them turns the camera shutter on (bhrt_scene_set_shutter): the
+// camera moves from the scene's pose (after the camera flags) to this one during the exposure, every sample at a time of its own; a missing one
+// is taken from pose 0.  Scene state, so it reaches every render the other options choose, --guide-spp's guides included.  A malformed value is a
+// usage error before the scene is loaded; poses the library refuses (a quarter turn or more apart, up along the view) fail with its message.
+// Off unless asked for: without the flags the frame is the scene file's pinhole or lens frame.
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
@@ -110,7 +119,32 @@ struct Args {
     bool progressive_given = false;
     double time_limit = -1.0;          // --time-limit SECONDS; < 0: not given
     std::string live_png;              // --live-png PATH
+    // --camera-pos / -target / -up, --fov and --shutter-pos / -target / -up: values for bhrt_scene_set_camera and bhrt_scene_set_shutter
+    struct Vec { bool given = false; float v[3] = {0, 0, 0}; };
+    Vec cam_pos, cam_target, cam_up, sh_pos, sh_target, sh_up;
+    float fov = 0.f;                   // 0: not given
+    bool Camera() const { return cam_pos.given || cam_target.given || cam_up.given || fov > 0.f; }
+    bool Shutter() const { return sh_pos.given || sh_target.given || sh_up.given; }
 };
+
+// three finite numbers "X,Y,Z" (--camera-*, --shutter-*), else a usage error
+static Args::Vec vector_value(const char *opt, const char *text)
+{
+    Args::Vec r;
+    const char *p = text;
+    for (int k = 0; k < 3; k++) {
+        char *end = nullptr;
+        r.v[k] = strtof(p, &end);
+        const bool last = k == 2;
+        if (end == p || !(r.v[k] >= -3.402823466e38f && r.v[k] <= 3.402823466e38f) || (last ? *end != 0 : *end != ',')) {
+            fprintf(stderr, "bhrt: usage: %s needs three finite numbers X,Y,Z, got \"%s\"\n", opt, text);
+            exit(2);
+        }
+        p = end + 1;
+    }
+    r.given = true;
+    return r;
+}
 
 // a finite number >= 0 (--dof, --time-limit) or > 0 (--focaldist, --global-radius), else a usage error
 static float number_value(const char *opt, const char *text, bool positive)
@@ -480,6 +514,16 @@ int main(int argc, char **argv)
         else if (s == "--live-png") A.live_png = next();
         else if (s == "--dof") { A.dof = number_value("--dof", next(), false); o.lens = 1; }
         else if (s == "--focaldist") { A.focaldist = number_value("--focaldist", next(), true); o.lens = 1; }
+        else if (s == "--camera-pos") A.cam_pos = vector_value("--camera-pos", next());
+        else if (s == "--camera-target") A.cam_target = vector_value("--camera-target", next());
+        else if (s == "--camera-up") A.cam_up = vector_value("--camera-up", next());
+        else if (s == "--shutter-pos") A.sh_pos = vector_value("--shutter-pos", next());
+        else if (s == "--shutter-target") A.sh_target = vector_value("--shutter-target", next());
+        else if (s == "--shutter-up") A.sh_up = vector_value("--shutter-up", next());
+        else if (s == "--fov") {
+            A.fov = number_value("--fov", next(), true);
+            if (!(A.fov < 180.f)) { fprintf(stderr, "bhrt: usage: --fov needs a number of degrees below 180\n"); return 2; }
+        }
         else { fprintf(stderr, "bhrt: unknown option %s\n", s.c_str()); return 2; }
     }
     if (A.gpus < 0 || A.gpus > 64 || (A.gpus > 0 && (o.rank != 0 || o.world_size != 1))) { fprintf(stderr, "bhrt: --gpus N drives all N ranks itself (no --rank / --world)\n"); return 2; }
@@ -536,6 +580,35 @@ int main(int argc, char **argv)
         if (!(fh->camera.dof >= 0.f && fh->camera.dof <= 3.402823466e38f)) { fprintf(stderr, "bhrt: usage: --lens: the scene's <dof> must be a finite number >= 0 (or give --dof)\n"); return 2; }
         printf("lens: focal distance %g, aperture radius %g%s\n", fh->camera.focaldist, fh->camera.dof, fh->camera.dof > 0.f ? "" : " (pinhole)");
         if (A.denoise && A.guide_spp <= 0) printf("note: --denoise guides (depth, normal, albedo) are those of the pinhole ray; --guide-spp N forms them from the lens rays\n");
+    }
+    if (A.Camera() || A.Shutter()) { // before the upload and before --gpus N clones the scene; after --focaldist, which places the default target
+        const bhrt_flat_header *fh = nullptr;
+        uint64_t fb = 0;
+        if (bhrt_scene_flat(scene, (const void **)&fh, &fb)) return fail("scene blob");
+        auto pose = [&](const Args::Vec &gp, const Args::Vec &gt, const Args::Vec &gu, float *pos, float *target, float *up) {
+            const bhrt_camera &c = fh->camera; // the scene's pose now: the missing values
+            for (int k = 0; k < 3; k++) {
+                pos[k] = gp.given ? gp.v[k] : c.pos[k];
+                target[k] = gt.given ? gt.v[k] : c.pos[k] + c.dir[k] * c.focaldist;
+                up[k] = gu.given ? gu.v[k] : c.up[k];
+            }
+        };
+        float p[3], t[3], u[3];
+        if (A.Camera()) {
+            pose(A.cam_pos, A.cam_target, A.cam_up, p, t, u);
+            if (bhrt_scene_set_camera(scene, p, t, u, A.fov)) return fail("set camera");
+        }
+        pose(A.cam_pos, A.cam_target, A.cam_up, p, t, u); // pose 0 as it stands
+        printf("camera: position %g,%g,%g target %g,%g,%g up %g,%g,%g fov %g\n", p[0], p[1], p[2], t[0], t[1], t[2], u[0], u[1], u[2], fh->camera.fov);
+        if (A.Shutter()) {
+            float p1[3], t1[3], u1[3];
+            pose(A.sh_pos, A.sh_target, A.sh_up, p1, t1, u1);
+            if (!A.sh_target.given) for (int k = 0; k < 3; k++) t1[k] = t[k]; // pose 0's target as given, not recomputed
+            if (!A.sh_pos.given) for (int k = 0; k < 3; k++) p1[k] = p[k];
+            if (!A.sh_up.given) for (int k = 0; k < 3; k++) u1[k] = u[k];
+            if (bhrt_scene_set_shutter(scene, 1, p1, t1, u1)) return fail("set shutter");
+            printf("shutter: to position %g,%g,%g target %g,%g,%g up %g,%g,%g during the exposure\n", p1[0], p1[1], p1[2], t1[0], t1[1], t1[2], u1[0], u1[1], u1[2]);
+        }
     }
     if (A.denoise && A.guide_spp > 0) printf("denoise guides: %d sample(s) per pixel%s\n", A.guide_spp, o.lens ? ", through the lens" : "");
     if (A.coverage_filter) printf("denoise filter: for sampled guides, coverage tolerance %g\n", A.sigma_coverage);

@@ -146,6 +146,7 @@ struct DeviceState : DeviceQueues {
     DevBuf<int32_t> d_fm_tab;
     FaceMtlTable fm = {nullptr, 0}; // fm.tab != null: bhrt_scene_set_face_materials is on and the scene has sub-materials
     DevScene S;
+    ShutterInfo shutter = {};                  // the kernels' copy of the scene's shutter (RefreshShutter): pose 1's frame; on = 0: no shutter kernel runs
     // wavefront workspace (EnsureWorkspace)
     uint32_t cap_samples = 0, cap_rays = 0, cap_frames = 0;
     DevBuf<float> d_rayf[2];                   // 6 * cap_rays floats each

@@ -33,6 +33,14 @@ struct DevScene {
     float tapx[32], tapy[32]; // the 31 elliptic Halton taps of Texture::Sample (scene.h:322-329)
 };
 
+// The camera shutter (bhrt_scene_set_shutter): the frame of pose 1, the camera at the end of the exposure; pose 0 is DevScene::cam.
+// A kernel argument of the shutter kernels alone (k_shutter_rays, k_guides_shutter, k_camera_rays_shutter): PassInfo and DevScene stay what
+// they are, and so do the arguments of every other kernel.  `on` is read by the host only: it chooses those kernels.
+struct ShutterInfo {
+    float pos1[3], top_left1[3], dd_x1[3], dd_y1[3];
+    int32_t on;
+};
+
 // continuation kinds of a closest-hit ray
 enum : uint32_t {
     RK_CAMERA = 0,   // Main.cpp:153-158      frame = sample slot

@@ -3,6 +3,7 @@
 // One launch of each kernel processes one "wave step" of all paths in flight:
 //   camera_ray()    Main.cpp:132-153,179-192   the camera ray of a (pixel, sample) slot, computed inside the first step's kernels
 //   k_lens_rays     viewport.cpp:236-243       bhrt_opts.lens: the thin-lens camera rays of a pass, written into its ray queue
+//   k_shutter_rays  (no counterpart)           bhrt_scene_set_shutter: the camera rays of a pass at each sample's time, written likewise
 //   k_trace_closest Main.cpp:389-413 + Objects/* ordered scene-graph closest hit -> compact hits; files every ray under its
 //                                              shading class; with meshes in the scene it parks the rays that enter a mesh
 //   k_trace_mesh    TriObj.cpp:17-39,192-270   the parked rays, key-sorted, in dense workgroups: BVH traversal + rest of the scene graph
@@ -216,19 +217,34 @@ __device__ inline V3 ld3i(const float *a, uint32_t i) { return v3(a[3 * (size_t)
 // the image plane, which BeginRender puts at <focaldist> (Main.cpp:181-189): the plane of focus (viewport.cpp:236-243 as a render).  The two
 // draws are a stream of their own: section BHRT_SEC_LENS of path code 0, which no Shade() call has; the jitter draws and the Shade()
 // streams of the sample stay what they are.
-template <bool kLens = false>
-__device__ inline bool camera_ray(const DevScene &S, const PassInfo &P, uint32_t idx, V3 &o, V3 &d)
+// kShutter (bhrt_scene_set_shutter; k_shutter_rays, k_guides_shutter and k_camera_rays_shutter only): the camera moves during the
+// exposure.  The sample's time t is one draw of a stream of its own, section BHRT_SEC_SHUTTER of path code 0; pos, top_left, dd_x and dd_y are
+// each X0 + (X1 - X0) * t, per component, between DevScene::cam and Sh; the jitter's and the lens's unit axes and pixel length are formed from
+// that frame with the operations the host uses for PassInfo::jx, jy, pixel_len.  Equal poses give X0 + 0 * t = X0: the ray without a shutter.
+template <bool kLens = false, bool kShutter = false>
+__device__ inline bool camera_ray(const DevScene &S, const PassInfo &P, uint32_t idx, V3 &o, V3 &d, const ShutterInfo *Sh = nullptr)
 {
     int i = 0, j = 0;
     uint32_t s;
     o = v3(0, 0, 0); d = v3(0, 0, 0);
     if (!slot_pixel(P, idx, i, j, s)) return false;
     // PathTracing(), Main.cpp:145: pixel "centre" = corner because 1/2 == 0
-    const V3 topLeft = ld3(S.cam.top_left), ddx = ld3(S.cam.dd_x), ddy = ld3(S.cam.dd_y), pos = ld3(S.cam.pos);
+    V3 topLeft = ld3(S.cam.top_left), ddx = ld3(S.cam.dd_x), ddy = ld3(S.cam.dd_y), pos = ld3(S.cam.pos);
+    V3 sux = v3(0, 0, 0), suy = v3(0, 0, 0);
+    float s_len = 0.f;
+    if (kShutter) {
+        const uint32_t tkey = bhrt_section_key(bhrt_sample_key(P.seed, (uint32_t)(j * P.W + i), P.s0 + s), 0, BHRT_SEC_SHUTTER);
+        const float t = dm::rand_to_unit(bhrt_rand31(tkey, 0));
+        pos = pos + (ld3(Sh->pos1) - pos) * t;
+        topLeft = topLeft + (ld3(Sh->top_left1) - topLeft) * t;
+        ddx = ddx + (ld3(Sh->dd_x1) - ddx) * t;
+        ddy = ddy + (ld3(Sh->dd_y1) - ddy) * t;
+        sux = normalized(ddx); suy = normalized(ddy); s_len = length(ddx);
+    }
     V3 target = (topLeft + (float)i * ddx) - (float)j * ddy;
     if (P.jitter) { // RandomPositionInPixel, Main.cpp:132-139: two raw rand() draws in double
-        const float pixelLen = P.pixel_len;
-        const V3 ux = ld3(P.jx), uy = ld3(P.jy);
+        const float pixelLen = kShutter ? s_len : P.pixel_len;
+        const V3 ux = kShutter ? sux : ld3(P.jx), uy = kShutter ? suy : ld3(P.jy);
         const uint32_t key = bhrt_sample_key(P.seed, (uint32_t)(j * P.W + i), P.s0 + s);
         float fx = (float)(((double)bhrt_rand31(key, 0) / (BHRT_RAND_MAX)) * 2 - 1);
         target = target + ((ux * fx) * pixelLen) / 2.f;
@@ -243,7 +259,7 @@ __device__ inline bool camera_ray(const DevScene &S, const PassInfo &P, uint32_t
         const float a = ((float)M_PI * 2.0f) * u2; // viewport.cpp:241
         float sn, cs;
         dm::sincos_f(a, &sn, &cs);
-        const V3 ux = ld3(P.jx), uy = ld3(P.jy);   // unit dd_x, dd_y: the reference's v = dir ^ up and up (camXAxis, camYAxis, Main.cpp:185-187)
+        const V3 ux = kShutter ? sux : ld3(P.jx), uy = kShutter ? suy : ld3(P.jy); // unit dd_x, dd_y: the reference's v = dir ^ up and up (camXAxis, camYAxis, Main.cpp:185-187)
         const V3 off = (ux * (r * cs)) + (uy * (r * sn));
         o = pos + off;
         d = target - o;
@@ -1604,9 +1620,15 @@ __global__ void __launch_bounds__(kBlock) k_first_hit(DevScene S, FaceMtlTable T
 // first / last: the chunk is the call's first / last one.  Between chunks the running sums live in acc, two float4 per pixel of the pass:
 // (sum t, sum N), (sum kd, the hit count's bits); a call of one chunk reads and writes none.  The last chunk divides and stores:
 //   coverage = k / n, z = k ? sum t / k : BIGFLOAT, normal = sum N / n, albedo = sum kd / n      (n = n_total, the call's spp)
-template <bool kFm>
-__global__ void __launch_bounds__(kBlock) k_guides(DevScene S, FaceMtlTable T, PassInfo P, uint32_t ppb, uint32_t n_total, int first, int last, float4 *acc,
-                                                   float *z, float *normal, float *albedo, float *coverage)
+// The shutter's camera ray of a slot, pinhole or lens by the kernel argument P.lens_r (uniform), as the callers without a shutter choose
+__device__ inline bool shutter_camera_ray(const DevScene &S, const PassInfo &P, const ShutterInfo &Sh, uint32_t slot, V3 &o, V3 &d)
+{
+    return P.lens_r > 0.f ? camera_ray<true, true>(S, P, slot, o, d, &Sh) : camera_ray<false, true>(S, P, slot, o, d, &Sh);
+}
+// One body, two kernels: k_guides keeps its arguments and its code; k_guides_shutter takes the frame of pose 1 as well (kShutter).
+template <bool kFm, bool kShutter>
+__device__ inline void guides_body(const DevScene &S, const FaceMtlTable &T, const PassInfo &P, const ShutterInfo *Sh, uint32_t ppb, uint32_t n_total, int first, int last,
+                                   float4 *acc, float *z, float *normal, float *albedo, float *coverage)
 {
     __shared__ bhrt_bvh_node nodelet[BHRT_LDS_NODES];
     __shared__ float s_v[7][kBlock];
@@ -1619,7 +1641,8 @@ __global__ void __launch_bounds__(kBlock) k_guides(DevScene S, FaceMtlTable T, P
     bool active = false;
     if (pl < ppb && q_local < P.n_pixels) {
         const uint32_t slot = q_local * c + s;
-        active = P.lens_r > 0.f ? camera_ray<true>(S, P, slot, o, d) : camera_ray(S, P, slot, o, d); // a kernel argument: uniform
+        if (kShutter) active = shutter_camera_ray(S, P, *Sh, slot, o, d);
+        else active = P.lens_r > 0.f ? camera_ray<true>(S, P, slot, o, d) : camera_ray(S, P, slot, o, d); // a kernel argument: uniform
     }
     Hit hit;
     trace_closest(S, o, d, BHRT_HIT_FRONT, hit, active, nodelet); // uniform call: the block stages nodelets together
@@ -1668,6 +1691,18 @@ __global__ void __launch_bounds__(kBlock) k_guides(DevScene S, FaceMtlTable T, P
     if (z) z[pix] = k ? st / (float)k : BHRT_BIGFLOAT;
     if (normal) st3(normal, pix, sN / n);
     if (albedo) st3(albedo, pix, sk / n);
+}
+template <bool kFm>
+__global__ void __launch_bounds__(kBlock) k_guides(DevScene S, FaceMtlTable T, PassInfo P, uint32_t ppb, uint32_t n_total, int first, int last, float4 *acc,
+                                                   float *z, float *normal, float *albedo, float *coverage)
+{
+    guides_body<kFm, false>(S, T, P, nullptr, ppb, n_total, first, last, acc, z, normal, albedo, coverage);
+}
+template <bool kFm>
+__global__ void __launch_bounds__(kBlock) k_guides_shutter(DevScene S, FaceMtlTable T, PassInfo P, ShutterInfo Sh, uint32_t ppb, uint32_t n_total, int first, int last,
+                                                           float4 *acc, float *z, float *normal, float *albedo, float *coverage)
+{
+    guides_body<kFm, true>(S, T, P, &Sh, ppb, n_total, first, last, acc, z, normal, albedo, coverage);
 }
 
 // RenderImage::ComputeZBufferImage (scene.h:578-600): min / max over the hits, then (zmax - z) / (zmax - zmin) * 255 truncated.
@@ -1760,6 +1795,16 @@ __global__ void __launch_bounds__(kBlock) k_lens_rays(DevScene S, PassInfo P, Ra
     const bool valid = camera_ray<true>(S, P, i, o, d);
     put_ray(q, i, o, d, i, make_meta(valid ? RK_CAMERA : RK_DEAD, BHRT_HIT_FRONT, 0), 0u);
 }
+// k_lens_rays' sibling for a pass with the shutter on: the same 36 B per slot in the same form, the ray formed at the sample's
+// time, through the lens where P.lens_r > 0 and from the moving pinhole where not.  Every pass of such a render takes this route.
+__global__ void __launch_bounds__(kBlock) k_shutter_rays(DevScene S, PassInfo P, ShutterInfo Sh, RayQueue q, uint32_t n)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    V3 o, d;
+    const bool valid = shutter_camera_ray(S, P, Sh, i, o, d);
+    put_ray(q, i, o, d, i, make_meta(valid ? RK_CAMERA : RK_DEAD, BHRT_HIT_FRONT, 0), 0u);
+}
 // test hook (bhrt_camera_rays): the camera ray of every slot of a pass through the render's own device function, the rays of the
 // pixels inside the region written as ox, oy, oz, dx, dy, dz per sample in the order of k_copy_samples
 __global__ void __launch_bounds__(kBlock) k_camera_rays(DevScene S, PassInfo P, uint32_t n, int x0, int y0, int x1, int y1, float *out)
@@ -1768,6 +1813,21 @@ __global__ void __launch_bounds__(kBlock) k_camera_rays(DevScene S, PassInfo P, 
     if (slot >= n) return;
     V3 o, d;
     const bool valid = P.lens_r > 0.f ? camera_ray<true>(S, P, slot, o, d) : camera_ray(S, P, slot, o, d); // a kernel argument: uniform
+    int i, j;
+    uint32_t s;
+    if (!valid || !slot_pixel(P, slot, i, j, s)) return;
+    if (i < x0 || i >= x1 || j < y0 || j >= y1) return;
+    const size_t pix = (size_t)(j - y0) * (x1 - x0) + (i - x0);
+    float *r = out + (pix * P.spp + s) * 6;
+    r[0] = o.x; r[1] = o.y; r[2] = o.z; r[3] = d.x; r[4] = d.y; r[5] = d.z;
+}
+// the same hook with the scene's shutter on: the body of k_shutter_rays (k_camera_rays keeps its text, so the compiler's report of it stays the parent's)
+__global__ void __launch_bounds__(kBlock) k_camera_rays_shutter(DevScene S, PassInfo P, ShutterInfo Sh, uint32_t n, int x0, int y0, int x1, int y1, float *out)
+{
+    const uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x;
+    if (slot >= n) return;
+    V3 o, d;
+    const bool valid = shutter_camera_ray(S, P, Sh, slot, o, d);
     int i, j;
     uint32_t s;
     if (!valid || !slot_pixel(P, slot, i, j, s)) return;
@@ -2808,7 +2868,8 @@ struct WavePass {
     // kernels go to a stream of their own as soon as k_shade has written them, with a shadow queue per step parity, and fill what the pass's stream leaves
     // idle — above all the tail of every k_trace_mesh_stream launch (the longest walks of its last batch: 0.1-0.5 ms per wave step).
     const bool sh_overlap;
-    const bool lens;           // thin-lens camera: the pass's camera rays come from k_lens_rays (Begin)
+    const bool shutter;        // camera shutter (DeviceState::shutter.on): the pass's camera rays come from k_shutter_rays, with and without the lens
+    const bool lens;           // thin-lens camera or shutter: the pass's camera rays are stored rays (Begin)
     const bool gg;             // the global gather is on and its map installed: the kGg instantiations of k_shade mark the frames gi < 0 cuts.
                                // Not a field of RenderParams: a longer kernel argument costs the switch-off camera kernels 20-36 B of scratch per lane
     uint32_t *const root_of;   // fuse_root: k_shade's slot -> root frame map
@@ -2845,7 +2906,7 @@ struct WavePass {
     WavePass(bhrt_scene *scene, const bhrt_opts &o, bhrt_stats *stats, const RenderParams &Rp, const PassInfo &Pp, bool fuse_root, TimePoint render_start)
         : D(scene->dev), st(stats), R(Rp), P(Pp), wall0(render_start), meshes(scene->flat.hdr()->n_meshes > 0), tex(scene->flat.hdr()->n_texmaps > 0), ls(o.leaf_skip != 0),
           path_mode(PathMode(scene)), stream_waves(D->knobs.stream_waves >= 0 ? (uint32_t)D->knobs.stream_waves : D->n_cus * 4u * (uint32_t)BHRT_STREAM_OCC),
-          sh_overlap(D->knobs.shadow_overlap && D->stream3 != nullptr && D->d_shf2.p != nullptr), lens(Pp.lens_r > 0.f), gg(scene->flat.global_gather != 0 && D->gmap.n_photons > 0), root_of(fuse_root ? D->d_root.p : nullptr),
+          sh_overlap(D->knobs.shadow_overlap && D->stream3 != nullptr && D->d_shf2.p != nullptr), shutter(D->shutter.on != 0), lens(Pp.lens_r > 0.f || D->shutter.on != 0), gg(scene->flat.global_gather != 0 && D->gmap.n_photons > 0), root_of(fuse_root ? D->d_root.p : nullptr),
           finish(D->knobs.finish_misses && scene->flat.hdr()->environment.map < 0), V(MakePassViews(D, sh_overlap)), n_cur(Pp.n_pixels * (uint32_t)Pp.spp)
     {
     }
@@ -2886,7 +2947,8 @@ struct WavePass {
         // coherently than pinhole rays.  Inside the pass, so a pass that overflows and is redone in halves forms its rays again.
         if (lens) {
             Timer t(D, &st->seconds_other);
-            hipLaunchKernelGGL(k_lens_rays, dim3((n_cur + kBlock - 1) / kBlock), dim3(kBlock), 0, D->stream, D->S, P, V.Q[0], n_cur);
+            if (shutter) hipLaunchKernelGGL(k_shutter_rays, dim3((n_cur + kBlock - 1) / kBlock), dim3(kBlock), 0, D->stream, D->S, P, D->shutter, V.Q[0], n_cur);
+            else hipLaunchKernelGGL(k_lens_rays, dim3((n_cur + kBlock - 1) / kBlock), dim3(kBlock), 0, D->stream, D->S, P, V.Q[0], n_cur);
             t.Stop();
         }
         if (D->stream2) HIP_CHECK(hipStreamSynchronize(D->stream2)); // nothing of an abandoned pass still reads the queue
@@ -3488,6 +3550,41 @@ try {
     return BHRT_OK;
 } catch (...) { return bhrt::AbiException(); }
 
+// DevScene::cam_chain of the scene's camera: its position through every node's chain, p' = itm * (p - pos) per level, the depth-1 ancestor
+// first.  cc: n_nodes x BHRT_MAX_NODE_DEPTH x 3 floats.  The upload and bhrt_scene_set_camera share it.
+static void FillCamChain(const bhrt::FlatScene &flat, float *cc)
+{
+    const bhrt_flat_header *H = flat.hdr();
+    const bhrt_node *nodes = (const bhrt_node *)(flat.blob.data() + H->off_nodes);
+    for (uint32_t n = 0; n < H->n_nodes; n++) {
+        int32_t chain[BHRT_MAX_NODE_DEPTH] = {};
+        const int depth = std::min<int>(nodes[n].depth, BHRT_MAX_NODE_DEPTH);
+        for (int k = depth - 1, c = (int)n; c >= 0 && k >= 0; k--) { chain[k] = c; c = nodes[c].parent; }
+        V3 p = v3(H->camera.pos[0], H->camera.pos[1], H->camera.pos[2]);
+        for (int k = 0; k < depth; k++) {
+            const bhrt_xform &t = nodes[chain[k]].xf;
+            p = mat_mul(t.itm, p - v3(t.pos[0], t.pos[1], t.pos[2]));
+            float *o3 = cc + ((size_t)n * BHRT_MAX_NODE_DEPTH + k) * 3;
+            o3[0] = p.x; o3[1] = p.y; o3[2] = p.z;
+        }
+    }
+}
+
+// The kernels' copy of the scene's shutter (FlatScene::shutter*): at upload, and again by the setters of an uploaded scene.  A
+// kernel argument, so there is nothing to copy to the device.
+static void RefreshShutter(bhrt_scene *scene)
+{
+    DeviceState *D = scene->dev;
+    if (!D) return;
+    const bhrt_camera &c = scene->flat.shutter_cam;
+    ShutterInfo sh = {};
+    if (scene->flat.shutter) {
+        for (int k = 0; k < 3; k++) { sh.pos1[k] = c.pos[k]; sh.top_left1[k] = c.top_left[k]; sh.dd_x1[k] = c.dd_x[k]; sh.dd_y1[k] = c.dd_y[k]; }
+        sh.on = 1;
+    }
+    D->shutter = sh;
+}
+
 int bhrt_scene_upload(bhrt_scene *scene, int device)
 try {
     if (!scene) { SetError("null scene"); return BHRT_ERR_ARG; }
@@ -3564,18 +3661,7 @@ try {
         const bhrt_light *lts = (const bhrt_light *)(scene->flat.blob.data() + H->off_lights);
         const size_t n_cam = (size_t)std::max<uint32_t>(H->n_nodes, 1) * BHRT_MAX_NODE_DEPTH * 3;
         std::vector<float> aux(H->n_materials + H->n_lights + 1 + n_cam, 0.f);
-        { // DevScene::cam_chain: the camera position through every node's chain, p' = itm * (p - pos) per level
-            float *cc = aux.data() + H->n_materials + H->n_lights + 1;
-            for (uint32_t n = 0; n < H->n_nodes; n++) {
-                V3 p = v3(H->camera.pos[0], H->camera.pos[1], H->camera.pos[2]);
-                for (int k = 0; k < nodes[n].depth; k++) {
-                    const bhrt_xform &t = nodes[chain[(size_t)n * BHRT_MAX_NODE_DEPTH + k]].xf;
-                    p = mat_mul(t.itm, p - v3(t.pos[0], t.pos[1], t.pos[2]));
-                    float *o3 = cc + ((size_t)n * BHRT_MAX_NODE_DEPTH + k) * 3;
-                    o3[0] = p.x; o3[1] = p.y; o3[2] = p.z;
-                }
-            }
-        }
+        FillCamChain(scene->flat, aux.data() + H->n_materials + H->n_lights + 1);
         for (uint32_t m = 0; m < H->n_materials; m++) {
             const float ior = mats[m].ior;
             const double r0d = (double)((1 - ior) / (1 + ior));
@@ -3589,6 +3675,7 @@ try {
         S.cam_chain = D->d_aux + H->n_materials + H->n_lights + 1;
     }
     S.cam = H->camera; S.background = H->background; S.environment = H->environment;
+    RefreshShutter(scene);
     BHRT_TRY(RefreshEmission(scene));
     BHRT_TRY(RefreshFaceMaterials(scene));
     S.tapx[0] = S.tapy[0] = 0;
@@ -3977,7 +4064,9 @@ try {
     BHRT_TRY(d_r.Reserve(nfl));
     DeviceState *D = scene->dev;
     HIP_CHECK(hipMemsetAsync(d_r, 0, nfl * sizeof(float), D->stream));
-    hipLaunchKernelGGL(k_camera_rays, dim3((unsigned)((slots + kBlock - 1) / kBlock)), dim3(kBlock), 0, D->stream, D->S, P, (uint32_t)slots, x0, y0, x1, y1, d_r.p);
+    const dim3 grid((unsigned)((slots + kBlock - 1) / kBlock));
+    if (D->shutter.on) hipLaunchKernelGGL(k_camera_rays_shutter, grid, dim3(kBlock), 0, D->stream, D->S, P, D->shutter, (uint32_t)slots, x0, y0, x1, y1, d_r.p);
+    else hipLaunchKernelGGL(k_camera_rays, grid, dim3(kBlock), 0, D->stream, D->S, P, (uint32_t)slots, x0, y0, x1, y1, d_r.p);
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipMemcpyAsync(rays, d_r, nfl * sizeof(float), hipMemcpyDeviceToHost, D->stream));
     HIP_CHECK(hipStreamSynchronize(D->stream));
@@ -3994,7 +4083,88 @@ try {
     if (focaldist > 0.f) H->camera.focaldist = focaldist;
     H->camera.dof = dof;
     DeriveCameraFrame(H->camera);
+    if (scene->flat.shutter) { // pose 1 takes the scene's focaldist and dof: its frame follows
+        bhrt_camera &c1 = scene->flat.shutter_cam;
+        c1.focaldist = H->camera.focaldist; c1.dof = H->camera.dof;
+        DeriveCameraFrame(c1);
+    }
     if (scene->dev) scene->dev->S.cam = H->camera;
+    RefreshShutter(scene);
+    return BHRT_OK;
+} catch (...) { return bhrt::AbiException(); }
+
+// ---- the camera and its shutter.  In this translation unit because the setters refresh an uploaded scene.
+static bool Finite3(const float *v) { return v && std::isfinite(v[0]) && std::isfinite(v[1]) && std::isfinite(v[2]); }
+// Pose 1 of a shutter: the camera `base` (fov, focaldist, dof, size) at (pos, target, up); "" = a valid pose, else what is wrong
+static const char *PoseCamera(const bhrt_camera &base, const float pos[3], const float target[3], const float up[3], bhrt_camera &out)
+{
+    if (!pos || !target || !up) return "a NULL pointer";
+    if (!Finite3(pos) || !Finite3(target) || !Finite3(up)) return "a component that is not finite";
+    out = base;
+    if (!SetCameraPose(out, pos, target, up, base.fov)) return "target == pos, or up parallel to target - pos";
+    for (int k = 0; k < 3; k++)
+        if (!std::isfinite(out.dir[k]) || !std::isfinite(out.up[k]) || !std::isfinite(out.top_left[k]) || !std::isfinite(out.dd_x[k]) || !std::isfinite(out.dd_y[k]))
+            return "a camera frame that is not finite";
+    return "";
+}
+
+int bhrt_scene_set_camera(bhrt_scene *scene, const float pos[3], const float target[3], const float up[3], float fov)
+try {
+    if (!scene) { SetError("bhrt_scene_set_camera: null scene"); return BHRT_ERR_ARG; }
+    if (!std::isfinite(fov) || fov >= 180.f) { SetError("bhrt_scene_set_camera: fov must be finite and below 180 (<= 0 keeps the current one)"); return BHRT_ERR_ARG; }
+    bhrt_flat_header *H = reinterpret_cast<bhrt_flat_header *>(scene->flat.blob.data());
+    bhrt_camera base = H->camera, cam, cam1 = scene->flat.shutter_cam;
+    if (fov > 0.f) base.fov = fov;
+    const char *bad = PoseCamera(base, pos, target, up, cam);
+    if (*bad) { SetError(std::string("bhrt_scene_set_camera: ") + bad); return BHRT_ERR_ARG; }
+    if (scene->flat.shutter) { // pose 1 takes the new fov; the pair that results must still be less than a quarter turn apart
+        bad = PoseCamera(base, scene->flat.shutter_pos, scene->flat.shutter_target, scene->flat.shutter_up, cam1);
+        if (!*bad) bad = ShutterPairError(cam, cam1);
+        if (*bad) { SetError(std::string("bhrt_scene_set_camera: with the shutter's pose 1: ") + bad); return BHRT_ERR_ARG; }
+    }
+    H->camera = cam; // nothing above changed the scene
+    scene->flat.shutter_cam = cam1;
+    if (DeviceState *D = scene->dev) { // the kernels' camera and the camera position through every node's chain; nothing else is uploaded again
+        HIP_CHECK(hipSetDevice(D->device));
+        std::vector<float> cc((size_t)std::max<uint32_t>(H->n_nodes, 1) * BHRT_MAX_NODE_DEPTH * 3, 0.f);
+        FillCamChain(scene->flat, cc.data());
+        HIP_CHECK(hipMemcpy(const_cast<float *>(D->S.cam_chain), cc.data(), cc.size() * sizeof(float), hipMemcpyHostToDevice));
+        D->S.cam = H->camera;
+        RefreshShutter(scene);
+    }
+    return BHRT_OK;
+} catch (...) { return bhrt::AbiException(); }
+
+int bhrt_scene_set_shutter(bhrt_scene *scene, int on, const float pos1[3], const float target1[3], const float up1[3])
+try {
+    if (!scene) { SetError("bhrt_scene_set_shutter: null scene"); return BHRT_ERR_ARG; }
+    bhrt::FlatScene &F = scene->flat;
+    if (!on) {
+        F.shutter = 0;
+        memset(F.shutter_pos, 0, sizeof F.shutter_pos); memset(F.shutter_target, 0, sizeof F.shutter_target); memset(F.shutter_up, 0, sizeof F.shutter_up);
+        memset(&F.shutter_cam, 0, sizeof F.shutter_cam);
+        RefreshShutter(scene);
+        return BHRT_OK;
+    }
+    bhrt_camera cam1;
+    const char *bad = PoseCamera(F.hdr()->camera, pos1, target1, up1, cam1);
+    if (!*bad) bad = ShutterPairError(F.hdr()->camera, cam1);
+    if (*bad) { SetError(std::string("bhrt_scene_set_shutter: ") + bad); return BHRT_ERR_ARG; }
+    F.shutter = 1;
+    for (int k = 0; k < 3; k++) { F.shutter_pos[k] = pos1[k]; F.shutter_target[k] = target1[k]; F.shutter_up[k] = up1[k]; }
+    F.shutter_cam = cam1;
+    RefreshShutter(scene);
+    return BHRT_OK;
+} catch (...) { return bhrt::AbiException(); }
+
+int bhrt_scene_get_shutter(const bhrt_scene *scene, int *on, float pose1[9], float frame1[12])
+try {
+    if (!scene) { SetError("bhrt_scene_get_shutter: null scene"); return BHRT_ERR_ARG; }
+    const bhrt::FlatScene &F = scene->flat;
+    const bhrt_camera &c = F.shutter_cam;
+    if (on) *on = F.shutter;
+    if (pose1) for (int k = 0; k < 3; k++) { pose1[k] = F.shutter_pos[k]; pose1[3 + k] = F.shutter_target[k]; pose1[6 + k] = F.shutter_up[k]; }
+    if (frame1) for (int k = 0; k < 3; k++) { frame1[k] = c.pos[k]; frame1[3 + k] = c.top_left[k]; frame1[6 + k] = c.dd_x[k]; frame1[9 + k] = c.dd_y[k]; }
     return BHRT_OK;
 } catch (...) { return bhrt::AbiException(); }
 
@@ -4127,6 +4297,7 @@ try {
     const uint64_t pass_px = std::min<uint64_t>(std::min<uint64_t>(owned_pixels, std::max<uint32_t>(cap / c, 1u)), (1u << 30) / c); // slots of a pass fit 32 bits
     if (n_chunks > 1) BHRT_TRY(D->d_guides.Reserve((size_t)pass_px * 2));
     auto kernel = D->fm.tab ? k_guides<true> : k_guides<false>;
+    auto shutter_kernel = D->fm.tab ? k_guides_shutter<true> : k_guides_shutter<false>; // chosen by the scene's shutter, as lens_r > 0 chooses the lens
     for (uint64_t q = 0; q < owned_pixels; q += pass_px) {
         const uint32_t npx = (uint32_t)std::min<uint64_t>(pass_px, owned_pixels - q);
         for (uint32_t k = 0; k < n_chunks; k++) {
@@ -4135,8 +4306,12 @@ try {
             Pp.s0 = k * c; Pp.spp = (int32_t)std::min(c, n - k * c);
             Pp.by_spp = MakeFastDiv((uint32_t)Pp.spp);
             const uint32_t ppb = (uint32_t)kBlock / (uint32_t)Pp.spp;
-            hipLaunchKernelGGL(kernel, dim3((npx + ppb - 1) / ppb), dim3(kBlock), 0, st, D->S, D->fm, Pp, ppb, n, k == 0, k + 1 == n_chunks, D->d_guides.p, d_z, d_normal,
-                               d_albedo, d_coverage);
+            if (D->shutter.on)
+                hipLaunchKernelGGL(shutter_kernel, dim3((npx + ppb - 1) / ppb), dim3(kBlock), 0, st, D->S, D->fm, Pp, D->shutter, ppb, n, k == 0, k + 1 == n_chunks, D->d_guides.p,
+                                   d_z, d_normal, d_albedo, d_coverage);
+            else
+                hipLaunchKernelGGL(kernel, dim3((npx + ppb - 1) / ppb), dim3(kBlock), 0, st, D->S, D->fm, Pp, ppb, n, k == 0, k + 1 == n_chunks, D->d_guides.p, d_z, d_normal,
+                                   d_albedo, d_coverage);
         }
     }
     HIP_CHECK(hipGetLastError());

@@ -1042,7 +1042,7 @@ void BuildBvh(HostMesh &m, unsigned maxPer)
 // LoadSceneXml
 // ------------------------------------------------------------------------------------------------
 // BeginRender's camera frame, Main.cpp:179-192 (tan in double, PI = 3.14159265), from the camera's pos, dir, up (orthonormal, as the loader
-// stores them), fov, focaldist and size.  The loader and bhrt_scene_set_lens both run this: one copy of the arithmetic.
+// stores them), fov, focaldist and size.  The loader (through SetCameraPose), bhrt_scene_set_lens and both camera setters run this: one copy of the arithmetic.
 void DeriveCameraFrame(bhrt_camera &C)
 {
     const V3 pos = {C.pos[0], C.pos[1], C.pos[2]}, dir = {C.dir[0], C.dir[1], C.dir[2]}, up = {C.up[0], C.up[1], C.up[2]};
@@ -1059,6 +1059,41 @@ void DeriveCameraFrame(bhrt_camera &C)
     C.top_left[0] = topLeft.x; C.top_left[1] = topLeft.y; C.top_left[2] = topLeft.z;
     C.dd_x[0] = ddx.x; C.dd_x[1] = ddx.y; C.dd_x[2] = ddx.z;
     C.dd_y[0] = ddy.x; C.dd_y[1] = ddy.y; C.dd_y[2] = ddy.z;
+}
+
+// The loader's own treatment of <position>, <target>, <up> and <fov> (xmlload.cpp:109-127): dir = normalized(target - pos), x = dir ^ up,
+// up = normalized(x ^ dir), then the frame.  focaldist, dof, width and height are C's.  The loader, bhrt_scene_set_camera and the shutter's
+// pose 1 (bhrt_scene_set_shutter) all run this: one copy of the arithmetic.  false: target == pos or up parallel to target - pos (a zero
+// x); the fields are stored all the same, as the loader always has.
+bool SetCameraPose(bhrt_camera &C, const float pos3[3], const float target3[3], const float up3[3], float fov)
+{
+    const V3 pos = {pos3[0], pos3[1], pos3[2]};
+    V3 dir = {target3[0], target3[1], target3[2]}, up = {up3[0], up3[1], up3[2]};
+    dir = dir - pos;
+    const bool has_dir = dir.x != 0 || dir.y != 0 || dir.z != 0;
+    dir = normalized(dir);
+    V3 x = cross(dir, up);
+    const bool has_x = x.x != 0 || x.y != 0 || x.z != 0;
+    up = normalized(cross(x, dir));
+    C.pos[0] = pos.x; C.pos[1] = pos.y; C.pos[2] = pos.z;
+    C.dir[0] = dir.x; C.dir[1] = dir.y; C.dir[2] = dir.z;
+    C.up[0] = up.x; C.up[1] = up.y; C.up[2] = up.z;
+    C.fov = fov;
+    DeriveCameraFrame(C);
+    return has_dir && has_x;
+}
+
+// Poses more than a quarter turn apart are refused: with dir0 . dir1, dd_x0 . dd_x1 and dd_y0 . dd_y1 all positive, a . (a + (b - a) t) =
+// (1 - t) a . a + t a . b > 0 for every t in [0, 1), so no interpolated axis is zero and no ray of the shutter is NaN.
+const char *ShutterPairError(const bhrt_camera &a, const bhrt_camera &b)
+{
+    auto dot3 = [](const float *u, const float *v) { return (double)u[0] * v[0] + (double)u[1] * v[1] + (double)u[2] * v[2]; };
+    for (int k = 0; k < 3; k++)
+        if (!std::isfinite(b.pos[k]) || !std::isfinite(b.top_left[k]) || !std::isfinite(b.dd_x[k]) || !std::isfinite(b.dd_y[k])) return "the camera frame of a pose is not finite";
+    if (!(dot3(a.dir, b.dir) > 0)) return "the two poses look more than a quarter turn apart (dir0 . dir1 <= 0)";
+    if (!(dot3(a.dd_x, b.dd_x) > 0)) return "the two poses are more than a quarter turn apart (dd_x0 . dd_x1 <= 0)";
+    if (!(dot3(a.dd_y, b.dd_y) > 0)) return "the two poses are more than a quarter turn apart (dd_y0 . dd_y1 <= 0)";
+    return "";
 }
 
 int LoadSceneXml(const char *path, FlatScene &out, std::string &err, int bvh_device)
@@ -1113,16 +1148,10 @@ int LoadSceneXml(const char *path, FlatScene &out, std::string &err, int bvh_dev
             else if (NameIs(c, "width")) c->QueryInt("value", &w);
             else if (NameIs(c, "height")) c->QueryInt("value", &h);
         }
-        dir = dir - pos;
-        dir = normalized(dir);
-        V3 x = cross(dir, up);
-        up = normalized(cross(x, dir));
         if (w <= 0 || h <= 0) { err = "camera width/height must be positive"; return 5; }
-        C.pos[0] = pos.x; C.pos[1] = pos.y; C.pos[2] = pos.z;
-        C.dir[0] = dir.x; C.dir[1] = dir.y; C.dir[2] = dir.z;
-        C.up[0] = up.x; C.up[1] = up.y; C.up[2] = up.z;
-        C.fov = fov; C.focaldist = focaldist; C.dof = dof; C.width = w; C.height = h;
-        DeriveCameraFrame(C);
+        C.focaldist = focaldist; C.dof = dof; C.width = w; C.height = h;
+        const float p3[3] = {pos.x, pos.y, pos.z}, t3[3] = {dir.x, dir.y, dir.z}, u3[3] = {up.x, up.y, up.z}; // `dir` holds the target here
+        (void)SetCameraPose(C, p3, t3, u3, fov);
     }
 
     // CalculateLightsIntensity (Main.cpp:116-123): std::sort ascending by Gray(), then a float sum
@@ -1300,6 +1329,7 @@ int LoadSceneXml(const char *path, FlatScene &out, std::string &err, int bvh_dev
         out.material_names[i] = L.materials[i].name;
     }
     out.emissive = 0;
+    out.shutter = 0;
     H.off_materials = W.Append(mats.data(), mats.size() * sizeof(bhrt_material));
 
     std::vector<bhrt_light> lights(L.lights.size());

@@ -30,6 +30,12 @@ struct FlatScene {
     // is device state (DeviceState::gmap): a clone carries these two and no map.
     int global_gather = 0;
     float global_radius = 0.5f; // MAX_Area, MtlBlinn.cpp:29
+    // The camera shutter, beside the blob too: the switch, pose 1 as the caller gave it (position, target, up: the camera at the
+    // end of the exposure; pose 0 is the blob's camera) and the camera derived from it with the blob camera's fov, focaldist, dof and size
+    // (SetCameraPose).  shutter_cam is derived again whenever bhrt_scene_set_lens or bhrt_scene_set_camera changes what it depends on.
+    int shutter = 0;
+    float shutter_pos[3] = {0, 0, 0}, shutter_target[3] = {0, 0, 0}, shutter_up[3] = {0, 0, 0};
+    bhrt_camera shutter_cam = {};
     const bhrt_flat_header *hdr() const { return reinterpret_cast<const bhrt_flat_header *>(blob.data()); }
 };
 
@@ -39,6 +45,12 @@ int LoadSceneXml(const char *path, FlatScene &out, std::string &err, int bvh_dev
 
 // top_left, dd_x, dd_y of a camera whose other fields are set (the loader's own derivation; bhrt_scene_set_lens runs it again)
 void DeriveCameraFrame(bhrt_camera &C);
+// pos, dir, up and fov of C from a position, a target and an up vector, as the loader treats the <camera> tags, then DeriveCameraFrame;
+// false: target == pos, or up parallel to target - pos
+bool SetCameraPose(bhrt_camera &C, const float pos[3], const float target[3], const float up[3], float fov);
+// The pair of poses of a shutter: "" when dir, dd_x and dd_y of the two cameras each have a positive dot product and every value of
+// b's frame is finite (no interpolated axis can then be zero), else what is wrong
+const char *ShutterPairError(const bhrt_camera &a, const bhrt_camera &b);
 
 // OBJ mesh -> arrays, same face/index rules as cyTriMesh::LoadFromFileObj (cyTriMesh.h:263-547)
 struct HostMesh {

@@ -153,6 +153,35 @@ int bhrt_scene_flat(const bhrt_scene *scene, const void **blob, uint64_t *bytes)
  * afterwards byte-identical to the blob of the same XML with the two values written into its <camera>.  Needs no device; on an uploaded scene
  * the device's copy of the camera is refreshed (nothing else is uploaded again).  The pointer bhrt_scene_flat returned stays valid. */
 int bhrt_scene_set_lens(bhrt_scene *scene, float focaldist, float dof);
+/* The camera's <position>, <target>, <up> and <fov> of a loaded scene (xmlload.cpp:109-127), through the loader's own operations:
+ * dir = normalized(target - pos), x = dir ^ up, up = normalized(x ^ dir), then the camera frame.  fov <= 0 keeps the current fov; focaldist, dof,
+ * width and height are kept.  bhrt_scene_flat is afterwards byte-identical to the blob of the same XML with the four values written into its
+ * <camera>, and the pointer it returned stays valid.  Needs no device; on an uploaded scene the device's copy of the camera and the camera
+ * position carried through every node's chain are refreshed (nothing else is uploaded again), so the call is cheap enough for a viewport: between
+ * two steps of a progressive session later samples use the new camera, as with the other setters.  BHRT_ERR_ARG, with nothing changed and before
+ * any device is touched: a NULL pointer; a component that is not finite; a fov that is NaN, infinite or >= 180; target == pos; up parallel to
+ * target - pos; and, while a shutter is on, a camera that is a quarter turn or more from the shutter's pose 1 (see below). */
+int bhrt_scene_set_camera(bhrt_scene *scene, const float pos[3], const float target[3], const float up[3], float fov);
+/* The camera shutter: camera motion blur.  Pose 0 is the scene's camera, pose 1 = (pos1, target1, up1) the camera at the end of the
+ * exposure, with the scene's fov, focaldist, dof and size and a frame derived by the loader's own operations (it is derived again whenever
+ * bhrt_scene_set_lens or bhrt_scene_set_camera changes what it depends on).  With the shutter on every camera sample (pixel i, j, sample s) draws
+ * a time t, uniform on [0, 1): rand_to_unit of draw 0 of the stream keyed by section BHRT_SEC_SHUTTER of path code 0 under the sample's key
+ * (include/bhrt_rng.h: sample key of seed, j * W + i, s), a stream of its own, and its ray is the camera ray — jitter and lens as without a shutter — of the frame
+ *     X_t = X0 + (X1 - X0) * t      per component, in float32, for X = pos, top_left, dd_x, dd_y
+ * with the jitter's and the lens's axes normalized(dd_x_t), normalized(dd_y_t) and pixel length |dd_x_t|.  Equal poses give the render without a
+ * shutter bit for bit.  All later bhrt_render*, _samples, _var*, _adaptive*, bhrt_progressive_*, bhrt_guides* and bhrt_camera_rays of the scene
+ * follow the shutter.  bhrt_first_hit* and the guides bhrt_denoise* computes itself stay those of pose 0's pinhole ray.  One stated limit: the
+ * texture footprint of a plane hit reads the camera's dd_x, dd_y (Plane.cpp:51-70) and keeps reading pose 0's at every bounce, as under the lens:
+ * exact under a translation; under a rotation a textured plane is filtered with pose 0's footprint.
+ * The state lives beside the flat blob: bhrt_scene_flat's bytes do not change, bhrt_scene_clone carries it, bhrt_opts has no field for it.  Needs
+ * no device; on an uploaded scene the device's copy is refreshed.  Default: off.
+ *   on == 0   clears the state; the three pointers may be NULL
+ *   on != 0   BHRT_ERR_ARG with nothing changed, before any device is touched, for a NULL pointer, a component that is not finite,
+ *             target1 == pos1, up1 parallel to target1 - pos1, and for poses a quarter turn or more apart: dir0 . dir1 <= 0, dd_x0 . dd_x1 <= 0 or
+ *             dd_y0 . dd_y1 <= 0 (with positive products no interpolated axis can be zero, so no ray is ever NaN)
+ * get_shutter: the switch, pose 1 as given (pos1, target1, up1) and its derived frame (pos1, top_left1, dd_x1, dd_y1); any pointer may be NULL. */
+int bhrt_scene_set_shutter(bhrt_scene *scene, int on, const float pos1[3], const float target1[3], const float up1[3]);
+int bhrt_scene_get_shutter(const bhrt_scene *scene, int *on, float pose1[9], float frame1[12]);
 /* The emission term.  Every Blinn material carries the <emission> of its XML (xmlload.cpp:344-348: a colour, optionally a texture
  * map); the reference parses it and never shades it, and so does a scene here until it is switched on.  With the term on, every Shade() frame of
  * a Blinn material evaluates to  Shade(hit) + emission.Sample(uvw, duvw)  — one float addition per channel, behind everything Shade() does, on
@@ -241,7 +270,7 @@ int bhrt_render_samples(bhrt_scene *scene, const bhrt_opts *opts, int x0, int y0
 
 /* test hook: the camera rays of a pixel region as the render's first wave step forms them (bhrt_opts.lens 0: the device function the camera
  * kernels inline; 1: the lens kernel's body), on the device.  rays: region_pixels * spp * 6 floats (ox, oy, oz, dx, dy, dz per sample), host,
- * in the order of bhrt_render_samples.  Uses spp, seed, jitter and lens of the options. */
+ * in the order of bhrt_render_samples.  Uses spp, seed, jitter and lens of the options, and the scene's shutter (the shutter kernels' body). */
 int bhrt_camera_rays(bhrt_scene *scene, const bhrt_opts *opts, int x0, int y0, int x1, int y1, float *rays);
 
 /* ---- caustic photon map (Main.cpp:342-386, DataStructure/cyPhotonMap.h) -------------------------- */
@@ -425,7 +454,7 @@ int bhrt_save_png_gray(const char *path, const uint8_t *gray, int width, int hei
  * session holds state there, bhrt_scene_upload to another device returns BHRT_ERR_ARG and changes nothing (end the session first); to the same
  * device it stays the no-op it is.  bhrt_render*, bhrt_render_adaptive*,
  * bhrt_first_hit* and bhrt_denoise* on the same scene between two steps do not disturb the session.  The scene setters (bhrt_scene_set_lens,
- * _set_emissive, _set_material_emission, _set_face_materials, _set_global_gather, the photon and global maps) between two steps apply to
+ * _set_camera, _set_shutter, _set_emissive, _set_material_emission, _set_face_materials, _set_global_gather, the photon and global maps) between two steps apply to
  * the samples rendered afterwards: the frame then mixes samples of both states. */
 typedef struct bhrt_progress {
     uint32_t steps;            /* bhrt_progressive_step calls that rendered something */

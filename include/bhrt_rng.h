@@ -35,6 +35,8 @@
 #define BHRT_SEC_DIRECT 2u
 /* the thin-lens camera's aperture point (bhrt_opts.lens): section 3 of path code 0, which no Shade() call has (the root is 1) */
 #define BHRT_SEC_LENS 3u
+/* the camera shutter's time of a sample (bhrt_scene_set_shutter): section 4 of path code 0, counter 0 */
+#define BHRT_SEC_SHUTTER 4u
 
 static inline BHRT_HD uint32_t bhrt_mix32(uint32_t x)
 {
