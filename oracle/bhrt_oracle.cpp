@@ -1003,9 +1003,12 @@ template <class M> struct Shader {
 // ------------------------------------------------------------------------------------------------
 // frame loop
 // ------------------------------------------------------------------------------------------------
-inline uint8_t FloatToByte(float r) // cyColor.h:271-272
+// cyColor.h:271-272.  The reference's int(float) is cvttss2si on x86-64: INT_MIN for NaN and for anything outside int's range (undefined in
+// C++, so spelled out here); the same form as color24_channel (csrc/device_color24.h)
+inline uint8_t FloatToByte(float r)
 {
-    int v = int(r * 255 + 0.5f);
+    const float t = r * 255 + 0.5f;
+    const int v = t != t ? (int)0x80000000 : (t >= 2147483648.f ? (int)0x80000000 : (t <= -2147483649.f ? (int)0x80000000 : int(t)));
     return v < 0 ? 0 : (v > 255 ? 255 : v);
 }
 
@@ -1212,6 +1215,15 @@ int oracle_color_image(const float *radiance, size_t n_floats, int gamma, int ma
     const float inverseGama = 1 / 2.2f;
     for (size_t i = 0; i < n_floats; i++)
         color[i] = !gamma ? radiance[i] : (math_mode == ORACLE_MATH_DEVICE ? MathDevice::Pow(radiance[i], inverseGama) : MathLibm::Pow(radiance[i], inverseGama));
+    return 0;
+}
+
+// the tail of every 8-bit image (Main.cpp:220-226 + cyColor.h:271-272) on n floats: gamma, then FloatToByte
+int oracle_color24(const float *rgb, size_t n, int gamma, int math_mode, uint8_t *out)
+{
+    const float inverseGama = 1 / 2.2f;
+    for (size_t i = 0; i < n; i++)
+        out[i] = FloatToByte(!gamma ? rgb[i] : (math_mode == ORACLE_MATH_DEVICE ? MathDevice::Pow(rgb[i], inverseGama) : MathLibm::Pow(rgb[i], inverseGama)));
     return 0;
 }
 

@@ -72,6 +72,9 @@ int oracle_photon_build(const void *blob, const oracle_opts *opts, uint32_t max_
 int oracle_first_hit(const void *blob, int math_mode, float *z, float *normal, float *albedo);
 int oracle_zbuffer_image(const float *zbuffer, size_t size, uint8_t *zbufferImg);
 int oracle_color_image(const float *radiance, size_t n_floats, int gamma, int math_mode, float *color);
+/* gamma (Main.cpp:220-226) and Color24::FloatToByte (cyColor.h:271-272) of n floats: what oracle_render stores in rgb8.  NaN, +-inf and
+ * any v * 255 + 0.5 outside int's range convert as on x86-64 (INT_MIN), hence to byte 0 */
+int oracle_color24(const float *rgb, size_t n, int gamma, int math_mode, uint8_t *out);
 /* global photon map, BuildPhotonMap (Main.cpp:251-317, MtlBlinn.cpp:140-202): balanced + emission-order records (24 B each) */
 int oracle_photon_build_global(const void *blob, const oracle_opts *opts, uint32_t max_photons, void *photons_out, void *emitted_out,
                                uint32_t *n_stored, uint64_t *n_emitted);

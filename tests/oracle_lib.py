@@ -149,6 +149,14 @@ def color_image(radiance, gamma=1, math=MATH_DEVICE):
     return out
 
 
+def color24(rgb, gamma=1, math=MATH_DEVICE):
+    """Gamma and Color24::FloatToByte (cyColor.h:271-272) per float: the bytes of every 8-bit image, same shape as rgb."""
+    r = np.ascontiguousarray(rgb, np.float32)
+    out = np.zeros(r.shape, np.uint8)
+    _check(lib().oracle_color24(_p(r), C.c_size_t(r.size), int(gamma), int(math), _p(out)))
+    return out
+
+
 def photon_attach(balanced):
     a = np.ascontiguousarray(balanced, np.uint8)
     _check(lib().oracle_photon_attach(_p(a), a.shape[0]))
