@@ -68,6 +68,16 @@ class Progress(C.Structure):
                 ("camera_samples", C.c_uint64), ("finished", C.c_int32), ("reserved", C.c_int32 * 3)]
 
 
+class ReprojectOpts(C.Structure):
+    """bhrt_reproject_opts: when a tap of the previous view counts as the same surface (csrc/temporal.hip states the stage)."""
+    _fields_ = [("depth_tolerance", C.c_float), ("normal_threshold", C.c_float), ("reserved", C.c_int32 * 6)]
+
+
+class TemporalOpts(C.Structure):
+    """bhrt_temporal_opts: the history clamp, the longest history and the output gamma of bhrt_temporal_accumulate (csrc/temporal.hip)."""
+    _fields_ = [("clamp_k", C.c_float), ("max_length", C.c_float), ("gamma", C.c_int32), ("reserved", C.c_int32 * 5)]
+
+
 class Hits(C.Structure):
     _fields_ = [("t", C.c_void_p), ("node", C.c_void_p), ("prim", C.c_void_p), ("front", C.c_void_p)]
 
@@ -96,10 +106,17 @@ EXPORTS = [
     "bhrt_guides", "bhrt_guides_dev",
     "bhrt_denoise_sampled", "bhrt_denoise_sampled_dev",
     "bhrt_scene_set_camera", "bhrt_scene_set_shutter", "bhrt_scene_get_shutter",
+    "bhrt_scene_get_camera_frame", "bhrt_default_reproject_opts", "bhrt_default_temporal_opts",
+    "bhrt_reproject", "bhrt_reproject_dev", "bhrt_temporal_accumulate", "bhrt_temporal_accumulate_dev",
 ]
 
 # BHRT_DENOISE_SIGMA_COVERAGE of include/bhrt.h: the default coverage tolerance of the denoiser for sampled guides
 DENOISE_SIGMA_COVERAGE = 0.5
+# BHRT_REPROJECT_* and BHRT_TEMPORAL_* of include/bhrt.h: the measured defaults of temporal reprojection
+REPROJECT_DEPTH_TOLERANCE = 0.01
+REPROJECT_NORMAL_THRESHOLD = 0.99
+TEMPORAL_CLAMP_K = 1.0
+TEMPORAL_MAX_LENGTH = 16.0
 
 
 def lib():
@@ -124,6 +141,8 @@ def lib():
         L.bhrt_default_opts.restype = None
         L.bhrt_default_denoise_opts.restype = None
         L.bhrt_default_adaptive_opts.restype = None
+        L.bhrt_default_reproject_opts.restype = None
+        L.bhrt_default_temporal_opts.restype = None
         _lib = L
     return _lib
 
@@ -154,6 +173,24 @@ def default_adaptive_opts(**kw) -> AdaptiveOpts:
     """bhrt_default_adaptive_opts (min_spp = 16, threshold and floor from DESIGN.md 10), fields overridden by kw."""
     o = AdaptiveOpts()
     lib().bhrt_default_adaptive_opts(C.byref(o))
+    for k, v in kw.items():
+        setattr(o, k, v)
+    return o
+
+
+def default_reproject_opts(**kw) -> ReprojectOpts:
+    """bhrt_default_reproject_opts (depth_tolerance, normal_threshold: DESIGN.md 19), fields overridden by kw."""
+    o = ReprojectOpts()
+    lib().bhrt_default_reproject_opts(C.byref(o))
+    for k, v in kw.items():
+        setattr(o, k, v)
+    return o
+
+
+def default_temporal_opts(**kw) -> TemporalOpts:
+    """bhrt_default_temporal_opts (clamp_k, max_length: DESIGN.md 19; gamma = 1), fields overridden by kw."""
+    o = TemporalOpts()
+    lib().bhrt_default_temporal_opts(C.byref(o))
     for k, v in kw.items():
         setattr(o, k, v)
     return o
@@ -539,6 +576,71 @@ class Scene:
         v = lambda x: C.c_void_p(x or None)  # noqa: E731
         _check(lib().bhrt_denoise_sampled_dev(self._h, C.byref(opts), C.c_float(sigma_coverage), v(d_radiance), v(d_variance), v(d_z), v(d_normal),
                                               v(d_albedo), v(d_coverage), v(d_out), v(d_rgb8), v(stream)))
+
+    # ---- temporal reprojection: carry a frame's light across a camera move ------------------------------------------------
+    def camera_frame(self):
+        """bhrt_scene_get_camera_frame: (4, 3) float32 = pos, top_left, dd_x, dd_y of the scene's camera now.  A host that reprojects reads it
+        before it moves the camera."""
+        f = np.zeros((4, 3), np.float32)
+        _check(lib().bhrt_scene_get_camera_frame(self._h, _ptr(f)))
+        return f
+
+    def _image(self, a, shape, what):
+        if a is None:
+            return None
+        a = np.ascontiguousarray(a, np.float32)
+        if a.size != int(np.prod(shape)):
+            raise ValueError(f"{what}: expected {shape} floats, got {a.shape}")
+        return a
+
+    def reproject(self, opts: ReprojectOpts, prev_frame, prev_z, prev_normal, prev_radiance=None, prev_length=None, prev_albedo=None, z=None, normal=None,
+                  albedo=None, want=("history", "length", "motion")):
+        """bhrt_reproject on host arrays of the scene's W x H frame: the previous view's camera_frame(), first hit (prev_z, prev_normal, optionally
+        prev_albedo), radiance and length image (None = 1 everywhere), and the current view's first hit, each None = computed on the device.
+        Returns (history (H, W, 3), length (H, W), motion (H, W, 2)) float32, None for those not named in `want`."""
+        W, H = self.width, self.height
+        pf = None if prev_frame is None else np.ascontiguousarray(prev_frame, np.float32).reshape(-1)
+        if pf is not None and pf.size != 12:
+            raise ValueError("prev_frame: expected 12 floats")
+        i = [self._image(a, sh, k) for a, sh, k in ((prev_z, (H, W), "prev_z"), (prev_normal, (H, W, 3), "prev_normal"), (prev_radiance, (H, W, 3), "prev_radiance"),
+                                                    (prev_length, (H, W), "prev_length"), (prev_albedo, (H, W, 3), "prev_albedo"), (z, (H, W), "z"),
+                                                    (normal, (H, W, 3), "normal"), (albedo, (H, W, 3), "albedo"))]
+        shapes = {"history": (H, W, 3), "length": (H, W), "motion": (H, W, 2)}
+        o = [np.zeros(shapes[k], np.float32) if k in want else None for k in ("history", "length", "motion")]
+        p = lambda x: _ptr(x) if x is not None else None  # noqa: E731
+        _check(lib().bhrt_reproject(self._h, C.byref(opts) if opts is not None else None, p(pf), *[p(a) for a in i], *[p(a) for a in o]))
+        return tuple(o)
+
+    def reproject_dev(self, opts: ReprojectOpts, prev_frame, d_prev_z: int, d_prev_normal: int, d_prev_radiance: int = 0, d_prev_length: int = 0,
+                      d_prev_albedo: int = 0, d_z: int = 0, d_normal: int = 0, d_albedo: int = 0, d_history: int = 0, d_length: int = 0, d_motion: int = 0,
+                      stream: int = 0):
+        """bhrt_reproject_dev on raw device pointers (0 = NULL; prev_frame stays a host array of 12 floats); with a stream the call does not
+        synchronise."""
+        pf = np.ascontiguousarray(prev_frame, np.float32).reshape(-1)
+        if pf.size != 12:
+            raise ValueError("prev_frame: expected 12 floats")
+        v = lambda x: C.c_void_p(x or None)  # noqa: E731
+        _check(lib().bhrt_reproject_dev(self._h, C.byref(opts), _ptr(pf), v(d_prev_z), v(d_prev_normal), v(d_prev_radiance), v(d_prev_length), v(d_prev_albedo),
+                                        v(d_z), v(d_normal), v(d_albedo), v(d_history), v(d_length), v(d_motion), v(stream)))
+
+    def temporal_accumulate(self, opts: TemporalOpts, radiance, cur_samples: float, history=None, length=None):
+        """bhrt_temporal_accumulate on host arrays: the current frame's radiance (H, W, 3) with cur_samples samples behind it, blended into
+        reproject()'s history and length (either None: no pixel has a history).  Returns (out (H, W, 3) float32, out_length (H, W) float32,
+        rgb8 (H, W, 3) uint8)."""
+        W, H = self.width, self.height
+        c, h, l = self._image(radiance, (H, W, 3), "radiance"), self._image(history, (H, W, 3), "history"), self._image(length, (H, W), "length")
+        out, ol, rgb = np.zeros((H, W, 3), np.float32), np.zeros((H, W), np.float32), np.zeros((H, W, 3), np.uint8)
+        p = lambda x: _ptr(x) if x is not None else None  # noqa: E731
+        _check(lib().bhrt_temporal_accumulate(self._h, C.byref(opts) if opts is not None else None, p(c), C.c_float(cur_samples), p(h), p(l), _ptr(out), _ptr(ol),
+                                              _ptr(rgb)))
+        return out, ol, rgb
+
+    def temporal_accumulate_dev(self, opts: TemporalOpts, d_radiance: int, cur_samples: float, d_history: int = 0, d_length: int = 0, d_out: int = 0,
+                                d_out_length: int = 0, d_rgb8: int = 0, stream: int = 0):
+        """bhrt_temporal_accumulate_dev on raw device pointers (0 = NULL); with a stream the call does not synchronise."""
+        v = lambda x: C.c_void_p(x or None)  # noqa: E731
+        _check(lib().bhrt_temporal_accumulate_dev(self._h, C.byref(opts), v(d_radiance), C.c_float(cur_samples), v(d_history), v(d_length), v(d_out), v(d_out_length),
+                                                  v(d_rgb8), v(stream)))
 
     # ---- images beside the colour image (RenderImage z-buffer, DenoiseImage inputs) ------------
     def first_hit(self):

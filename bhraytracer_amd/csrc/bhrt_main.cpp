@@ -15,6 +15,7 @@
 //               [--progressive N [--time-limit SECONDS] [--live-png path]]       (BeginRender .. StopRender, Main.cpp:178,243: the frame in steps)
 //               [--camera-pos X,Y,Z] [--camera-target X,Y,Z] [--camera-up X,Y,Z] [--fov F]   (the <camera> tags, xmlload.cpp:109-127, replaced)
 //               [--shutter-pos X,Y,Z] [--shutter-target X,Y,Z] [--shutter-up X,Y,Z]           (camera motion blur: the camera at the end of the exposure)
+//               [--temporal N --to-pos X,Y,Z [--to-target X,Y,Z] [--to-up X,Y,Z] [--frames-png PREFIX]]   (N frames along a camera move, each carried into the next)
 //   bhrt info   <scene.xml>
 //
 // --gpus N: ONE process drives N GPUs of the node (the reference's one process drives 16 OpenMP threads, Main.cpp:422): the
@@ -66,6 +67,14 @@
 // is taken from pose 0.  Scene state, so it reaches every render the other options choose, --guide-spp's guides included.  A malformed value is a
 // usage error before the scene is loaded; poses the library refuses (a quarter turn or more apart, up along the view) fail with its message.
 // Off unless asked for: without the flags the frame is the scene file's pinhole or lens frame.
+// --temporal N (N >= 2): temporal reprojection.  N frames of --spp samples each, frame k with seed --seed + k and the camera
+//     X_k = X0 + (X1 - X0) * ((float)k / (float)(N - 1))      per component, in float32, for X = position, target, up
+// set through bhrt_scene_set_camera; pose 0 is the scene's camera (after the camera flags; a missing value as --camera-* reads it), pose 1 the
+// --to-* values, a missing one taken from pose 0.  Frame 0 is its render; frame k + 1 is its render blended (bhrt_temporal_accumulate) into
+// frame k's accumulated output and length reprojected into its view (bhrt_reproject with both views' first hits, albedo included), with the
+// library's default options.  -o gets the last frame, --frames-png PREFIX every frame as PREFIX000.png, PREFIX001.png, ...; --radiance the last
+// frame's accumulated radiance.  One device, whole frames, no further stage: with --progressive, --adaptive, --gpus, --denoise or --world > 1,
+// with N < 2, or --to-* / --frames-png without --temporal: a usage error.
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
@@ -123,6 +132,10 @@ struct Args {
     struct Vec { bool given = false; float v[3] = {0, 0, 0}; };
     Vec cam_pos, cam_target, cam_up, sh_pos, sh_target, sh_up;
     float fov = 0.f;                   // 0: not given
+    int temporal = 0;                  // --temporal N: frames of the camera move; 0 = one frame
+    bool temporal_given = false;
+    Vec to_pos, to_target, to_up;      // --to-pos / -target / -up: the pose of the last frame
+    std::string frames_png;            // --frames-png PREFIX
     bool Camera() const { return cam_pos.given || cam_target.given || cam_up.given || fov > 0.f; }
     bool Shutter() const { return sh_pos.given || sh_target.given || sh_up.given; }
 };
@@ -231,6 +244,51 @@ static int denoise_frame(bhrt_scene *scene, const Args &A, const bhrt_info &info
     }
     if (bhrt_guides(scene, &g, z.data(), nrm.data(), alb.data(), nullptr)) return fail("guide images");
     return bhrt_denoise(scene, &A.dn, rad, var, z.data(), nrm.data(), alb.data(), nullptr, rgb) ? fail("DenoiseImage") : 0;
+}
+
+// --temporal N: N frames along the camera move p0 -> p1 (position, target, up), each reprojected into the next view and accumulated there.
+// rgb / rad: the last frame (rad may be empty); st: the sums over the frames' renders.
+static int render_temporal(bhrt_scene *scene, const Args &A, const bhrt_info &info, const float p0[9], const float p1[9], std::vector<uint8_t> &rgb, std::vector<float> &rad,
+                           bhrt_stats &st)
+{
+    const size_t npx = (size_t)info.width * info.height;
+    bhrt_reproject_opts ro;
+    bhrt_temporal_opts to;
+    bhrt_default_reproject_opts(&ro);
+    bhrt_default_temporal_opts(&to);
+    to.gamma = A.o.gamma;
+    // the previous view (frame, first hit, accumulated light and its length) and the current one
+    std::vector<float> pz(npx), pn(npx * 3), pa(npx * 3), acc(npx * 3), len(npx), z(npx), n(npx * 3), a(npx * 3), cur(npx * 3), hist(npx * 3), hl(npx), out(npx * 3), ol(npx);
+    float prev_frame[12];
+    for (int k = 0; k < A.temporal; k++) {
+        const float s = (float)k / (float)(A.temporal - 1);
+        float p[9];
+        for (int c = 0; c < 9; c++) p[c] = p0[c] + (p1[c] - p0[c]) * s;
+        if (bhrt_scene_set_camera(scene, p, p + 3, p + 6, 0.f)) return fail("set camera");
+        bhrt_opts o = A.o;
+        o.seed = A.o.seed + (uint32_t)k;
+        bhrt_stats one;
+        if (bhrt_first_hit(scene, z.data(), n.data(), a.data())) return fail("first hit");
+        if (bhrt_render(scene, &o, nullptr, cur.data(), &one)) return fail("BeginRender");
+        st.closest_rays += one.closest_rays; st.shadow_rays += one.shadow_rays; st.shade_calls += one.shade_calls; st.camera_samples += one.camera_samples;
+        st.passes += one.passes; st.wave_iterations += one.wave_iterations; st.seconds_total += one.seconds_total;
+        if (k > 0 && bhrt_reproject(scene, &ro, prev_frame, pz.data(), pn.data(), acc.data(), len.data(), pa.data(), z.data(), n.data(), a.data(), hist.data(), hl.data(), nullptr))
+            return fail("reproject");
+        if (bhrt_temporal_accumulate(scene, &to, cur.data(), (float)o.spp, k > 0 ? hist.data() : nullptr, k > 0 ? hl.data() : nullptr, out.data(), ol.data(), rgb.data()))
+            return fail("temporal accumulate");
+        size_t carried = 0;
+        for (size_t q = 0; k > 0 && q < npx; q++) carried += hl[q] > 0.f;
+        printf("frame %d: camera %g,%g,%g, history on %.1f%% of the pixels\n", k, p[0], p[1], p[2], 100.0 * (double)carried / (double)npx);
+        if (!A.frames_png.empty()) {
+            char name[16];
+            snprintf(name, sizeof name, "%03d.png", k);
+            if (bhrt_save_png((A.frames_png + name).c_str(), rgb.data(), info.width, info.height)) return fail("SaveImage (frame)");
+        }
+        if (bhrt_scene_get_camera_frame(scene, prev_frame)) return fail("camera frame");
+        pz.swap(z); pn.swap(n); pa.swap(a); acc.swap(out); len.swap(ol);
+    }
+    if (!rad.empty()) rad = acc;
+    return 0;
 }
 
 // Everything render_multi owns besides the caller's scene: released on every way out (the early returns included).
@@ -520,6 +578,11 @@ int main(int argc, char **argv)
         else if (s == "--shutter-pos") A.sh_pos = vector_value("--shutter-pos", next());
         else if (s == "--shutter-target") A.sh_target = vector_value("--shutter-target", next());
         else if (s == "--shutter-up") A.sh_up = vector_value("--shutter-up", next());
+        else if (s == "--temporal") { A.temporal = atoi(next()); A.temporal_given = true; }
+        else if (s == "--to-pos") A.to_pos = vector_value("--to-pos", next());
+        else if (s == "--to-target") A.to_target = vector_value("--to-target", next());
+        else if (s == "--to-up") A.to_up = vector_value("--to-up", next());
+        else if (s == "--frames-png") A.frames_png = next();
         else if (s == "--fov") {
             A.fov = number_value("--fov", next(), true);
             if (!(A.fov < 180.f)) { fprintf(stderr, "bhrt: usage: --fov needs a number of degrees below 180\n"); return 2; }
@@ -555,6 +618,14 @@ int main(int argc, char **argv)
         fprintf(stderr, "bhrt: usage: --progressive runs on one device; --gpus %d would need a tile exchange per step\n", A.gpus);
         return 2;
     }
+    if (!A.temporal_given && (A.to_pos.given || A.to_target.given || A.to_up.given || !A.frames_png.empty())) {
+        fprintf(stderr, "bhrt: usage: --to-pos, --to-target, --to-up and --frames-png need --temporal N\n");
+        return 2;
+    }
+    if (A.temporal_given && (A.temporal < 2 || A.progressive_given || A.adaptive || A.gpus > 0 || A.denoise || o.world_size > 1)) { // before any device is touched
+        fprintf(stderr, "bhrt: usage: --temporal needs N >= 2 frames and renders whole frames on one device (no --progressive, --adaptive, --gpus, --denoise, --world)\n");
+        return 2;
+    }
     if (A.progressive_given && A.gpus == 1) A.gpus = 0; // one device: the session needs no communicator
     A.dn.gamma = o.gamma;
     bhrt_scene *scene = nullptr;
@@ -581,7 +652,8 @@ int main(int argc, char **argv)
         printf("lens: focal distance %g, aperture radius %g%s\n", fh->camera.focaldist, fh->camera.dof, fh->camera.dof > 0.f ? "" : " (pinhole)");
         if (A.denoise && A.guide_spp <= 0) printf("note: --denoise guides (depth, normal, albedo) are those of the pinhole ray; --guide-spp N forms them from the lens rays\n");
     }
-    if (A.Camera() || A.Shutter()) { // before the upload and before --gpus N clones the scene; after --focaldist, which places the default target
+    float pose0[9] = {0}, pose1[9] = {0}; // --temporal: the first and the last frame's position, target, up
+    if (A.Camera() || A.Shutter() || A.temporal_given) { // before the upload and before --gpus N clones the scene; after --focaldist, which places the default target
         const bhrt_flat_header *fh = nullptr;
         uint64_t fb = 0;
         if (bhrt_scene_flat(scene, (const void **)&fh, &fb)) return fail("scene blob");
@@ -608,6 +680,10 @@ int main(int argc, char **argv)
             if (!A.sh_up.given) for (int k = 0; k < 3; k++) u1[k] = u[k];
             if (bhrt_scene_set_shutter(scene, 1, p1, t1, u1)) return fail("set shutter");
             printf("shutter: to position %g,%g,%g target %g,%g,%g up %g,%g,%g during the exposure\n", p1[0], p1[1], p1[2], t1[0], t1[1], t1[2], u1[0], u1[1], u1[2]);
+        }
+        for (int k = 0; k < 3; k++) {
+            pose0[k] = p[k]; pose0[3 + k] = t[k]; pose0[6 + k] = u[k];
+            pose1[k] = A.to_pos.given ? A.to_pos.v[k] : p[k]; pose1[3 + k] = A.to_target.given ? A.to_target.v[k] : t[k]; pose1[6 + k] = A.to_up.given ? A.to_up.v[k] : u[k];
         }
     }
     if (A.denoise && A.guide_spp > 0) printf("denoise guides: %d sample(s) per pixel%s\n", A.guide_spp, o.lens ? ", through the lens" : "");
@@ -650,7 +726,9 @@ int main(int argc, char **argv)
             o.photon_map = 1;
         }
         if (o.photon_map && !A.photon_out.empty() && bhrt_photon_export(scene, A.photon_out.c_str())) return fail("photon export");
-        if (A.progressive_given) {
+        if (A.temporal_given) {
+            if (render_temporal(scene, A, info, pose0, pose1, rgb, rad, st)) return 1;
+        } else if (A.progressive_given) {
             std::vector<float> var(A.denoise ? rad.size() : 0, 0.f);
             if (render_progressive(scene, A, info, rgb, rad, var, cnt, st)) return 1;
             if (A.denoise && denoise_frame(scene, A, info, rad.data(), var.data(), rgb.data())) return 1;

@@ -61,6 +61,23 @@ void bhrt_default_adaptive_opts(bhrt_adaptive_opts *a)
     a->floor = 0.1f; // threshold, floor: the quality grid of tools/adaptive_quality.py over c3_room, c2_glass, c3_mesh
 }
 
+void bhrt_default_reproject_opts(bhrt_reproject_opts *o)
+{
+    if (!o) return;
+    memset(o, 0, sizeof *o);
+    o->depth_tolerance = BHRT_REPROJECT_DEPTH_TOLERANCE;
+    o->normal_threshold = BHRT_REPROJECT_NORMAL_THRESHOLD; // both: the MSE grid of tools/temporal_defaults.py over c3_mesh_small and c4_textured
+}
+
+void bhrt_default_temporal_opts(bhrt_temporal_opts *o)
+{
+    if (!o) return;
+    memset(o, 0, sizeof *o);
+    o->clamp_k = BHRT_TEMPORAL_CLAMP_K;
+    o->max_length = BHRT_TEMPORAL_MAX_LENGTH; // both: the same grid
+    o->gamma = 1; // as bhrt_opts.gamma (Main.cpp:128)
+}
+
 int bhrt_scene_load_xml(const char *path, bhrt_scene **out) { return bhrt_scene_load_xml_ex(path, -1, out); }
 
 int bhrt_scene_load_xml_ex(const char *path, int bvh_device, bhrt_scene **out)

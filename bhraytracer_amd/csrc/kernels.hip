@@ -38,6 +38,7 @@
 
 #include "bhrt.h"
 #include "denoise.h"
+#include "temporal.h"
 #include "device_color24.h"
 #include "device_photon.h"
 #include "photon_host.h"
@@ -4168,6 +4169,14 @@ try {
     return BHRT_OK;
 } catch (...) { return bhrt::AbiException(); }
 
+int bhrt_scene_get_camera_frame(const bhrt_scene *scene, float frame[12])
+try {
+    if (!scene || !frame) { SetError("bhrt_scene_get_camera_frame: null argument"); return BHRT_ERR_ARG; }
+    const bhrt_camera &c = scene->flat.hdr()->camera;
+    for (int k = 0; k < 3; k++) { frame[k] = c.pos[k]; frame[3 + k] = c.top_left[k]; frame[6 + k] = c.dd_x[k]; frame[9 + k] = c.dd_y[k]; }
+    return BHRT_OK;
+} catch (...) { return bhrt::AbiException(); }
+
 // ---- the emission term: scene state beside the blob.  In this translation unit because the setters refresh an uploaded scene.
 int bhrt_scene_set_emissive(bhrt_scene *scene, int on)
 try {
@@ -4507,6 +4516,138 @@ try {
     BHRT_TRY(bhrt_denoise_sampled_dev(scene, opts, sigma_coverage, d_c, variance ? d_v : nullptr, z ? d_z : nullptr, normal ? d_n : nullptr, albedo ? d_a : nullptr,
                                       coverage ? d_cov : nullptr, out ? d_o : nullptr, rgb8 ? d_rgb : nullptr, nullptr));
     if (out) HIP_CHECK(hipMemcpy(out, d_o, n * 12, hipMemcpyDeviceToHost));
+    if (rgb8) HIP_CHECK(hipMemcpy(rgb8, d_rgb, n * 3, hipMemcpyDeviceToHost));
+    return BHRT_OK;
+} catch (...) { return bhrt::AbiException(); }
+
+// ---- temporal reprojection (temporal.hip) ---------------------------------------------------
+// The arguments of both bhrt_reproject entry points, checked alike and before any device is touched
+static int ReprojectArgs(const bhrt_scene *scene, const bhrt_reproject_opts *opts, const float *prev_frame, const float *prev_z, const float *prev_normal,
+                         const float *prev_radiance, const float *prev_albedo, const float *history)
+{
+    if (!scene) { SetError("reproject: null scene"); return BHRT_ERR_ARG; }
+    const char *bad = ReprojectArgsError(opts, prev_frame, prev_radiance, prev_albedo);
+    if (!*bad && (!prev_z || !prev_normal)) bad = "reproject: the previous view's z and normal images are required";
+    if (!*bad && history && !prev_radiance) bad = "reproject: a history image needs the previous radiance";
+    if (*bad) { SetError(bad); return BHRT_ERR_ARG; }
+    return BHRT_OK;
+}
+
+int bhrt_reproject_dev(bhrt_scene *scene, const bhrt_reproject_opts *opts, const float prev_frame[12], const float *d_prev_z, const float *d_prev_normal,
+                       const float *d_prev_radiance, const float *d_prev_length, const float *d_prev_albedo, const float *d_z, const float *d_normal,
+                       const float *d_albedo, float *d_history, float *d_length, float *d_motion, void *stream)
+try {
+    BHRT_TRY(ReprojectArgs(scene, opts, prev_frame, d_prev_z, d_prev_normal, d_prev_radiance, d_prev_albedo, d_history));
+    int rc = EnsureUploaded(scene);
+    if (rc) return rc;
+    if (!d_history && !d_length && !d_motion) return BHRT_OK;
+    DeviceState *D = scene->dev;
+    const bhrt_flat_header *H = scene->flat.hdr();
+    const int W = H->camera.width, Hh = H->camera.height;
+    const size_t n = (size_t)W * Hh;
+    if (n == 0 || n > 0x7fffffffull) { SetError("reproject: frame size out of range"); return BHRT_ERR_ARG; }
+    hipStream_t st = stream ? (hipStream_t)stream : D->stream;
+    ReprojectJob J;
+    J.W = W; J.H = Hh; J.o = *opts;
+    bhrt_scene_get_camera_frame(scene, J.cur);
+    memcpy(J.prev, prev_frame, sizeof J.prev);
+    J.prev_z = d_prev_z; J.prev_normal = d_prev_normal; J.prev_radiance = d_prev_radiance; J.prev_length = d_prev_length; J.prev_albedo = d_prev_albedo;
+    J.z = d_z; J.normal = d_normal; J.albedo = d_albedo; J.history = d_history; J.length = d_length; J.motion = d_motion;
+    const bool want_albedo = d_prev_albedo && d_history; // without albedo' no albedo is read or computed
+    if (!d_z || !d_normal || (want_albedo && !d_albedo)) { // the first hit of bhrt_first_hit_dev, into the scene's scratch, for the guides not given
+        BHRT_TRY(D->d_dn.Reserve(n * 7 * sizeof(float)));
+        float *g = (float *)D->d_dn.p;
+        float *gz = d_z ? nullptr : g, *gn = d_normal ? nullptr : g + n, *ga = !want_albedo || d_albedo ? nullptr : g + 4 * n;
+        hipLaunchKernelGGL(D->fm.tab ? k_first_hit<true> : k_first_hit<false>, dim3(((uint32_t)n + kBlock - 1) / kBlock), dim3(kBlock), 0, st, D->S, D->fm, W, Hh, gz, gn, ga);
+        HIP_CHECK(hipGetLastError());
+        if (gz) J.z = gz;
+        if (gn) J.normal = gn;
+        if (ga) J.albedo = ga;
+    }
+    HIP_CHECK(ReprojectLaunch(J, st));
+    if (!stream) HIP_CHECK(hipStreamSynchronize(st));
+    return BHRT_OK;
+} catch (...) { return bhrt::AbiException(); }
+
+int bhrt_reproject(bhrt_scene *scene, const bhrt_reproject_opts *opts, const float prev_frame[12], const float *prev_z, const float *prev_normal,
+                   const float *prev_radiance, const float *prev_length, const float *prev_albedo, const float *z, const float *normal, const float *albedo,
+                   float *history, float *length, float *motion)
+try {
+    BHRT_TRY(ReprojectArgs(scene, opts, prev_frame, prev_z, prev_normal, prev_radiance, prev_albedo, history));
+    int rc = EnsureUploaded(scene);
+    if (rc) return rc;
+    if (!history && !length && !motion) return BHRT_OK;
+    DeviceState *D = scene->dev;
+    const bhrt_flat_header *H = scene->flat.hdr();
+    const size_t n = (size_t)H->camera.width * H->camera.height;
+    // device copies, back to back, in floats per pixel: z' 1, n' 3, c' 3, l' 1, a' 3, z 1, n 3, a 3, history 3, length 1, motion 2
+    const float *const in[8] = {prev_z, prev_normal, prev_radiance, prev_length, prev_albedo, z, normal, albedo};
+    float *const out[3] = {history, length, motion};
+    const size_t width[11] = {1, 3, 3, 1, 3, 1, 3, 3, 3, 1, 2};
+    DevBuf<float> d;
+    BHRT_TRY(d.Reserve(n * 24));
+    float *at[11];
+    for (size_t k = 0, off = 0; k < 11; off += width[k] * n, k++) at[k] = d.p + off;
+    for (int k = 0; k < 8; k++)
+        if (in[k]) HIP_CHECK(hipMemcpyAsync(at[k], in[k], width[k] * n * sizeof(float), hipMemcpyHostToDevice, D->stream));
+    auto given = [&](int k) -> float * { return (k < 8 ? (const void *)in[k] : (const void *)out[k - 8]) ? at[k] : nullptr; };
+    BHRT_TRY(bhrt_reproject_dev(scene, opts, prev_frame, given(0), given(1), given(2), given(3), given(4), given(5), given(6), given(7), given(8), given(9), given(10), nullptr));
+    for (int k = 0; k < 3; k++)
+        if (out[k]) HIP_CHECK(hipMemcpy(out[k], at[8 + k], width[8 + k] * n * sizeof(float), hipMemcpyDeviceToHost));
+    return BHRT_OK;
+} catch (...) { return bhrt::AbiException(); }
+
+static int TemporalArgs(const bhrt_scene *scene, const bhrt_temporal_opts *opts, const float *radiance, float cur_samples)
+{
+    if (!scene || !radiance) { SetError("temporal accumulate: null scene or radiance"); return BHRT_ERR_ARG; }
+    const char *bad = TemporalArgsError(opts, cur_samples);
+    if (*bad) { SetError(bad); return BHRT_ERR_ARG; }
+    return BHRT_OK;
+}
+
+int bhrt_temporal_accumulate_dev(bhrt_scene *scene, const bhrt_temporal_opts *opts, const float *d_radiance, float cur_samples, const float *d_history,
+                                 const float *d_length, float *d_out, float *d_out_length, uint8_t *d_rgb8, void *stream)
+try {
+    BHRT_TRY(TemporalArgs(scene, opts, d_radiance, cur_samples));
+    int rc = EnsureUploaded(scene);
+    if (rc) return rc;
+    if (!d_out && !d_out_length && !d_rgb8) return BHRT_OK;
+    DeviceState *D = scene->dev;
+    const bhrt_flat_header *H = scene->flat.hdr();
+    const size_t n = (size_t)H->camera.width * H->camera.height;
+    if (n == 0 || n > 0x7fffffffull) { SetError("temporal accumulate: frame size out of range"); return BHRT_ERR_ARG; }
+    hipStream_t st = stream ? (hipStream_t)stream : D->stream;
+    TemporalJob J;
+    J.W = H->camera.width; J.H = H->camera.height; J.o = *opts; J.cur_samples = cur_samples;
+    J.radiance = d_radiance; J.history = d_history; J.length = d_length; J.out = d_out; J.out_length = d_out_length; J.rgb8 = d_rgb8;
+    HIP_CHECK(TemporalLaunch(J, st));
+    if (!stream) HIP_CHECK(hipStreamSynchronize(st));
+    return BHRT_OK;
+} catch (...) { return bhrt::AbiException(); }
+
+int bhrt_temporal_accumulate(bhrt_scene *scene, const bhrt_temporal_opts *opts, const float *radiance, float cur_samples, const float *history, const float *length,
+                             float *out, float *out_length, uint8_t *rgb8)
+try {
+    BHRT_TRY(TemporalArgs(scene, opts, radiance, cur_samples));
+    int rc = EnsureUploaded(scene);
+    if (rc) return rc;
+    if (!out && !out_length && !rgb8) return BHRT_OK;
+    DeviceState *D = scene->dev;
+    const bhrt_flat_header *H = scene->flat.hdr();
+    const size_t n = (size_t)H->camera.width * H->camera.height;
+    // device copies, back to back: radiance, history, out (3n floats each), length, out_length (n each), rgb8 (3n bytes)
+    DevBuf<uint8_t> d;
+    BHRT_TRY(d.Reserve(n * 47));
+    float *f = (float *)d.p;
+    float *d_c = f, *d_h = f + 3 * n, *d_o = f + 6 * n, *d_l = f + 9 * n, *d_ol = f + 10 * n;
+    uint8_t *d_rgb = d.p + n * 44;
+    HIP_CHECK(hipMemcpyAsync(d_c, radiance, n * 12, hipMemcpyHostToDevice, D->stream));
+    if (history) HIP_CHECK(hipMemcpyAsync(d_h, history, n * 12, hipMemcpyHostToDevice, D->stream));
+    if (length) HIP_CHECK(hipMemcpyAsync(d_l, length, n * 4, hipMemcpyHostToDevice, D->stream));
+    BHRT_TRY(bhrt_temporal_accumulate_dev(scene, opts, d_c, cur_samples, history ? d_h : nullptr, length ? d_l : nullptr, out ? d_o : nullptr, out_length ? d_ol : nullptr,
+                                          rgb8 ? d_rgb : nullptr, nullptr));
+    if (out) HIP_CHECK(hipMemcpy(out, d_o, n * 12, hipMemcpyDeviceToHost));
+    if (out_length) HIP_CHECK(hipMemcpy(out_length, d_ol, n * 4, hipMemcpyDeviceToHost));
     if (rgb8) HIP_CHECK(hipMemcpy(rgb8, d_rgb, n * 3, hipMemcpyDeviceToHost));
     return BHRT_OK;
 } catch (...) { return bhrt::AbiException(); }

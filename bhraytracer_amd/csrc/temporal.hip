@@ -1,0 +1,278 @@
+// temporal.hip — temporal reprojection: what interactive path tracers do when the camera moves.  For every pixel of the new view,
+// find where its surface point was in the previous view, fetch the light gathered there if it is still the same surface (k_reproject), and
+// blend the new samples into it (k_temporal_accumulate).  Two image-space stages beside the render path, guided by the first hit of
+// k_first_hit (z, normal, albedo) of both views.
+//
+// THE DEFINITION.  All arithmetic is IEEE float32, evaluated left to right as written, IEEE division, no contraction, the correctly rounded
+// square root dm::sqrt_f (tests/test_reproject.py restates both stages in numpy with the same order).
+//   dot(a, b)  = (a.x b.x + a.y b.y) + a.z b.z
+//   a ^ b      = (a.y b.z - a.z b.y, a.z b.x - a.x b.z, a.x b.y - a.y b.x)
+//   unit(n)    = rule B of denoise.hip: l = sqrt((n.x n.x + n.y n.y) + n.z n.z); n / l per component where l > 0, else 0
+//   divisor(a) = dn_divisor of denoise.hip: max(a', 1e-3) per channel, a' = a if max(a.r, a.g, a.b) >= 1e-3, else (1, 1, 1)
+//
+// 1. REPROJECTION, pixel (i, j) of the W x H frame of the current camera C = (pos, top_left, dd_x, dd_y); primed symbols are the previous view's:
+//   its frame (pos', top_left', dd_x', dd_y'), first hit z', n', albedo a' (optional), radiance c' and length l' (the samples behind each pixel;
+//   without a length image 1 everywhere).  z, n, a: the current view's first hit.
+//   miss (z >= BHRT_BIGFLOAT)
+//            u = i, v = j: one tap of weight 1, valid when it is a miss too (z' >= BHRT_BIGFLOAT) and l' > 0.  (The reference's background is
+//            sampled in screen space, Main.cpp:159-168: a background pixel's history is its own pixel.)
+//   hit      d = ((top_left + (float)i dd_x) - (float)j dd_y) - pos            (k_first_hit's expression)
+//            x = pos + d * z                                                   (z is a parameter along the un-normalised d: no square root)
+//            q = x - pos',  A = top_left' - pos',  m = dd_x' ^ dd_y'
+//            t = dot(q, m) / dot(A, m)                                         (the ray parameter the previous view must have stored for x)
+//            the pixel is invalid unless t > 0 and t is finite
+//            r = q / t - A
+//            u = dot(r, dd_x') / dot(dd_x', dd_x'),   v = -(dot(r, dd_y') / dot(dd_y', dd_y'))
+//   snap     where |u - rintf(u)| <= 2^-7: u = rintf(u); likewise v.  A design rule: a bilinear weight below 1/128 is dropped, so that a camera
+//            that did not move gives the previous frame's bits.
+//   bounds   the pixel is invalid unless u >= -1 && u < W && v >= -1 && v < H  (a NaN fails)
+//   taps     i0 = floorf(u), fx = u - i0, j0 = floorf(v), fy = v - j0;  taps (i0, j0), (i0 + 1, j0), (i0, j0 + 1), (i0 + 1, j0 + 1) in that order with
+//            weights (1 - fx)(1 - fy), fx (1 - fy), (1 - fx) fy, fx fy;  a tap of weight 0 is skipped
+//            a hit pixel's tap is valid when it lies inside the image, l' > 0, z' < BHRT_BIGFLOAT, |z' - t| <= depth_tolerance * t and
+//            dot(unit(n), unit(n')) >= normal_threshold
+//   result   sw = the sum of the valid weights, in tap order, from 0; the pixel is invalid unless sw > 0
+//            history = (sum w e') / sw * g per channel:  e' = c' / divisor(a'), g = divisor(a) when albedo images take part, else e' = c' and
+//            there is no multiplication;  length = (sum w l') / sw;  motion = (u - i, v - j)
+//   invalid  history = 0, length = 0, motion = 0
+//
+// 2. ACCUMULATION, per pixel: c = the current radiance, n_c = cur_samples (the samples behind it), h, l = history and length of stage 1.
+//   no history (not l > 0):  out = c, out_length = min(n_c, max_length)
+//   else, with clamp_k >= 0:  the taps of the 3 x 3 block of the current radiance that lie inside the image, row-major, m of them; per channel
+//            mu = (sum c) / m,  sigma = sqrt((sum (c - mu)(c - mu)) / m),  h = min(max(h, mu - clamp_k sigma), mu + clamp_k sigma)
+//   then     l = min(l, max_length),  a = n_c / (l + n_c),  out = h + (c - h) * a,  out_length = min(l + n_c, max_length)
+//   rgb8 = store_color24(out) (device_color24.h: the gamma and Color24 of k_resolve)
+//
+// KERNELS.  k_reproject: one lane per pixel of the current camera, 256 in a row; the call's constants (A, m, the three dots) come from the host,
+// in the same float32 operations.  It reads 28 B per pixel of the current view (40 B with albedo) and, per tap, 32 B of the previous one (44 B
+// with albedo); it writes 24 B.  k_temporal_accumulate: the denoiser's 16 x 16 workgroups; the 3 x 3 block is read through the cache (a wave
+// is 16 x 4 pixels: its taps share cache lines; a tile staged through LDS measured no better).  Fixed tap order, no atomics:
+// the same inputs give the same bytes.
+#include <hip/hip_runtime.h>
+#include <math.h>
+
+#include "bhrt_flat.h"
+#include "device_color24.h"
+#include "temporal.h"
+
+namespace bhrt {
+
+constexpr int kTaTx = 16, kTaTy = 16;
+
+// divisor(a): dn_divisor of denoise.hip
+__device__ inline V3 tp_divisor(const float *albedo, size_t p)
+{
+    V3 a = v3(albedo[3 * p], albedo[3 * p + 1], albedo[3 * p + 2]);
+    const float m = fmaxf(fmaxf(a.x, a.y), a.z);
+    if (!(m >= 1e-3f)) a = v3(1, 1, 1);
+    return v3(fmaxf(a.x, 1e-3f), fmaxf(a.y, 1e-3f), fmaxf(a.z, 1e-3f));
+}
+
+// unit(n): rule B of denoise.hip
+__device__ inline V3 tp_unit(const float *normal, size_t p)
+{
+    const V3 n = v3(normal[3 * p], normal[3 * p + 1], normal[3 * p + 2]);
+    const float l = dm::sqrt_f((n.x * n.x + n.y * n.y) + n.z * n.z);
+    return l > 0.f ? v3(n.x / l, n.y / l, n.z / l) : v3(0, 0, 0);
+}
+
+// the constants of one call, in the definition's operations (ReprojectConsts, on the host)
+struct ReprojectFrame {
+    V3 pos, top_left, dd_x, dd_y; // C
+    V3 ppos, pdd_x, pdd_y;        // pos', dd_x', dd_y'
+    V3 A, m;                      // top_left' - pos', dd_x' ^ dd_y'
+    float Am, xx, yy;             // dot(A, m), dot(dd_x', dd_x'), dot(dd_y', dd_y')
+};
+
+template <bool kAlbedo>
+__global__ void __launch_bounds__(256) k_reproject(int W, int H, ReprojectFrame F, float depth_tolerance, float normal_threshold, const float *__restrict__ pz,
+                                                   const float *__restrict__ pn, const float *__restrict__ pc, const float *__restrict__ pl,
+                                                   const float *__restrict__ pa, const float *__restrict__ z, const float *__restrict__ n,
+                                                   const float *__restrict__ a, float *__restrict__ history, float *__restrict__ length,
+                                                   float *__restrict__ motion)
+{
+    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= (uint32_t)(W * H)) return;
+    const int j = (int)(p / (uint32_t)W), i = (int)(p - (uint32_t)j * (uint32_t)W);
+    const float fi = (float)i, fj = (float)j, zp = z[p];
+    const bool miss = zp >= BHRT_BIGFLOAT;
+    float u = fi, v = fj, t = 0.f;
+    bool ok = true;
+    V3 nu = v3(0, 0, 0);
+    if (!miss) {
+        const V3 d = ((F.top_left + fi * F.dd_x) - fj * F.dd_y) - F.pos;
+        const V3 x = F.pos + d * zp;
+        const V3 q = x - F.ppos;
+        t = dot(q, F.m) / F.Am;
+        ok = t > 0.f && t <= 3.402823466e38f;
+        const V3 r = q / t - F.A;
+        u = dot(r, F.pdd_x) / F.xx;
+        v = -(dot(r, F.pdd_y) / F.yy);
+        const float ru = rintf(u), rv = rintf(v);
+        if (fabsf(u - ru) <= 0.0078125f) u = ru;
+        if (fabsf(v - rv) <= 0.0078125f) v = rv;
+        nu = tp_unit(n, p);
+    }
+    ok = ok && u >= -1.f && u < (float)W && v >= -1.f && v < (float)H;
+    float sw = 0.f, sr = 0.f, sg = 0.f, sb = 0.f, sl = 0.f;
+    if (ok) {
+        const float f0 = floorf(u), g0 = floorf(v);
+        const float fx = u - f0, fy = v - g0, ax = 1.f - fx, ay = 1.f - fy;
+        const int i0 = (int)f0, j0 = (int)g0;
+        const float w4[4] = {ax * ay, fx * ay, ax * fy, fx * fy};
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const float w = w4[k];
+            const int qi = i0 + (k & 1), qj = j0 + (k >> 1);
+            if (w == 0.f || qi < 0 || qi >= W || qj < 0 || qj >= H) continue;
+            const size_t q = (size_t)qj * W + qi;
+            const float lq = pl ? pl[q] : 1.f, zq = pz[q];
+            if (!(lq > 0.f)) continue;
+            if (miss) {
+                if (!(zq >= BHRT_BIGFLOAT)) continue;
+            } else {
+                if (!(zq < BHRT_BIGFLOAT) || !(fabsf(zq - t) <= depth_tolerance * t)) continue;
+                if (!(dot(nu, tp_unit(pn, q)) >= normal_threshold)) continue;
+            }
+            sw = sw + w;
+            sl = sl + w * lq;
+            if (history) {
+                V3 e = v3(pc[3 * q], pc[3 * q + 1], pc[3 * q + 2]);
+                if (kAlbedo) {
+                    const V3 dq = tp_divisor(pa, q);
+                    e = v3(e.x / dq.x, e.y / dq.y, e.z / dq.z);
+                }
+                sr = sr + w * e.x;
+                sg = sg + w * e.y;
+                sb = sb + w * e.z;
+            }
+        }
+        ok = sw > 0.f;
+    }
+    V3 h = v3(0, 0, 0);
+    float l = 0.f, mu = 0.f, mv = 0.f;
+    if (ok) {
+        h = v3(sr / sw, sg / sw, sb / sw);
+        if (kAlbedo && history) {
+            const V3 g = tp_divisor(a, p);
+            h = v3(h.x * g.x, h.y * g.y, h.z * g.z);
+        }
+        l = sl / sw;
+        mu = u - fi;
+        mv = v - fj;
+    }
+    if (history) { history[3 * (size_t)p] = h.x; history[3 * (size_t)p + 1] = h.y; history[3 * (size_t)p + 2] = h.z; }
+    if (length) length[p] = l;
+    if (motion) { motion[2 * (size_t)p] = mu; motion[2 * (size_t)p + 1] = mv; }
+}
+
+__global__ void __launch_bounds__(kTaTx *kTaTy) k_temporal_accumulate(int W, int H, float clamp_k, float max_length, float cur_samples, const float *__restrict__ c,
+                                                                      const float *__restrict__ history, const float *__restrict__ length, float *__restrict__ out,
+                                                                      float *__restrict__ out_length, uint8_t *__restrict__ rgb8, int gamma)
+{
+    const int x = (int)(blockIdx.x * kTaTx + threadIdx.x), y = (int)(blockIdx.y * kTaTy + threadIdx.y);
+    if (x >= W || y >= H) return;
+    const size_t p = (size_t)y * W + x;
+    const V3 cp = v3(c[3 * p], c[3 * p + 1], c[3 * p + 2]);
+    const float lp = history && length ? length[p] : 0.f;
+    V3 o = cp;
+    float ol = fminf(cur_samples, max_length);
+    if (lp > 0.f) {
+        V3 h = v3(history[3 * p], history[3 * p + 1], history[3 * p + 2]);
+        if (clamp_k >= 0.f) {
+            V3 q[9]; // statically indexed: registers
+            bool in[9];
+            int m = 0;
+            V3 s = v3(0, 0, 0);
+#pragma unroll
+            for (int k = 0; k < 9; k++) {
+                const int dy = k / 3 - 1, dx = k % 3 - 1, qy = y + dy, qx = x + dx;
+                in[k] = qy >= 0 && qy < H && qx >= 0 && qx < W;
+                q[k] = v3(0, 0, 0);
+                if (!in[k]) continue;
+                const size_t g = ((size_t)qy * W + qx) * 3;
+                q[k] = v3(c[g], c[g + 1], c[g + 2]);
+                s = s + q[k];
+                m++;
+            }
+            const float fm = (float)m;
+            const V3 mu = s / fm;
+            V3 s2 = v3(0, 0, 0);
+#pragma unroll
+            for (int k = 0; k < 9; k++) {
+                if (!in[k]) continue;
+                const V3 e = q[k] - mu;
+                s2 = s2 + e * e;
+            }
+            const V3 sd = v3(dm::sqrt_f(s2.x / fm), dm::sqrt_f(s2.y / fm), dm::sqrt_f(s2.z / fm));
+            const V3 ks = clamp_k * sd;
+            h = v3(fminf(fmaxf(h.x, mu.x - ks.x), mu.x + ks.x), fminf(fmaxf(h.y, mu.y - ks.y), mu.y + ks.y), fminf(fmaxf(h.z, mu.z - ks.z), mu.z + ks.z));
+        }
+        const float l = fminf(lp, max_length);
+        const float a = cur_samples / (l + cur_samples);
+        o = h + (cp - h) * a;
+        ol = fminf(l + cur_samples, max_length);
+    }
+    if (out) { out[3 * p] = o.x; out[3 * p + 1] = o.y; out[3 * p + 2] = o.z; }
+    if (out_length) out_length[p] = ol;
+    if (rgb8) store_color24(rgb8, p, o, gamma);
+}
+
+static inline bool Finite(float x) { return x >= -3.402823466e38f && x <= 3.402823466e38f; }
+static inline V3 H3(const float *p) { return v3(p[0], p[1], p[2]); }
+
+static ReprojectFrame ReprojectConsts(const float *cur, const float *prev)
+{
+    ReprojectFrame F;
+    F.pos = H3(cur); F.top_left = H3(cur + 3); F.dd_x = H3(cur + 6); F.dd_y = H3(cur + 9);
+    F.ppos = H3(prev); F.pdd_x = H3(prev + 6); F.pdd_y = H3(prev + 9);
+    F.A = H3(prev + 3) - F.ppos;
+    F.m = cross(F.pdd_x, F.pdd_y);
+    F.Am = dot(F.A, F.m);
+    F.xx = dot(F.pdd_x, F.pdd_x);
+    F.yy = dot(F.pdd_y, F.pdd_y);
+    return F;
+}
+
+const char *ReprojectArgsError(const bhrt_reproject_opts *o, const float *prev_frame, const float *prev_radiance, const float *prev_albedo)
+{
+    if (!o) return "reproject: null options";
+    if (!prev_frame) return "reproject: null previous camera frame";
+    for (int k = 0; k < 12; k++)
+        if (!Finite(prev_frame[k])) return "reproject: the previous camera frame must be finite";
+    if (!(o->depth_tolerance >= 0.f) || !Finite(o->depth_tolerance)) return "reproject: depth_tolerance must be finite and >= 0";
+    if (o->normal_threshold != o->normal_threshold) return "reproject: normal_threshold is not a number";
+    const float zero[12] = {0};
+    if (ReprojectConsts(zero, prev_frame).Am == 0.f) return "reproject: the previous camera frame is degenerate (its image plane holds its eye)";
+    if (prev_albedo && !prev_radiance) return "reproject: a previous albedo without a previous radiance";
+    return "";
+}
+
+hipError_t ReprojectLaunch(const ReprojectJob &J, hipStream_t s)
+{
+    if (!J.history && !J.length && !J.motion) return hipSuccess;
+    const uint32_t n_px = (uint32_t)((size_t)J.W * J.H);
+    const ReprojectFrame F = ReprojectConsts(J.cur, J.prev);
+    const bool alb = J.prev_albedo && J.history;
+    hipLaunchKernelGGL(alb ? k_reproject<true> : k_reproject<false>, dim3((n_px + 255) / 256), dim3(256), 0, s, J.W, J.H, F, J.o.depth_tolerance, J.o.normal_threshold,
+                       J.prev_z, J.prev_normal, J.prev_radiance, J.prev_length, J.prev_albedo, J.z, J.normal, J.albedo, J.history, J.length, J.motion);
+    return hipGetLastError();
+}
+
+const char *TemporalArgsError(const bhrt_temporal_opts *o, float cur_samples)
+{
+    if (!o) return "temporal accumulate: null options";
+    if (!(cur_samples > 0.f)) return "temporal accumulate: cur_samples must be > 0";
+    if (!(o->max_length > 0.f)) return "temporal accumulate: max_length must be > 0";
+    return "";
+}
+
+hipError_t TemporalLaunch(const TemporalJob &J, hipStream_t s)
+{
+    if (!J.out && !J.out_length && !J.rgb8) return hipSuccess;
+    const dim3 grid((unsigned)((J.W + kTaTx - 1) / kTaTx), (unsigned)((J.H + kTaTy - 1) / kTaTy)), block(kTaTx, kTaTy);
+    hipLaunchKernelGGL(k_temporal_accumulate, grid, block, 0, s, J.W, J.H, J.o.clamp_k, J.o.max_length, J.cur_samples, J.radiance, J.history, J.length,
+                       J.out, J.out_length, J.rgb8, J.o.gamma ? 1 : 0);
+    return hipGetLastError();
+}
+
+} // namespace bhrt

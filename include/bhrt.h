@@ -182,6 +182,10 @@ int bhrt_scene_set_camera(bhrt_scene *scene, const float pos[3], const float tar
  * get_shutter: the switch, pose 1 as given (pos1, target1, up1) and its derived frame (pos1, top_left1, dd_x1, dd_y1); any pointer may be NULL. */
 int bhrt_scene_set_shutter(bhrt_scene *scene, int on, const float pos1[3], const float target1[3], const float up1[3]);
 int bhrt_scene_get_shutter(const bhrt_scene *scene, int *on, float pose1[9], float frame1[12]);
+/* The camera frame of the scene's camera: pos, top_left, dd_x, dd_y, in the layout of bhrt_scene_get_shutter's frame1; the blob's bhrt_camera,
+ * before and after bhrt_scene_set_camera / bhrt_scene_set_lens.  Needs no device.  A host that reprojects (bhrt_reproject*) calls it before it
+ * moves the camera. */
+int bhrt_scene_get_camera_frame(const bhrt_scene *scene, float frame[12]);
 /* The emission term.  Every Blinn material carries the <emission> of its XML (xmlload.cpp:344-348: a colour, optionally a texture
  * map); the reference parses it and never shades it, and so does a scene here until it is switched on.  With the term on, every Shade() frame of
  * a Blinn material evaluates to  Shade(hit) + emission.Sample(uvw, duvw)  — one float addition per channel, behind everything Shade() does, on
@@ -401,6 +405,60 @@ int bhrt_denoise_sampled_dev(bhrt_scene *scene, const bhrt_denoise_opts *opts, f
                              const float *d_normal, const float *d_albedo, const float *d_coverage, float *d_out, uint8_t *d_rgb8, void *stream);
 int bhrt_denoise_sampled(bhrt_scene *scene, const bhrt_denoise_opts *opts, float sigma_coverage, const float *radiance, const float *variance, const float *z,
                          const float *normal, const float *albedo, const float *coverage, float *out, uint8_t *rgb8);
+
+/* ---- temporal reprojection: carry a frame's light across a camera move ---------------------------------------------
+ * When the camera moves between two frames, bhrt_reproject* finds for every pixel of the new view where its surface point was in the previous
+ * view and fetches the light gathered there if it is still the same surface; bhrt_temporal_accumulate* blends the new frame's samples into it.
+ * Both stages are stated exactly in csrc/temporal.hip (float32, a fixed order: the same inputs give the same bytes).  They run beside the
+ * render path and change no render.  Not covered: moving objects (the scene has none); lens and shutter (the guides stay the pinhole ray's, as
+ * for bhrt_denoise*); reflections and refractions are reprojected as if they were surface light; a progressive session's state is not seeded.
+ *
+ * bhrt_reproject*: the current view is the scene's camera, W x H.  prev_frame: the previous view's bhrt_scene_get_camera_frame, a HOST pointer
+ * in both variants.  prev_z (W*H), prev_normal (W*H*3): the previous view's first hit (bhrt_first_hit*), required.  prev_radiance (W*H*3):
+ * the light to carry (a render's radiance or an accumulated frame), required when history is asked for.  prev_length (W*H floats): the
+ * samples behind each previous pixel; NULL = 1 everywhere.  prev_albedo (W*H*3, optional): with it the history is carried as irradiance,
+ * prev_radiance / divisor(prev_albedo) * divisor(albedo); without it no albedo is read or computed.  z, normal, albedo: the current view's
+ * first hit; each may be NULL = computed here by the same kernel.  Outputs, each may be NULL: history (W*H*3), length (W*H; 0 = the pixel has
+ * no history), motion (W*H*2: where the pixel was, in pixels, minus where it is).
+ * BHRT_ERR_ARG before any device is touched: a NULL scene, options, prev_frame, prev_z or prev_normal; a prev_frame component that is not
+ * finite; a depth_tolerance that is negative or not finite; a NaN normal_threshold; a prev_frame whose image plane holds its eye
+ * (dot(top_left - pos, dd_x ^ dd_y) == 0); prev_albedo without prev_radiance; history without prev_radiance.
+ * _dev: device pointers; with a stream the call does not synchronise.  Scratch for guides computed here (28 B per pixel) is the scene's,
+ * shared with bhrt_denoise*: calls on one scene must not overlap, a call on another stream included. */
+#define BHRT_REPROJECT_DEPTH_TOLERANCE 0.01f
+#define BHRT_REPROJECT_NORMAL_THRESHOLD 0.99f
+#define BHRT_TEMPORAL_CLAMP_K 1.0f
+#define BHRT_TEMPORAL_MAX_LENGTH 16.0f
+typedef struct bhrt_reproject_opts {
+    float depth_tolerance;  /* a tap is the same surface when |z' - t| <= depth_tolerance * t; default BHRT_REPROJECT_DEPTH_TOLERANCE */
+    float normal_threshold; /* ... and dot(unit(n), unit(n')) >= normal_threshold; default BHRT_REPROJECT_NORMAL_THRESHOLD */
+    int32_t reserved[6];
+} bhrt_reproject_opts;
+void bhrt_default_reproject_opts(bhrt_reproject_opts *opts);
+int bhrt_reproject_dev(bhrt_scene *scene, const bhrt_reproject_opts *opts, const float prev_frame[12], const float *d_prev_z, const float *d_prev_normal,
+                       const float *d_prev_radiance, const float *d_prev_length, const float *d_prev_albedo, const float *d_z, const float *d_normal,
+                       const float *d_albedo, float *d_history, float *d_length, float *d_motion, void *stream);
+int bhrt_reproject(bhrt_scene *scene, const bhrt_reproject_opts *opts, const float prev_frame[12], const float *prev_z, const float *prev_normal,
+                   const float *prev_radiance, const float *prev_length, const float *prev_albedo, const float *z, const float *normal, const float *albedo,
+                   float *history, float *length, float *motion);
+/* bhrt_temporal_accumulate*: radiance (W*H*3, required): the current frame; cur_samples: the samples behind it (> 0); history, length:
+ * bhrt_reproject*'s (either NULL: no pixel has a history, out = radiance).  A pixel with length > 0 blends: out = h + (c - h) * a with
+ * a = cur_samples / (l + cur_samples), l = min(length, max_length), after h has been clamped to mean +- clamp_k standard deviations of the
+ * current frame's 3 x 3 block (clamp_k < 0: no clamp).  Outputs, each may be NULL: out (W*H*3), out_length (W*H: min(l + cur_samples,
+ * max_length), the length to hand to the next bhrt_reproject*), rgb8 (gamma + Color24 of out, as in bhrt_render).
+ * BHRT_ERR_ARG before any device is touched: a NULL scene, options or radiance; cur_samples or max_length that is not > 0 (a NaN included;
+ * max_length = +inf is allowed).  _dev: device pointers; with a stream the call does not synchronise.  No scratch. */
+typedef struct bhrt_temporal_opts {
+    float clamp_k;    /* the history is clamped to mean +- clamp_k sigma of the 3 x 3 block; < 0 = off; default BHRT_TEMPORAL_CLAMP_K */
+    float max_length; /* the most samples a history counts for (a floor under the blend weight of new samples); default BHRT_TEMPORAL_MAX_LENGTH */
+    int32_t gamma;    /* rgb8: 1 = pow(c, 1/2.2f) before Color24, as bhrt_opts.gamma; default 1 */
+    int32_t reserved[5];
+} bhrt_temporal_opts;
+void bhrt_default_temporal_opts(bhrt_temporal_opts *opts);
+int bhrt_temporal_accumulate_dev(bhrt_scene *scene, const bhrt_temporal_opts *opts, const float *d_radiance, float cur_samples, const float *d_history,
+                                 const float *d_length, float *d_out, float *d_out_length, uint8_t *d_rgb8, void *stream);
+int bhrt_temporal_accumulate(bhrt_scene *scene, const bhrt_temporal_opts *opts, const float *radiance, float cur_samples, const float *history, const float *length,
+                             float *out, float *out_length, uint8_t *rgb8);
 
 /* ---- adaptive sampling: RenderImage's per-pixel sample counts (Scenes/scene.h:534,570), which BeginRender only ever sets to 0
  * (Main.cpp:214), filled by a render that stops sampling a pixel once its mean is good enough ------------------------
