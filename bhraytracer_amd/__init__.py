@@ -78,6 +78,28 @@ class TemporalOpts(C.Structure):
     _fields_ = [("clamp_k", C.c_float), ("max_length", C.c_float), ("gamma", C.c_int32), ("reserved", C.c_int32 * 5)]
 
 
+class XformOp(C.Structure):
+    """bhrt_xform_op: one <scale> / <rotate> / <translate> of bhrt_scene_set_node_transform."""
+    _fields_ = [("kind", C.c_int32), ("v", C.c_float * 4)]
+
+
+XFORM_SCALE, XFORM_ROTATE, XFORM_TRANSLATE = 0, 1, 2
+# a node's bhrt_xform as a numpy record: tm (9, column-major), pos (3), itm (9); 84 bytes
+XFORM_DTYPE = np.dtype([("tm", np.float32, 9), ("pos", np.float32, 3), ("itm", np.float32, 9)])
+
+
+def scale(x, y, z):
+    return XformOp(XFORM_SCALE, (x, y, z, 0.0))
+
+
+def rotate(x, y, z, degrees):
+    return XformOp(XFORM_ROTATE, (x, y, z, degrees))
+
+
+def translate(x, y, z):
+    return XformOp(XFORM_TRANSLATE, (x, y, z, 0.0))
+
+
 class Hits(C.Structure):
     _fields_ = [("t", C.c_void_p), ("node", C.c_void_p), ("prim", C.c_void_p), ("front", C.c_void_p)]
 
@@ -108,6 +130,8 @@ EXPORTS = [
     "bhrt_scene_set_camera", "bhrt_scene_set_shutter", "bhrt_scene_get_shutter",
     "bhrt_scene_get_camera_frame", "bhrt_default_reproject_opts", "bhrt_default_temporal_opts",
     "bhrt_reproject", "bhrt_reproject_dev", "bhrt_temporal_accumulate", "bhrt_temporal_accumulate_dev",
+    "bhrt_scene_node_index", "bhrt_scene_get_node_transform", "bhrt_scene_get_node_transforms", "bhrt_scene_set_node_transform",
+    "bhrt_first_hit_node", "bhrt_first_hit_node_dev", "bhrt_reproject_moving", "bhrt_reproject_moving_dev",
 ]
 
 # BHRT_DENOISE_SIGMA_COVERAGE of include/bhrt.h: the default coverage tolerance of the denoiser for sampled guides
@@ -286,6 +310,35 @@ class Scene:
         _check(lib().bhrt_scene_get_shutter(self._h, C.byref(on), _ptr(pose), _ptr(frame)))
         return bool(on.value), pose, frame
 
+    # ---- moving objects: node names and transforms ------------------------------------------------------------------------
+    def node_index(self, name: str) -> int:
+        """bhrt_scene_node_index: the first node named `name` in the blob's pre-order (BhrtError, BHRT_ERR_ARG, when there is none)."""
+        i = C.c_int32(-1)
+        _check(lib().bhrt_scene_node_index(self._h, None if name is None else name.encode(), C.byref(i)))
+        return i.value
+
+    def node_transform(self, node: int):
+        """bhrt_scene_get_node_transform: the blob's record of that node, a numpy record of XFORM_DTYPE (tm, pos, itm)."""
+        out = np.zeros(1, XFORM_DTYPE)
+        _check(lib().bhrt_scene_get_node_transform(self._h, int(node), _ptr(out)))
+        return out[0]
+
+    def node_transforms(self):
+        """bhrt_scene_get_node_transforms: all n_nodes records, (n_nodes,) of XFORM_DTYPE: the snapshot reproject_moving reads."""
+        out = np.zeros(max(self.info.n_nodes, 1), XFORM_DTYPE)
+        n = C.c_uint32(0)
+        _check(lib().bhrt_scene_get_node_transforms(self._h, _ptr(out), C.c_uint32(out.shape[0]), C.byref(n)))
+        return out[:n.value].copy()
+
+    def set_node_transform(self, node: int, tm=None, pos=None, ops=()):
+        """bhrt_scene_set_node_transform: start from (tm, pos) (both None: the identity), apply the ops (scale(), rotate(), translate() of this
+        module) in order with the loader's own operations; the blob becomes that of the edited scene file, and an uploaded scene's node and camera
+        chain are refreshed.  Restoring a saved record r: set_node_transform(node, r["tm"], r["pos"])."""
+        v = [None if a is None else (C.c_float * k)(*[float(x) for x in np.asarray(a).reshape(-1)]) for a, k in ((tm, 9), (pos, 3))]
+        arr = None if ops is None else (XformOp * max(len(ops), 1))(*ops)
+        _check(lib().bhrt_scene_set_node_transform(self._h, int(node), v[0], v[1], arr, C.c_uint32(0 if ops is None else len(ops))))
+        self._flat = None
+
     # ---- the emission term (DESIGN.md 12): scene state beside the flat blob, which keeps its bytes --------------------
     def set_emissive(self, on: bool = True):
         """bhrt_scene_set_emissive: with the term on, every Shade() frame of a Blinn material adds its <emission> (colour x optional texture) last,
@@ -372,7 +425,7 @@ class Scene:
         return irr, d
 
     def clone(self) -> "Scene":
-        """bhrt_scene_clone: a second handle on the same loaded scene (host state only: the emission, face-material, global-gather and shutter state included;
+        """bhrt_scene_clone: a second handle on the same loaded scene (host state only: the emission, face-material, global-gather and shutter state, node names and edited node transforms included;
         no device state, so no photon map)."""
         other = Scene.__new__(Scene)
         other._h = C.c_void_p()
@@ -623,6 +676,57 @@ class Scene:
         _check(lib().bhrt_reproject_dev(self._h, C.byref(opts), _ptr(pf), v(d_prev_z), v(d_prev_normal), v(d_prev_radiance), v(d_prev_length), v(d_prev_albedo),
                                         v(d_z), v(d_normal), v(d_albedo), v(d_history), v(d_length), v(d_motion), v(stream)))
 
+    def _xforms(self, prev_xforms):
+        if prev_xforms is None:
+            return None
+        x = np.ascontiguousarray(prev_xforms, XFORM_DTYPE).reshape(-1)
+        if x.shape[0] != self.info.n_nodes:
+            raise ValueError(f"prev_xforms: expected {self.info.n_nodes} records, got {x.shape[0]}")
+        return x if x.shape[0] else np.zeros(1, XFORM_DTYPE)
+
+    def _ids(self, a, what):
+        if a is None:
+            return None
+        a = np.ascontiguousarray(a, np.int32)
+        if a.size != self.width * self.height:
+            raise ValueError(f"{what}: expected {(self.height, self.width)} int32, got {a.shape}")
+        return a
+
+    def reproject_moving(self, opts: ReprojectOpts, prev_frame, prev_xforms, prev_z, prev_normal, prev_radiance=None, prev_length=None, prev_albedo=None,
+                         prev_id=None, z=None, normal=None, albedo=None, id=None, want=("history", "length", "motion")):
+        """bhrt_reproject_moving on host arrays: reproject() with the previous frame's node_transforms() snapshot, its first_hit_node() image
+        (optional) and the current view's (None = computed on the device).  Pixels of a node that moved, or whose ancestor moved, are carried
+        through the node's motion.  Returns (history, length, motion) as reproject()."""
+        W, H = self.width, self.height
+        pf = None if prev_frame is None else np.ascontiguousarray(prev_frame, np.float32).reshape(-1)
+        if pf is not None and pf.size != 12:
+            raise ValueError("prev_frame: expected 12 floats")
+        px = self._xforms(prev_xforms)
+        i = [self._image(a, sh, k) for a, sh, k in ((prev_z, (H, W), "prev_z"), (prev_normal, (H, W, 3), "prev_normal"), (prev_radiance, (H, W, 3), "prev_radiance"),
+                                                    (prev_length, (H, W), "prev_length"), (prev_albedo, (H, W, 3), "prev_albedo"))]
+        g = [self._image(a, sh, k) for a, sh, k in ((z, (H, W), "z"), (normal, (H, W, 3), "normal"), (albedo, (H, W, 3), "albedo"))]
+        pid, cid = self._ids(prev_id, "prev_id"), self._ids(id, "id")
+        shapes = {"history": (H, W, 3), "length": (H, W), "motion": (H, W, 2)}
+        o = [np.zeros(shapes[k], np.float32) if k in want else None for k in ("history", "length", "motion")]
+        p = lambda x: _ptr(x) if x is not None else None  # noqa: E731
+        _check(lib().bhrt_reproject_moving(self._h, C.byref(opts) if opts is not None else None, p(pf), p(px), *[p(a) for a in i], p(pid), *[p(a) for a in g], p(cid),
+                                           *[p(a) for a in o]))
+        return tuple(o)
+
+    def reproject_moving_dev(self, opts: ReprojectOpts, prev_frame, prev_xforms, d_prev_z: int, d_prev_normal: int, d_prev_radiance: int = 0, d_prev_length: int = 0,
+                             d_prev_albedo: int = 0, d_prev_id: int = 0, d_z: int = 0, d_normal: int = 0, d_albedo: int = 0, d_id: int = 0, d_history: int = 0,
+                             d_length: int = 0, d_motion: int = 0, stream: int = 0):
+        """bhrt_reproject_moving_dev on raw device pointers (0 = NULL; prev_frame and prev_xforms stay host arrays); with a stream the call does
+        not synchronise."""
+        pf = np.ascontiguousarray(prev_frame, np.float32).reshape(-1)
+        if pf.size != 12:
+            raise ValueError("prev_frame: expected 12 floats")
+        px = self._xforms(prev_xforms)
+        v = lambda x: C.c_void_p(x or None)  # noqa: E731
+        _check(lib().bhrt_reproject_moving_dev(self._h, C.byref(opts), _ptr(pf), _ptr(px), v(d_prev_z), v(d_prev_normal), v(d_prev_radiance), v(d_prev_length),
+                                               v(d_prev_albedo), v(d_prev_id), v(d_z), v(d_normal), v(d_albedo), v(d_id), v(d_history), v(d_length), v(d_motion),
+                                               v(stream)))
+
     def temporal_accumulate(self, opts: TemporalOpts, radiance, cur_samples: float, history=None, length=None):
         """bhrt_temporal_accumulate on host arrays: the current frame's radiance (H, W, 3) with cur_samples samples behind it, blended into
         reproject()'s history and length (either None: no pixel has a history).  Returns (out (H, W, 3) float32, out_length (H, W) float32,
@@ -653,6 +757,15 @@ class Scene:
     def first_hit_dev(self, d_z: int = 0, d_normal: int = 0, d_albedo: int = 0, stream: int = 0):
         _check(lib().bhrt_first_hit_dev(self._h, C.c_void_p(d_z or None), C.c_void_p(d_normal or None), C.c_void_p(d_albedo or None),
                                         C.c_void_p(stream or None)))
+
+    def first_hit_node(self):
+        """bhrt_first_hit_node: (H, W) int32, the node index of the first hit of every pixel's un-jittered camera ray, -1 on a miss."""
+        node = np.zeros((self.height, self.width), np.int32)
+        _check(lib().bhrt_first_hit_node(self._h, _ptr(node)))
+        return node
+
+    def first_hit_node_dev(self, d_node: int, stream: int = 0):
+        _check(lib().bhrt_first_hit_node_dev(self._h, C.c_void_p(d_node or None), C.c_void_p(stream or None)))
 
     def guides(self, opts: Opts, want=("z", "normal", "albedo", "coverage"), into=None):
         """Sampled guide images (bhrt_guides): z (H, W), normal (H, W, 3), albedo (H, W, 3) and coverage (H, W), formed by the

@@ -15,7 +15,8 @@
 //               [--progressive N [--time-limit SECONDS] [--live-png path]]       (BeginRender .. StopRender, Main.cpp:178,243: the frame in steps)
 //               [--camera-pos X,Y,Z] [--camera-target X,Y,Z] [--camera-up X,Y,Z] [--fov F]   (the <camera> tags, xmlload.cpp:109-127, replaced)
 //               [--shutter-pos X,Y,Z] [--shutter-target X,Y,Z] [--shutter-up X,Y,Z]           (camera motion blur: the camera at the end of the exposure)
-//               [--temporal N --to-pos X,Y,Z [--to-target X,Y,Z] [--to-up X,Y,Z] [--frames-png PREFIX]]   (N frames along a camera move, each carried into the next)
+//               [--temporal N [--to-pos X,Y,Z] [--to-target X,Y,Z] [--to-up X,Y,Z] [--node-to-translate NAME:X,Y,Z] [--frames-png PREFIX]]   (N frames along a camera or object move, each carried into the next)
+//               [--node-translate NAME:X,Y,Z]   (repeatable: one translate op on that node before anything is rendered)
 //   bhrt info   <scene.xml>
 //
 // --gpus N: ONE process drives N GPUs of the node (the reference's one process drives 16 OpenMP threads, Main.cpp:422): the
@@ -75,6 +76,11 @@
 // library's default options.  -o gets the last frame, --frames-png PREFIX every frame as PREFIX000.png, PREFIX001.png, ...; --radiance the last
 // frame's accumulated radiance.  One device, whole frames, no further stage: with --progressive, --adaptive, --gpus, --denoise or --world > 1,
 // with N < 2, or --to-* / --frames-png without --temporal: a usage error.
+// --node-translate NAME:X,Y,Z (repeatable, any mode): one translate op appended to the node of that <object name=> through
+// bhrt_scene_set_node_transform, before anything is rendered.  --node-to-translate NAME:X,Y,Z (repeatable, needs --temporal N): frame k sets the
+// node to the record it had before frame 0 plus a translate of delta * ((float)k / (float)(N - 1)) per component in float32, and frames are
+// reprojected with bhrt_reproject_moving from the previous frame's node snapshot, id image (bhrt_first_hit_node) and accumulated output; without
+// --to-* the camera stays.  An unknown name, a malformed value, or --node-to-translate without --temporal: a usage error before any device is touched.
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
@@ -136,6 +142,10 @@ struct Args {
     bool temporal_given = false;
     Vec to_pos, to_target, to_up;      // --to-pos / -target / -up: the pose of the last frame
     std::string frames_png;            // --frames-png PREFIX
+    // --node-translate NAME:X,Y,Z (any mode: one translate op before anything is rendered) and --node-to-translate NAME:X,Y,Z (--temporal: the
+    // node's translation at the last frame); `node` is resolved once the scene is loaded
+    struct NodeMove { std::string name; float v[3] = {0, 0, 0}; int32_t node = -1; };
+    std::vector<NodeMove> node_translate, node_to_translate;
     bool Camera() const { return cam_pos.given || cam_target.given || cam_up.given || fov > 0.f; }
     bool Shutter() const { return sh_pos.given || sh_target.given || sh_up.given; }
 };
@@ -157,6 +167,21 @@ static Args::Vec vector_value(const char *opt, const char *text)
     }
     r.given = true;
     return r;
+}
+
+// "NAME:X,Y,Z" (--node-translate, --node-to-translate): a node's name and three finite numbers, else a usage error
+static Args::NodeMove node_move_value(const char *opt, const char *text)
+{
+    Args::NodeMove m;
+    const char *colon = strrchr(text, ':');
+    if (!colon || colon == text) {
+        fprintf(stderr, "bhrt: usage: %s needs NAME:X,Y,Z, got \"%s\"\n", opt, text);
+        exit(2);
+    }
+    m.name.assign(text, colon);
+    const Args::Vec v = vector_value(opt, colon + 1);
+    for (int k = 0; k < 3; k++) m.v[k] = v.v[k];
+    return m;
 }
 
 // a finite number >= 0 (--dof, --time-limit) or > 0 (--focaldist, --global-radius), else a usage error
@@ -260,11 +285,22 @@ static int render_temporal(bhrt_scene *scene, const Args &A, const bhrt_info &in
     // the previous view (frame, first hit, accumulated light and its length) and the current one
     std::vector<float> pz(npx), pn(npx * 3), pa(npx * 3), acc(npx * 3), len(npx), z(npx), n(npx * 3), a(npx * 3), cur(npx * 3), hist(npx * 3), hl(npx), out(npx * 3), ol(npx);
     float prev_frame[12];
+    // --node-to-translate: the moved nodes' records as they stand before frame 0, the previous frame's snapshot of all nodes and the id images
+    const bool moving = !A.node_to_translate.empty();
+    std::vector<bhrt_xform> saved(A.node_to_translate.size()), prev_xf(moving ? std::max<uint32_t>(info.n_nodes, 1) : 0);
+    std::vector<int32_t> pid(moving ? npx : 0), id(moving ? npx : 0);
+    for (size_t m = 0; m < saved.size(); m++)
+        if (bhrt_scene_get_node_transform(scene, A.node_to_translate[m].node, &saved[m])) return fail("node transform");
     for (int k = 0; k < A.temporal; k++) {
         const float s = (float)k / (float)(A.temporal - 1);
         float p[9];
         for (int c = 0; c < 9; c++) p[c] = p0[c] + (p1[c] - p0[c]) * s;
         if (bhrt_scene_set_camera(scene, p, p + 3, p + 6, 0.f)) return fail("set camera");
+        for (size_t m = 0; m < saved.size(); m++) { // the saved record plus a translate of delta * s
+            const Args::NodeMove &mv = A.node_to_translate[m];
+            bhrt_xform_op op = {BHRT_XFORM_TRANSLATE, {mv.v[0] * s, mv.v[1] * s, mv.v[2] * s, 0.f}};
+            if (bhrt_scene_set_node_transform(scene, mv.node, saved[m].tm, saved[m].pos, &op, 1)) return fail("set node transform");
+        }
         bhrt_opts o = A.o;
         o.seed = A.o.seed + (uint32_t)k;
         bhrt_stats one;
@@ -272,7 +308,12 @@ static int render_temporal(bhrt_scene *scene, const Args &A, const bhrt_info &in
         if (bhrt_render(scene, &o, nullptr, cur.data(), &one)) return fail("BeginRender");
         st.closest_rays += one.closest_rays; st.shadow_rays += one.shadow_rays; st.shade_calls += one.shade_calls; st.camera_samples += one.camera_samples;
         st.passes += one.passes; st.wave_iterations += one.wave_iterations; st.seconds_total += one.seconds_total;
-        if (k > 0 && bhrt_reproject(scene, &ro, prev_frame, pz.data(), pn.data(), acc.data(), len.data(), pa.data(), z.data(), n.data(), a.data(), hist.data(), hl.data(), nullptr))
+        if (moving && bhrt_first_hit_node(scene, id.data())) return fail("first hit node");
+        if (k > 0 && moving) {
+            if (bhrt_reproject_moving(scene, &ro, prev_frame, prev_xf.data(), pz.data(), pn.data(), acc.data(), len.data(), pa.data(), pid.data(), z.data(), n.data(), a.data(),
+                                      id.data(), hist.data(), hl.data(), nullptr))
+                return fail("reproject moving");
+        } else if (k > 0 && bhrt_reproject(scene, &ro, prev_frame, pz.data(), pn.data(), acc.data(), len.data(), pa.data(), z.data(), n.data(), a.data(), hist.data(), hl.data(), nullptr))
             return fail("reproject");
         if (bhrt_temporal_accumulate(scene, &to, cur.data(), (float)o.spp, k > 0 ? hist.data() : nullptr, k > 0 ? hl.data() : nullptr, out.data(), ol.data(), rgb.data()))
             return fail("temporal accumulate");
@@ -285,6 +326,8 @@ static int render_temporal(bhrt_scene *scene, const Args &A, const bhrt_info &in
             if (bhrt_save_png((A.frames_png + name).c_str(), rgb.data(), info.width, info.height)) return fail("SaveImage (frame)");
         }
         if (bhrt_scene_get_camera_frame(scene, prev_frame)) return fail("camera frame");
+        if (moving && bhrt_scene_get_node_transforms(scene, prev_xf.data(), (uint32_t)prev_xf.size(), nullptr)) return fail("node transforms");
+        pid.swap(id);
         pz.swap(z); pn.swap(n); pa.swap(a); acc.swap(out); len.swap(ol);
     }
     if (!rad.empty()) rad = acc;
@@ -583,6 +626,8 @@ int main(int argc, char **argv)
         else if (s == "--to-target") A.to_target = vector_value("--to-target", next());
         else if (s == "--to-up") A.to_up = vector_value("--to-up", next());
         else if (s == "--frames-png") A.frames_png = next();
+        else if (s == "--node-translate") A.node_translate.push_back(node_move_value("--node-translate", next()));
+        else if (s == "--node-to-translate") A.node_to_translate.push_back(node_move_value("--node-to-translate", next()));
         else if (s == "--fov") {
             A.fov = number_value("--fov", next(), true);
             if (!(A.fov < 180.f)) { fprintf(stderr, "bhrt: usage: --fov needs a number of degrees below 180\n"); return 2; }
@@ -622,6 +667,7 @@ int main(int argc, char **argv)
         fprintf(stderr, "bhrt: usage: --to-pos, --to-target, --to-up and --frames-png need --temporal N\n");
         return 2;
     }
+    if (!A.temporal_given && !A.node_to_translate.empty()) { fprintf(stderr, "bhrt: usage: --node-to-translate needs --temporal N\n"); return 2; }
     if (A.temporal_given && (A.temporal < 2 || A.progressive_given || A.adaptive || A.gpus > 0 || A.denoise || o.world_size > 1)) { // before any device is touched
         fprintf(stderr, "bhrt: usage: --temporal needs N >= 2 frames and renders whole frames on one device (no --progressive, --adaptive, --gpus, --denoise, --world)\n");
         return 2;
@@ -639,7 +685,20 @@ int main(int argc, char **argv)
     printf("Render image width: %d\nRender image height: %d\n", info.width, info.height); // Main.cpp:426-427
     printf("nodes %u, meshes %u (%u triangles, %u BVH nodes), materials %u, lights %u, textures %u, scene blob %llu bytes\n", info.n_nodes,
            info.n_meshes, info.n_triangles, info.n_bvh_nodes, info.n_materials, info.n_lights, info.n_textures, (unsigned long long)info.flat_bytes);
+    for (std::vector<Args::NodeMove> *moves : {&A.node_translate, &A.node_to_translate}) // before any device is touched
+        for (Args::NodeMove &m : *moves)
+            if (bhrt_scene_node_index(scene, m.name.c_str(), &m.node)) {
+                fprintf(stderr, "bhrt: usage: %s: the scene has no node named \"%s\"\n", moves == &A.node_translate ? "--node-translate" : "--node-to-translate", m.name.c_str());
+                bhrt_scene_free(scene);
+                return 2;
+            }
     if (!render) { bhrt_scene_free(scene); return 0; }
+    for (const Args::NodeMove &m : A.node_translate) { // one translate op appended to the node, before the upload and before --gpus N clones the scene
+        bhrt_xform xf;
+        bhrt_xform_op op = {BHRT_XFORM_TRANSLATE, {m.v[0], m.v[1], m.v[2], 0.f}};
+        if (bhrt_scene_get_node_transform(scene, m.node, &xf) || bhrt_scene_set_node_transform(scene, m.node, xf.tm, xf.pos, &op, 1)) return fail("node translate");
+        printf("node %s (%d): translated by %g,%g,%g\n", m.name.c_str(), m.node, m.v[0], m.v[1], m.v[2]);
+    }
     if (A.emission && bhrt_scene_set_emissive(scene, 1)) return fail("set emissive"); // before the upload and before --gpus N clones the scene
     if (A.face_materials && bhrt_scene_set_face_materials(scene, 1)) return fail("set face materials"); // likewise
     if (A.global_map && bhrt_scene_set_global_gather(scene, 1, A.global_radius)) return fail("set global gather"); // likewise; the map is built after the upload

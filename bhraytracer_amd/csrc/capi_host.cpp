@@ -107,7 +107,7 @@ int bhrt_scene_clone(const bhrt_scene *src, bhrt_scene **out)
 try {
     if (!src || !out) { bhrt::SetError("bhrt_scene_clone: null argument"); return BHRT_ERR_ARG; }
     bhrt_scene *s = new bhrt_scene;
-    s->flat = src->flat; // the host copy only: the clone is uploaded to a device of its own (one handle per GPU)
+    s->flat = src->flat; // the host copy only, node names and edited node transforms included: the clone is uploaded to a device of its own (one handle per GPU)
     s->n_triangles = src->n_triangles; s->n_bvh_nodes = src->n_bvh_nodes; s->max_bvh_depth = src->max_bvh_depth;
     *out = s;
     return BHRT_OK;

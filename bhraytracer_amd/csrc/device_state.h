@@ -234,6 +234,21 @@ struct DeviceState : DeviceQueues {
     DevBuf<uint8_t> d_dn;
     // bhrt_guides_dev: the running sums between the sample chunks of a call (k_guides), 32 B per pixel of a pass; only when spp exceeds one chunk
     DevBuf<float4> d_guides;
+    // bhrt_reproject_moving_dev: the previous node records with moved[] (88 B per node), and the node-id image it computes itself (4 B per pixel).
+    // The records travel on the call's stream from pinned memory.  Two slots used in turn, each with an event recorded behind the call's kernel:
+    // a slot's pinned words are written again only after the stream has passed the call that used them last.
+    struct MovingNodeSlot {
+        PinnedBuf<uint32_t> h;
+        DevBuf<uint32_t> d;
+        hipEvent_t done = nullptr;
+        bool used = false;
+        MovingNodeSlot() = default;
+        MovingNodeSlot(const MovingNodeSlot &) = delete;
+        MovingNodeSlot &operator=(const MovingNodeSlot &) = delete;
+        ~MovingNodeSlot() { if (done) (void)hipEventDestroy(done); }
+    } moving_nodes[2];
+    uint32_t moving_turn = 0;
+    DevBuf<int32_t> d_moving_id;
     // scratch for the public trace API (EnsureApiScratch)
     size_t api_cap = 0; // rays
     DevBuf<float> d_api_f;   // 9 * api_cap

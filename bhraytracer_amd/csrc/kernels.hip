@@ -1612,6 +1612,21 @@ __global__ void __launch_bounds__(kBlock) k_first_hit(DevScene S, FaceMtlTable T
     if (albedo) st3(albedo, q, kd);
 }
 
+// The node-id image (bhrt_first_hit_node*): k_first_hit's ray and trace, and the hit's node (-1 on a miss) as the only output.  A
+// kernel of its own: k_first_hit keeps its signature and its code.
+__global__ void __launch_bounds__(kBlock) k_first_hit_node(DevScene S, int W, int H, int32_t *node)
+{
+    __shared__ bhrt_bvh_node nodelet[BHRT_LDS_NODES];
+    const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
+    const bool active = q < (uint32_t)(W * H);
+    const int j = (int)(q / (uint32_t)W), i = (int)(q - (uint32_t)j * (uint32_t)W);
+    const V3 topLeft = ld3(S.cam.top_left), ddx = ld3(S.cam.dd_x), ddy = ld3(S.cam.dd_y), pos = ld3(S.cam.pos);
+    const V3 o = pos, d = ((topLeft + (float)i * ddx) - (float)j * ddy) - pos; // Main.cpp:145,153
+    Hit hit;
+    trace_closest(S, o, d, BHRT_HIT_FRONT, hit, active, nodelet); // uniform call: the block stages nodelets together
+    if (active) node[q] = hit.node >= 0 ? hit.node : -1;
+}
+
 // The sampled guide images (bhrt_guides*): k_first_hit's three values and a hit flag for every camera sample of a pixel — the
 // render's own ray of (seed, pixel, sample): camera_ray, jitter and lens included — summed per pixel in float32, in sample order.
 // A launch covers samples [P.s0, P.s0 + P.spp) (a chunk of at most kBlock) of the pass's pixels.  A workgroup holds ppb = kBlock / P.spp
@@ -4177,6 +4192,57 @@ try {
     return BHRT_OK;
 } catch (...) { return bhrt::AbiException(); }
 
+// ---- moving objects: node names and transforms.  In this translation unit because the setter refreshes an uploaded scene.
+int bhrt_scene_node_index(const bhrt_scene *scene, const char *name, int32_t *index)
+try {
+    if (!scene || !name || !index) { SetError("bhrt_scene_node_index: null argument"); return BHRT_ERR_ARG; }
+    const std::vector<std::string> &names = scene->flat.node_names;
+    for (size_t i = 0; i < names.size(); i++) // the first of that name in the blob's pre-order
+        if (names[i] == name) { *index = (int32_t)i; return BHRT_OK; }
+    SetError(std::string("bhrt_scene_node_index: no node named \"") + name + "\"");
+    return BHRT_ERR_ARG;
+} catch (...) { return bhrt::AbiException(); }
+
+static const bhrt_node *HostNodes(const bhrt_scene *scene) { return (const bhrt_node *)(scene->flat.blob.data() + scene->flat.hdr()->off_nodes); }
+
+int bhrt_scene_get_node_transform(const bhrt_scene *scene, int32_t node, bhrt_xform *out)
+try {
+    if (!scene || !out) { SetError("bhrt_scene_get_node_transform: null argument"); return BHRT_ERR_ARG; }
+    if (node < 0 || (uint32_t)node >= scene->flat.hdr()->n_nodes) { SetError("bhrt_scene_get_node_transform: node index out of range"); return BHRT_ERR_ARG; }
+    *out = HostNodes(scene)[node].xf;
+    return BHRT_OK;
+} catch (...) { return bhrt::AbiException(); }
+
+int bhrt_scene_get_node_transforms(const bhrt_scene *scene, bhrt_xform *out, uint32_t capacity, uint32_t *n)
+try {
+    if (!scene) { SetError("bhrt_scene_get_node_transforms: null scene"); return BHRT_ERR_ARG; }
+    const uint32_t n_nodes = scene->flat.hdr()->n_nodes;
+    if (n) *n = n_nodes;
+    if (capacity < n_nodes || (n_nodes > 0 && !out)) { SetError("bhrt_scene_get_node_transforms: room for " + std::to_string(n_nodes) + " records is needed"); return BHRT_ERR_ARG; }
+    for (uint32_t k = 0; k < n_nodes; k++) out[k] = HostNodes(scene)[k].xf;
+    return BHRT_OK;
+} catch (...) { return bhrt::AbiException(); }
+
+int bhrt_scene_set_node_transform(bhrt_scene *scene, int32_t node, const float tm[9], const float pos[3], const bhrt_xform_op *ops, uint32_t n_ops)
+try {
+    if (!scene) { SetError("bhrt_scene_set_node_transform: null scene"); return BHRT_ERR_ARG; }
+    const bhrt_flat_header *H = scene->flat.hdr();
+    if (node < 0 || (uint32_t)node >= H->n_nodes) { SetError("bhrt_scene_set_node_transform: node index out of range"); return BHRT_ERR_ARG; }
+    bhrt_xform xf;
+    const char *bad = bhrt::BuildNodeXform(tm, pos, ops, n_ops, xf);
+    if (*bad) { SetError(std::string("bhrt_scene_set_node_transform: ") + bad); return BHRT_ERR_ARG; }
+    const size_t off = (size_t)H->off_nodes + (size_t)node * sizeof(bhrt_node) + offsetof(bhrt_node, xf);
+    memcpy(scene->flat.blob.data() + off, &xf, sizeof xf); // nothing above changed the scene
+    if (DeviceState *D = scene->dev) { // the node's 84 bytes and the camera position through every node's chain; nothing else is uploaded again
+        HIP_CHECK(hipSetDevice(D->device));
+        HIP_CHECK(hipMemcpy(D->d_blob.p + off, &xf, sizeof xf, hipMemcpyHostToDevice));
+        std::vector<float> cc((size_t)std::max<uint32_t>(H->n_nodes, 1) * BHRT_MAX_NODE_DEPTH * 3, 0.f);
+        FillCamChain(scene->flat, cc.data());
+        HIP_CHECK(hipMemcpy(const_cast<float *>(D->S.cam_chain), cc.data(), cc.size() * sizeof(float), hipMemcpyHostToDevice));
+    }
+    return BHRT_OK;
+} catch (...) { return bhrt::AbiException(); }
+
 // ---- the emission term: scene state beside the blob.  In this translation unit because the setters refresh an uploaded scene.
 int bhrt_scene_set_emissive(bhrt_scene *scene, int on)
 try {
@@ -4272,6 +4338,35 @@ try {
     if (z) HIP_CHECK(hipMemcpy(z, d, n * sizeof(float), hipMemcpyDeviceToHost));
     if (normal) HIP_CHECK(hipMemcpy(normal, d + n, 3 * n * sizeof(float), hipMemcpyDeviceToHost));
     if (albedo) HIP_CHECK(hipMemcpy(albedo, d + 4 * n, 3 * n * sizeof(float), hipMemcpyDeviceToHost));
+    return BHRT_OK;
+} catch (...) { return bhrt::AbiException(); }
+
+int bhrt_first_hit_node_dev(bhrt_scene *scene, int32_t *d_node, void *stream)
+try {
+    if (!scene || !d_node) { SetError("bhrt_first_hit_node: null argument"); return BHRT_ERR_ARG; }
+    int rc = EnsureUploaded(scene);
+    if (rc) return rc;
+    DeviceState *D = scene->dev;
+    const bhrt_flat_header *H = scene->flat.hdr();
+    const int W = H->camera.width, Hh = H->camera.height;
+    hipStream_t st = stream ? (hipStream_t)stream : D->stream;
+    hipLaunchKernelGGL(k_first_hit_node, dim3(((uint32_t)(W * Hh) + kBlock - 1) / kBlock), dim3(kBlock), 0, st, D->S, W, Hh, d_node);
+    HIP_CHECK(hipGetLastError());
+    if (!stream) HIP_CHECK(hipStreamSynchronize(st));
+    return BHRT_OK;
+} catch (...) { return bhrt::AbiException(); }
+
+int bhrt_first_hit_node(bhrt_scene *scene, int32_t *node)
+try {
+    if (!scene || !node) { SetError("bhrt_first_hit_node: null argument"); return BHRT_ERR_ARG; }
+    int rc = EnsureUploaded(scene);
+    if (rc) return rc;
+    const bhrt_flat_header *H = scene->flat.hdr();
+    const size_t n = (size_t)H->camera.width * H->camera.height;
+    DevBuf<int32_t> d;
+    BHRT_TRY(d.Reserve(n));
+    BHRT_TRY(bhrt_first_hit_node_dev(scene, d.p, nullptr));
+    HIP_CHECK(hipMemcpy(node, d, n * sizeof(int32_t), hipMemcpyDeviceToHost));
     return BHRT_OK;
 } catch (...) { return bhrt::AbiException(); }
 
@@ -4592,6 +4687,108 @@ try {
         if (in[k]) HIP_CHECK(hipMemcpyAsync(at[k], in[k], width[k] * n * sizeof(float), hipMemcpyHostToDevice, D->stream));
     auto given = [&](int k) -> float * { return (k < 8 ? (const void *)in[k] : (const void *)out[k - 8]) ? at[k] : nullptr; };
     BHRT_TRY(bhrt_reproject_dev(scene, opts, prev_frame, given(0), given(1), given(2), given(3), given(4), given(5), given(6), given(7), given(8), given(9), given(10), nullptr));
+    for (int k = 0; k < 3; k++)
+        if (out[k]) HIP_CHECK(hipMemcpy(out[k], at[8 + k], width[8 + k] * n * sizeof(float), hipMemcpyDeviceToHost));
+    return BHRT_OK;
+} catch (...) { return bhrt::AbiException(); }
+
+// bhrt_reproject_moving* (k_reproject_moving): the checks of bhrt_reproject* and those of the snapshot, before any device is touched
+static int ReprojectMovingArgs(const bhrt_scene *scene, const bhrt_reproject_opts *opts, const float *prev_frame, const bhrt_xform *prev_xforms, const float *prev_z,
+                               const float *prev_normal, const float *prev_radiance, const float *prev_albedo, const float *history)
+{
+    BHRT_TRY(ReprojectArgs(scene, opts, prev_frame, prev_z, prev_normal, prev_radiance, prev_albedo, history));
+    const char *bad = ReprojectMovingArgsError(prev_xforms, scene->flat.hdr()->n_nodes);
+    if (*bad) { SetError(bad); return BHRT_ERR_ARG; }
+    return BHRT_OK;
+}
+
+int bhrt_reproject_moving_dev(bhrt_scene *scene, const bhrt_reproject_opts *opts, const float prev_frame[12], const bhrt_xform *prev_xforms, const float *d_prev_z,
+                              const float *d_prev_normal, const float *d_prev_radiance, const float *d_prev_length, const float *d_prev_albedo, const int32_t *d_prev_id,
+                              const float *d_z, const float *d_normal, const float *d_albedo, const int32_t *d_id, float *d_history, float *d_length, float *d_motion,
+                              void *stream)
+try {
+    BHRT_TRY(ReprojectMovingArgs(scene, opts, prev_frame, prev_xforms, d_prev_z, d_prev_normal, d_prev_radiance, d_prev_albedo, d_history));
+    int rc = EnsureUploaded(scene);
+    if (rc) return rc;
+    if (!d_history && !d_length && !d_motion) return BHRT_OK;
+    DeviceState *D = scene->dev;
+    const bhrt_flat_header *H = scene->flat.hdr();
+    const int W = H->camera.width, Hh = H->camera.height;
+    const size_t n = (size_t)W * Hh;
+    if (n == 0 || n > 0x7fffffffull) { SetError("reproject moving: frame size out of range"); return BHRT_ERR_ARG; }
+    hipStream_t st = stream ? (hipStream_t)stream : D->stream;
+    ReprojectMovingJob J;
+    J.W = W; J.H = Hh; J.o = *opts;
+    bhrt_scene_get_camera_frame(scene, J.cur);
+    memcpy(J.prev, prev_frame, sizeof J.prev);
+    J.prev_z = d_prev_z; J.prev_normal = d_prev_normal; J.prev_radiance = d_prev_radiance; J.prev_length = d_prev_length; J.prev_albedo = d_prev_albedo;
+    J.z = d_z; J.normal = d_normal; J.albedo = d_albedo; J.history = d_history; J.length = d_length; J.motion = d_motion;
+    J.prev_id = d_prev_id; J.id = d_id;
+    // the previous records and moved[], 88 B per node (at least one record's room: a scene without nodes launches with a real buffer it never
+    // reads), through pinned memory on the call's own stream: ordered behind what the stream holds, and no wait for the device.  The slot's
+    // words were last read by the call before the previous one; its event says when the stream has passed that call.
+    DeviceState::MovingNodeSlot &slot = D->moving_nodes[D->moving_turn++ & 1u];
+    const size_t pn_words = (size_t)std::max<uint32_t>(H->n_nodes, 1) * kPrevNodeWords; // fixed for a scene: its node count never changes
+    if (!slot.h) {
+        BHRT_TRY(slot.h.Alloc(pn_words));
+        BHRT_TRY(slot.d.Reserve(pn_words));
+        HIP_CHECK(hipEventCreateWithFlags(&slot.done, hipEventDisableTiming));
+    }
+    if (slot.used) HIP_CHECK(hipEventSynchronize(slot.done));
+    memset(slot.h.p, 0, pn_words * sizeof(uint32_t));
+    FillPrevNodes(HostNodes(scene), prev_xforms, H->n_nodes, slot.h.p);
+    HIP_CHECK(hipMemcpyAsync(slot.d, slot.h.p, pn_words * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    J.nodes = D->S.nodes; J.chain = D->S.chain; J.prev_nodes = slot.d; J.n_nodes = (int)H->n_nodes;
+    const bool want_albedo = d_prev_albedo && d_history; // without albedo' no albedo is read or computed
+    if (!d_z || !d_normal || (want_albedo && !d_albedo)) { // as bhrt_reproject_dev
+        BHRT_TRY(D->d_dn.Reserve(n * 7 * sizeof(float)));
+        float *g = (float *)D->d_dn.p;
+        float *gz = d_z ? nullptr : g, *gn = d_normal ? nullptr : g + n, *ga = !want_albedo || d_albedo ? nullptr : g + 4 * n;
+        hipLaunchKernelGGL(D->fm.tab ? k_first_hit<true> : k_first_hit<false>, dim3(((uint32_t)n + kBlock - 1) / kBlock), dim3(kBlock), 0, st, D->S, D->fm, W, Hh, gz, gn, ga);
+        HIP_CHECK(hipGetLastError());
+        if (gz) J.z = gz;
+        if (gn) J.normal = gn;
+        if (ga) J.albedo = ga;
+    }
+    if (!d_id) { // the node-id image of bhrt_first_hit_node_dev, into scratch of its own (4 B per pixel)
+        BHRT_TRY(D->d_moving_id.Reserve(n));
+        hipLaunchKernelGGL(k_first_hit_node, dim3(((uint32_t)n + kBlock - 1) / kBlock), dim3(kBlock), 0, st, D->S, W, Hh, D->d_moving_id.p);
+        HIP_CHECK(hipGetLastError());
+        J.id = D->d_moving_id;
+    }
+    HIP_CHECK(ReprojectMovingLaunch(J, st));
+    HIP_CHECK(hipEventRecord(slot.done, st));
+    slot.used = true;
+    if (!stream) HIP_CHECK(hipStreamSynchronize(st));
+    return BHRT_OK;
+} catch (...) { return bhrt::AbiException(); }
+
+int bhrt_reproject_moving(bhrt_scene *scene, const bhrt_reproject_opts *opts, const float prev_frame[12], const bhrt_xform *prev_xforms, const float *prev_z,
+                          const float *prev_normal, const float *prev_radiance, const float *prev_length, const float *prev_albedo, const int32_t *prev_id, const float *z,
+                          const float *normal, const float *albedo, const int32_t *id, float *history, float *length, float *motion)
+try {
+    BHRT_TRY(ReprojectMovingArgs(scene, opts, prev_frame, prev_xforms, prev_z, prev_normal, prev_radiance, prev_albedo, history));
+    int rc = EnsureUploaded(scene);
+    if (rc) return rc;
+    if (!history && !length && !motion) return BHRT_OK;
+    DeviceState *D = scene->dev;
+    const bhrt_flat_header *H = scene->flat.hdr();
+    const size_t n = (size_t)H->camera.width * H->camera.height;
+    // device copies, back to back, in 4-byte words per pixel: bhrt_reproject's eleven images, then id' 1, id 1
+    const void *const in[10] = {prev_z, prev_normal, prev_radiance, prev_length, prev_albedo, z, normal, albedo, prev_id, id};
+    float *const out[3] = {history, length, motion};
+    const size_t width[13] = {1, 3, 3, 1, 3, 1, 3, 3, 3, 1, 2, 1, 1};
+    const int slot_in[10] = {0, 1, 2, 3, 4, 5, 6, 7, 11, 12};
+    DevBuf<float> d;
+    BHRT_TRY(d.Reserve(n * 26));
+    float *at[13];
+    for (size_t k = 0, off = 0; k < 13; off += width[k] * n, k++) at[k] = d.p + off;
+    for (int k = 0; k < 10; k++)
+        if (in[k]) HIP_CHECK(hipMemcpyAsync(at[slot_in[k]], in[k], width[slot_in[k]] * n * 4, hipMemcpyHostToDevice, D->stream));
+    auto gin = [&](int k) -> float * { return in[k] ? at[slot_in[k]] : nullptr; };
+    auto gout = [&](int k) -> float * { return out[k] ? at[8 + k] : nullptr; };
+    BHRT_TRY(bhrt_reproject_moving_dev(scene, opts, prev_frame, prev_xforms, gin(0), gin(1), gin(2), gin(3), gin(4), (const int32_t *)gin(8), gin(5), gin(6), gin(7),
+                                       (const int32_t *)gin(9), gout(0), gout(1), gout(2), nullptr));
     for (int k = 0; k < 3; k++)
         if (out[k]) HIP_CHECK(hipMemcpy(out[k], at[8 + k], width[8 + k] * n * sizeof(float), hipMemcpyDeviceToHost));
     return BHRT_OK;

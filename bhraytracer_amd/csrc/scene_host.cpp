@@ -212,6 +212,7 @@ struct NodeData {
     Xform xf;
     int parent = -1, depth = 1, obj_type = BHRT_OBJ_NONE, mesh = -1, material = -1;
     int subtree_end = 0;
+    std::string name; // the XML name= ("" when absent), kept beside the blob (FlatScene::node_names)
     std::string material_name;
     bool has_material_name = false;
 };
@@ -432,6 +433,7 @@ struct Loader {
         nodes[idx].parent = parent;
         nodes[idx].depth = depth;
         const char *name = e->Attribute("name");
+        if (name) nodes[idx].name = name;
         const char *mtlName = e->Attribute("material");
         if (mtlName) node_mtl_list.emplace_back(idx, mtlName);
         const char *type = e->Attribute("type");
@@ -1187,6 +1189,8 @@ int LoadSceneXml(const char *path, FlatScene &out, std::string &err, int bvh_dev
     }
     H.n_nodes = (uint32_t)nodes.size();
     H.off_nodes = W.Append(nodes.data(), nodes.size() * sizeof(bhrt_node));
+    out.node_names.resize(L.nodes.size());
+    for (size_t i = 0; i < L.nodes.size(); i++) out.node_names[i] = L.nodes[i].name;
 
     std::vector<bhrt_mesh> meshes(L.meshes.size());
     for (size_t i = 0; i < L.meshes.size(); i++) {
@@ -1348,6 +1352,47 @@ int LoadSceneXml(const char *path, FlatScene &out, std::string &err, int bvh_dev
     H.total_bytes = blob.size();
     memcpy(blob.data(), &H, sizeof H);
     return 0;
+}
+
+const char *BuildNodeXform(const float tm[9], const float pos[3], const bhrt_xform_op *ops, uint32_t n_ops, bhrt_xform &out)
+{
+    auto finite = [](const float *v, int n) { for (int k = 0; k < n; k++) if (!std::isfinite(v[k])) return false; return true; };
+    if ((tm == nullptr) != (pos == nullptr)) return "tm and pos are given together or not at all";
+    if (n_ops > 0 && !ops) return "null ops with n_ops > 0";
+    if (tm && (!finite(tm, 9) || !finite(pos, 3))) return "a component that is not finite";
+    Xform t; // the identity, as LoadNode starts from
+    if (tm) {
+        memcpy(t.tm.c, tm, sizeof t.tm.c);
+        t.pos = v3(pos[0], pos[1], pos[2]);
+        t.itm = MatInverse(t.tm);
+    }
+    for (uint32_t i = 0; i < n_ops; i++) {
+        const float *v = ops[i].v;
+        switch (ops[i].kind) {
+        case BHRT_XFORM_SCALE:
+            if (!finite(v, 3)) return "a component that is not finite";
+            t.Scale(v[0], v[1], v[2]);
+            break;
+        case BHRT_XFORM_ROTATE: {
+            if (!finite(v, 4)) return "a component that is not finite";
+            const V3 axis = v3(v[0], v[1], v[2]);
+            if (!(length(axis) > 0.f)) return "a rotate axis of length 0";
+            t.Rotate(normalized(axis), v[3]);
+            break;
+        }
+        case BHRT_XFORM_TRANSLATE:
+            if (!finite(v, 3)) return "a component that is not finite";
+            t.Translate(v3(v[0], v[1], v[2]));
+            break;
+        default:
+            return "an unknown op kind";
+        }
+    }
+    bhrt_xform r;
+    t.Store(r);
+    if (!finite(r.tm, 9) || !finite(r.pos, 3) || !finite(r.itm, 9)) return "a transform that is not finite (a singular matrix)";
+    out = r;
+    return "";
 }
 
 } // namespace bhrt

@@ -7,6 +7,8 @@
 
 #include "bhrt_flat.h"
 
+struct bhrt_xform_op; // include/bhrt.h
+
 namespace bhrt {
 
 struct FlatScene {
@@ -17,6 +19,7 @@ struct FlatScene {
     // bytes are what they were before the term existed.
     std::vector<bhrt_texcolor> emission;      // [n_materials]
     std::vector<std::string> material_names;  // [n_materials]
+    std::vector<std::string> node_names;      // [n_nodes]: the <object name=> of every node in the blob's pre-order, "" where there is none
     int emissive = 0;
     // Face materials, beside the blob too: the sub-materials of every MultiMtl (one per `newmtl` of the mesh's .mtl, converted as
     // the blob's record is from the first; xmlload.cpp:219-250) and the cumulative face counts that group the mesh's faces by them
@@ -51,6 +54,11 @@ bool SetCameraPose(bhrt_camera &C, const float pos[3], const float target[3], co
 // The pair of poses of a shutter: "" when dir, dd_x and dd_y of the two cameras each have a positive dot product and every value of
 // b's frame is finite (no interpolated axis can then be zero), else what is wrong
 const char *ShutterPairError(const bhrt_camera &a, const bhrt_camera &b);
+
+// The record bhrt_scene_set_node_transform stores: (tm, pos) — both NULL = the identity — with itm = MatInverse(tm), then the ops in
+// order through LoadTransform's own Scale / Rotate / Translate, stored as the loader stores a node's.  "" and `out` written when every input
+// and every value of the result is finite, else what is wrong and `out` untouched.
+const char *BuildNodeXform(const float tm[9], const float pos[3], const bhrt_xform_op *ops, uint32_t n_ops, bhrt_xform &out);
 
 // OBJ mesh -> arrays, same face/index rules as cyTriMesh::LoadFromFileObj (cyTriMesh.h:263-547)
 struct HostMesh {

@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "bhrt.h"
+#include "bhrt_flat.h"
 
 namespace bhrt {
 
@@ -29,6 +30,22 @@ struct ReprojectJob {
 // "" when the arguments are usable, else what is wrong with them (host arithmetic only)
 const char *ReprojectArgsError(const bhrt_reproject_opts *o, const float *prev_frame, const float *prev_radiance, const float *prev_albedo);
 hipError_t ReprojectLaunch(const ReprojectJob &J, hipStream_t s);
+
+// stage 1 through object motion (k_reproject_moving): the job above and what says where every node was
+constexpr int kPrevNodeWords = 22; // a node's previous record in the scene's scratch: tm'[9], pos'[3], itm'[9], then moved (int32): 88 B
+struct ReprojectMovingJob : ReprojectJob {
+    const bhrt_node *nodes;    // device: the scene's nodes, the current records
+    const int32_t *chain;      // device: n_nodes x BHRT_MAX_NODE_DEPTH, the depth-1 ancestor first (DeviceState::d_chain)
+    const uint32_t *prev_nodes; // device: n_nodes x kPrevNodeWords
+    int n_nodes;
+    const int32_t *prev_id;    // W*H, or NULL: the previous view's node ids take no part
+    const int32_t *id;         // W*H: the current view's
+};
+// "" when the snapshot is usable (non-NULL, every value finite; n_nodes == 0 reads nothing)
+const char *ReprojectMovingArgsError(const bhrt_xform *prev_xforms, uint32_t n_nodes);
+// fills n_nodes x kPrevNodeWords words from the snapshot and the scene's nodes: moved = the bytes of the node's record or of an ancestor's differ
+void FillPrevNodes(const bhrt_node *nodes, const bhrt_xform *prev_xforms, uint32_t n_nodes, uint32_t *out);
+hipError_t ReprojectMovingLaunch(const ReprojectMovingJob &J, hipStream_t s);
 
 struct TemporalJob {
     int W, H;

@@ -35,6 +35,22 @@
 //            there is no multiplication;  length = (sum w l') / sw;  motion = (u - i, v - j)
 //   invalid  history = 0, length = 0, motion = 0
 //
+// 1M. REPROJECTION THROUGH OBJECT MOTION (k_reproject_moving): stage 1 with these changes for a hit pixel.  k = id (the node of the
+//   pixel's first hit, bhrt_first_hit_node), xf_c = (tm, pos, itm) the scene's record of node c now, xf'_c the previous one (prev_xforms);
+//   mat_mul(M, p) = (p.x M0 + p.y M3 + p.z M6, p.x M1 + p.y M4 + p.z M7, p.x M2 + p.y M5 + p.z M8), mat_tmul(M, d) = (M0 d.x + M1 d.y + M2 d.z,
+//   M3 d.x + M4 d.y + M5 d.z, M6 d.x + M7 d.y + M8 d.z), each sum left to right (vecmath.h).
+//   id       k < 0 or k >= n_nodes: the pixel is invalid (nothing is indexed with such a k)
+//   moved[k] formed on the host: 1 when the 84 bytes of xf_c and xf'_c differ for c = k or any ancestor of k
+//   moved    with the chain c_1 .. c_m of k (the depth-1 ancestor first, k last; m = min(depth, BHRT_MAX_NODE_DEPTH)):
+//            p = x;       for a = 1 .. m: p = mat_mul(itm_a, p - pos_a)         (into the node's space with the current records: FillCamChain's expression)
+//                         for a = m .. 1: p = mat_mul(tm'_a, p) + pos'_a        (back out with the previous ones)
+//            x' = p replaces x in q = x - pos'
+//            nl = n;      for a = 1 .. m: nl = mat_tmul(tm_a, nl);  for a = m .. 1: nl = mat_tmul(itm'_a, nl);  no normalisation on the way;
+//            unit(nl) replaces unit(n) in the normal test
+//   unmoved  x' = x and n is untouched: with nothing moved every output is stage 1's bit for bit
+//   taps     with a prev_id image, a hit pixel's tap is valid only if prev_id[tap] == k as well
+//   Misses, snap, bounds, taps, result and motion are stage 1's; motion now contains the object's motion.
+//
 // 2. ACCUMULATION, per pixel: c = the current radiance, n_c = cur_samples (the samples behind it), h, l = history and length of stage 1.
 //   no history (not l > 0):  out = c, out_length = min(n_c, max_length)
 //   else, with clamp_k >= 0:  the taps of the 3 x 3 block of the current radiance that lie inside the image, row-major, m of them; per channel
@@ -46,9 +62,14 @@
 // in the same float32 operations.  It reads 28 B per pixel of the current view (40 B with albedo) and, per tap, 32 B of the previous one (44 B
 // with albedo); it writes 24 B.  k_temporal_accumulate: the denoiser's 16 x 16 workgroups; the 3 x 3 block is read through the cache (a wave
 // is 16 x 4 pixels: its taps share cache lines; a tile staged through LDS measured no better).  Fixed tap order, no atomics:
-// the same inputs give the same bytes.
+// the same inputs give the same bytes.  k_reproject_moving: k_reproject's lane layout and taps (its body is repeated rather than shared, so
+// that k_reproject keeps its code); 4 B more per pixel (8 B with prev_id per tap), and for a pixel of a moved node 84 B of the current and
+// 88 B of the previous record per chain level, from the scene's nodes and from a scratch buffer of 88 B per node.  The chain loop is bounded
+// by BHRT_MAX_NODE_DEPTH; no array is indexed dynamically (no scratch memory).
 #include <hip/hip_runtime.h>
 #include <math.h>
+#include <stddef.h>
+#include <string.h>
 
 #include "bhrt_flat.h"
 #include "device_color24.h"
@@ -131,6 +152,118 @@ __global__ void __launch_bounds__(256) k_reproject(int W, int H, ReprojectFrame 
                 if (!(zq >= BHRT_BIGFLOAT)) continue;
             } else {
                 if (!(zq < BHRT_BIGFLOAT) || !(fabsf(zq - t) <= depth_tolerance * t)) continue;
+                if (!(dot(nu, tp_unit(pn, q)) >= normal_threshold)) continue;
+            }
+            sw = sw + w;
+            sl = sl + w * lq;
+            if (history) {
+                V3 e = v3(pc[3 * q], pc[3 * q + 1], pc[3 * q + 2]);
+                if (kAlbedo) {
+                    const V3 dq = tp_divisor(pa, q);
+                    e = v3(e.x / dq.x, e.y / dq.y, e.z / dq.z);
+                }
+                sr = sr + w * e.x;
+                sg = sg + w * e.y;
+                sb = sb + w * e.z;
+            }
+        }
+        ok = sw > 0.f;
+    }
+    V3 h = v3(0, 0, 0);
+    float l = 0.f, mu = 0.f, mv = 0.f;
+    if (ok) {
+        h = v3(sr / sw, sg / sw, sb / sw);
+        if (kAlbedo && history) {
+            const V3 g = tp_divisor(a, p);
+            h = v3(h.x * g.x, h.y * g.y, h.z * g.z);
+        }
+        l = sl / sw;
+        mu = u - fi;
+        mv = v - fj;
+    }
+    if (history) { history[3 * (size_t)p] = h.x; history[3 * (size_t)p + 1] = h.y; history[3 * (size_t)p + 2] = h.z; }
+    if (length) length[p] = l;
+    if (motion) { motion[2 * (size_t)p] = mu; motion[2 * (size_t)p + 1] = mv; }
+}
+
+// the nodes of one k_reproject_moving call (ReprojectMovingJob)
+struct MovingNodes {
+    const bhrt_node *nodes;
+    const int32_t *chain;
+    const uint32_t *prev; // kPrevNodeWords per node
+    int n_nodes;
+};
+
+// Stage 1M.  k_reproject's body with the id check, the chain walk of a moved node and the prev_id test added.
+template <bool kAlbedo>
+__global__ void __launch_bounds__(256) k_reproject_moving(int W, int H, ReprojectFrame F, float depth_tolerance, float normal_threshold, MovingNodes M,
+                                                          const float *__restrict__ pz, const float *__restrict__ pn, const float *__restrict__ pc,
+                                                          const float *__restrict__ pl, const float *__restrict__ pa, const int32_t *__restrict__ pid,
+                                                          const float *__restrict__ z, const float *__restrict__ n, const float *__restrict__ a,
+                                                          const int32_t *__restrict__ id, float *__restrict__ history, float *__restrict__ length,
+                                                          float *__restrict__ motion)
+{
+    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= (uint32_t)(W * H)) return;
+    const int j = (int)(p / (uint32_t)W), i = (int)(p - (uint32_t)j * (uint32_t)W);
+    const float fi = (float)i, fj = (float)j, zp = z[p];
+    const bool miss = zp >= BHRT_BIGFLOAT;
+    float u = fi, v = fj, t = 0.f;
+    bool ok = true;
+    V3 nu = v3(0, 0, 0);
+    int32_t k = -1;
+    if (!miss) {
+        const V3 d = ((F.top_left + fi * F.dd_x) - fj * F.dd_y) - F.pos;
+        V3 x = F.pos + d * zp;
+        V3 nl = v3(n[3 * (size_t)p], n[3 * (size_t)p + 1], n[3 * (size_t)p + 2]);
+        k = id[p];
+        const bool known = (uint32_t)k < (uint32_t)M.n_nodes; // a negative k wraps above every n_nodes
+        if (known && M.prev[(size_t)k * kPrevNodeWords + 21] != 0u) {
+            const int32_t *c = M.chain + (size_t)k * BHRT_MAX_NODE_DEPTH;
+            const int m = min(M.nodes[k].depth, BHRT_MAX_NODE_DEPTH);
+            for (int l = 0; l < m; l++) {
+                const bhrt_xform &xf = M.nodes[c[l]].xf;
+                x = mat_mul(xf.itm, x - v3(xf.pos[0], xf.pos[1], xf.pos[2]));
+                nl = mat_tmul(xf.tm, nl);
+            }
+            for (int l = m - 1; l >= 0; l--) {
+                const float *r = (const float *)(M.prev + (size_t)c[l] * kPrevNodeWords);
+                x = mat_mul(r, x) + v3(r[9], r[10], r[11]);
+                nl = mat_tmul(r + 12, nl);
+            }
+        }
+        const V3 q = x - F.ppos;
+        t = dot(q, F.m) / F.Am;
+        ok = known && t > 0.f && t <= 3.402823466e38f;
+        const V3 r = q / t - F.A;
+        u = dot(r, F.pdd_x) / F.xx;
+        v = -(dot(r, F.pdd_y) / F.yy);
+        const float ru = rintf(u), rv = rintf(v);
+        if (fabsf(u - ru) <= 0.0078125f) u = ru;
+        if (fabsf(v - rv) <= 0.0078125f) v = rv;
+        const float ln = dm::sqrt_f((nl.x * nl.x + nl.y * nl.y) + nl.z * nl.z); // unit(nl)
+        nu = ln > 0.f ? v3(nl.x / ln, nl.y / ln, nl.z / ln) : v3(0, 0, 0);
+    }
+    ok = ok && u >= -1.f && u < (float)W && v >= -1.f && v < (float)H;
+    float sw = 0.f, sr = 0.f, sg = 0.f, sb = 0.f, sl = 0.f;
+    if (ok) {
+        const float f0 = floorf(u), g0 = floorf(v);
+        const float fx = u - f0, fy = v - g0, ax = 1.f - fx, ay = 1.f - fy;
+        const int i0 = (int)f0, j0 = (int)g0;
+        const float w4[4] = {ax * ay, fx * ay, ax * fy, fx * fy};
+#pragma unroll
+        for (int e4 = 0; e4 < 4; e4++) {
+            const float w = w4[e4];
+            const int qi = i0 + (e4 & 1), qj = j0 + (e4 >> 1);
+            if (w == 0.f || qi < 0 || qi >= W || qj < 0 || qj >= H) continue;
+            const size_t q = (size_t)qj * W + qi;
+            const float lq = pl ? pl[q] : 1.f, zq = pz[q];
+            if (!(lq > 0.f)) continue;
+            if (miss) {
+                if (!(zq >= BHRT_BIGFLOAT)) continue;
+            } else {
+                if (!(zq < BHRT_BIGFLOAT) || !(fabsf(zq - t) <= depth_tolerance * t)) continue;
+                if (pid && pid[q] != k) continue;
                 if (!(dot(nu, tp_unit(pn, q)) >= normal_threshold)) continue;
             }
             sw = sw + w;
@@ -255,6 +388,43 @@ hipError_t ReprojectLaunch(const ReprojectJob &J, hipStream_t s)
     const bool alb = J.prev_albedo && J.history;
     hipLaunchKernelGGL(alb ? k_reproject<true> : k_reproject<false>, dim3((n_px + 255) / 256), dim3(256), 0, s, J.W, J.H, F, J.o.depth_tolerance, J.o.normal_threshold,
                        J.prev_z, J.prev_normal, J.prev_radiance, J.prev_length, J.prev_albedo, J.z, J.normal, J.albedo, J.history, J.length, J.motion);
+    return hipGetLastError();
+}
+
+const char *ReprojectMovingArgsError(const bhrt_xform *prev_xforms, uint32_t n_nodes)
+{
+    if (!prev_xforms) return "reproject moving: null previous node transforms";
+    auto finite = [](const float *f, int n) { for (int e = 0; e < n; e++) if (!Finite(f[e])) return false; return true; };
+    for (uint32_t k = 0; k < n_nodes; k++) {
+        const bhrt_xform &x = prev_xforms[k];
+        if (!finite(x.tm, 9) || !finite(x.pos, 3) || !finite(x.itm, 9)) return "reproject moving: the previous node transforms must be finite";
+    }
+    return "";
+}
+
+void FillPrevNodes(const bhrt_node *nodes, const bhrt_xform *prev_xforms, uint32_t n_nodes, uint32_t *out)
+{
+    static_assert(sizeof(bhrt_xform) == 84 && kPrevNodeWords * 4 == 88, "a previous record and its flag");
+    static_assert(offsetof(bhrt_xform, tm) == 0 && offsetof(bhrt_xform, pos) == 36 && offsetof(bhrt_xform, itm) == 48, "the kernel reads tm', pos', itm' at words 0, 9, 12");
+    for (uint32_t k = 0; k < n_nodes; k++) { // pre-order: a parent comes before its children
+        uint32_t *o = out + (size_t)k * kPrevNodeWords;
+        memcpy(o, &prev_xforms[k], sizeof(bhrt_xform));
+        const int32_t parent = nodes[k].parent;
+        const bool up = parent >= 0 && (uint32_t)parent < k && out[(size_t)parent * kPrevNodeWords + 21] != 0u;
+        o[21] = up || memcmp(&prev_xforms[k], &nodes[k].xf, sizeof(bhrt_xform)) != 0 ? 1u : 0u;
+    }
+}
+
+hipError_t ReprojectMovingLaunch(const ReprojectMovingJob &J, hipStream_t s)
+{
+    if (!J.history && !J.length && !J.motion) return hipSuccess;
+    const uint32_t n_px = (uint32_t)((size_t)J.W * J.H);
+    const ReprojectFrame F = ReprojectConsts(J.cur, J.prev);
+    const bool alb = J.prev_albedo && J.history;
+    const MovingNodes M = {J.nodes, J.chain, J.prev_nodes, J.n_nodes};
+    hipLaunchKernelGGL(alb ? k_reproject_moving<true> : k_reproject_moving<false>, dim3((n_px + 255) / 256), dim3(256), 0, s, J.W, J.H, F, J.o.depth_tolerance,
+                       J.o.normal_threshold, M, J.prev_z, J.prev_normal, J.prev_radiance, J.prev_length, J.prev_albedo, J.prev_id, J.z, J.normal, J.albedo, J.id, J.history,
+                       J.length, J.motion);
     return hipGetLastError();
 }
 

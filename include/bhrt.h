@@ -186,6 +186,37 @@ int bhrt_scene_get_shutter(const bhrt_scene *scene, int *on, float pose1[9], flo
  * before and after bhrt_scene_set_camera / bhrt_scene_set_lens.  Needs no device.  A host that reprojects (bhrt_reproject*) calls it before it
  * moves the camera. */
 int bhrt_scene_get_camera_frame(const bhrt_scene *scene, float frame[12]);
+/* Moving objects: the names and transforms of the nodes of a loaded scene.  A node is named by its index in the blob's nodes[]
+ * (DFS pre-order of the XML's <object> elements, include/bhrt_flat.h), which is also what bhrt_hits::node and bhrt_first_hit_node* report.
+ *   node_index           the first node whose <object name=> is `name`, in that order; an unknown name or a NULL argument: BHRT_ERR_ARG
+ *   get_node_transform   the blob's record (tm, pos, itm) of that node
+ *   get_node_transforms  all n_nodes records; capacity < n_nodes: BHRT_ERR_ARG.  *n (may be NULL) = n_nodes.  The snapshot a host takes before it
+ *                        moves something (bhrt_reproject_moving* reads it), as bhrt_scene_get_camera_frame is for the camera
+ *   set_node_transform   starts from (tm, pos) — both NULL: the identity; exactly one NULL: BHRT_ERR_ARG — applies the ops in order with the
+ *                        loader's own Transformation operations (xmlload.cpp:275-303: a rotate's axis is normalised, its angle is in degrees) and
+ *                        stores tm, pos and itm as the loader stores them.  Called with the node's current tm / pos and ops o_1 .. o_n,
+ *                        bhrt_scene_flat is afterwards byte-identical to the blob of the same XML with <scale> / <rotate> / <translate> elements
+ *                        for o_1 .. o_n appended to that <object>; called with NULL / NULL, to the blob with the node's transform children
+ *                        replaced by them.  Restoring a saved record is (tm, pos, no ops).  The pointer bhrt_scene_flat returned stays valid.
+ * BHRT_ERR_ARG, with nothing changed and before any device is touched: a NULL scene; a node outside [0, n_nodes); ops == NULL with n_ops > 0; an
+ * unknown kind; a component that is not finite; a rotate axis of length 0; a result whose tm, pos or itm holds a value that is not finite (a
+ * singular matrix).  ("Nothing changed" covers BHRT_ERR_ARG: after a BHRT_ERR_HIP from an uploaded scene's refresh the host blob holds the new
+ * record and the device may not.)  None of the calls needs a device.  The refresh writes into the device's live blob with blocking copies, as
+ * the other setters do: the host calls it when the scene's renders and image calls on its own streams have finished.  On an uploaded scene the node's 84 bytes in the device's blob and the camera position
+ * carried through every node's chain are refreshed, and nothing else is uploaded again: between two steps of a progressive session later
+ * samples see the new transform, as with the other setters.  Stated limits: an installed caustic or global photon map is the old scene's (the
+ * host builds it again); the shutter does not interpolate nodes, so there is no object motion blur; lights do not move.  bhrt_scene_clone
+ * carries the names and the edits. */
+enum { BHRT_XFORM_SCALE = 0, BHRT_XFORM_ROTATE = 1, BHRT_XFORM_TRANSLATE = 2 };
+typedef struct bhrt_xform_op {
+    int32_t kind; /* BHRT_XFORM_* */
+    float v[4];   /* scale: x, y, z; rotate: axis x, y, z and the angle in degrees; translate: x, y, z */
+} bhrt_xform_op;
+struct bhrt_xform; /* include/bhrt_flat.h: tm[9], pos[3], itm[9], 84 bytes */
+int bhrt_scene_node_index(const bhrt_scene *scene, const char *name, int32_t *index);
+int bhrt_scene_get_node_transform(const bhrt_scene *scene, int32_t node, struct bhrt_xform *out);
+int bhrt_scene_get_node_transforms(const bhrt_scene *scene, struct bhrt_xform *out, uint32_t capacity, uint32_t *n);
+int bhrt_scene_set_node_transform(bhrt_scene *scene, int32_t node, const float tm[9], const float pos[3], const bhrt_xform_op *ops, uint32_t n_ops);
 /* The emission term.  Every Blinn material carries the <emission> of its XML (xmlload.cpp:344-348: a colour, optionally a texture
  * map); the reference parses it and never shades it, and so does a scene here until it is switched on.  With the term on, every Shade() frame of
  * a Blinn material evaluates to  Shade(hit) + emission.Sample(uvw, duvw)  — one float addition per channel, behind everything Shade() does, on
@@ -339,6 +370,12 @@ int bhrt_tiles_unpack_dev(const void *d_blocks /* world blocks, rank-major */, i
  * Any pointer may be NULL. */
 int bhrt_first_hit_dev(bhrt_scene *scene, float *d_z, float *d_normal, float *d_albedo, void *stream);
 int bhrt_first_hit(bhrt_scene *scene, float *z, float *normal, float *albedo);
+/* The node-id image: W*H int32, row-major, the index into the blob's nodes[] of the first hit of the same un-jittered camera
+ * ray, -1 where nothing is hit: bhrt_hits::node of bhrt_trace_closest* for that ray with BHRT_SIDE_FRONT.  It tells a host which object a
+ * pixel shows.  A kernel of its own beside bhrt_first_hit*'s, whose three images and code are unchanged.  _dev: a device pointer; with a
+ * stream the call does not synchronise.  A NULL image: BHRT_ERR_ARG. */
+int bhrt_first_hit_node_dev(bhrt_scene *scene, int32_t *d_node, void *stream);
+int bhrt_first_hit_node(bhrt_scene *scene, int32_t *node);
 /* Sampled guide images: the same three images, and the coverage, formed by the render's own camera samples, so that they are
  * averaged over the pixel footprint the colour image is averaged over: jitter and, with bhrt_opts.lens, the aperture.  For an owned pixel inside
  * the image and n = spp, sample s = 0 .. n-1 has the camera ray the render forms for (seed, pixel, s) (what bhrt_camera_rays returns), its first
@@ -410,7 +447,7 @@ int bhrt_denoise_sampled(bhrt_scene *scene, const bhrt_denoise_opts *opts, float
  * When the camera moves between two frames, bhrt_reproject* finds for every pixel of the new view where its surface point was in the previous
  * view and fetches the light gathered there if it is still the same surface; bhrt_temporal_accumulate* blends the new frame's samples into it.
  * Both stages are stated exactly in csrc/temporal.hip (float32, a fixed order: the same inputs give the same bytes).  They run beside the
- * render path and change no render.  Not covered: moving objects (the scene has none); lens and shutter (the guides stay the pinhole ray's, as
+ * render path and change no render.  Moving objects: bhrt_reproject_moving* below.  Not covered: lens and shutter (the guides stay the pinhole ray's, as
  * for bhrt_denoise*); reflections and refractions are reprojected as if they were surface light; a progressive session's state is not seeded.
  *
  * bhrt_reproject*: the current view is the scene's camera, W x H.  prev_frame: the previous view's bhrt_scene_get_camera_frame, a HOST pointer
@@ -441,6 +478,25 @@ int bhrt_reproject_dev(bhrt_scene *scene, const bhrt_reproject_opts *opts, const
 int bhrt_reproject(bhrt_scene *scene, const bhrt_reproject_opts *opts, const float prev_frame[12], const float *prev_z, const float *prev_normal,
                    const float *prev_radiance, const float *prev_length, const float *prev_albedo, const float *z, const float *normal, const float *albedo,
                    float *history, float *length, float *motion);
+/* Reprojection through object motion (stated exactly in csrc/temporal.hip beside stage 1).  bhrt_reproject* with three more
+ * arguments: prev_xforms, the bhrt_scene_get_node_transforms snapshot of the previous frame (n_nodes records, a HOST pointer in both variants);
+ * prev_id (W*H int32, optional), the previous view's bhrt_first_hit_node*; id (W*H int32), the current view's, NULL = computed here.  A hit
+ * pixel whose node, or an ancestor of it, has other bhrt_xform bytes in prev_xforms than in the scene is carried to where its surface point was
+ * before the move — through the node's chain with the current records, back out with the previous ones — and its normal takes the same path;
+ * with prev_id a tap is valid only if the previous view showed the same node there.  A hit pixel whose id is outside [0, n_nodes) is invalid
+ * (the kernel does not index with it).  With nothing moved every output is bhrt_reproject*'s bit for bit.  motion contains the object's motion.
+ * BHRT_ERR_ARG before any device is touched: everything bhrt_reproject* refuses, a NULL prev_xforms, a prev_xforms value that is not finite.
+ * Scratch is the scene's, as for bhrt_reproject*: 28 B per pixel for guides computed here, 4 B per pixel for an id computed here; calls on one
+ * scene must not overlap.  The previous records (88 B per node) reach the device on the call's own stream from pinned memory of the scene, two
+ * buffers used in turn: calls issued one after the other on one stream are ordered by it and each keeps its own records, and with a stream
+ * the call does not wait for the device, except that the third call in a row waits until the stream has passed the first. */
+int bhrt_reproject_moving_dev(bhrt_scene *scene, const bhrt_reproject_opts *opts, const float prev_frame[12], const struct bhrt_xform *prev_xforms,
+                              const float *d_prev_z, const float *d_prev_normal, const float *d_prev_radiance, const float *d_prev_length, const float *d_prev_albedo,
+                              const int32_t *d_prev_id, const float *d_z, const float *d_normal, const float *d_albedo, const int32_t *d_id, float *d_history,
+                              float *d_length, float *d_motion, void *stream);
+int bhrt_reproject_moving(bhrt_scene *scene, const bhrt_reproject_opts *opts, const float prev_frame[12], const struct bhrt_xform *prev_xforms, const float *prev_z,
+                          const float *prev_normal, const float *prev_radiance, const float *prev_length, const float *prev_albedo, const int32_t *prev_id,
+                          const float *z, const float *normal, const float *albedo, const int32_t *id, float *history, float *length, float *motion);
 /* bhrt_temporal_accumulate*: radiance (W*H*3, required): the current frame; cur_samples: the samples behind it (> 0); history, length:
  * bhrt_reproject*'s (either NULL: no pixel has a history, out = radiance).  A pixel with length > 0 blends: out = h + (c - h) * a with
  * a = cur_samples / (l + cur_samples), l = min(length, max_length), after h has been clamped to mean +- clamp_k standard deviations of the
