@@ -240,6 +240,11 @@ __device__ inline unsigned long long wave_max64(unsigned long long v)
     }
     return v;
 }
+// One element's entry in a box reduction.  A NaN bound never enters a box: `if (b > v) b = v` is false for it (only an element's
+// FIRST vertex can leave one in its bounds, elem_bounds seeds from it), so it contributes the neutral key, per axis and per side,
+// which k_bvh_boxes reads as "no element".  ord_key alone would sort +NaN above +inf and -NaN below -inf and let it win.
+__device__ inline unsigned long long min_key(float lo, uint32_t i) { return lo != lo ? ~0ull : (((unsigned long long)ord_key(lo) << 32) | i); }
+__device__ inline unsigned long long max_key(float hi, uint32_t i) { return hi != hi ? 0ull : (((unsigned long long)ord_key(hi) << 32) | (0xffffffffu - i)); }
 // elements move to their child node; the children's boxes gather (value, first position) extremes
 __global__ void __launch_bounds__(kB) k_bvh_assign(Mesh M, const uint32_t *elems, uint32_t *enode, TNode *nodes, uint32_t n, uint32_t level)
 {
@@ -259,8 +264,8 @@ __global__ void __launch_bounds__(kB) k_bvh_assign(Mesh M, const uint32_t *elems
     if (uniform && target == 0xffffffffu) return;
     unsigned long long kmin[3], kmax[3];
     for (int k = 0; k < 3; k++) {
-        kmin[k] = target != 0xffffffffu ? (((unsigned long long)ord_key(eb[k]) << 32) | i) : ~0ull;
-        kmax[k] = target != 0xffffffffu ? (((unsigned long long)ord_key(eb[k + 3]) << 32) | (0xffffffffu - i)) : 0ull;
+        kmin[k] = target != 0xffffffffu ? min_key(eb[k], i) : ~0ull;
+        kmax[k] = target != 0xffffffffu ? max_key(eb[k + 3], i) : 0ull;
     }
     if (uniform) { // whole wave feeds one child: six atomics per wave
         for (int k = 0; k < 3; k++) { kmin[k] = wave_min64(kmin[k]); kmax[k] = wave_max64(kmax[k]); }
@@ -291,8 +296,8 @@ __global__ void __launch_bounds__(kB) k_bvh_root_keys(Mesh M, const uint32_t *el
     float eb[6];
     if (i < n) elem_bounds(M, elems[i], eb);
     for (int k = 0; k < 3; k++) {
-        unsigned long long kmin = i < n ? (((unsigned long long)ord_key(eb[k]) << 32) | i) : ~0ull;
-        unsigned long long kmax = i < n ? (((unsigned long long)ord_key(eb[k + 3]) << 32) | (0xffffffffu - i)) : 0ull;
+        unsigned long long kmin = i < n ? min_key(eb[k], i) : ~0ull;
+        unsigned long long kmax = i < n ? max_key(eb[k + 3], i) : 0ull;
         kmin = wave_min64(kmin); kmax = wave_max64(kmax);
         if (__lane_id() == 0) { atomicMin(&nodes[0].key[k], kmin); atomicMax(&nodes[0].key[k + 3], kmax); }
     }
