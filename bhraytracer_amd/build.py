@@ -18,7 +18,7 @@ OUT = os.path.join(HERE, "_build")
 LIB = os.path.join(HERE, "libbhrt.so")
 CLI = os.path.join(HERE, "bhrt")
 
-HOST_SRCS = ["scene_host.cpp", "png_io.cpp", "capi_host.cpp", "photon_host.cpp"]
+HOST_SRCS = ["scene_host.cpp", "png_io.cpp", "capi_host.cpp", "scene_edit.cpp", "photon_host.cpp"]
 HIP_SRCS = ["kernels.hip", "bvh_build.hip", "gather_sort.hip", "denoise.hip", "temporal.hip"]
 COMMON = ["-O3", "-ffp-contract=off", "-fPIC", "-std=c++17", "-I" + os.path.join(ROOT, "include"), "-I" + CSRC]
 

@@ -1,6 +1,6 @@
 // device_state.h — what a scene owns on its device: memory, streams, events, the installed photon map.
 // Part of the kernels.hip translation unit, included there behind the kernels (it uses their argument types and HIP_CHECK); not a header for
-// other files: they see `struct DeviceState;` (scene_internal.h) and DestroyDeviceState.
+// other files: they see `struct DeviceState;`, DestroyDeviceState and the Refresh* hooks of the scene setters (scene_internal.h).
 #pragma once
 
 namespace bhrt {

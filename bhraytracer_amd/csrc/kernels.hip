@@ -2305,7 +2305,7 @@ static int EnsureUploaded(bhrt_scene *scene)
 
 // The device's copy of the scene's emission state (FlatScene::emission / emissive): at upload, and again by the setters of an uploaded scene.
 // Calls on one scene do not overlap and every render synchronises its stream before it returns, so no kernel is reading the array.
-static int RefreshEmission(bhrt_scene *scene)
+int RefreshEmission(bhrt_scene *scene)
 {
     DeviceState *D = scene->dev;
     if (!D) return BHRT_OK;
@@ -2332,7 +2332,7 @@ static int RefreshEmission(bhrt_scene *scene)
 // The device's copy of the scene's face-material state (FlatScene::sub_* / face_materials): at upload, and again by the setter of
 // an uploaded scene.  With the switch on the kernels' material table and R0s are the extended ones and DeviceState::fm selects the kFm kernels;
 // with it off everything points where it did before the switch existed.  Between renders, as RefreshEmission.
-static int RefreshFaceMaterials(bhrt_scene *scene)
+int RefreshFaceMaterials(bhrt_scene *scene)
 {
     DeviceState *D = scene->dev;
     if (!D) return BHRT_OK;
@@ -2369,6 +2369,74 @@ static int RefreshFaceMaterials(bhrt_scene *scene)
         D->fm.tab = nullptr; D->fm.base = 0;
     }
     return BHRT_OK;
+}
+
+// DevScene::cam_chain of the scene's camera: its position through every node's chain, p' = itm * (p - pos) per level, the depth-1 ancestor
+// first.  cc: n_nodes x BHRT_MAX_NODE_DEPTH x 3 floats.  The upload and UploadCamChain share it.
+static void FillCamChain(const bhrt::FlatScene &flat, float *cc)
+{
+    const bhrt_flat_header *H = flat.hdr();
+    const bhrt_node *nodes = (const bhrt_node *)(flat.blob.data() + H->off_nodes);
+    for (uint32_t n = 0; n < H->n_nodes; n++) {
+        int32_t chain[BHRT_MAX_NODE_DEPTH] = {};
+        const int depth = std::min<int>(nodes[n].depth, BHRT_MAX_NODE_DEPTH);
+        for (int k = depth - 1, c = (int)n; c >= 0 && k >= 0; k--) { chain[k] = c; c = nodes[c].parent; }
+        V3 p = v3(H->camera.pos[0], H->camera.pos[1], H->camera.pos[2]);
+        for (int k = 0; k < depth; k++) {
+            const bhrt_xform &t = nodes[chain[k]].xf;
+            p = mat_mul(t.itm, p - v3(t.pos[0], t.pos[1], t.pos[2]));
+            float *o3 = cc + ((size_t)n * BHRT_MAX_NODE_DEPTH + k) * 3;
+            o3[0] = p.x; o3[1] = p.y; o3[2] = p.z;
+        }
+    }
+}
+
+// cam_chain of an uploaded scene again, on the current device: the camera or a node on some chain has moved
+static int UploadCamChain(bhrt_scene *scene)
+{
+    DeviceState *D = scene->dev;
+    std::vector<float> cc((size_t)std::max<uint32_t>(scene->flat.hdr()->n_nodes, 1) * BHRT_MAX_NODE_DEPTH * 3, 0.f);
+    FillCamChain(scene->flat, cc.data());
+    HIP_CHECK(hipMemcpy(const_cast<float *>(D->S.cam_chain), cc.data(), cc.size() * sizeof(float), hipMemcpyHostToDevice));
+    return BHRT_OK;
+}
+
+// These three and RefreshShutter, RefreshEmission, RefreshFaceMaterials are what the setters of scene_edit.cpp end in (scene_internal.h)
+int RefreshCamChain(bhrt_scene *scene)
+{
+    DeviceState *D = scene->dev;
+    if (!D) return BHRT_OK;
+    HIP_CHECK(hipSetDevice(D->device));
+    return UploadCamChain(scene);
+}
+
+int RefreshNodeXform(bhrt_scene *scene, size_t off, const bhrt_xform &xf)
+{
+    DeviceState *D = scene->dev;
+    if (!D) return BHRT_OK;
+    HIP_CHECK(hipSetDevice(D->device));
+    HIP_CHECK(hipMemcpy(D->d_blob.p + off, &xf, sizeof xf, hipMemcpyHostToDevice));
+    return UploadCamChain(scene);
+}
+
+void RefreshCamera(bhrt_scene *scene)
+{
+    if (scene->dev) scene->dev->S.cam = scene->flat.hdr()->camera;
+}
+
+// The kernels' copy of the scene's shutter (FlatScene::shutter*, DESIGN.md 18): at upload, and again by the setters of an uploaded scene.  A
+// kernel argument, so there is nothing to copy to the device.
+void RefreshShutter(bhrt_scene *scene)
+{
+    DeviceState *D = scene->dev;
+    if (!D) return;
+    const bhrt_camera &c = scene->flat.shutter_cam;
+    ShutterInfo sh = {};
+    if (scene->flat.shutter) {
+        for (int k = 0; k < 3; k++) { sh.pos1[k] = c.pos[k]; sh.top_left1[k] = c.top_left[k]; sh.dd_x1[k] = c.dd_x[k]; sh.dd_y1[k] = c.dd_y[k]; }
+        sh.on = 1;
+    }
+    D->shutter = sh;
 }
 
 static int EnsureWorkspace(DeviceState *D, uint32_t cap_samples, double frames_per_sample)
@@ -3566,41 +3634,6 @@ try {
     return BHRT_OK;
 } catch (...) { return bhrt::AbiException(); }
 
-// DevScene::cam_chain of the scene's camera: its position through every node's chain, p' = itm * (p - pos) per level, the depth-1 ancestor
-// first.  cc: n_nodes x BHRT_MAX_NODE_DEPTH x 3 floats.  The upload and bhrt_scene_set_camera share it.
-static void FillCamChain(const bhrt::FlatScene &flat, float *cc)
-{
-    const bhrt_flat_header *H = flat.hdr();
-    const bhrt_node *nodes = (const bhrt_node *)(flat.blob.data() + H->off_nodes);
-    for (uint32_t n = 0; n < H->n_nodes; n++) {
-        int32_t chain[BHRT_MAX_NODE_DEPTH] = {};
-        const int depth = std::min<int>(nodes[n].depth, BHRT_MAX_NODE_DEPTH);
-        for (int k = depth - 1, c = (int)n; c >= 0 && k >= 0; k--) { chain[k] = c; c = nodes[c].parent; }
-        V3 p = v3(H->camera.pos[0], H->camera.pos[1], H->camera.pos[2]);
-        for (int k = 0; k < depth; k++) {
-            const bhrt_xform &t = nodes[chain[k]].xf;
-            p = mat_mul(t.itm, p - v3(t.pos[0], t.pos[1], t.pos[2]));
-            float *o3 = cc + ((size_t)n * BHRT_MAX_NODE_DEPTH + k) * 3;
-            o3[0] = p.x; o3[1] = p.y; o3[2] = p.z;
-        }
-    }
-}
-
-// The kernels' copy of the scene's shutter (FlatScene::shutter*, DESIGN.md 18): at upload, and again by the setters of an uploaded scene.  A
-// kernel argument, so there is nothing to copy to the device.
-static void RefreshShutter(bhrt_scene *scene)
-{
-    DeviceState *D = scene->dev;
-    if (!D) return;
-    const bhrt_camera &c = scene->flat.shutter_cam;
-    ShutterInfo sh = {};
-    if (scene->flat.shutter) {
-        for (int k = 0; k < 3; k++) { sh.pos1[k] = c.pos[k]; sh.top_left1[k] = c.top_left[k]; sh.dd_x1[k] = c.dd_x[k]; sh.dd_y1[k] = c.dd_y[k]; }
-        sh.on = 1;
-    }
-    D->shutter = sh;
-}
-
 int bhrt_scene_upload(bhrt_scene *scene, int device)
 try {
     if (!scene) { SetError("null scene"); return BHRT_ERR_ARG; }
@@ -4089,227 +4122,6 @@ try {
     return BHRT_OK;
 } catch (...) { return bhrt::AbiException(); }
 
-// bhrt_scene_set_lens lives in this translation unit because it refreshes the kernels' copy of the camera (DeviceState::S)
-int bhrt_scene_set_lens(bhrt_scene *scene, float focaldist, float dof)
-try {
-    if (!scene) { SetError("bhrt_scene_set_lens: null scene"); return BHRT_ERR_ARG; }
-    if (!(dof >= 0.f && dof <= 3.402823466e38f)) { SetError("bhrt_scene_set_lens: dof must be finite and >= 0"); return BHRT_ERR_ARG; }
-    if (!(focaldist >= -3.402823466e38f && focaldist <= 3.402823466e38f)) { SetError("bhrt_scene_set_lens: focaldist is not finite"); return BHRT_ERR_ARG; }
-    bhrt_flat_header *H = reinterpret_cast<bhrt_flat_header *>(scene->flat.blob.data());
-    if (focaldist > 0.f) H->camera.focaldist = focaldist;
-    H->camera.dof = dof;
-    DeriveCameraFrame(H->camera);
-    if (scene->flat.shutter) { // pose 1 takes the scene's focaldist and dof: its frame follows
-        bhrt_camera &c1 = scene->flat.shutter_cam;
-        c1.focaldist = H->camera.focaldist; c1.dof = H->camera.dof;
-        DeriveCameraFrame(c1);
-    }
-    if (scene->dev) scene->dev->S.cam = H->camera;
-    RefreshShutter(scene);
-    return BHRT_OK;
-} catch (...) { return bhrt::AbiException(); }
-
-// ---- the camera and its shutter.  In this translation unit because the setters refresh an uploaded scene.
-static bool Finite3(const float *v) { return v && std::isfinite(v[0]) && std::isfinite(v[1]) && std::isfinite(v[2]); }
-// Pose 1 of a shutter: the camera `base` (fov, focaldist, dof, size) at (pos, target, up); "" = a valid pose, else what is wrong
-static const char *PoseCamera(const bhrt_camera &base, const float pos[3], const float target[3], const float up[3], bhrt_camera &out)
-{
-    if (!pos || !target || !up) return "a NULL pointer";
-    if (!Finite3(pos) || !Finite3(target) || !Finite3(up)) return "a component that is not finite";
-    out = base;
-    if (!SetCameraPose(out, pos, target, up, base.fov)) return "target == pos, or up parallel to target - pos";
-    for (int k = 0; k < 3; k++)
-        if (!std::isfinite(out.dir[k]) || !std::isfinite(out.up[k]) || !std::isfinite(out.top_left[k]) || !std::isfinite(out.dd_x[k]) || !std::isfinite(out.dd_y[k]))
-            return "a camera frame that is not finite";
-    return "";
-}
-
-int bhrt_scene_set_camera(bhrt_scene *scene, const float pos[3], const float target[3], const float up[3], float fov)
-try {
-    if (!scene) { SetError("bhrt_scene_set_camera: null scene"); return BHRT_ERR_ARG; }
-    if (!std::isfinite(fov) || fov >= 180.f) { SetError("bhrt_scene_set_camera: fov must be finite and below 180 (<= 0 keeps the current one)"); return BHRT_ERR_ARG; }
-    bhrt_flat_header *H = reinterpret_cast<bhrt_flat_header *>(scene->flat.blob.data());
-    bhrt_camera base = H->camera, cam, cam1 = scene->flat.shutter_cam;
-    if (fov > 0.f) base.fov = fov;
-    const char *bad = PoseCamera(base, pos, target, up, cam);
-    if (*bad) { SetError(std::string("bhrt_scene_set_camera: ") + bad); return BHRT_ERR_ARG; }
-    if (scene->flat.shutter) { // pose 1 takes the new fov; the pair that results must still be less than a quarter turn apart
-        bad = PoseCamera(base, scene->flat.shutter_pos, scene->flat.shutter_target, scene->flat.shutter_up, cam1);
-        if (!*bad) bad = ShutterPairError(cam, cam1);
-        if (*bad) { SetError(std::string("bhrt_scene_set_camera: with the shutter's pose 1: ") + bad); return BHRT_ERR_ARG; }
-    }
-    H->camera = cam; // nothing above changed the scene
-    scene->flat.shutter_cam = cam1;
-    if (DeviceState *D = scene->dev) { // the kernels' camera and the camera position through every node's chain; nothing else is uploaded again
-        HIP_CHECK(hipSetDevice(D->device));
-        std::vector<float> cc((size_t)std::max<uint32_t>(H->n_nodes, 1) * BHRT_MAX_NODE_DEPTH * 3, 0.f);
-        FillCamChain(scene->flat, cc.data());
-        HIP_CHECK(hipMemcpy(const_cast<float *>(D->S.cam_chain), cc.data(), cc.size() * sizeof(float), hipMemcpyHostToDevice));
-        D->S.cam = H->camera;
-        RefreshShutter(scene);
-    }
-    return BHRT_OK;
-} catch (...) { return bhrt::AbiException(); }
-
-int bhrt_scene_set_shutter(bhrt_scene *scene, int on, const float pos1[3], const float target1[3], const float up1[3])
-try {
-    if (!scene) { SetError("bhrt_scene_set_shutter: null scene"); return BHRT_ERR_ARG; }
-    bhrt::FlatScene &F = scene->flat;
-    if (!on) {
-        F.shutter = 0;
-        memset(F.shutter_pos, 0, sizeof F.shutter_pos); memset(F.shutter_target, 0, sizeof F.shutter_target); memset(F.shutter_up, 0, sizeof F.shutter_up);
-        memset(&F.shutter_cam, 0, sizeof F.shutter_cam);
-        RefreshShutter(scene);
-        return BHRT_OK;
-    }
-    bhrt_camera cam1;
-    const char *bad = PoseCamera(F.hdr()->camera, pos1, target1, up1, cam1);
-    if (!*bad) bad = ShutterPairError(F.hdr()->camera, cam1);
-    if (*bad) { SetError(std::string("bhrt_scene_set_shutter: ") + bad); return BHRT_ERR_ARG; }
-    F.shutter = 1;
-    for (int k = 0; k < 3; k++) { F.shutter_pos[k] = pos1[k]; F.shutter_target[k] = target1[k]; F.shutter_up[k] = up1[k]; }
-    F.shutter_cam = cam1;
-    RefreshShutter(scene);
-    return BHRT_OK;
-} catch (...) { return bhrt::AbiException(); }
-
-int bhrt_scene_get_shutter(const bhrt_scene *scene, int *on, float pose1[9], float frame1[12])
-try {
-    if (!scene) { SetError("bhrt_scene_get_shutter: null scene"); return BHRT_ERR_ARG; }
-    const bhrt::FlatScene &F = scene->flat;
-    const bhrt_camera &c = F.shutter_cam;
-    if (on) *on = F.shutter;
-    if (pose1) for (int k = 0; k < 3; k++) { pose1[k] = F.shutter_pos[k]; pose1[3 + k] = F.shutter_target[k]; pose1[6 + k] = F.shutter_up[k]; }
-    if (frame1) for (int k = 0; k < 3; k++) { frame1[k] = c.pos[k]; frame1[3 + k] = c.top_left[k]; frame1[6 + k] = c.dd_x[k]; frame1[9 + k] = c.dd_y[k]; }
-    return BHRT_OK;
-} catch (...) { return bhrt::AbiException(); }
-
-int bhrt_scene_get_camera_frame(const bhrt_scene *scene, float frame[12])
-try {
-    if (!scene || !frame) { SetError("bhrt_scene_get_camera_frame: null argument"); return BHRT_ERR_ARG; }
-    const bhrt_camera &c = scene->flat.hdr()->camera;
-    for (int k = 0; k < 3; k++) { frame[k] = c.pos[k]; frame[3 + k] = c.top_left[k]; frame[6 + k] = c.dd_x[k]; frame[9 + k] = c.dd_y[k]; }
-    return BHRT_OK;
-} catch (...) { return bhrt::AbiException(); }
-
-// ---- moving objects: node names and transforms.  In this translation unit because the setter refreshes an uploaded scene.
-int bhrt_scene_node_index(const bhrt_scene *scene, const char *name, int32_t *index)
-try {
-    if (!scene || !name || !index) { SetError("bhrt_scene_node_index: null argument"); return BHRT_ERR_ARG; }
-    const std::vector<std::string> &names = scene->flat.node_names;
-    for (size_t i = 0; i < names.size(); i++) // the first of that name in the blob's pre-order
-        if (names[i] == name) { *index = (int32_t)i; return BHRT_OK; }
-    SetError(std::string("bhrt_scene_node_index: no node named \"") + name + "\"");
-    return BHRT_ERR_ARG;
-} catch (...) { return bhrt::AbiException(); }
-
-static const bhrt_node *HostNodes(const bhrt_scene *scene) { return (const bhrt_node *)(scene->flat.blob.data() + scene->flat.hdr()->off_nodes); }
-
-int bhrt_scene_get_node_transform(const bhrt_scene *scene, int32_t node, bhrt_xform *out)
-try {
-    if (!scene || !out) { SetError("bhrt_scene_get_node_transform: null argument"); return BHRT_ERR_ARG; }
-    if (node < 0 || (uint32_t)node >= scene->flat.hdr()->n_nodes) { SetError("bhrt_scene_get_node_transform: node index out of range"); return BHRT_ERR_ARG; }
-    *out = HostNodes(scene)[node].xf;
-    return BHRT_OK;
-} catch (...) { return bhrt::AbiException(); }
-
-int bhrt_scene_get_node_transforms(const bhrt_scene *scene, bhrt_xform *out, uint32_t capacity, uint32_t *n)
-try {
-    if (!scene) { SetError("bhrt_scene_get_node_transforms: null scene"); return BHRT_ERR_ARG; }
-    const uint32_t n_nodes = scene->flat.hdr()->n_nodes;
-    if (n) *n = n_nodes;
-    if (capacity < n_nodes || (n_nodes > 0 && !out)) { SetError("bhrt_scene_get_node_transforms: room for " + std::to_string(n_nodes) + " records is needed"); return BHRT_ERR_ARG; }
-    for (uint32_t k = 0; k < n_nodes; k++) out[k] = HostNodes(scene)[k].xf;
-    return BHRT_OK;
-} catch (...) { return bhrt::AbiException(); }
-
-int bhrt_scene_set_node_transform(bhrt_scene *scene, int32_t node, const float tm[9], const float pos[3], const bhrt_xform_op *ops, uint32_t n_ops)
-try {
-    if (!scene) { SetError("bhrt_scene_set_node_transform: null scene"); return BHRT_ERR_ARG; }
-    const bhrt_flat_header *H = scene->flat.hdr();
-    if (node < 0 || (uint32_t)node >= H->n_nodes) { SetError("bhrt_scene_set_node_transform: node index out of range"); return BHRT_ERR_ARG; }
-    bhrt_xform xf;
-    const char *bad = bhrt::BuildNodeXform(tm, pos, ops, n_ops, xf);
-    if (*bad) { SetError(std::string("bhrt_scene_set_node_transform: ") + bad); return BHRT_ERR_ARG; }
-    const size_t off = (size_t)H->off_nodes + (size_t)node * sizeof(bhrt_node) + offsetof(bhrt_node, xf);
-    memcpy(scene->flat.blob.data() + off, &xf, sizeof xf); // nothing above changed the scene
-    if (DeviceState *D = scene->dev) { // the node's 84 bytes and the camera position through every node's chain; nothing else is uploaded again
-        HIP_CHECK(hipSetDevice(D->device));
-        HIP_CHECK(hipMemcpy(D->d_blob.p + off, &xf, sizeof xf, hipMemcpyHostToDevice));
-        std::vector<float> cc((size_t)std::max<uint32_t>(H->n_nodes, 1) * BHRT_MAX_NODE_DEPTH * 3, 0.f);
-        FillCamChain(scene->flat, cc.data());
-        HIP_CHECK(hipMemcpy(const_cast<float *>(D->S.cam_chain), cc.data(), cc.size() * sizeof(float), hipMemcpyHostToDevice));
-    }
-    return BHRT_OK;
-} catch (...) { return bhrt::AbiException(); }
-
-// ---- the emission term: scene state beside the blob.  In this translation unit because the setters refresh an uploaded scene.
-int bhrt_scene_set_emissive(bhrt_scene *scene, int on)
-try {
-    if (!scene) { SetError("bhrt_scene_set_emissive: null scene"); return BHRT_ERR_ARG; }
-    scene->flat.emissive = on ? 1 : 0;
-    return RefreshEmission(scene);
-} catch (...) { return bhrt::AbiException(); }
-
-int bhrt_scene_material_index(const bhrt_scene *scene, const char *name, int32_t *index)
-try {
-    if (!scene || !name || !index) { SetError("bhrt_scene_material_index: null argument"); return BHRT_ERR_ARG; }
-    const std::vector<std::string> &names = scene->flat.material_names;
-    for (size_t i = 0; i < names.size(); i++) // the first of that name, as the loader's own lookup (xmlload.cpp:101-107)
-        if (names[i] == name) { *index = (int32_t)i; return BHRT_OK; }
-    SetError(std::string("bhrt_scene_material_index: no material named \"") + name + "\"");
-    return BHRT_ERR_ARG;
-} catch (...) { return bhrt::AbiException(); }
-
-int bhrt_scene_set_material_emission(bhrt_scene *scene, int32_t material, const float rgb[3])
-try {
-    if (!scene || !rgb) { SetError("bhrt_scene_set_material_emission: null argument"); return BHRT_ERR_ARG; }
-    if (material < 0 || (size_t)material >= scene->flat.emission.size()) { SetError("bhrt_scene_set_material_emission: material index out of range"); return BHRT_ERR_ARG; }
-    bhrt_texcolor &e = scene->flat.emission[(size_t)material];
-    e.color[0] = rgb[0]; e.color[1] = rgb[1]; e.color[2] = rgb[2];
-    e.map = -1;
-    return RefreshEmission(scene);
-} catch (...) { return bhrt::AbiException(); }
-
-int bhrt_scene_get_material_emission(const bhrt_scene *scene, int32_t material, float rgb[3], int32_t *texmap)
-try {
-    if (!scene) { SetError("bhrt_scene_get_material_emission: null scene"); return BHRT_ERR_ARG; }
-    if (material < 0 || (size_t)material >= scene->flat.emission.size()) { SetError("bhrt_scene_get_material_emission: material index out of range"); return BHRT_ERR_ARG; }
-    const bhrt_texcolor &e = scene->flat.emission[(size_t)material];
-    if (rgb) { rgb[0] = e.color[0]; rgb[1] = e.color[1]; rgb[2] = e.color[2]; }
-    if (texmap) *texmap = e.map;
-    return BHRT_OK;
-} catch (...) { return bhrt::AbiException(); }
-
-// ---- face materials: scene state beside the blob.  The setter is in this translation unit because it refreshes an uploaded scene.
-int bhrt_scene_set_face_materials(bhrt_scene *scene, int on)
-try {
-    if (!scene) { SetError("bhrt_scene_set_face_materials: null scene"); return BHRT_ERR_ARG; }
-    scene->flat.face_materials = on ? 1 : 0;
-    return RefreshFaceMaterials(scene);
-} catch (...) { return bhrt::AbiException(); }
-
-int bhrt_scene_submaterial_count(const bhrt_scene *scene, int32_t material, int32_t *n)
-try {
-    if (!scene || !n) { SetError("bhrt_scene_submaterial_count: null argument"); return BHRT_ERR_ARG; }
-    const std::vector<int32_t> &first = scene->flat.sub_first;
-    if (material < 0 || (size_t)material + 1 >= first.size()) { SetError("bhrt_scene_submaterial_count: material index out of range"); return BHRT_ERR_ARG; }
-    *n = first[(size_t)material + 1] - first[(size_t)material];
-    return BHRT_OK;
-} catch (...) { return bhrt::AbiException(); }
-
-int bhrt_scene_get_submaterial(const bhrt_scene *scene, int32_t material, int32_t sub, struct bhrt_material *out, uint32_t *face_end)
-try {
-    if (!scene) { SetError("bhrt_scene_get_submaterial: null scene"); return BHRT_ERR_ARG; }
-    const std::vector<int32_t> &first = scene->flat.sub_first;
-    if (material < 0 || (size_t)material + 1 >= first.size()) { SetError("bhrt_scene_get_submaterial: material index out of range"); return BHRT_ERR_ARG; }
-    if (sub < 0 || sub >= first[(size_t)material + 1] - first[(size_t)material]) { SetError("bhrt_scene_get_submaterial: sub-material index out of range"); return BHRT_ERR_ARG; }
-    const size_t k = (size_t)(first[(size_t)material] + sub);
-    if (out) *out = scene->flat.sub_materials[k];
-    if (face_end) *face_end = scene->flat.sub_face_end[k];
-    return BHRT_OK;
-} catch (...) { return bhrt::AbiException(); }
-
 // ---- images beside the colour image ---------------------------------------------------------------
 int bhrt_first_hit_dev(bhrt_scene *scene, float *d_z, float *d_normal, float *d_albedo, void *stream)
 try {
@@ -4736,7 +4548,7 @@ try {
     }
     if (slot.used) HIP_CHECK(hipEventSynchronize(slot.done));
     memset(slot.h.p, 0, pn_words * sizeof(uint32_t));
-    FillPrevNodes(HostNodes(scene), prev_xforms, H->n_nodes, slot.h.p);
+    FillPrevNodes((const bhrt_node *)(scene->flat.blob.data() + H->off_nodes), prev_xforms, H->n_nodes, slot.h.p);
     HIP_CHECK(hipMemcpyAsync(slot.d, slot.h.p, pn_words * sizeof(uint32_t), hipMemcpyHostToDevice, st));
     J.nodes = D->S.nodes; J.chain = D->S.chain; J.prev_nodes = slot.d; J.n_nodes = (int)H->n_nodes;
     const bool want_albedo = d_prev_albedo && d_history; // without albedo' no albedo is read or computed

@@ -15,6 +15,15 @@ void SetError(const std::string &msg);
 int AbiException();
 void DestroyDeviceState(DeviceState *d); // defined in the HIP TU
 
+// What the setters of scene_edit.cpp call after they have changed scene->flat; defined in the HIP TU.  Each brings one part of an uploaded
+// scene's device copy up to date, and returns (BHRT_OK) at once when the scene is not uploaded.  The two that cannot fail return nothing.
+void RefreshCamera(bhrt_scene *scene);       // the kernels' camera (DevScene::cam) from the header's
+void RefreshShutter(bhrt_scene *scene);      // the kernels' shutter (DeviceState::shutter) from FlatScene::shutter*
+int RefreshCamChain(bhrt_scene *scene);      // DevScene::cam_chain, filled and uploaded again: the camera has moved
+int RefreshNodeXform(bhrt_scene *scene, size_t off, const bhrt_xform &xf); // a node's record, at byte off of the blob, then cam_chain: the node is on some chain
+int RefreshEmission(bhrt_scene *scene);      // FlatScene::emission / emissive
+int RefreshFaceMaterials(bhrt_scene *scene); // FlatScene::face_materials
+
 // The host side of a progressive session (bhrt_progressive_*): the options it was begun with and what the steps so far have left.
 // Everything bhrt_progressive_status reports is kept here: a step reads back one word (the next list's length), and every pixel that left
 // the list in a step retired at that step's count.  The per-pixel state is device memory (DeviceState::d_prog), allocated by the first step or frame.
