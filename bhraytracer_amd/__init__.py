@@ -132,6 +132,7 @@ EXPORTS = [
     "bhrt_reproject", "bhrt_reproject_dev", "bhrt_temporal_accumulate", "bhrt_temporal_accumulate_dev",
     "bhrt_scene_node_index", "bhrt_scene_get_node_transform", "bhrt_scene_get_node_transforms", "bhrt_scene_set_node_transform",
     "bhrt_first_hit_node", "bhrt_first_hit_node_dev", "bhrt_reproject_moving", "bhrt_reproject_moving_dev",
+    "bhrt_reproject_var", "bhrt_reproject_var_dev", "bhrt_temporal_accumulate_var", "bhrt_temporal_accumulate_var_dev",
 ]
 
 # BHRT_DENOISE_SIGMA_COVERAGE of include/bhrt.h: the default coverage tolerance of the denoiser for sampled guides
@@ -745,6 +746,63 @@ class Scene:
         v = lambda x: C.c_void_p(x or None)  # noqa: E731
         _check(lib().bhrt_temporal_accumulate_dev(self._h, C.byref(opts), v(d_radiance), C.c_float(cur_samples), v(d_history), v(d_length), v(d_out), v(d_out_length),
                                                   v(d_rgb8), v(stream)))
+
+    # ---- the variance of a temporally accumulated frame ----------------------------------------------------------------------
+    def reproject_var(self, opts: ReprojectOpts, prev_frame, prev_z, prev_normal, prev_radiance=None, prev_variance=None, prev_length=None, prev_albedo=None,
+                      z=None, normal=None, albedo=None, prev_xforms=None, prev_id=None, id=None, want=("history", "history_variance", "length", "motion")):
+        """bhrt_reproject_var on host arrays: reproject() (reproject_moving() when prev_xforms, the previous frame's node_transforms(), is given)
+        that also carries prev_variance, the variance of prev_radiance, into the new view.  Returns (history (H, W, 3), history_variance
+        (H, W, 3), length (H, W), motion (H, W, 2)) float32, None for those not named in `want`."""
+        W, H = self.width, self.height
+        pf = None if prev_frame is None else np.ascontiguousarray(prev_frame, np.float32).reshape(-1)
+        if pf is not None and pf.size != 12:
+            raise ValueError("prev_frame: expected 12 floats")
+        px = self._xforms(prev_xforms)
+        i = [self._image(a, sh, k) for a, sh, k in ((prev_z, (H, W), "prev_z"), (prev_normal, (H, W, 3), "prev_normal"), (prev_radiance, (H, W, 3), "prev_radiance"),
+                                                    (prev_variance, (H, W, 3), "prev_variance"), (prev_length, (H, W), "prev_length"),
+                                                    (prev_albedo, (H, W, 3), "prev_albedo"))]
+        g = [self._image(a, sh, k) for a, sh, k in ((z, (H, W), "z"), (normal, (H, W, 3), "normal"), (albedo, (H, W, 3), "albedo"))]
+        pid, cid = self._ids(prev_id, "prev_id"), self._ids(id, "id")
+        shapes = {"history": (H, W, 3), "history_variance": (H, W, 3), "length": (H, W), "motion": (H, W, 2)}
+        o = [np.zeros(shapes[k], np.float32) if k in want else None for k in ("history", "history_variance", "length", "motion")]
+        p = lambda x: _ptr(x) if x is not None else None  # noqa: E731
+        _check(lib().bhrt_reproject_var(self._h, C.byref(opts) if opts is not None else None, p(pf), p(px), *[p(a) for a in i], p(pid), *[p(a) for a in g], p(cid),
+                                        *[p(a) for a in o]))
+        return tuple(o)
+
+    def reproject_var_dev(self, opts: ReprojectOpts, prev_frame, d_prev_z: int, d_prev_normal: int, d_prev_radiance: int = 0, d_prev_variance: int = 0,
+                          d_prev_length: int = 0, d_prev_albedo: int = 0, d_z: int = 0, d_normal: int = 0, d_albedo: int = 0, d_history: int = 0,
+                          d_history_variance: int = 0, d_length: int = 0, d_motion: int = 0, prev_xforms=None, d_prev_id: int = 0, d_id: int = 0, stream: int = 0):
+        """bhrt_reproject_var_dev on raw device pointers (0 = NULL; prev_frame and prev_xforms stay host arrays, prev_xforms None = camera only);
+        with a stream the call does not synchronise."""
+        pf = np.ascontiguousarray(prev_frame, np.float32).reshape(-1)
+        if pf.size != 12:
+            raise ValueError("prev_frame: expected 12 floats")
+        px = self._xforms(prev_xforms)
+        v = lambda x: C.c_void_p(x or None)  # noqa: E731
+        _check(lib().bhrt_reproject_var_dev(self._h, C.byref(opts), _ptr(pf), _ptr(px) if px is not None else None, v(d_prev_z), v(d_prev_normal), v(d_prev_radiance),
+                                            v(d_prev_variance), v(d_prev_length), v(d_prev_albedo), v(d_prev_id), v(d_z), v(d_normal), v(d_albedo), v(d_id), v(d_history),
+                                            v(d_history_variance), v(d_length), v(d_motion), v(stream)))
+
+    def temporal_accumulate_var(self, opts: TemporalOpts, radiance, variance, cur_samples: float, history=None, history_variance=None, length=None):
+        """bhrt_temporal_accumulate_var on host arrays: temporal_accumulate() with the current frame's variance (render_var's) and
+        reproject_var()'s history_variance.  Returns (out (H, W, 3), out_variance (H, W, 3), out_length (H, W)) float32 and rgb8 (H, W, 3) uint8;
+        out_variance is denoise()'s variance and the next reproject_var()'s prev_variance."""
+        W, H = self.width, self.height
+        c, vv = self._image(radiance, (H, W, 3), "radiance"), self._image(variance, (H, W, 3), "variance")
+        h, hv, l = self._image(history, (H, W, 3), "history"), self._image(history_variance, (H, W, 3), "history_variance"), self._image(length, (H, W), "length")
+        out, ov, ol, rgb = np.zeros((H, W, 3), np.float32), np.zeros((H, W, 3), np.float32), np.zeros((H, W), np.float32), np.zeros((H, W, 3), np.uint8)
+        p = lambda x: _ptr(x) if x is not None else None  # noqa: E731
+        _check(lib().bhrt_temporal_accumulate_var(self._h, C.byref(opts) if opts is not None else None, p(c), p(vv), C.c_float(cur_samples), p(h), p(hv), p(l), _ptr(out),
+                                                  _ptr(ov), _ptr(ol), _ptr(rgb)))
+        return out, ov, ol, rgb
+
+    def temporal_accumulate_var_dev(self, opts: TemporalOpts, d_radiance: int, d_variance: int, cur_samples: float, d_history: int = 0, d_history_variance: int = 0,
+                                    d_length: int = 0, d_out: int = 0, d_out_variance: int = 0, d_out_length: int = 0, d_rgb8: int = 0, stream: int = 0):
+        """bhrt_temporal_accumulate_var_dev on raw device pointers (0 = NULL); with a stream the call does not synchronise."""
+        v = lambda x: C.c_void_p(x or None)  # noqa: E731
+        _check(lib().bhrt_temporal_accumulate_var_dev(self._h, C.byref(opts), v(d_radiance), v(d_variance), C.c_float(cur_samples), v(d_history), v(d_history_variance),
+                                                      v(d_length), v(d_out), v(d_out_variance), v(d_out_length), v(d_rgb8), v(stream)))
 
     # ---- images beside the colour image (RenderImage z-buffer, DenoiseImage inputs) ------------
     def first_hit(self):

@@ -15,7 +15,8 @@
 //               [--progressive N [--time-limit SECONDS] [--live-png path]]       (BeginRender .. StopRender, Main.cpp:178,243: the frame in steps)
 //               [--camera-pos X,Y,Z] [--camera-target X,Y,Z] [--camera-up X,Y,Z] [--fov F]   (the <camera> tags, xmlload.cpp:109-127, replaced)
 //               [--shutter-pos X,Y,Z] [--shutter-target X,Y,Z] [--shutter-up X,Y,Z]           (camera motion blur: the camera at the end of the exposure)
-//               [--temporal N [--to-pos X,Y,Z] [--to-target X,Y,Z] [--to-up X,Y,Z] [--node-to-translate NAME:X,Y,Z] [--frames-png PREFIX]]   (N frames along a camera or object move, each carried into the next)
+//               [--temporal N [--to-pos X,Y,Z] [--to-target X,Y,Z] [--to-up X,Y,Z] [--node-to-translate NAME:X,Y,Z] [--frames-png PREFIX]   (N frames along a camera or object move, each carried into the next)
+//                   [--denoise [--denoise-iters K]]]   (each frame written denoised with its carried variance)
 //               [--node-translate NAME:X,Y,Z]   (repeatable: one translate op on that node before anything is rendered)
 //   bhrt info   <scene.xml>
 //
@@ -74,8 +75,13 @@
 // --to-* values, a missing one taken from pose 0.  Frame 0 is its render; frame k + 1 is its render blended (bhrt_temporal_accumulate) into
 // frame k's accumulated output and length reprojected into its view (bhrt_reproject with both views' first hits, albedo included), with the
 // library's default options.  -o gets the last frame, --frames-png PREFIX every frame as PREFIX000.png, PREFIX001.png, ...; --radiance the last
-// frame's accumulated radiance.  One device, whole frames, no further stage: with --progressive, --adaptive, --gpus, --denoise or --world > 1,
+// frame's accumulated radiance.  One device, whole frames: with --progressive, --adaptive, --gpus or --world > 1,
 // with N < 2, or --to-* / --frames-png without --temporal: a usage error.
+// --temporal N --denoise [--denoise-iters K]: every frame is rendered with bhrt_render_var, reprojected with bhrt_reproject_var
+// (with the node snapshot and id images under --node-to-translate) and accumulated with bhrt_temporal_accumulate_var, and what is written is
+// bhrt_denoise(accumulated frame, its carried variance, this view's first hit).  The next frame gets the un-denoised accumulated frame and its
+// variance: the denoised image is for display and is never fed back.  Needs --spp >= 2 (a 1-spp frame has no variance); --guide-spp and
+// --coverage-filter beside it are usage errors (sampled guides are not carried).  Without --denoise the calls are those named above.
 // --node-translate NAME:X,Y,Z (repeatable, any mode): one translate op appended to the node of that <object name=> through
 // bhrt_scene_set_node_transform, before anything is rendered.  --node-to-translate NAME:X,Y,Z (repeatable, needs --temporal N): frame k sets the
 // node to the record it had before frame 0 plus a translate of delta * ((float)k / (float)(N - 1)) per component in float32, and frames are
@@ -284,6 +290,9 @@ static int render_temporal(bhrt_scene *scene, const Args &A, const bhrt_info &in
     to.gamma = A.o.gamma;
     // the previous view (frame, first hit, accumulated light and its length) and the current one
     std::vector<float> pz(npx), pn(npx * 3), pa(npx * 3), acc(npx * 3), len(npx), z(npx), n(npx * 3), a(npx * 3), cur(npx * 3), hist(npx * 3), hl(npx), out(npx * 3), ol(npx);
+    // --denoise: the variance beside the light: the current frame's, the history's, the accumulated frame's and the previous one's
+    const size_t nv = A.denoise ? npx * 3 : 0;
+    std::vector<float> cv(nv), hv(nv), ov(nv), accv(nv);
     float prev_frame[12];
     // --node-to-translate: the moved nodes' records as they stand before frame 0, the previous frame's snapshot of all nodes and the id images
     const bool moving = !A.node_to_translate.empty();
@@ -305,17 +314,25 @@ static int render_temporal(bhrt_scene *scene, const Args &A, const bhrt_info &in
         o.seed = A.o.seed + (uint32_t)k;
         bhrt_stats one;
         if (bhrt_first_hit(scene, z.data(), n.data(), a.data())) return fail("first hit");
-        if (bhrt_render(scene, &o, nullptr, cur.data(), &one)) return fail("BeginRender");
+        if (A.denoise ? bhrt_render_var(scene, &o, nullptr, cur.data(), cv.data(), &one) : bhrt_render(scene, &o, nullptr, cur.data(), &one)) return fail("BeginRender");
         st.closest_rays += one.closest_rays; st.shadow_rays += one.shadow_rays; st.shade_calls += one.shade_calls; st.camera_samples += one.camera_samples;
         st.passes += one.passes; st.wave_iterations += one.wave_iterations; st.seconds_total += one.seconds_total;
         if (moving && bhrt_first_hit_node(scene, id.data())) return fail("first hit node");
-        if (k > 0 && moving) {
+        if (A.denoise) { // the same sequence through the calls that carry the variance; the file gets the denoised frame, the next frame the un-denoised one
+            if (k > 0 && bhrt_reproject_var(scene, &ro, prev_frame, moving ? prev_xf.data() : nullptr, pz.data(), pn.data(), acc.data(), accv.data(), len.data(), pa.data(),
+                                            moving ? pid.data() : nullptr, z.data(), n.data(), a.data(), moving ? id.data() : nullptr, hist.data(), hv.data(), hl.data(), nullptr))
+                return fail("reproject var");
+            if (bhrt_temporal_accumulate_var(scene, &to, cur.data(), cv.data(), (float)o.spp, k > 0 ? hist.data() : nullptr, k > 0 ? hv.data() : nullptr,
+                                             k > 0 ? hl.data() : nullptr, out.data(), ov.data(), ol.data(), nullptr))
+                return fail("temporal accumulate var");
+            if (bhrt_denoise(scene, &A.dn, out.data(), ov.data(), z.data(), n.data(), a.data(), nullptr, rgb.data())) return fail("DenoiseImage");
+        } else if (k > 0 && moving) {
             if (bhrt_reproject_moving(scene, &ro, prev_frame, prev_xf.data(), pz.data(), pn.data(), acc.data(), len.data(), pa.data(), pid.data(), z.data(), n.data(), a.data(),
                                       id.data(), hist.data(), hl.data(), nullptr))
                 return fail("reproject moving");
         } else if (k > 0 && bhrt_reproject(scene, &ro, prev_frame, pz.data(), pn.data(), acc.data(), len.data(), pa.data(), z.data(), n.data(), a.data(), hist.data(), hl.data(), nullptr))
             return fail("reproject");
-        if (bhrt_temporal_accumulate(scene, &to, cur.data(), (float)o.spp, k > 0 ? hist.data() : nullptr, k > 0 ? hl.data() : nullptr, out.data(), ol.data(), rgb.data()))
+        if (!A.denoise && bhrt_temporal_accumulate(scene, &to, cur.data(), (float)o.spp, k > 0 ? hist.data() : nullptr, k > 0 ? hl.data() : nullptr, out.data(), ol.data(), rgb.data()))
             return fail("temporal accumulate");
         size_t carried = 0;
         for (size_t q = 0; k > 0 && q < npx; q++) carried += hl[q] > 0.f;
@@ -329,6 +346,7 @@ static int render_temporal(bhrt_scene *scene, const Args &A, const bhrt_info &in
         if (moving && bhrt_scene_get_node_transforms(scene, prev_xf.data(), (uint32_t)prev_xf.size(), nullptr)) return fail("node transforms");
         pid.swap(id);
         pz.swap(z); pn.swap(n); pa.swap(a); acc.swap(out); len.swap(ol);
+        accv.swap(ov);
     }
     if (!rad.empty()) rad = acc;
     return 0;
@@ -668,8 +686,16 @@ int main(int argc, char **argv)
         return 2;
     }
     if (!A.temporal_given && !A.node_to_translate.empty()) { fprintf(stderr, "bhrt: usage: --node-to-translate needs --temporal N\n"); return 2; }
-    if (A.temporal_given && (A.temporal < 2 || A.progressive_given || A.adaptive || A.gpus > 0 || A.denoise || o.world_size > 1)) { // before any device is touched
-        fprintf(stderr, "bhrt: usage: --temporal needs N >= 2 frames and renders whole frames on one device (no --progressive, --adaptive, --gpus, --denoise, --world)\n");
+    if (A.temporal_given && (A.temporal < 2 || A.progressive_given || A.adaptive || A.gpus > 0 || o.world_size > 1)) { // before any device is touched
+        fprintf(stderr, "bhrt: usage: --temporal needs N >= 2 frames and renders whole frames on one device (no --progressive, --adaptive, --gpus, --world)\n");
+        return 2;
+    }
+    if (A.temporal_given && A.denoise && o.spp < 2) {
+        fprintf(stderr, "bhrt: usage: --temporal with --denoise needs --spp >= 2 (at 1 sample per pixel a frame's variance is 0 by definition)\n");
+        return 2;
+    }
+    if (A.temporal_given && A.denoise && (A.guide_spp_given || A.coverage_filter)) {
+        fprintf(stderr, "bhrt: usage: --temporal with --denoise filters with the first-hit guides (no --guide-spp, --coverage-filter)\n");
         return 2;
     }
     if (A.progressive_given && A.gpus == 1) A.gpus = 0; // one device: the session needs no communicator

@@ -4606,6 +4606,118 @@ try {
     return BHRT_OK;
 } catch (...) { return bhrt::AbiException(); }
 
+// bhrt_reproject_var* (k_reproject_var): the checks of bhrt_reproject*, those of the snapshot when one is given, and those of the
+// variance pair, before any device is touched
+static int ReprojectVarArgs(const bhrt_scene *scene, const bhrt_reproject_opts *opts, const float *prev_frame, const bhrt_xform *prev_xforms, const float *prev_z,
+                            const float *prev_normal, const float *prev_radiance, const float *prev_variance, const float *prev_albedo, const int32_t *prev_id,
+                            const int32_t *id, const float *history, const float *history_variance)
+{
+    BHRT_TRY(ReprojectArgs(scene, opts, prev_frame, prev_z, prev_normal, prev_radiance, prev_albedo, history));
+    const char *bad = prev_xforms ? ReprojectMovingArgsError(prev_xforms, scene->flat.hdr()->n_nodes) : "";
+    if (!*bad && !prev_xforms && (prev_id || id)) bad = "reproject var: node id images without the previous node transforms";
+    if (!*bad && history_variance && !prev_variance) bad = "reproject var: a history variance needs the previous variance";
+    if (!*bad && prev_variance && !prev_radiance) bad = "reproject var: a previous variance without a previous radiance";
+    if (*bad) { SetError(bad); return BHRT_ERR_ARG; }
+    return BHRT_OK;
+}
+
+int bhrt_reproject_var_dev(bhrt_scene *scene, const bhrt_reproject_opts *opts, const float prev_frame[12], const bhrt_xform *prev_xforms, const float *d_prev_z,
+                           const float *d_prev_normal, const float *d_prev_radiance, const float *d_prev_variance, const float *d_prev_length, const float *d_prev_albedo,
+                           const int32_t *d_prev_id, const float *d_z, const float *d_normal, const float *d_albedo, const int32_t *d_id, float *d_history,
+                           float *d_history_variance, float *d_length, float *d_motion, void *stream)
+try {
+    BHRT_TRY(ReprojectVarArgs(scene, opts, prev_frame, prev_xforms, d_prev_z, d_prev_normal, d_prev_radiance, d_prev_variance, d_prev_albedo, d_prev_id, d_id, d_history,
+                              d_history_variance));
+    int rc = EnsureUploaded(scene);
+    if (rc) return rc;
+    if (!d_history && !d_history_variance && !d_length && !d_motion) return BHRT_OK;
+    DeviceState *D = scene->dev;
+    const bhrt_flat_header *H = scene->flat.hdr();
+    const int W = H->camera.width, Hh = H->camera.height;
+    const size_t n = (size_t)W * Hh;
+    if (n == 0 || n > 0x7fffffffull) { SetError("reproject var: frame size out of range"); return BHRT_ERR_ARG; }
+    hipStream_t st = stream ? (hipStream_t)stream : D->stream;
+    ReprojectVarJob J;
+    J.W = W; J.H = Hh; J.o = *opts;
+    bhrt_scene_get_camera_frame(scene, J.cur);
+    memcpy(J.prev, prev_frame, sizeof J.prev);
+    J.prev_z = d_prev_z; J.prev_normal = d_prev_normal; J.prev_radiance = d_prev_radiance; J.prev_length = d_prev_length; J.prev_albedo = d_prev_albedo;
+    J.z = d_z; J.normal = d_normal; J.albedo = d_albedo; J.history = d_history; J.length = d_length; J.motion = d_motion;
+    J.prev_id = d_prev_id; J.id = d_id;
+    J.prev_variance = d_prev_variance; J.history_variance = d_history_variance;
+    J.nodes = nullptr; J.chain = nullptr; J.prev_nodes = nullptr; J.n_nodes = 0;
+    DeviceState::MovingNodeSlot *slot = nullptr;
+    if (prev_xforms) { // the previous records through the scene's pinned double buffer, under the rules of bhrt_reproject_moving_dev
+        slot = &D->moving_nodes[D->moving_turn++ & 1u];
+        const size_t pn_words = (size_t)std::max<uint32_t>(H->n_nodes, 1) * kPrevNodeWords;
+        if (!slot->h) {
+            BHRT_TRY(slot->h.Alloc(pn_words));
+            BHRT_TRY(slot->d.Reserve(pn_words));
+            HIP_CHECK(hipEventCreateWithFlags(&slot->done, hipEventDisableTiming));
+        }
+        if (slot->used) HIP_CHECK(hipEventSynchronize(slot->done));
+        memset(slot->h.p, 0, pn_words * sizeof(uint32_t));
+        FillPrevNodes((const bhrt_node *)(scene->flat.blob.data() + H->off_nodes), prev_xforms, H->n_nodes, slot->h.p);
+        HIP_CHECK(hipMemcpyAsync(slot->d, slot->h.p, pn_words * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        J.nodes = D->S.nodes; J.chain = D->S.chain; J.prev_nodes = slot->d; J.n_nodes = (int)H->n_nodes;
+    }
+    const bool want_albedo = d_prev_albedo && (d_history || d_history_variance); // without albedo' no albedo is read or computed
+    if (!d_z || !d_normal || (want_albedo && !d_albedo)) { // as bhrt_reproject_dev
+        BHRT_TRY(D->d_dn.Reserve(n * 7 * sizeof(float)));
+        float *g = (float *)D->d_dn.p;
+        float *gz = d_z ? nullptr : g, *gn = d_normal ? nullptr : g + n, *ga = !want_albedo || d_albedo ? nullptr : g + 4 * n;
+        hipLaunchKernelGGL(D->fm.tab ? k_first_hit<true> : k_first_hit<false>, dim3(((uint32_t)n + kBlock - 1) / kBlock), dim3(kBlock), 0, st, D->S, D->fm, W, Hh, gz, gn, ga);
+        HIP_CHECK(hipGetLastError());
+        if (gz) J.z = gz;
+        if (gn) J.normal = gn;
+        if (ga) J.albedo = ga;
+    }
+    if (prev_xforms && !d_id) { // as bhrt_reproject_moving_dev
+        BHRT_TRY(D->d_moving_id.Reserve(n));
+        hipLaunchKernelGGL(k_first_hit_node, dim3(((uint32_t)n + kBlock - 1) / kBlock), dim3(kBlock), 0, st, D->S, W, Hh, D->d_moving_id.p);
+        HIP_CHECK(hipGetLastError());
+        J.id = D->d_moving_id;
+    }
+    HIP_CHECK(ReprojectVarLaunch(J, st));
+    if (slot) {
+        HIP_CHECK(hipEventRecord(slot->done, st));
+        slot->used = true;
+    }
+    if (!stream) HIP_CHECK(hipStreamSynchronize(st));
+    return BHRT_OK;
+} catch (...) { return bhrt::AbiException(); }
+
+int bhrt_reproject_var(bhrt_scene *scene, const bhrt_reproject_opts *opts, const float prev_frame[12], const bhrt_xform *prev_xforms, const float *prev_z,
+                       const float *prev_normal, const float *prev_radiance, const float *prev_variance, const float *prev_length, const float *prev_albedo,
+                       const int32_t *prev_id, const float *z, const float *normal, const float *albedo, const int32_t *id, float *history, float *history_variance,
+                       float *length, float *motion)
+try {
+    BHRT_TRY(ReprojectVarArgs(scene, opts, prev_frame, prev_xforms, prev_z, prev_normal, prev_radiance, prev_variance, prev_albedo, prev_id, id, history, history_variance));
+    int rc = EnsureUploaded(scene);
+    if (rc) return rc;
+    if (!history && !history_variance && !length && !motion) return BHRT_OK;
+    DeviceState *D = scene->dev;
+    const bhrt_flat_header *H = scene->flat.hdr();
+    const size_t n = (size_t)H->camera.width * H->camera.height;
+    // device copies, back to back, in 4-byte words per pixel: z' 1, n' 3, c' 3, v' 3, l' 1, a' 3, id' 1, z 1, n 3, a 3, id 1, then history 3, its variance 3, length 1, motion 2
+    const void *const in[11] = {prev_z, prev_normal, prev_radiance, prev_variance, prev_length, prev_albedo, prev_id, z, normal, albedo, id};
+    float *const out[4] = {history, history_variance, length, motion};
+    const size_t width[15] = {1, 3, 3, 3, 1, 3, 1, 1, 3, 3, 1, 3, 3, 1, 2};
+    DevBuf<float> d;
+    BHRT_TRY(d.Reserve(n * 32));
+    float *at[15];
+    for (size_t k = 0, off = 0; k < 15; off += width[k] * n, k++) at[k] = d.p + off;
+    for (int k = 0; k < 11; k++)
+        if (in[k]) HIP_CHECK(hipMemcpyAsync(at[k], in[k], width[k] * n * 4, hipMemcpyHostToDevice, D->stream));
+    auto gin = [&](int k) -> float * { return in[k] ? at[k] : nullptr; };
+    auto gout = [&](int k) -> float * { return out[k] ? at[11 + k] : nullptr; };
+    BHRT_TRY(bhrt_reproject_var_dev(scene, opts, prev_frame, prev_xforms, gin(0), gin(1), gin(2), gin(3), gin(4), gin(5), (const int32_t *)gin(6), gin(7), gin(8), gin(9),
+                                    (const int32_t *)gin(10), gout(0), gout(1), gout(2), gout(3), nullptr));
+    for (int k = 0; k < 4; k++)
+        if (out[k]) HIP_CHECK(hipMemcpy(out[k], at[11 + k], width[11 + k] * n * sizeof(float), hipMemcpyDeviceToHost));
+    return BHRT_OK;
+} catch (...) { return bhrt::AbiException(); }
+
 static int TemporalArgs(const bhrt_scene *scene, const bhrt_temporal_opts *opts, const float *radiance, float cur_samples)
 {
     if (!scene || !radiance) { SetError("temporal accumulate: null scene or radiance"); return BHRT_ERR_ARG; }
@@ -4656,6 +4768,68 @@ try {
     BHRT_TRY(bhrt_temporal_accumulate_dev(scene, opts, d_c, cur_samples, history ? d_h : nullptr, length ? d_l : nullptr, out ? d_o : nullptr, out_length ? d_ol : nullptr,
                                           rgb8 ? d_rgb : nullptr, nullptr));
     if (out) HIP_CHECK(hipMemcpy(out, d_o, n * 12, hipMemcpyDeviceToHost));
+    if (out_length) HIP_CHECK(hipMemcpy(out_length, d_ol, n * 4, hipMemcpyDeviceToHost));
+    if (rgb8) HIP_CHECK(hipMemcpy(rgb8, d_rgb, n * 3, hipMemcpyDeviceToHost));
+    return BHRT_OK;
+} catch (...) { return bhrt::AbiException(); }
+
+// bhrt_temporal_accumulate_var* (k_temporal_accumulate_var): the checks of bhrt_temporal_accumulate* and those of the variances
+static int TemporalVarArgs(const bhrt_scene *scene, const bhrt_temporal_opts *opts, const float *radiance, const float *variance, float cur_samples, const float *history,
+                           const float *history_variance, const float *length)
+{
+    BHRT_TRY(TemporalArgs(scene, opts, radiance, cur_samples));
+    if (!variance) { SetError("temporal accumulate var: null variance"); return BHRT_ERR_ARG; }
+    if (history && length && !history_variance) { SetError("temporal accumulate var: a history needs its variance"); return BHRT_ERR_ARG; }
+    return BHRT_OK;
+}
+
+int bhrt_temporal_accumulate_var_dev(bhrt_scene *scene, const bhrt_temporal_opts *opts, const float *d_radiance, const float *d_variance, float cur_samples,
+                                     const float *d_history, const float *d_history_variance, const float *d_length, float *d_out, float *d_out_variance,
+                                     float *d_out_length, uint8_t *d_rgb8, void *stream)
+try {
+    BHRT_TRY(TemporalVarArgs(scene, opts, d_radiance, d_variance, cur_samples, d_history, d_history_variance, d_length));
+    int rc = EnsureUploaded(scene);
+    if (rc) return rc;
+    if (!d_out && !d_out_variance && !d_out_length && !d_rgb8) return BHRT_OK;
+    DeviceState *D = scene->dev;
+    const bhrt_flat_header *H = scene->flat.hdr();
+    const size_t n = (size_t)H->camera.width * H->camera.height;
+    if (n == 0 || n > 0x7fffffffull) { SetError("temporal accumulate var: frame size out of range"); return BHRT_ERR_ARG; }
+    hipStream_t st = stream ? (hipStream_t)stream : D->stream;
+    TemporalVarJob J;
+    J.W = H->camera.width; J.H = H->camera.height; J.o = *opts; J.cur_samples = cur_samples;
+    J.radiance = d_radiance; J.history = d_history; J.length = d_length; J.out = d_out; J.out_length = d_out_length; J.rgb8 = d_rgb8;
+    J.variance = d_variance; J.history_variance = d_history_variance; J.out_variance = d_out_variance;
+    HIP_CHECK(TemporalVarLaunch(J, st));
+    if (!stream) HIP_CHECK(hipStreamSynchronize(st));
+    return BHRT_OK;
+} catch (...) { return bhrt::AbiException(); }
+
+int bhrt_temporal_accumulate_var(bhrt_scene *scene, const bhrt_temporal_opts *opts, const float *radiance, const float *variance, float cur_samples, const float *history,
+                                 const float *history_variance, const float *length, float *out, float *out_variance, float *out_length, uint8_t *rgb8)
+try {
+    BHRT_TRY(TemporalVarArgs(scene, opts, radiance, variance, cur_samples, history, history_variance, length));
+    int rc = EnsureUploaded(scene);
+    if (rc) return rc;
+    if (!out && !out_variance && !out_length && !rgb8) return BHRT_OK;
+    DeviceState *D = scene->dev;
+    const bhrt_flat_header *H = scene->flat.hdr();
+    const size_t n = (size_t)H->camera.width * H->camera.height;
+    // device copies, back to back: radiance, variance, history, its variance, out, its variance (3n floats each), length, out_length (n each), rgb8 (3n bytes)
+    DevBuf<uint8_t> d;
+    BHRT_TRY(d.Reserve(n * 83));
+    float *f = (float *)d.p;
+    float *d_c = f, *d_v = f + 3 * n, *d_h = f + 6 * n, *d_hv = f + 9 * n, *d_o = f + 12 * n, *d_ov = f + 15 * n, *d_l = f + 18 * n, *d_ol = f + 19 * n;
+    uint8_t *d_rgb = d.p + n * 80;
+    HIP_CHECK(hipMemcpyAsync(d_c, radiance, n * 12, hipMemcpyHostToDevice, D->stream));
+    HIP_CHECK(hipMemcpyAsync(d_v, variance, n * 12, hipMemcpyHostToDevice, D->stream));
+    if (history) HIP_CHECK(hipMemcpyAsync(d_h, history, n * 12, hipMemcpyHostToDevice, D->stream));
+    if (history_variance) HIP_CHECK(hipMemcpyAsync(d_hv, history_variance, n * 12, hipMemcpyHostToDevice, D->stream));
+    if (length) HIP_CHECK(hipMemcpyAsync(d_l, length, n * 4, hipMemcpyHostToDevice, D->stream));
+    BHRT_TRY(bhrt_temporal_accumulate_var_dev(scene, opts, d_c, d_v, cur_samples, history ? d_h : nullptr, history_variance ? d_hv : nullptr, length ? d_l : nullptr,
+                                              out ? d_o : nullptr, out_variance ? d_ov : nullptr, out_length ? d_ol : nullptr, rgb8 ? d_rgb : nullptr, nullptr));
+    if (out) HIP_CHECK(hipMemcpy(out, d_o, n * 12, hipMemcpyDeviceToHost));
+    if (out_variance) HIP_CHECK(hipMemcpy(out_variance, d_ov, n * 12, hipMemcpyDeviceToHost));
     if (out_length) HIP_CHECK(hipMemcpy(out_length, d_ol, n * 4, hipMemcpyDeviceToHost));
     if (rgb8) HIP_CHECK(hipMemcpy(rgb8, d_rgb, n * 3, hipMemcpyDeviceToHost));
     return BHRT_OK;

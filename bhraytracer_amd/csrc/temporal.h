@@ -1,5 +1,6 @@
-// temporal.h — launchers of the two image-space stages of temporal.hip (bhrt_reproject*, bhrt_temporal_accumulate*; kernels.hip owns the
-// scene state and the first-hit kernel that fills in the guides a caller leaves out).
+// temporal.h — launchers of the image-space stages of temporal.hip (bhrt_reproject*, bhrt_temporal_accumulate* and their variance-carrying
+// forms bhrt_reproject_var*, bhrt_temporal_accumulate_var*; kernels.hip owns the scene state and the first-hit kernel that fills in the guides
+// a caller leaves out).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -47,6 +48,13 @@ const char *ReprojectMovingArgsError(const bhrt_xform *prev_xforms, uint32_t n_n
 void FillPrevNodes(const bhrt_node *nodes, const bhrt_xform *prev_xforms, uint32_t n_nodes, uint32_t *out);
 hipError_t ReprojectMovingLaunch(const ReprojectMovingJob &J, hipStream_t s);
 
+// stage 1V (k_reproject_var): the moving job and the variance pair; prev_nodes == NULL = camera only (stage 1: nodes, chain, the ids unread)
+struct ReprojectVarJob : ReprojectMovingJob {
+    const float *prev_variance; // W*H*3, or NULL when no history variance is asked for
+    float *history_variance;    // W*H*3, or NULL
+};
+hipError_t ReprojectVarLaunch(const ReprojectVarJob &J, hipStream_t s);
+
 struct TemporalJob {
     int W, H;
     bhrt_temporal_opts o;
@@ -61,5 +69,13 @@ struct TemporalJob {
 
 const char *TemporalArgsError(const bhrt_temporal_opts *o, float cur_samples);
 hipError_t TemporalLaunch(const TemporalJob &J, hipStream_t s);
+
+// stage 2V (k_temporal_accumulate_var)
+struct TemporalVarJob : TemporalJob {
+    const float *variance;         // W*H*3: the current frame's
+    const float *history_variance; // W*H*3: stage 1V's; NULL only when history or length is
+    float *out_variance;           // W*H*3, or NULL
+};
+hipError_t TemporalVarLaunch(const TemporalVarJob &J, hipStream_t s);
 
 } // namespace bhrt

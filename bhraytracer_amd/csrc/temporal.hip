@@ -51,12 +51,35 @@
 //   taps     with a prev_id image, a hit pixel's tap is valid only if prev_id[tap] == k as well
 //   Misses, snap, bounds, taps, result and motion are stage 1's; motion now contains the object's motion.
 //
+// 1V. REPROJECTION THAT ALSO CARRIES A VARIANCE (k_reproject_var<kAlbedo, kMoving>): everything stage 1 computes (stage 1M when
+//   kMoving), in the same operations and order, so history, length and motion are those stages' bits.  In addition, with v' the previous view's
+//   variance image (W*H*3, laid out like c': the per-channel variance of each pixel's mean, bhrt_render_var's or stage 2V's):
+//   taps     per valid tap, in tap order, per channel, from 0:  sv = sv + w * ve'
+//            ve' = v' without albedo images;  with them ve' = v' / (dq * dq), dq = divisor(a'(q)): the product first, then one IEEE division
+//            (e' = c' / dq is the carried light, so its variance is v' / dq^2)
+//   result   hv = sv / sw;  with albedo images hv = hv * (g * g), g = divisor(a): the product first, then one multiplication
+//   invalid  hv = 0
+//   The weights are the bilinear w, not w^2: the variance is interpolated linearly, as SVGF interpolates its moments.  A design rule.  With
+//   the normalised weights w / sw <= 1, sum (w / sw) v >= sum (w / sw)^2 v: for independent taps the linear interpolation never understates
+//   the variance of the interpolated value (it overstates it by up to 4 x at the centre of four taps, where neighbouring pixels then share
+//   taps and are no longer independent: the squared weights would understate their common noise).  And it is exact for the single tap of
+//   a snapped or static pixel: a camera that did not move carries the previous variance's bits.
+//
 // 2. ACCUMULATION, per pixel: c = the current radiance, n_c = cur_samples (the samples behind it), h, l = history and length of stage 1.
 //   no history (not l > 0):  out = c, out_length = min(n_c, max_length)
 //   else, with clamp_k >= 0:  the taps of the 3 x 3 block of the current radiance that lie inside the image, row-major, m of them; per channel
 //            mu = (sum c) / m,  sigma = sqrt((sum (c - mu)(c - mu)) / m),  h = min(max(h, mu - clamp_k sigma), mu + clamp_k sigma)
 //   then     l = min(l, max_length),  a = n_c / (l + n_c),  out = h + (c - h) * a,  out_length = min(l + n_c, max_length)
 //   rgb8 = store_color24(out) (device_color24.h: the gamma and Color24 of k_resolve)
+//
+// 2V. ACCUMULATION THAT ALSO BLENDS THE VARIANCE (k_temporal_accumulate_var): out, out_length and rgb8 are stage 2's operations
+//   exactly.  v = the current frame's variance (bhrt_render_var's), hv = the history's of stage 1V.
+//   no history (not l > 0):  out_variance = v
+//   else, per channel, with h0 the history before the clamp and h after it (h = h0 with the clamp off):
+//            hv = (h != h0) ? fmaxf(hv, v) : hv       a clamped history channel is a value taken from the current frame's neighbourhood: it
+//                                                     cannot be trusted more than the current pixel.  A design rule.
+//            out_variance = ((1 - a) * (1 - a)) * hv + (a * a) * v      with stage 2's a: out = (1 - a) h + a c, h and c independent
+//   With the clamp off and max_length = +inf, two frames of n1 and n2 samples pool to (n1^2 vA + n2^2 vB) / (n1 + n2)^2.
 //
 // KERNELS.  k_reproject: one lane per pixel of the current camera, 256 in a row; the call's constants (A, m, the three dots) come from the host,
 // in the same float32 operations.  It reads 28 B per pixel of the current view (40 B with albedo) and, per tap, 32 B of the previous one (44 B
@@ -65,7 +88,9 @@
 // the same inputs give the same bytes.  k_reproject_moving: k_reproject's lane layout and taps (its body is repeated rather than shared, so
 // that k_reproject keeps its code); 4 B more per pixel (8 B with prev_id per tap), and for a pixel of a moved node 84 B of the current and
 // 88 B of the previous record per chain level, from the scene's nodes and from a scratch buffer of 88 B per node.  The chain loop is bounded
-// by BHRT_MAX_NODE_DEPTH; no array is indexed dynamically (no scratch memory).
+// by BHRT_MAX_NODE_DEPTH; no array is indexed dynamically (no scratch memory).  k_reproject_var: the same lane layout and taps, one body for
+// the camera-only and the moving case (it is new: no existing kernel's code depends on it); per tap 12 B more (v'), 12 B more written (hv).
+// k_temporal_accumulate_var: k_temporal_accumulate's workgroups and 3 x 3 block; 24 B more read (v, hv), 12 B more written.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stddef.h>
@@ -298,6 +323,190 @@ __global__ void __launch_bounds__(256) k_reproject_moving(int W, int H, Reprojec
     if (motion) { motion[2 * (size_t)p] = mu; motion[2 * (size_t)p + 1] = mv; }
 }
 
+// the images of one k_reproject_var call (the parameter list of k_reproject_moving plus v' and hv)
+struct ReprojectVarImages {
+    const float *pz, *pn, *pc, *pv, *pl, *pa; // the previous view: z', n', c', v', l', a'
+    const int32_t *pid;                       // id' (kMoving only)
+    const float *z, *n, *a;                   // the current view
+    const int32_t *id;                        // kMoving only
+    float *history, *history_variance, *length, *motion;
+};
+
+// Stage 1V.  Stage 1's body (stage 1M's with kMoving), statement for statement, with the variance sums beside the radiance sums.
+template <bool kAlbedo, bool kMoving>
+__global__ void __launch_bounds__(256) k_reproject_var(int W, int H, ReprojectFrame F, float depth_tolerance, float normal_threshold, MovingNodes M, ReprojectVarImages I)
+{
+    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= (uint32_t)(W * H)) return;
+    const int j = (int)(p / (uint32_t)W), i = (int)(p - (uint32_t)j * (uint32_t)W);
+    const float fi = (float)i, fj = (float)j, zp = I.z[p];
+    const bool miss = zp >= BHRT_BIGFLOAT;
+    float u = fi, v = fj, t = 0.f;
+    bool ok = true;
+    V3 nu = v3(0, 0, 0);
+    int32_t k = -1;
+    if (!miss) {
+        const V3 d = ((F.top_left + fi * F.dd_x) - fj * F.dd_y) - F.pos;
+        V3 x = F.pos + d * zp;
+        V3 nl = v3(I.n[3 * (size_t)p], I.n[3 * (size_t)p + 1], I.n[3 * (size_t)p + 2]);
+        bool known = true;
+        if (kMoving) {
+            k = I.id[p];
+            known = (uint32_t)k < (uint32_t)M.n_nodes; // a negative k wraps above every n_nodes
+            if (known && M.prev[(size_t)k * kPrevNodeWords + 21] != 0u) {
+                const int32_t *c = M.chain + (size_t)k * BHRT_MAX_NODE_DEPTH;
+                const int m = min(M.nodes[k].depth, BHRT_MAX_NODE_DEPTH);
+                for (int l = 0; l < m; l++) {
+                    const bhrt_xform &xf = M.nodes[c[l]].xf;
+                    x = mat_mul(xf.itm, x - v3(xf.pos[0], xf.pos[1], xf.pos[2]));
+                    nl = mat_tmul(xf.tm, nl);
+                }
+                for (int l = m - 1; l >= 0; l--) {
+                    const float *r = (const float *)(M.prev + (size_t)c[l] * kPrevNodeWords);
+                    x = mat_mul(r, x) + v3(r[9], r[10], r[11]);
+                    nl = mat_tmul(r + 12, nl);
+                }
+            }
+        }
+        const V3 q = x - F.ppos;
+        t = dot(q, F.m) / F.Am;
+        ok = known && t > 0.f && t <= 3.402823466e38f;
+        const V3 r = q / t - F.A;
+        u = dot(r, F.pdd_x) / F.xx;
+        v = -(dot(r, F.pdd_y) / F.yy);
+        const float ru = rintf(u), rv = rintf(v);
+        if (fabsf(u - ru) <= 0.0078125f) u = ru;
+        if (fabsf(v - rv) <= 0.0078125f) v = rv;
+        const float ln = dm::sqrt_f((nl.x * nl.x + nl.y * nl.y) + nl.z * nl.z); // unit(nl)
+        nu = ln > 0.f ? v3(nl.x / ln, nl.y / ln, nl.z / ln) : v3(0, 0, 0);
+    }
+    ok = ok && u >= -1.f && u < (float)W && v >= -1.f && v < (float)H;
+    float sw = 0.f, sr = 0.f, sg = 0.f, sb = 0.f, sl = 0.f, vr = 0.f, vg = 0.f, vb = 0.f;
+    if (ok) {
+        const float f0 = floorf(u), g0 = floorf(v);
+        const float fx = u - f0, fy = v - g0, ax = 1.f - fx, ay = 1.f - fy;
+        const int i0 = (int)f0, j0 = (int)g0;
+        const float w4[4] = {ax * ay, fx * ay, ax * fy, fx * fy};
+#pragma unroll
+        for (int e4 = 0; e4 < 4; e4++) {
+            const float w = w4[e4];
+            const int qi = i0 + (e4 & 1), qj = j0 + (e4 >> 1);
+            if (w == 0.f || qi < 0 || qi >= W || qj < 0 || qj >= H) continue;
+            const size_t q = (size_t)qj * W + qi;
+            const float lq = I.pl ? I.pl[q] : 1.f, zq = I.pz[q];
+            if (!(lq > 0.f)) continue;
+            if (miss) {
+                if (!(zq >= BHRT_BIGFLOAT)) continue;
+            } else {
+                if (!(zq < BHRT_BIGFLOAT) || !(fabsf(zq - t) <= depth_tolerance * t)) continue;
+                if (kMoving && I.pid && I.pid[q] != k) continue;
+                if (!(dot(nu, tp_unit(I.pn, q)) >= normal_threshold)) continue;
+            }
+            sw = sw + w;
+            sl = sl + w * lq;
+            V3 dq = v3(1, 1, 1);
+            if (kAlbedo) dq = tp_divisor(I.pa, q);
+            if (I.history) {
+                V3 e = v3(I.pc[3 * q], I.pc[3 * q + 1], I.pc[3 * q + 2]);
+                if (kAlbedo) e = v3(e.x / dq.x, e.y / dq.y, e.z / dq.z);
+                sr = sr + w * e.x;
+                sg = sg + w * e.y;
+                sb = sb + w * e.z;
+            }
+            if (I.history_variance) {
+                V3 e = v3(I.pv[3 * q], I.pv[3 * q + 1], I.pv[3 * q + 2]);
+                if (kAlbedo) e = v3(e.x / (dq.x * dq.x), e.y / (dq.y * dq.y), e.z / (dq.z * dq.z));
+                vr = vr + w * e.x;
+                vg = vg + w * e.y;
+                vb = vb + w * e.z;
+            }
+        }
+        ok = sw > 0.f;
+    }
+    V3 h = v3(0, 0, 0), hv = v3(0, 0, 0);
+    float l = 0.f, mu = 0.f, mv = 0.f;
+    if (ok) {
+        h = v3(sr / sw, sg / sw, sb / sw);
+        hv = v3(vr / sw, vg / sw, vb / sw);
+        if (kAlbedo) {
+            const V3 g = tp_divisor(I.a, p);
+            h = v3(h.x * g.x, h.y * g.y, h.z * g.z);
+            hv = v3(hv.x * (g.x * g.x), hv.y * (g.y * g.y), hv.z * (g.z * g.z));
+        }
+        l = sl / sw;
+        mu = u - fi;
+        mv = v - fj;
+    }
+    if (I.history) { I.history[3 * (size_t)p] = h.x; I.history[3 * (size_t)p + 1] = h.y; I.history[3 * (size_t)p + 2] = h.z; }
+    if (I.history_variance) { I.history_variance[3 * (size_t)p] = hv.x; I.history_variance[3 * (size_t)p + 1] = hv.y; I.history_variance[3 * (size_t)p + 2] = hv.z; }
+    if (I.length) I.length[p] = l;
+    if (I.motion) { I.motion[2 * (size_t)p] = mu; I.motion[2 * (size_t)p + 1] = mv; }
+}
+
+// Stage 2V.  k_temporal_accumulate's body, statement for statement, with the variance blended beside the radiance.
+__global__ void __launch_bounds__(kTaTx *kTaTy) k_temporal_accumulate_var(int W, int H, float clamp_k, float max_length, float cur_samples, const float *__restrict__ c,
+                                                                          const float *__restrict__ var, const float *__restrict__ history,
+                                                                          const float *__restrict__ history_variance, const float *__restrict__ length,
+                                                                          float *__restrict__ out, float *__restrict__ out_variance, float *__restrict__ out_length,
+                                                                          uint8_t *__restrict__ rgb8, int gamma)
+{
+    const int x = (int)(blockIdx.x * kTaTx + threadIdx.x), y = (int)(blockIdx.y * kTaTy + threadIdx.y);
+    if (x >= W || y >= H) return;
+    const size_t p = (size_t)y * W + x;
+    const V3 cp = v3(c[3 * p], c[3 * p + 1], c[3 * p + 2]);
+    const V3 vp = v3(var[3 * p], var[3 * p + 1], var[3 * p + 2]);
+    const float lp = history && length ? length[p] : 0.f;
+    V3 o = cp, ov = vp;
+    float ol = fminf(cur_samples, max_length);
+    if (lp > 0.f) {
+        const V3 h0 = v3(history[3 * p], history[3 * p + 1], history[3 * p + 2]);
+        V3 h = h0;
+        if (clamp_k >= 0.f) {
+            V3 q[9]; // statically indexed: registers
+            bool in[9];
+            int m = 0;
+            V3 s = v3(0, 0, 0);
+#pragma unroll
+            for (int k = 0; k < 9; k++) {
+                const int dy = k / 3 - 1, dx = k % 3 - 1, qy = y + dy, qx = x + dx;
+                in[k] = qy >= 0 && qy < H && qx >= 0 && qx < W;
+                q[k] = v3(0, 0, 0);
+                if (!in[k]) continue;
+                const size_t g = ((size_t)qy * W + qx) * 3;
+                q[k] = v3(c[g], c[g + 1], c[g + 2]);
+                s = s + q[k];
+                m++;
+            }
+            const float fm = (float)m;
+            const V3 mu = s / fm;
+            V3 s2 = v3(0, 0, 0);
+#pragma unroll
+            for (int k = 0; k < 9; k++) {
+                if (!in[k]) continue;
+                const V3 e = q[k] - mu;
+                s2 = s2 + e * e;
+            }
+            const V3 sd = v3(dm::sqrt_f(s2.x / fm), dm::sqrt_f(s2.y / fm), dm::sqrt_f(s2.z / fm));
+            const V3 ks = clamp_k * sd;
+            h = v3(fminf(fmaxf(h.x, mu.x - ks.x), mu.x + ks.x), fminf(fmaxf(h.y, mu.y - ks.y), mu.y + ks.y), fminf(fmaxf(h.z, mu.z - ks.z), mu.z + ks.z));
+        }
+        V3 hv = v3(history_variance[3 * p], history_variance[3 * p + 1], history_variance[3 * p + 2]);
+        if (h.x != h0.x) hv.x = fmaxf(hv.x, vp.x);
+        if (h.y != h0.y) hv.y = fmaxf(hv.y, vp.y);
+        if (h.z != h0.z) hv.z = fmaxf(hv.z, vp.z);
+        const float l = fminf(lp, max_length);
+        const float a = cur_samples / (l + cur_samples);
+        o = h + (cp - h) * a;
+        const float b = 1.f - a, bb = b * b, aa = a * a;
+        ov = v3(bb * hv.x + aa * vp.x, bb * hv.y + aa * vp.y, bb * hv.z + aa * vp.z);
+        ol = fminf(l + cur_samples, max_length);
+    }
+    if (out) { out[3 * p] = o.x; out[3 * p + 1] = o.y; out[3 * p + 2] = o.z; }
+    if (out_variance) { out_variance[3 * p] = ov.x; out_variance[3 * p + 1] = ov.y; out_variance[3 * p + 2] = ov.z; }
+    if (out_length) out_length[p] = ol;
+    if (rgb8) store_color24(rgb8, p, o, gamma);
+}
+
 __global__ void __launch_bounds__(kTaTx *kTaTy) k_temporal_accumulate(int W, int H, float clamp_k, float max_length, float cur_samples, const float *__restrict__ c,
                                                                       const float *__restrict__ history, const float *__restrict__ length, float *__restrict__ out,
                                                                       float *__restrict__ out_length, uint8_t *__restrict__ rgb8, int gamma)
@@ -428,6 +637,21 @@ hipError_t ReprojectMovingLaunch(const ReprojectMovingJob &J, hipStream_t s)
     return hipGetLastError();
 }
 
+hipError_t ReprojectVarLaunch(const ReprojectVarJob &J, hipStream_t s)
+{
+    if (!J.history && !J.history_variance && !J.length && !J.motion) return hipSuccess;
+    const uint32_t n_px = (uint32_t)((size_t)J.W * J.H);
+    const ReprojectFrame F = ReprojectConsts(J.cur, J.prev);
+    const bool alb = J.prev_albedo && (J.history || J.history_variance);
+    const bool moving = J.prev_nodes != nullptr;
+    const MovingNodes M = {J.nodes, J.chain, J.prev_nodes, J.n_nodes};
+    const ReprojectVarImages I = {J.prev_z, J.prev_normal, J.prev_radiance, J.prev_variance, J.prev_length, J.prev_albedo, J.prev_id, J.z, J.normal, J.albedo, J.id,
+                                  J.history, J.history_variance, J.length, J.motion};
+    auto kernel = moving ? (alb ? k_reproject_var<true, true> : k_reproject_var<false, true>) : (alb ? k_reproject_var<true, false> : k_reproject_var<false, false>);
+    hipLaunchKernelGGL(kernel, dim3((n_px + 255) / 256), dim3(256), 0, s, J.W, J.H, F, J.o.depth_tolerance, J.o.normal_threshold, M, I);
+    return hipGetLastError();
+}
+
 const char *TemporalArgsError(const bhrt_temporal_opts *o, float cur_samples)
 {
     if (!o) return "temporal accumulate: null options";
@@ -442,6 +666,15 @@ hipError_t TemporalLaunch(const TemporalJob &J, hipStream_t s)
     const dim3 grid((unsigned)((J.W + kTaTx - 1) / kTaTx), (unsigned)((J.H + kTaTy - 1) / kTaTy)), block(kTaTx, kTaTy);
     hipLaunchKernelGGL(k_temporal_accumulate, grid, block, 0, s, J.W, J.H, J.o.clamp_k, J.o.max_length, J.cur_samples, J.radiance, J.history, J.length,
                        J.out, J.out_length, J.rgb8, J.o.gamma ? 1 : 0);
+    return hipGetLastError();
+}
+
+hipError_t TemporalVarLaunch(const TemporalVarJob &J, hipStream_t s)
+{
+    if (!J.out && !J.out_variance && !J.out_length && !J.rgb8) return hipSuccess;
+    const dim3 grid((unsigned)((J.W + kTaTx - 1) / kTaTx), (unsigned)((J.H + kTaTy - 1) / kTaTy)), block(kTaTx, kTaTy);
+    hipLaunchKernelGGL(k_temporal_accumulate_var, grid, block, 0, s, J.W, J.H, J.o.clamp_k, J.o.max_length, J.cur_samples, J.radiance, J.variance, J.history,
+                       J.history_variance, J.length, J.out, J.out_variance, J.out_length, J.rgb8, J.o.gamma ? 1 : 0);
     return hipGetLastError();
 }
 

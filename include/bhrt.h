@@ -516,6 +516,53 @@ int bhrt_temporal_accumulate_dev(bhrt_scene *scene, const bhrt_temporal_opts *op
 int bhrt_temporal_accumulate(bhrt_scene *scene, const bhrt_temporal_opts *opts, const float *radiance, float cur_samples, const float *history, const float *length,
                              float *out, float *out_length, uint8_t *rgb8);
 
+/* ---- the variance of a temporally accumulated frame: SVGF's temporal half -----------------------------------------------
+ * bhrt_render_var* gives bhrt_denoise* the per-channel variance of a pixel's mean; once a frame has been blended with reprojected history that
+ * variance no longer describes it.  The two calls below are bhrt_reproject* / bhrt_reproject_moving* and bhrt_temporal_accumulate* with the
+ * variance carried beside the light, stated exactly in csrc/temporal.hip as stages 1V and 2V (new kernels beside the existing ones, which
+ * do not change): reproject -> accumulate -> denoise then works end to end.  The limits are those of the stages above: lens and shutter are not
+ * covered, reflections are carried as surface light, a progressive session is not seeded; and a frame needs >= 2 samples per pixel for a
+ * variance (bhrt_render_var's is 0 at 1 spp).
+ *
+ * bhrt_reproject_var*: prev_xforms == NULL: camera only, the arguments and outputs of bhrt_reproject* (prev_id and id must then be NULL too);
+ * else those of bhrt_reproject_moving*.  Two more images: prev_variance (W*H*3), the variance of prev_radiance (bhrt_render_var*'s of a rendered
+ * frame, out_variance of an accumulated one), and history_variance (W*H*3, may be NULL), the variance of history: the previous variance
+ * interpolated with the history's own bilinear weights over the same valid taps (w, not w^2: never below the variance of the interpolated
+ * value for independent taps, and exact for the single tap of a pixel that did not move); with albedo images divided by divisor(prev_albedo)^2
+ * and multiplied by divisor(albedo)^2, the square of what the light is rescaled by; 0 where the pixel has no history.  history, length and
+ * motion are bhrt_reproject*'s (bhrt_reproject_moving*'s) bytes for the same inputs, with or without the variance pair.  With prev_albedo
+ * given, the albedo takes part when history or history_variance is asked for.
+ * BHRT_ERR_ARG before any device is touched: everything bhrt_reproject* refuses; with prev_xforms everything bhrt_reproject_moving* refuses;
+ * without prev_xforms a prev_id or id that is not NULL; history_variance without prev_variance; prev_variance without prev_radiance.
+ * _dev: device pointers (prev_frame and prev_xforms stay HOST pointers); with a stream the call does not synchronise.  Scratch is the scene's
+ * and shared with bhrt_reproject* / bhrt_reproject_moving* under their rules: 28 B per pixel for guides computed here, 4 B per pixel for an id
+ * computed here, and with prev_xforms the pinned double buffer of the previous records (the third call in a row waits until the stream has
+ * passed the first, whichever of the two entry points issued them).  Calls on one scene must not overlap. */
+int bhrt_reproject_var_dev(bhrt_scene *scene, const bhrt_reproject_opts *opts, const float prev_frame[12], const struct bhrt_xform *prev_xforms, const float *d_prev_z,
+                           const float *d_prev_normal, const float *d_prev_radiance, const float *d_prev_variance, const float *d_prev_length, const float *d_prev_albedo,
+                           const int32_t *d_prev_id, const float *d_z, const float *d_normal, const float *d_albedo, const int32_t *d_id, float *d_history,
+                           float *d_history_variance, float *d_length, float *d_motion, void *stream);
+int bhrt_reproject_var(bhrt_scene *scene, const bhrt_reproject_opts *opts, const float prev_frame[12], const struct bhrt_xform *prev_xforms, const float *prev_z,
+                       const float *prev_normal, const float *prev_radiance, const float *prev_variance, const float *prev_length, const float *prev_albedo,
+                       const int32_t *prev_id, const float *z, const float *normal, const float *albedo, const int32_t *id, float *history, float *history_variance,
+                       float *length, float *motion);
+/* bhrt_temporal_accumulate_var*: bhrt_temporal_accumulate* with variance (W*H*3, required): the current frame's, bhrt_render_var*'s;
+ * history_variance: bhrt_reproject_var*'s; out_variance (W*H*3, may be NULL): the variance of out.  A pixel without history: out_variance =
+ * variance.  A pixel that blends, per channel: out_variance = (1 - a)^2 hv + a^2 variance with the blend's own weight a, where hv =
+ * history_variance, raised to max(hv, variance) in a channel whose history the clamp changed (a clamped value comes from the current frame's
+ * neighbourhood: it is not trusted more than the current pixel).  With the clamp off and max_length = +inf, frames of n1 and n2 samples
+ * pool to (n1^2 v1 + n2^2 v2) / (n1 + n2)^2.  out, out_length and rgb8 are bhrt_temporal_accumulate*'s bytes for the same inputs.
+ * out_variance is what bhrt_denoise* takes as variance and what the next bhrt_reproject_var* takes as prev_variance (with out as
+ * prev_radiance: the denoised image is for display and is not fed back).
+ * BHRT_ERR_ARG before any device is touched: everything bhrt_temporal_accumulate* refuses; a NULL variance; history and length given while
+ * history_variance is NULL.  With history or length NULL no pixel has a history: out = radiance, out_variance = variance.
+ * _dev: device pointers; with a stream the call does not synchronise.  No scratch. */
+int bhrt_temporal_accumulate_var_dev(bhrt_scene *scene, const bhrt_temporal_opts *opts, const float *d_radiance, const float *d_variance, float cur_samples,
+                                     const float *d_history, const float *d_history_variance, const float *d_length, float *d_out, float *d_out_variance,
+                                     float *d_out_length, uint8_t *d_rgb8, void *stream);
+int bhrt_temporal_accumulate_var(bhrt_scene *scene, const bhrt_temporal_opts *opts, const float *radiance, const float *variance, float cur_samples, const float *history,
+                                 const float *history_variance, const float *length, float *out, float *out_variance, float *out_length, uint8_t *rgb8);
+
 /* ---- adaptive sampling: RenderImage's per-pixel sample counts (Scenes/scene.h:534,570), which BeginRender only ever sets to 0
  * (Main.cpp:214), filled by a render that stops sampling a pixel once its mean is good enough ------------------------
  * Rounds: round 0 gives every owned pixel samples [0, min_spp); round r >= 1 gives every pixel still active samples [n_{r-1}, n_r),
