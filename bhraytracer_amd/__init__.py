@@ -78,6 +78,12 @@ class TemporalOpts(C.Structure):
     _fields_ = [("clamp_k", C.c_float), ("max_length", C.c_float), ("gamma", C.c_int32), ("reserved", C.c_int32 * 5)]
 
 
+class SpatialVarianceOpts(C.Structure):
+    """bhrt_spatial_variance_opts: the window, the edge stops and the pass-through length of bhrt_variance_spatial (csrc/temporal.hip, stage 3S)."""
+    _fields_ = [("radius", C.c_int32), ("depth_tolerance", C.c_float), ("normal_threshold", C.c_float), ("min_length", C.c_float), ("demodulate", C.c_int32),
+                ("reserved", C.c_int32 * 3)]
+
+
 class XformOp(C.Structure):
     """bhrt_xform_op: one <scale> / <rotate> / <translate> of bhrt_scene_set_node_transform."""
     _fields_ = [("kind", C.c_int32), ("v", C.c_float * 4)]
@@ -133,6 +139,7 @@ EXPORTS = [
     "bhrt_scene_node_index", "bhrt_scene_get_node_transform", "bhrt_scene_get_node_transforms", "bhrt_scene_set_node_transform",
     "bhrt_first_hit_node", "bhrt_first_hit_node_dev", "bhrt_reproject_moving", "bhrt_reproject_moving_dev",
     "bhrt_reproject_var", "bhrt_reproject_var_dev", "bhrt_temporal_accumulate_var", "bhrt_temporal_accumulate_var_dev",
+    "bhrt_default_spatial_variance_opts", "bhrt_variance_spatial", "bhrt_variance_spatial_dev",
 ]
 
 # BHRT_DENOISE_SIGMA_COVERAGE of include/bhrt.h: the default coverage tolerance of the denoiser for sampled guides
@@ -168,6 +175,7 @@ def lib():
         L.bhrt_default_adaptive_opts.restype = None
         L.bhrt_default_reproject_opts.restype = None
         L.bhrt_default_temporal_opts.restype = None
+        L.bhrt_default_spatial_variance_opts.restype = None
         _lib = L
     return _lib
 
@@ -216,6 +224,15 @@ def default_temporal_opts(**kw) -> TemporalOpts:
     """bhrt_default_temporal_opts (clamp_k, max_length: DESIGN.md 19; gamma = 1), fields overridden by kw."""
     o = TemporalOpts()
     lib().bhrt_default_temporal_opts(C.byref(o))
+    for k, v in kw.items():
+        setattr(o, k, v)
+    return o
+
+
+def default_spatial_variance_opts(**kw) -> SpatialVarianceOpts:
+    """bhrt_default_spatial_variance_opts (radius 3, depth_tolerance 0.01, normal_threshold 0.99, min_length 4, demodulate 1: DESIGN.md 22), fields overridden by kw."""
+    o = SpatialVarianceOpts()
+    lib().bhrt_default_spatial_variance_opts(C.byref(o))
     for k, v in kw.items():
         setattr(o, k, v)
     return o
@@ -803,6 +820,26 @@ class Scene:
         v = lambda x: C.c_void_p(x or None)  # noqa: E731
         _check(lib().bhrt_temporal_accumulate_var_dev(self._h, C.byref(opts), v(d_radiance), v(d_variance), C.c_float(cur_samples), v(d_history), v(d_history_variance),
                                                       v(d_length), v(d_out), v(d_out_variance), v(d_out_length), v(d_rgb8), v(stream)))
+
+    # ---- spatial variance estimate ---------------------------------------------------------------------------------------------
+    def variance_spatial(self, opts: SpatialVarianceOpts, radiance, variance=None, length=None, z=None, normal=None, albedo=None):
+        """bhrt_variance_spatial on host arrays: the variance of `radiance` estimated from each pixel's neighbourhood on its own surface; where
+        length >= opts.min_length the pixel keeps `variance`.  z, normal, albedo None = computed here.  Returns out_variance (H, W, 3) float32,
+        what denoise() and temporal_accumulate_var() take as variance."""
+        W, H = self.width, self.height
+        i = [self._image(a, sh, k) for a, sh, k in ((radiance, (H, W, 3), "radiance"), (variance, (H, W, 3), "variance"), (length, (H, W), "length"), (z, (H, W), "z"),
+                                                    (normal, (H, W, 3), "normal"), (albedo, (H, W, 3), "albedo"))]
+        out = np.zeros((H, W, 3), np.float32)
+        p = lambda x: _ptr(x) if x is not None else None  # noqa: E731
+        _check(lib().bhrt_variance_spatial(self._h, C.byref(opts) if opts is not None else None, *[p(a) for a in i], _ptr(out)))
+        return out
+
+    def variance_spatial_dev(self, opts: SpatialVarianceOpts, d_radiance: int, d_variance: int = 0, d_length: int = 0, d_z: int = 0, d_normal: int = 0,
+                             d_albedo: int = 0, d_out_variance: int = 0, stream: int = 0):
+        """bhrt_variance_spatial_dev on raw device pointers (0 = NULL); with a stream the call does not synchronise."""
+        v = lambda x: C.c_void_p(x or None)  # noqa: E731
+        _check(lib().bhrt_variance_spatial_dev(self._h, C.byref(opts), v(d_radiance), v(d_variance), v(d_length), v(d_z), v(d_normal), v(d_albedo), v(d_out_variance),
+                                               v(stream)))
 
     # ---- images beside the colour image (RenderImage z-buffer, DenoiseImage inputs) ------------
     def first_hit(self):

@@ -16,7 +16,8 @@
 //               [--camera-pos X,Y,Z] [--camera-target X,Y,Z] [--camera-up X,Y,Z] [--fov F]   (the <camera> tags, xmlload.cpp:109-127, replaced)
 //               [--shutter-pos X,Y,Z] [--shutter-target X,Y,Z] [--shutter-up X,Y,Z]           (camera motion blur: the camera at the end of the exposure)
 //               [--temporal N [--to-pos X,Y,Z] [--to-target X,Y,Z] [--to-up X,Y,Z] [--node-to-translate NAME:X,Y,Z] [--frames-png PREFIX]   (N frames along a camera or object move, each carried into the next)
-//                   [--denoise [--denoise-iters K]]]   (each frame written denoised with its carried variance)
+//                   [--denoise [--denoise-iters K]   (each frame written denoised with its carried variance)
+//                       [--spatial-variance [--variance-radius R] [--variance-min-length X]]]]   (the variance of a short history estimated from its neighbourhood)
 //               [--node-translate NAME:X,Y,Z]   (repeatable: one translate op on that node before anything is rendered)
 //   bhrt info   <scene.xml>
 //
@@ -82,6 +83,12 @@
 // bhrt_denoise(accumulated frame, its carried variance, this view's first hit).  The next frame gets the un-denoised accumulated frame and its
 // variance: the denoised image is for display and is never fed back.  Needs --spp >= 2 (a 1-spp frame has no variance); --guide-spp and
 // --coverage-filter beside it are usage errors (sampled guides are not carried).  Without --denoise the calls are those named above.
+// --spatial-variance [--variance-radius R] [--variance-min-length X] (needs --temporal N --denoise; anywhere else, and R or X without the flag, a
+// usage error): --spp 1 becomes legal, and there the current frame's variance, for every pixel, is bhrt_variance_spatial's estimate
+// of the rendered frame (no variance or length image) in the place of bhrt_render_var's zeros.  At every --spp the variance bhrt_denoise gets is
+// bhrt_variance_spatial(accumulated frame, its carried variance, its length): a pixel with fewer than X samples behind it (default 4 x spp: four
+// frames) is filtered with the estimate from its (2R + 1)^2 neighbourhood (R in 1..4, default 3), the others with their carried variance.  The
+// next frame gets the un-denoised accumulated frame and its carried variance, unmodified.  Without the flag every command line behaves as before.
 // --node-translate NAME:X,Y,Z (repeatable, any mode): one translate op appended to the node of that <object name=> through
 // bhrt_scene_set_node_transform, before anything is rendered.  --node-to-translate NAME:X,Y,Z (repeatable, needs --temporal N): frame k sets the
 // node to the record it had before frame 0 plus a translate of delta * ((float)k / (float)(N - 1)) per component in float32, and frames are
@@ -148,6 +155,10 @@ struct Args {
     bool temporal_given = false;
     Vec to_pos, to_target, to_up;      // --to-pos / -target / -up: the pose of the last frame
     std::string frames_png;            // --frames-png PREFIX
+    bool spatial_variance = false;     // --spatial-variance (with --temporal N --denoise): bhrt_variance_spatial where a pixel's history is short
+    int variance_radius = 0;           // --variance-radius R; 0: not given (the library's default)
+    bool variance_radius_given = false;
+    float variance_min_length = -1.f;  // --variance-min-length X; < 0: not given (4 x spp: four frames)
     // --node-translate NAME:X,Y,Z (any mode: one translate op before anything is rendered) and --node-to-translate NAME:X,Y,Z (--temporal: the
     // node's translation at the last frame); `node` is resolved once the scene is loaded
     struct NodeMove { std::string name; float v[3] = {0, 0, 0}; int32_t node = -1; };
@@ -293,6 +304,12 @@ static int render_temporal(bhrt_scene *scene, const Args &A, const bhrt_info &in
     // --denoise: the variance beside the light: the current frame's, the history's, the accumulated frame's and the previous one's
     const size_t nv = A.denoise ? npx * 3 : 0;
     std::vector<float> cv(nv), hv(nv), ov(nv), accv(nv);
+    // --spatial-variance: the estimate the denoiser gets in the place of ov; ov itself goes on to the next frame unmodified
+    bhrt_spatial_variance_opts sv;
+    bhrt_default_spatial_variance_opts(&sv);
+    if (A.variance_radius_given) sv.radius = A.variance_radius;
+    sv.min_length = A.variance_min_length >= 0.f ? A.variance_min_length : 4.f * (float)A.o.spp;
+    std::vector<float> dv(A.spatial_variance ? nv : 0);
     float prev_frame[12];
     // --node-to-translate: the moved nodes' records as they stand before frame 0, the previous frame's snapshot of all nodes and the id images
     const bool moving = !A.node_to_translate.empty();
@@ -319,13 +336,18 @@ static int render_temporal(bhrt_scene *scene, const Args &A, const bhrt_info &in
         st.passes += one.passes; st.wave_iterations += one.wave_iterations; st.seconds_total += one.seconds_total;
         if (moving && bhrt_first_hit_node(scene, id.data())) return fail("first hit node");
         if (A.denoise) { // the same sequence through the calls that carry the variance; the file gets the denoised frame, the next frame the un-denoised one
-            if (k > 0 && bhrt_reproject_var(scene, &ro, prev_frame, moving ? prev_xf.data() : nullptr, pz.data(), pn.data(), acc.data(), accv.data(), len.data(), pa.data(),
+            // at 1 spp the rendered frame's variance is 0 by definition: every pixel's is estimated from its neighbourhood instead
+            if (A.spatial_variance && o.spp < 2 && bhrt_variance_spatial(scene, &sv, cur.data(), nullptr, nullptr, z.data(), n.data(), a.data(), cv.data()))
+                return fail("spatial variance");
+            if (k > 0 &&bhrt_reproject_var(scene, &ro, prev_frame, moving ? prev_xf.data() : nullptr, pz.data(), pn.data(), acc.data(), accv.data(), len.data(), pa.data(),
                                             moving ? pid.data() : nullptr, z.data(), n.data(), a.data(), moving ? id.data() : nullptr, hist.data(), hv.data(), hl.data(), nullptr))
                 return fail("reproject var");
             if (bhrt_temporal_accumulate_var(scene, &to, cur.data(), cv.data(), (float)o.spp, k > 0 ? hist.data() : nullptr, k > 0 ? hv.data() : nullptr,
                                              k > 0 ? hl.data() : nullptr, out.data(), ov.data(), ol.data(), nullptr))
                 return fail("temporal accumulate var");
-            if (bhrt_denoise(scene, &A.dn, out.data(), ov.data(), z.data(), n.data(), a.data(), nullptr, rgb.data())) return fail("DenoiseImage");
+            // a pixel whose history is shorter than min_length is filtered with the estimate of the accumulated frame, the others with their carried variance
+            if (A.spatial_variance && bhrt_variance_spatial(scene, &sv, out.data(), ov.data(), ol.data(), z.data(), n.data(), a.data(), dv.data())) return fail("spatial variance");
+            if (bhrt_denoise(scene, &A.dn, out.data(), A.spatial_variance ? dv.data() : ov.data(), z.data(), n.data(), a.data(), nullptr, rgb.data())) return fail("DenoiseImage");
         } else if (k > 0 && moving) {
             if (bhrt_reproject_moving(scene, &ro, prev_frame, prev_xf.data(), pz.data(), pn.data(), acc.data(), len.data(), pa.data(), pid.data(), z.data(), n.data(), a.data(),
                                       id.data(), hist.data(), hl.data(), nullptr))
@@ -644,6 +666,9 @@ int main(int argc, char **argv)
         else if (s == "--to-target") A.to_target = vector_value("--to-target", next());
         else if (s == "--to-up") A.to_up = vector_value("--to-up", next());
         else if (s == "--frames-png") A.frames_png = next();
+        else if (s == "--spatial-variance") A.spatial_variance = true;
+        else if (s == "--variance-radius") { A.variance_radius = atoi(next()); A.variance_radius_given = true; }
+        else if (s == "--variance-min-length") A.variance_min_length = number_value("--variance-min-length", next(), false);
         else if (s == "--node-translate") A.node_translate.push_back(node_move_value("--node-translate", next()));
         else if (s == "--node-to-translate") A.node_to_translate.push_back(node_move_value("--node-to-translate", next()));
         else if (s == "--fov") {
@@ -690,8 +715,13 @@ int main(int argc, char **argv)
         fprintf(stderr, "bhrt: usage: --temporal needs N >= 2 frames and renders whole frames on one device (no --progressive, --adaptive, --gpus, --world)\n");
         return 2;
     }
-    if (A.temporal_given && A.denoise && o.spp < 2) {
-        fprintf(stderr, "bhrt: usage: --temporal with --denoise needs --spp >= 2 (at 1 sample per pixel a frame's variance is 0 by definition)\n");
+    if ((A.spatial_variance || A.variance_radius_given || A.variance_min_length >= 0.f) && !(A.spatial_variance && A.temporal_given && A.denoise)) {
+        fprintf(stderr, "bhrt: usage: --spatial-variance needs --temporal N --denoise, and --variance-radius / --variance-min-length need --spatial-variance\n");
+        return 2;
+    }
+    if (A.variance_radius_given && (A.variance_radius < 1 || A.variance_radius > 4)) { fprintf(stderr, "bhrt: usage: --variance-radius must be in 1..4\n"); return 2; }
+    if (A.temporal_given && A.denoise && o.spp < (A.spatial_variance ? 1 : 2)) {
+        fprintf(stderr, "bhrt: usage: --temporal with --denoise needs --spp >= 2 (at 1 sample per pixel a frame's variance is 0 by definition; --spatial-variance estimates one)\n");
         return 2;
     }
     if (A.temporal_given && A.denoise && (A.guide_spp_given || A.coverage_filter)) {

@@ -78,6 +78,17 @@ void bhrt_default_temporal_opts(bhrt_temporal_opts *o)
     o->gamma = 1; // as bhrt_opts.gamma (Main.cpp:128)
 }
 
+void bhrt_default_spatial_variance_opts(bhrt_spatial_variance_opts *o)
+{
+    if (!o) return;
+    memset(o, 0, sizeof *o);
+    o->radius = 3; // SVGF's 7 x 7
+    o->depth_tolerance = 0.01f; // bhrt_default_denoise_opts' sigma_depth
+    o->normal_threshold = BHRT_REPROJECT_NORMAL_THRESHOLD;
+    o->min_length = 4.f; // the project's own numbers, not new measurements
+    o->demodulate = 1;
+}
+
 int bhrt_scene_load_xml(const char *path, bhrt_scene **out) { return bhrt_scene_load_xml_ex(path, -1, out); }
 
 int bhrt_scene_load_xml_ex(const char *path, int bvh_device, bhrt_scene **out)

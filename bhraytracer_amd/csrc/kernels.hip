@@ -4835,6 +4835,71 @@ try {
     return BHRT_OK;
 } catch (...) { return bhrt::AbiException(); }
 
+// bhrt_variance_spatial* (k_spatial_variance): the arguments of both entry points, checked alike and before any device is touched
+static int SpatialVarianceArgs(const bhrt_scene *scene, const bhrt_spatial_variance_opts *opts, const float *radiance, const float *variance, const float *length,
+                               const float *out_variance)
+{
+    if (!scene) { SetError("spatial variance: null scene"); return BHRT_ERR_ARG; }
+    const char *bad = SpatialVarianceArgsError(opts, radiance, variance, length, out_variance);
+    if (*bad) { SetError(bad); return BHRT_ERR_ARG; }
+    return BHRT_OK;
+}
+
+int bhrt_variance_spatial_dev(bhrt_scene *scene, const bhrt_spatial_variance_opts *opts, const float *d_radiance, const float *d_variance, const float *d_length,
+                              const float *d_z, const float *d_normal, const float *d_albedo, float *d_out_variance, void *stream)
+try {
+    BHRT_TRY(SpatialVarianceArgs(scene, opts, d_radiance, d_variance, d_length, d_out_variance));
+    int rc = EnsureUploaded(scene);
+    if (rc) return rc;
+    DeviceState *D = scene->dev;
+    const bhrt_flat_header *H = scene->flat.hdr();
+    const int W = H->camera.width, Hh = H->camera.height;
+    const size_t n = (size_t)W * Hh;
+    if (n == 0 || n > 0x7fffffffull) { SetError("spatial variance: frame size out of range"); return BHRT_ERR_ARG; }
+    hipStream_t st = stream ? (hipStream_t)stream : D->stream;
+    SpatialVarianceJob J;
+    J.W = W; J.H = Hh; J.o = *opts;
+    J.radiance = d_radiance; J.variance = d_variance; J.length = d_length; J.z = d_z; J.normal = d_normal; J.albedo = d_albedo; J.out_variance = d_out_variance;
+    const bool want_albedo = opts->demodulate != 0; // without demodulate no albedo is read or computed
+    if (!d_z || !d_normal || (want_albedo && !d_albedo)) { // as bhrt_reproject_dev
+        BHRT_TRY(D->d_dn.Reserve(n * 7 * sizeof(float)));
+        float *g = (float *)D->d_dn.p;
+        float *gz = d_z ? nullptr : g, *gn = d_normal ? nullptr : g + n, *ga = !want_albedo || d_albedo ? nullptr : g + 4 * n;
+        hipLaunchKernelGGL(D->fm.tab ? k_first_hit<true> : k_first_hit<false>, dim3(((uint32_t)n + kBlock - 1) / kBlock), dim3(kBlock), 0, st, D->S, D->fm, W, Hh, gz, gn, ga);
+        HIP_CHECK(hipGetLastError());
+        if (gz) J.z = gz;
+        if (gn) J.normal = gn;
+        if (ga) J.albedo = ga;
+    }
+    HIP_CHECK(SpatialVarianceLaunch(J, st));
+    if (!stream) HIP_CHECK(hipStreamSynchronize(st));
+    return BHRT_OK;
+} catch (...) { return bhrt::AbiException(); }
+
+int bhrt_variance_spatial(bhrt_scene *scene, const bhrt_spatial_variance_opts *opts, const float *radiance, const float *variance, const float *length, const float *z,
+                          const float *normal, const float *albedo, float *out_variance)
+try {
+    BHRT_TRY(SpatialVarianceArgs(scene, opts, radiance, variance, length, out_variance));
+    int rc = EnsureUploaded(scene);
+    if (rc) return rc;
+    DeviceState *D = scene->dev;
+    const bhrt_flat_header *H = scene->flat.hdr();
+    const size_t n = (size_t)H->camera.width * H->camera.height;
+    // device copies, back to back, in 4-byte words per pixel: radiance 3, variance 3, length 1, z 1, normal 3, albedo 3, then out_variance 3
+    const float *const in[6] = {radiance, variance, length, z, normal, albedo};
+    const size_t width[7] = {3, 3, 1, 1, 3, 3, 3};
+    DevBuf<float> d;
+    BHRT_TRY(d.Reserve(n * 17));
+    float *at[7];
+    for (size_t k = 0, off = 0; k < 7; off += width[k] * n, k++) at[k] = d.p + off;
+    for (int k = 0; k < 6; k++)
+        if (in[k]) HIP_CHECK(hipMemcpyAsync(at[k], in[k], width[k] * n * 4, hipMemcpyHostToDevice, D->stream));
+    auto gin = [&](int k) -> float * { return in[k] ? at[k] : nullptr; };
+    BHRT_TRY(bhrt_variance_spatial_dev(scene, opts, gin(0), gin(1), gin(2), gin(3), gin(4), gin(5), at[6], nullptr));
+    HIP_CHECK(hipMemcpy(out_variance, at[6], 3 * n * sizeof(float), hipMemcpyDeviceToHost));
+    return BHRT_OK;
+} catch (...) { return bhrt::AbiException(); }
+
 static bool TileArgsOk(int W, int H, int tile, int rank, int world)
 {
     if (W <= 0 || H <= 0 || tile <= 0 || world <= 0 || rank < 0 || rank >= world) { SetError("bad tile partition"); return false; }

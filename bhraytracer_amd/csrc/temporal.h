@@ -1,5 +1,5 @@
 // temporal.h — launchers of the image-space stages of temporal.hip (bhrt_reproject*, bhrt_temporal_accumulate* and their variance-carrying
-// forms bhrt_reproject_var*, bhrt_temporal_accumulate_var*; kernels.hip owns the scene state and the first-hit kernel that fills in the guides
+// forms bhrt_reproject_var*, bhrt_temporal_accumulate_var*, and bhrt_variance_spatial*; kernels.hip owns the scene state and the first-hit kernel that fills in the guides
 // a caller leaves out).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -77,5 +77,21 @@ struct TemporalVarJob : TemporalJob {
     float *out_variance;           // W*H*3, or NULL
 };
 hipError_t TemporalVarLaunch(const TemporalVarJob &J, hipStream_t s);
+
+// stage 3S (k_spatial_variance)
+struct SpatialVarianceJob {
+    int W, H;
+    bhrt_spatial_variance_opts o;
+    const float *radiance; // W*H*3
+    const float *variance; // W*H*3, or NULL
+    const float *length;   // W*H, or NULL (then every pixel is estimated); needs variance
+    const float *z;        // W*H
+    const float *normal;   // W*H*3
+    const float *albedo;   // W*H*3; read only with o.demodulate
+    float *out_variance;   // W*H*3; aliases no input
+};
+// "" when the arguments are usable, else what is wrong with them (host arithmetic only)
+const char *SpatialVarianceArgsError(const bhrt_spatial_variance_opts *o, const float *radiance, const float *variance, const float *length, const float *out_variance);
+hipError_t SpatialVarianceLaunch(const SpatialVarianceJob &J, hipStream_t s);
 
 } // namespace bhrt

@@ -81,6 +81,26 @@
 //            out_variance = ((1 - a) * (1 - a)) * hv + (a * a) * v      with stage 2's a: out = (1 - a) h + a c, h and c independent
 //   With the clamp off and max_length = +inf, two frames of n1 and n2 samples pool to (n1^2 vA + n2^2 vB) / (n1 + n2)^2.
 //
+// 3S. SPATIAL VARIANCE ESTIMATE (k_spatial_variance<R>): the variance of a frame that has none it can trust — a 1-spp frame, a
+//   pixel whose history is short, an imported radiance image — estimated from the pixel's neighbourhood on its own surface, as SVGF does while
+//   a history is shorter than four frames.  Divisions and square roots are correctly rounded.  c = the radiance, v = the frame's present
+//   variance (optional), l = the samples behind each pixel (optional; needs v), z, n, a = the first hit; R = radius (1..4).
+//   pass     with l: where l_p >= min_length, out_p = v_p, the same bits (a NaN l_p fails the comparison: the pixel is estimated)
+//   demod    with demodulate: d_q = divisor(a_q), else d_q = (1, 1, 1) and no albedo is read;  e_q = c_q / d_q per channel
+//   window   taps (dx, dy) in {-R..R}^2 row-major (dy outer), q = p + (dx, dy); taps outside the image are skipped; the centre tap is always valid
+//            p a miss (z_p >= BHRT_BIGFLOAT):  another tap is valid iff z_q >= BHRT_BIGFLOAT
+//            p a hit:  another tap is valid iff z_q < BHRT_BIGFLOAT and |z_q - z_p| <= (depth_tolerance z_p) r, r = sqrt((float)(dx dx + dy dy)),
+//                      and (n_p.x n_q.x + n_p.y n_q.y) + n_p.z n_q.z >= normal_threshold      (the normals as they are: no unit())
+//            a comparison with a NaN is false: the tap is invalid
+//   estimate k = the number of valid taps;  per channel, over the valid taps in tap order, from 0:
+//            s = s + e_q,  m = s / (float)k;   then  t = t + (e_q - m)(e_q - m),  ve = t / (float)(k - 1);   out_p = ve (d_p d_p)
+//   k < 2    out_p = v_p with a variance image, else 0
+//   Hard stops as stage 1's, no exp or pow: the restatement is equal bit for bit.  Two passes: a sum of squares is >= 0 by construction and
+//   has none of the cancellation of m2 - m1^2.  k - 1: the unbiased sample variance.  Every c_q is already a pixel's mean at the frame's sample
+//   count, so the spread of neighbouring means over one surface estimates the variance of a pixel's mean, the quantity bhrt_denoise* and
+//   stage 2V take.  It also contains the signal's own gradient over the window (texture left after demodulation, shading, shadow edges), as
+//   SVGF's estimate does: it overstates the noise where the image itself varies.
+//
 // KERNELS.  k_reproject: one lane per pixel of the current camera, 256 in a row; the call's constants (A, m, the three dots) come from the host,
 // in the same float32 operations.  It reads 28 B per pixel of the current view (40 B with albedo) and, per tap, 32 B of the previous one (44 B
 // with albedo); it writes 24 B.  k_temporal_accumulate: the denoiser's 16 x 16 workgroups; the 3 x 3 block is read through the cache (a wave
@@ -91,6 +111,13 @@
 // by BHRT_MAX_NODE_DEPTH; no array is indexed dynamically (no scratch memory).  k_reproject_var: the same lane layout and taps, one body for
 // the camera-only and the moving case (it is new: no existing kernel's code depends on it); per tap 12 B more (v'), 12 B more written (hv).
 // k_temporal_accumulate_var: k_temporal_accumulate's workgroups and 3 x 3 block; 24 B more read (v, hv), 12 B more written.
+// k_spatial_variance<R>: the 16 x 16 workgroups again.  A pixel reads up to 2 (2R + 1)^2 taps, so the workgroup first stages its (16 + 2R)^2
+// halo tile in LDS, demodulated once per tile pixel, as seven planes (e.r, e.g, e.b, z, n.x, n.y, n.z): 13.6 KB at R = 3, and a wave's 16 x 4
+// lanes read 16 consecutive words of a plane per row, rows 16 + 2R >= 18 words apart: no two lanes of a 32-lane half share a bank.  The r of
+// the up to 33 distances dx dx + dy dy sit in LDS as well, one correctly rounded square root each.  Pass 1 keeps each tap's verdict in an 81-bit
+// mask in registers; pass 2 reads e alone.  demodulate, "variance given" and "length given" are uniform branches, R a template parameter (fixed
+// trip counts, no dynamically indexed array: no scratch memory).  Per pixel 28 B read (40 B with albedo; 12 B and 4 B more with v and l), times
+// ((16 + 2R) / 16)^2 for the halo (1.89 at R = 3, from the cache), 12 B written.  Fixed tap order, no atomics.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stddef.h>
@@ -559,6 +586,106 @@ __global__ void __launch_bounds__(kTaTx *kTaTy) k_temporal_accumulate(int W, int
     if (rgb8) store_color24(rgb8, p, o, gamma);
 }
 
+// the images of one k_spatial_variance call
+struct SpatialVarianceImages {
+    const float *c, *v, *l; // radiance; variance and length, or NULL
+    const float *z, *n, *a; // the first hit; a is read only with demodulate
+    float *out;
+};
+
+// Stage 3S.  Every thread of the workgroup, also one outside the image, takes part in staging the tile.
+template <int R>
+__global__ void __launch_bounds__(kTaTx *kTaTy) k_spatial_variance(int W, int H, float depth_tolerance, float normal_threshold, float min_length, int demodulate,
+                                                                   SpatialVarianceImages I)
+{
+    constexpr int TW = kTaTx + 2 * R, TH = kTaTy + 2 * R, NT = TW * TH, D = 2 * R + 1;
+    __shared__ float tile[7][NT];         // e.r, e.g, e.b, z, n.x, n.y, n.z of the halo tile
+    __shared__ float root[2 * R * R + 1]; // sqrt((float)k), k = dx dx + dy dy
+    const int tid = (int)(threadIdx.y * kTaTx + threadIdx.x);
+    const int x0 = (int)(blockIdx.x * kTaTx) - R, y0 = (int)(blockIdx.y * kTaTy) - R;
+    for (int i = tid; i < NT; i += kTaTx * kTaTy) {
+        const int ly = i / TW, lx = i - ly * TW, gx = x0 + lx, gy = y0 + ly;
+        V3 e = v3(0, 0, 0), nq = v3(0, 0, 0);
+        float zq = 0.f;
+        if (gx >= 0 && gx < W && gy >= 0 && gy < H) { // a tile pixel outside the image is never read as a tap
+            const size_t q = (size_t)gy * W + gx;
+            e = v3(I.c[3 * q], I.c[3 * q + 1], I.c[3 * q + 2]);
+            if (demodulate) {
+                const V3 dq = tp_divisor(I.a, q);
+                e = v3(e.x / dq.x, e.y / dq.y, e.z / dq.z);
+            }
+            zq = I.z[q];
+            nq = v3(I.n[3 * q], I.n[3 * q + 1], I.n[3 * q + 2]);
+        }
+        tile[0][i] = e.x; tile[1][i] = e.y; tile[2][i] = e.z;
+        tile[3][i] = zq;
+        tile[4][i] = nq.x; tile[5][i] = nq.y; tile[6][i] = nq.z;
+    }
+    if (tid <= 2 * R * R) root[tid] = dm::sqrt_f((float)tid);
+    __syncthreads();
+    const int x = x0 + R + (int)threadIdx.x, y = y0 + R + (int)threadIdx.y;
+    if (x >= W || y >= H) return;
+    const size_t p = (size_t)y * W + x;
+    V3 vp = v3(0, 0, 0);
+    if (I.v) vp = v3(I.v[3 * p], I.v[3 * p + 1], I.v[3 * p + 2]);
+    V3 o = vp; // pass-through, and fewer than two valid taps
+    const bool keep = I.l && I.l[p] >= min_length;
+    if (!keep) {
+        const int cp = ((int)threadIdx.y + R) * TW + (int)threadIdx.x + R;
+        const float zp = tile[3][cp];
+        const V3 np = v3(tile[4][cp], tile[5][cp], tile[6][cp]);
+        const bool miss = zp >= BHRT_BIGFLOAT;
+        const float tz = depth_tolerance * zp;
+        uint64_t lo = 0, hi = 0; // the verdict of tap (dy + R) D + (dx + R): bits 0..63 and 64..80
+        int k = 0;
+        V3 s = v3(0, 0, 0);
+        for (int dy = -R; dy <= R; dy++) {
+            const int qy = y + dy;
+            if (qy < 0 || qy >= H) continue;
+#pragma unroll
+            for (int dx = -R; dx <= R; dx++) {
+                const int qx = x + dx;
+                if (qx < 0 || qx >= W) continue;
+                const int q = cp + dy * TW + dx;
+                bool ok = true;
+                if (dx != 0 || dy != 0) {
+                    const float zq = tile[3][q];
+                    if (miss) ok = zq >= BHRT_BIGFLOAT;
+                    else
+                        ok = zq < BHRT_BIGFLOAT && fabsf(zq - zp) <= tz * root[dx * dx + dy * dy] &&
+                             (np.x * tile[4][q] + np.y * tile[5][q]) + np.z * tile[6][q] >= normal_threshold;
+                }
+                if (!ok) continue;
+                const int bit = (dy + R) * D + (dx + R);
+                if (bit < 64) lo |= 1ull << bit;
+                else hi |= 1ull << (bit - 64);
+                k++;
+                s = s + v3(tile[0][q], tile[1][q], tile[2][q]);
+            }
+        }
+        if (k >= 2) {
+            const V3 m = s / (float)k;
+            V3 t = v3(0, 0, 0);
+            for (int dy = -R; dy <= R; dy++) {
+#pragma unroll
+                for (int dx = -R; dx <= R; dx++) {
+                    const int bit = (dy + R) * D + (dx + R);
+                    if (!(((bit < 64 ? lo >> bit : hi >> (bit - 64)) & 1ull))) continue;
+                    const int q = cp + dy * TW + dx;
+                    const V3 e = v3(tile[0][q], tile[1][q], tile[2][q]) - m;
+                    t = t + e * e;
+                }
+            }
+            o = t / (float)(k - 1);
+            if (demodulate) {
+                const V3 d = tp_divisor(I.a, p);
+                o = v3(o.x * (d.x * d.x), o.y * (d.y * d.y), o.z * (d.z * d.z));
+            }
+        }
+    }
+    I.out[3 * p] = o.x; I.out[3 * p + 1] = o.y; I.out[3 * p + 2] = o.z;
+}
+
 static inline bool Finite(float x) { return x >= -3.402823466e38f && x <= 3.402823466e38f; }
 static inline V3 H3(const float *p) { return v3(p[0], p[1], p[2]); }
 
@@ -675,6 +802,27 @@ hipError_t TemporalVarLaunch(const TemporalVarJob &J, hipStream_t s)
     const dim3 grid((unsigned)((J.W + kTaTx - 1) / kTaTx), (unsigned)((J.H + kTaTy - 1) / kTaTy)), block(kTaTx, kTaTy);
     hipLaunchKernelGGL(k_temporal_accumulate_var, grid, block, 0, s, J.W, J.H, J.o.clamp_k, J.o.max_length, J.cur_samples, J.radiance, J.variance, J.history,
                        J.history_variance, J.length, J.out, J.out_variance, J.out_length, J.rgb8, J.o.gamma ? 1 : 0);
+    return hipGetLastError();
+}
+
+const char *SpatialVarianceArgsError(const bhrt_spatial_variance_opts *o, const float *radiance, const float *variance, const float *length, const float *out_variance)
+{
+    if (!o) return "spatial variance: null options";
+    if (!radiance || !out_variance) return "spatial variance: null radiance or out_variance";
+    if (o->radius < 1 || o->radius > 4) return "spatial variance: radius must be in 1..4";
+    if (!(o->depth_tolerance >= 0.f) || !Finite(o->depth_tolerance)) return "spatial variance: depth_tolerance must be finite and >= 0";
+    if (o->normal_threshold != o->normal_threshold) return "spatial variance: normal_threshold is not a number";
+    if (o->min_length != o->min_length) return "spatial variance: min_length is not a number";
+    if (length && !variance) return "spatial variance: a length image needs the variance it lets through";
+    return "";
+}
+
+hipError_t SpatialVarianceLaunch(const SpatialVarianceJob &J, hipStream_t s)
+{
+    const dim3 grid((unsigned)((J.W + kTaTx - 1) / kTaTx), (unsigned)((J.H + kTaTy - 1) / kTaTy)), block(kTaTx, kTaTy);
+    const SpatialVarianceImages I = {J.radiance, J.variance, J.length, J.z, J.normal, J.albedo, J.out_variance};
+    auto kernel = J.o.radius == 1 ? k_spatial_variance<1> : J.o.radius == 2 ? k_spatial_variance<2> : J.o.radius == 3 ? k_spatial_variance<3> : k_spatial_variance<4>;
+    hipLaunchKernelGGL(kernel, grid, block, 0, s, J.W, J.H, J.o.depth_tolerance, J.o.normal_threshold, J.o.min_length, J.o.demodulate ? 1 : 0, I);
     return hipGetLastError();
 }
 

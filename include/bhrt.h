@@ -563,6 +563,38 @@ int bhrt_temporal_accumulate_var_dev(bhrt_scene *scene, const bhrt_temporal_opts
 int bhrt_temporal_accumulate_var(bhrt_scene *scene, const bhrt_temporal_opts *opts, const float *radiance, const float *variance, float cur_samples, const float *history,
                                  const float *history_variance, const float *length, float *out, float *out_variance, float *out_length, uint8_t *rgb8);
 
+/* ---- spatial variance estimate: SVGF's variance for a short history ---------------------------------------------------------
+ * bhrt_render_var*'s variance is 0 at 1 spp and comes from 2-4 samples at 2-4 spp; a pixel that bhrt_reproject* reports with length 0, every
+ * pixel of a sequence's first frame and an imported radiance image have none they can trust.  bhrt_variance_spatial* estimates the variance of
+ * such a pixel's mean from the pixel's neighbourhood on its own surface: the unbiased sample variance of the (demodulated) radiance over the
+ * taps of a (2 radius + 1)^2 window that pass hard depth and normal stops, in two passes (the mean, then the squared deviations), stated
+ * exactly in csrc/temporal.hip as stage 3S and equal to its numpy restatement bit for bit.  The estimate contains the signal's own gradient
+ * over the window beside the noise, as SVGF's does.  The limits of bhrt_reproject* stand (pinhole guides: no lens, no shutter).
+ *
+ * The frame is the scene's camera, W x H.  radiance (W*H*3, required).  variance (W*H*3, may be NULL): the frame's present variance.  length
+ * (W*H, may be NULL; needs variance): the samples behind each pixel, bhrt_temporal_accumulate*'s out_length or bhrt_reproject*'s length: a pixel
+ * with length >= min_length keeps its variance's bits; a NaN length, and every pixel without a length image, is estimated.  z, normal, albedo:
+ * the first hit; each may be NULL = computed here by the kernel of bhrt_first_hit*; albedo is read or computed only with opts.demodulate.
+ * out_variance (W*H*3, required): must not alias any input (a pixel's taps are its neighbours' inputs).  A pixel with fewer than two valid
+ * taps gets its variance's value, 0 without a variance image.
+ * BHRT_ERR_ARG before any device is touched: a NULL scene, options, radiance or out_variance; a radius outside 1..4; a depth_tolerance that is
+ * negative or not finite; a NaN normal_threshold; a NaN min_length; a length without a variance.
+ * _dev: device pointers; with a stream the call does not synchronise.  Scratch for guides computed here (28 B per pixel) is the scene's,
+ * shared with bhrt_denoise* and bhrt_reproject*: calls on one scene must not overlap, a call on another stream included. */
+typedef struct bhrt_spatial_variance_opts {
+    int32_t radius;         /* R: the window is (2R + 1)^2 taps, 1..4; default 3 (SVGF's 7 x 7) */
+    float depth_tolerance;  /* a tap at distance r pixels is the same surface when |z_q - z_p| <= (depth_tolerance * z_p) * r; default 0.01f, bhrt_denoise_opts.sigma_depth's */
+    float normal_threshold; /* ... and dot(n_p, n_q) >= normal_threshold; default BHRT_REPROJECT_NORMAL_THRESHOLD */
+    float min_length;       /* pixels with length >= min_length keep their variance; default 4 (SVGF: four frames at one sample) */
+    int32_t demodulate;     /* 1 (default): estimate on radiance / divisor(albedo); 0: on the radiance, no albedo read or computed */
+    int32_t reserved[3];
+} bhrt_spatial_variance_opts;
+void bhrt_default_spatial_variance_opts(bhrt_spatial_variance_opts *opts);
+int bhrt_variance_spatial_dev(bhrt_scene *scene, const bhrt_spatial_variance_opts *opts, const float *d_radiance, const float *d_variance, const float *d_length,
+                              const float *d_z, const float *d_normal, const float *d_albedo, float *d_out_variance, void *stream);
+int bhrt_variance_spatial(bhrt_scene *scene, const bhrt_spatial_variance_opts *opts, const float *radiance, const float *variance, const float *length, const float *z,
+                          const float *normal, const float *albedo, float *out_variance);
+
 /* ---- adaptive sampling: RenderImage's per-pixel sample counts (Scenes/scene.h:534,570), which BeginRender only ever sets to 0
  * (Main.cpp:214), filled by a render that stops sampling a pixel once its mean is good enough ------------------------
  * Rounds: round 0 gives every owned pixel samples [0, min_spp); round r >= 1 gives every pixel still active samples [n_{r-1}, n_r),
