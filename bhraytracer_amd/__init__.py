@@ -84,6 +84,24 @@ class SpatialVarianceOpts(C.Structure):
                 ("reserved", C.c_int32 * 3)]
 
 
+class TemporalSessionOpts(C.Structure):
+    """bhrt_temporal_session_opts: the four stages' options and the four switches of a temporal session (include/bhrt.h)."""
+    _fields_ = [("reproject", ReprojectOpts), ("temporal", TemporalOpts), ("spatial", SpatialVarianceOpts), ("denoise_opts", DenoiseOpts),
+                ("carry_variance", C.c_int32), ("spatial_variance", C.c_int32), ("denoise", C.c_int32), ("follow_nodes", C.c_int32),
+                ("reserved", C.c_int32 * 4)]
+
+
+class TemporalProgress(C.Structure):
+    """bhrt_temporal_progress: where a temporal session stands (bhrt_temporal_status)."""
+    _fields_ = [("frames", C.c_uint32), ("failed", C.c_int32), ("history_pixels", C.c_uint64), ("pixels", C.c_uint64), ("reserved", C.c_int32 * 4)]
+
+
+# BHRT_TEMPORAL_IMG_* of include/bhrt.h: the images a temporal session keeps, with their element type and channels
+(TEMPORAL_IMG_ACCUMULATED, TEMPORAL_IMG_VARIANCE, TEMPORAL_IMG_LENGTH, TEMPORAL_IMG_HISTORY_LENGTH, TEMPORAL_IMG_FILTER_VARIANCE, TEMPORAL_IMG_Z,
+ TEMPORAL_IMG_NORMAL, TEMPORAL_IMG_ALBEDO, TEMPORAL_IMG_NODE, TEMPORAL_IMG_CURRENT, TEMPORAL_IMG_CURRENT_VARIANCE) = range(11)
+_TEMPORAL_IMG_ONE_CHANNEL = (TEMPORAL_IMG_LENGTH, TEMPORAL_IMG_HISTORY_LENGTH, TEMPORAL_IMG_Z, TEMPORAL_IMG_NODE)
+
+
 class XformOp(C.Structure):
     """bhrt_xform_op: one <scale> / <rotate> / <translate> of bhrt_scene_set_node_transform."""
     _fields_ = [("kind", C.c_int32), ("v", C.c_float * 4)]
@@ -140,6 +158,9 @@ EXPORTS = [
     "bhrt_first_hit_node", "bhrt_first_hit_node_dev", "bhrt_reproject_moving", "bhrt_reproject_moving_dev",
     "bhrt_reproject_var", "bhrt_reproject_var_dev", "bhrt_temporal_accumulate_var", "bhrt_temporal_accumulate_var_dev",
     "bhrt_default_spatial_variance_opts", "bhrt_variance_spatial", "bhrt_variance_spatial_dev",
+    "bhrt_first_hit_ex", "bhrt_first_hit_ex_dev",
+    "bhrt_default_temporal_session_opts", "bhrt_temporal_begin", "bhrt_temporal_frame", "bhrt_temporal_frame_dev", "bhrt_temporal_reset",
+    "bhrt_temporal_status", "bhrt_temporal_image", "bhrt_temporal_image_dev", "bhrt_temporal_end",
 ]
 
 # BHRT_DENOISE_SIGMA_COVERAGE of include/bhrt.h: the default coverage tolerance of the denoiser for sampled guides
@@ -176,6 +197,7 @@ def lib():
         L.bhrt_default_reproject_opts.restype = None
         L.bhrt_default_temporal_opts.restype = None
         L.bhrt_default_spatial_variance_opts.restype = None
+        L.bhrt_default_temporal_session_opts.restype = None
         _lib = L
     return _lib
 
@@ -233,6 +255,15 @@ def default_spatial_variance_opts(**kw) -> SpatialVarianceOpts:
     """bhrt_default_spatial_variance_opts (radius 3, depth_tolerance 0.01, normal_threshold 0.99, min_length 4, demodulate 1: DESIGN.md 22), fields overridden by kw."""
     o = SpatialVarianceOpts()
     lib().bhrt_default_spatial_variance_opts(C.byref(o))
+    for k, v in kw.items():
+        setattr(o, k, v)
+    return o
+
+
+def default_temporal_session_opts(**kw) -> TemporalSessionOpts:
+    """bhrt_default_temporal_session_opts (the four stages' defaults, the four switches 0), fields overridden by kw."""
+    o = TemporalSessionOpts()
+    lib().bhrt_default_temporal_session_opts(C.byref(o))
     for k, v in kw.items():
         setattr(o, k, v)
     return o
@@ -583,6 +614,54 @@ class Scene:
         """bhrt_progressive_end (the seam's StopRender): closes the session and frees its state; fine when none is open."""
         _check(lib().bhrt_progressive_end(self._h))
 
+    # ---- temporal session (DESIGN.md 23): reproject -> accumulate -> estimate -> denoise as one device-resident call per frame ------------
+    def temporal_begin(self, opts: Opts, topts: TemporalSessionOpts):
+        """bhrt_temporal_begin: opens the scene's temporal session; frame k renders with opts.seed + k."""
+        _check(lib().bhrt_temporal_begin(self._h, C.byref(opts) if opts is not None else None, C.byref(topts) if topts is not None else None))
+
+    def temporal_frame(self, want_radiance=True):
+        """bhrt_temporal_frame: the next frame of the session at the scene's camera and node transforms; returns the displayed frame,
+        (rgb8 (H, W, 3) uint8, radiance (H, W, 3) float32 or None, Stats)."""
+        H, W = self.height, self.width
+        rgb = np.zeros((H, W, 3), np.uint8)
+        rad = np.zeros((H, W, 3), np.float32) if want_radiance else None
+        st = Stats()
+        _check(lib().bhrt_temporal_frame(self._h, _ptr(rgb), _ptr(rad) if want_radiance else None, C.byref(st)))
+        return rgb, rad, st
+
+    def temporal_frame_dev(self, d_rgb8_ptr: int = 0, d_radiance_ptr: int = 0) -> Stats:
+        """bhrt_temporal_frame_dev on raw device pointers (0 = not wanted); synchronises the scene's stream."""
+        st = Stats()
+        _check(lib().bhrt_temporal_frame_dev(self._h, C.c_void_p(d_rgb8_ptr or None), C.c_void_p(d_radiance_ptr or None), C.byref(st)))
+        return st
+
+    def temporal_reset(self):
+        """bhrt_temporal_reset: a cut; the next frame is frame 0 again, the images stay allocated."""
+        _check(lib().bhrt_temporal_reset(self._h))
+
+    def temporal_status(self) -> TemporalProgress:
+        """bhrt_temporal_status: frames, pixels with history in the last frame, W * H, failed."""
+        p = TemporalProgress()
+        _check(lib().bhrt_temporal_status(self._h, C.byref(p)))
+        return p
+
+    def temporal_image(self, which: int) -> np.ndarray:
+        """bhrt_temporal_image: a host copy of one kept image (TEMPORAL_IMG_*) of the last frame: (H, W) or (H, W, 3), float32 (int32: the node ids)."""
+        shape = (self.height, self.width) if which in _TEMPORAL_IMG_ONE_CHANNEL else (self.height, self.width, 3)
+        a = np.zeros(shape, np.int32 if which == TEMPORAL_IMG_NODE else np.float32)
+        _check(lib().bhrt_temporal_image(self._h, int(which), _ptr(a)))
+        return a
+
+    def temporal_image_dev(self, which: int) -> int:
+        """bhrt_temporal_image_dev: the device address of one kept image, borrowed until the next frame, reset or end."""
+        p = C.c_void_p()
+        _check(lib().bhrt_temporal_image_dev(self._h, int(which), C.byref(p)))
+        return p.value or 0
+
+    def temporal_end(self):
+        """bhrt_temporal_end: closes the session and frees its images; fine when none is open."""
+        _check(lib().bhrt_temporal_end(self._h))
+
     def sample_count_image(self, count):
         """RenderImage::ComputeSampleCountImage (scene.h:603-626, bhrt_sample_count_image) of a count image: returns (img uint8 shaped like
         count, smax)."""
@@ -861,6 +940,23 @@ class Scene:
 
     def first_hit_node_dev(self, d_node: int, stream: int = 0):
         _check(lib().bhrt_first_hit_node_dev(self._h, C.c_void_p(d_node or None), C.c_void_p(stream or None)))
+
+    def first_hit_ex(self, want=("z", "normal", "albedo", "node"), into=None):
+        """bhrt_first_hit_ex: the images of first_hit and first_hit_node from one trace per pixel.  Returns a dict of the images named in
+        `want` (the others are passed as NULL); `into`: a dict of host arrays to write into instead of fresh zeros."""
+        H, W = self.height, self.width
+        shapes = {"z": ((H, W), np.float32), "normal": ((H, W, 3), np.float32), "albedo": ((H, W, 3), np.float32), "node": ((H, W), np.int32)}
+        out = {}
+        for k in want:
+            out[k] = into[k] if into is not None and k in into else np.zeros(*shapes[k])
+            assert out[k].shape == shapes[k][0] and out[k].dtype == shapes[k][1] and out[k].flags["C_CONTIGUOUS"], k
+        p = lambda k: _ptr(out[k]) if k in out else None  # noqa: E731
+        _check(lib().bhrt_first_hit_ex(self._h, p("z"), p("normal"), p("albedo"), p("node")))
+        return out
+
+    def first_hit_ex_dev(self, d_z: int = 0, d_normal: int = 0, d_albedo: int = 0, d_node: int = 0, stream: int = 0):
+        v = lambda x: C.c_void_p(x or None)  # noqa: E731
+        _check(lib().bhrt_first_hit_ex_dev(self._h, v(d_z), v(d_normal), v(d_albedo), v(d_node), v(stream)))
 
     def guides(self, opts: Opts, want=("z", "normal", "albedo", "coverage"), into=None):
         """Sampled guide images (bhrt_guides): z (H, W), normal (H, W, 3), albedo (H, W, 3) and coverage (H, W), formed by the

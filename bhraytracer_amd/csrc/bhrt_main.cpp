@@ -77,7 +77,8 @@
 // frame k's accumulated output and length reprojected into its view (bhrt_reproject with both views' first hits, albedo included), with the
 // library's default options.  -o gets the last frame, --frames-png PREFIX every frame as PREFIX000.png, PREFIX001.png, ...; --radiance the last
 // frame's accumulated radiance.  One device, whole frames: with --progressive, --adaptive, --gpus or --world > 1,
-// with N < 2, or --to-* / --frames-png without --temporal: a usage error.
+// with N < 2, or --to-* / --frames-png without --temporal: a usage error.  The loop is a temporal session (bhrt_temporal_begin / _frame / _end,
+// DESIGN.md 23): the setters, then one call per frame; the stages named here and below are the session's, on images that stay on the device.
 // --temporal N --denoise [--denoise-iters K]: every frame is rendered with bhrt_render_var, reprojected with bhrt_reproject_var
 // (with the node snapshot and id images under --node-to-translate) and accumulated with bhrt_temporal_accumulate_var, and what is written is
 // bhrt_denoise(accumulated frame, its carried variance, this view's first hit).  The next frame gets the un-denoised accumulated frame and its
@@ -293,30 +294,22 @@ static int denoise_frame(bhrt_scene *scene, const Args &A, const bhrt_info &info
 static int render_temporal(bhrt_scene *scene, const Args &A, const bhrt_info &info, const float p0[9], const float p1[9], std::vector<uint8_t> &rgb, std::vector<float> &rad,
                            bhrt_stats &st)
 {
-    const size_t npx = (size_t)info.width * info.height;
-    bhrt_reproject_opts ro;
-    bhrt_temporal_opts to;
-    bhrt_default_reproject_opts(&ro);
-    bhrt_default_temporal_opts(&to);
-    to.gamma = A.o.gamma;
-    // the previous view (frame, first hit, accumulated light and its length) and the current one
-    std::vector<float> pz(npx), pn(npx * 3), pa(npx * 3), acc(npx * 3), len(npx), z(npx), n(npx * 3), a(npx * 3), cur(npx * 3), hist(npx * 3), hl(npx), out(npx * 3), ol(npx);
-    // --denoise: the variance beside the light: the current frame's, the history's, the accumulated frame's and the previous one's
-    const size_t nv = A.denoise ? npx * 3 : 0;
-    std::vector<float> cv(nv), hv(nv), ov(nv), accv(nv);
-    // --spatial-variance: the estimate the denoiser gets in the place of ov; ov itself goes on to the next frame unmodified
-    bhrt_spatial_variance_opts sv;
-    bhrt_default_spatial_variance_opts(&sv);
-    if (A.variance_radius_given) sv.radius = A.variance_radius;
-    sv.min_length = A.variance_min_length >= 0.f ? A.variance_min_length : 4.f * (float)A.o.spp;
-    std::vector<float> dv(A.spatial_variance ? nv : 0);
-    float prev_frame[12];
-    // --node-to-translate: the moved nodes' records as they stand before frame 0, the previous frame's snapshot of all nodes and the id images
-    const bool moving = !A.node_to_translate.empty();
-    std::vector<bhrt_xform> saved(A.node_to_translate.size()), prev_xf(moving ? std::max<uint32_t>(info.n_nodes, 1) : 0);
-    std::vector<int32_t> pid(moving ? npx : 0), id(moving ? npx : 0);
+    // the library's default stage options; --denoise carries the variance, --spatial-variance estimates it where the history is short
+    // (DESIGN.md 22), --node-to-translate follows the nodes.  The session keeps every image on the device
+    bhrt_temporal_session_opts ts;
+    bhrt_default_temporal_session_opts(&ts);
+    ts.temporal.gamma = A.o.gamma;
+    ts.denoise_opts = A.dn;
+    if (A.variance_radius_given) ts.spatial.radius = A.variance_radius;
+    ts.spatial.min_length = A.variance_min_length >= 0.f ? A.variance_min_length : 4.f * (float)A.o.spp;
+    ts.carry_variance = A.denoise; ts.denoise = A.denoise;
+    ts.spatial_variance = A.spatial_variance;
+    ts.follow_nodes = !A.node_to_translate.empty();
+    // --node-to-translate: the moved nodes' records as they stand before frame 0
+    std::vector<bhrt_xform> saved(A.node_to_translate.size());
     for (size_t m = 0; m < saved.size(); m++)
         if (bhrt_scene_get_node_transform(scene, A.node_to_translate[m].node, &saved[m])) return fail("node transform");
+    if (bhrt_temporal_begin(scene, &A.o, &ts)) return fail("temporal session");
     for (int k = 0; k < A.temporal; k++) {
         const float s = (float)k / (float)(A.temporal - 1);
         float p[9];
@@ -327,50 +320,21 @@ static int render_temporal(bhrt_scene *scene, const Args &A, const bhrt_info &in
             bhrt_xform_op op = {BHRT_XFORM_TRANSLATE, {mv.v[0] * s, mv.v[1] * s, mv.v[2] * s, 0.f}};
             if (bhrt_scene_set_node_transform(scene, mv.node, saved[m].tm, saved[m].pos, &op, 1)) return fail("set node transform");
         }
-        bhrt_opts o = A.o;
-        o.seed = A.o.seed + (uint32_t)k;
         bhrt_stats one;
-        if (bhrt_first_hit(scene, z.data(), n.data(), a.data())) return fail("first hit");
-        if (A.denoise ? bhrt_render_var(scene, &o, nullptr, cur.data(), cv.data(), &one) : bhrt_render(scene, &o, nullptr, cur.data(), &one)) return fail("BeginRender");
+        if (bhrt_temporal_frame(scene, rgb.data(), nullptr, &one)) return fail("temporal frame");
         st.closest_rays += one.closest_rays; st.shadow_rays += one.shadow_rays; st.shade_calls += one.shade_calls; st.camera_samples += one.camera_samples;
         st.passes += one.passes; st.wave_iterations += one.wave_iterations; st.seconds_total += one.seconds_total;
-        if (moving && bhrt_first_hit_node(scene, id.data())) return fail("first hit node");
-        if (A.denoise) { // the same sequence through the calls that carry the variance; the file gets the denoised frame, the next frame the un-denoised one
-            // at 1 spp the rendered frame's variance is 0 by definition: every pixel's is estimated from its neighbourhood instead
-            if (A.spatial_variance && o.spp < 2 && bhrt_variance_spatial(scene, &sv, cur.data(), nullptr, nullptr, z.data(), n.data(), a.data(), cv.data()))
-                return fail("spatial variance");
-            if (k > 0 &&bhrt_reproject_var(scene, &ro, prev_frame, moving ? prev_xf.data() : nullptr, pz.data(), pn.data(), acc.data(), accv.data(), len.data(), pa.data(),
-                                            moving ? pid.data() : nullptr, z.data(), n.data(), a.data(), moving ? id.data() : nullptr, hist.data(), hv.data(), hl.data(), nullptr))
-                return fail("reproject var");
-            if (bhrt_temporal_accumulate_var(scene, &to, cur.data(), cv.data(), (float)o.spp, k > 0 ? hist.data() : nullptr, k > 0 ? hv.data() : nullptr,
-                                             k > 0 ? hl.data() : nullptr, out.data(), ov.data(), ol.data(), nullptr))
-                return fail("temporal accumulate var");
-            // a pixel whose history is shorter than min_length is filtered with the estimate of the accumulated frame, the others with their carried variance
-            if (A.spatial_variance && bhrt_variance_spatial(scene, &sv, out.data(), ov.data(), ol.data(), z.data(), n.data(), a.data(), dv.data())) return fail("spatial variance");
-            if (bhrt_denoise(scene, &A.dn, out.data(), A.spatial_variance ? dv.data() : ov.data(), z.data(), n.data(), a.data(), nullptr, rgb.data())) return fail("DenoiseImage");
-        } else if (k > 0 && moving) {
-            if (bhrt_reproject_moving(scene, &ro, prev_frame, prev_xf.data(), pz.data(), pn.data(), acc.data(), len.data(), pa.data(), pid.data(), z.data(), n.data(), a.data(),
-                                      id.data(), hist.data(), hl.data(), nullptr))
-                return fail("reproject moving");
-        } else if (k > 0 && bhrt_reproject(scene, &ro, prev_frame, pz.data(), pn.data(), acc.data(), len.data(), pa.data(), z.data(), n.data(), a.data(), hist.data(), hl.data(), nullptr))
-            return fail("reproject");
-        if (!A.denoise && bhrt_temporal_accumulate(scene, &to, cur.data(), (float)o.spp, k > 0 ? hist.data() : nullptr, k > 0 ? hl.data() : nullptr, out.data(), ol.data(), rgb.data()))
-            return fail("temporal accumulate");
-        size_t carried = 0;
-        for (size_t q = 0; k > 0 && q < npx; q++) carried += hl[q] > 0.f;
-        printf("frame %d: camera %g,%g,%g, history on %.1f%% of the pixels\n", k, p[0], p[1], p[2], 100.0 * (double)carried / (double)npx);
+        bhrt_temporal_progress pg;
+        if (bhrt_temporal_status(scene, &pg)) return fail("temporal status");
+        printf("frame %d: camera %g,%g,%g, history on %.1f%% of the pixels\n", k, p[0], p[1], p[2], 100.0 * (double)pg.history_pixels / (double)pg.pixels);
         if (!A.frames_png.empty()) {
             char name[16];
             snprintf(name, sizeof name, "%03d.png", k);
             if (bhrt_save_png((A.frames_png + name).c_str(), rgb.data(), info.width, info.height)) return fail("SaveImage (frame)");
         }
-        if (bhrt_scene_get_camera_frame(scene, prev_frame)) return fail("camera frame");
-        if (moving && bhrt_scene_get_node_transforms(scene, prev_xf.data(), (uint32_t)prev_xf.size(), nullptr)) return fail("node transforms");
-        pid.swap(id);
-        pz.swap(z); pn.swap(n); pa.swap(a); acc.swap(out); len.swap(ol);
-        accv.swap(ov);
     }
-    if (!rad.empty()) rad = acc;
+    if (!rad.empty() && bhrt_temporal_image(scene, BHRT_TEMPORAL_IMG_ACCUMULATED, rad.data())) return fail("temporal image");
+    if (bhrt_temporal_end(scene)) return fail("temporal end");
     return 0;
 }
 

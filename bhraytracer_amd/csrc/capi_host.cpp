@@ -89,6 +89,16 @@ void bhrt_default_spatial_variance_opts(bhrt_spatial_variance_opts *o)
     o->demodulate = 1;
 }
 
+void bhrt_default_temporal_session_opts(bhrt_temporal_session_opts *o)
+{
+    if (!o) return;
+    memset(o, 0, sizeof *o); // the four switches off: bhrt_reproject* + bhrt_temporal_accumulate*, the camera alone
+    bhrt_default_reproject_opts(&o->reproject);
+    bhrt_default_temporal_opts(&o->temporal);
+    bhrt_default_spatial_variance_opts(&o->spatial);
+    bhrt_default_denoise_opts(&o->denoise_opts);
+}
+
 int bhrt_scene_load_xml(const char *path, bhrt_scene **out) { return bhrt_scene_load_xml_ex(path, -1, out); }
 
 int bhrt_scene_load_xml_ex(const char *path, int bvh_device, bhrt_scene **out)
@@ -127,6 +137,7 @@ try {
 void bhrt_scene_free(bhrt_scene *s)
 {
     if (!s) return;
+    if (s->temporal && s->temporal_release) s->temporal_release(s->temporal); // an open temporal session's images, before the streams of the device state go
     if (s->dev) bhrt::DestroyDeviceState(s->dev);
     delete s;
 }

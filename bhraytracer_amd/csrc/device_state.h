@@ -2,63 +2,9 @@
 // Part of the kernels.hip translation unit, included there behind the kernels (it uses their argument types and HIP_CHECK); not a header for
 // other files: they see `struct DeviceState;`, DestroyDeviceState and the Refresh* hooks of the scene setters (scene_internal.h).
 #pragma once
+#include "dev_buf.h" // DevBuf, PinnedBuf
 
 namespace bhrt {
-
-// Device memory owned by its holder; grow-only.  n: capacity in elements.
-template <class T> struct DevBuf {
-    T *p = nullptr;
-    size_t n = 0;
-    DevBuf() = default;
-    DevBuf(const DevBuf &) = delete;
-    DevBuf &operator=(const DevBuf &) = delete;
-    DevBuf(DevBuf &&o) noexcept : p(o.p), n(o.n) { o.p = nullptr; o.n = 0; }
-    DevBuf &operator=(DevBuf &&o) noexcept
-    {
-        if (this != &o) { Free(); p = o.p; n = o.n; o.p = nullptr; o.n = 0; }
-        return *this;
-    }
-    ~DevBuf() { Free(); }
-    // n >= want: nothing.  Otherwise the old memory is freed FIRST and the contents are not kept; a failed allocation leaves an empty buffer with
-    // capacity 0, so the next call tries again.  (hipFree waits for the device: kernels of an earlier call may still read the old memory.)
-    int Reserve(size_t want)
-    {
-        if (n >= want) return BHRT_OK;
-        Free();
-        HIP_CHECK(hipMalloc(&p, want * sizeof(T)));
-        n = want;
-        return BHRT_OK;
-    }
-    void Free()
-    {
-        if (p) (void)hipFree(p);
-        p = nullptr; n = 0;
-    }
-    T *Release() // hands the memory to the caller
-    {
-        T *r = p;
-        p = nullptr; n = 0;
-        return r;
-    }
-    operator T *() const { return p; }
-    T *operator->() const { return p; }
-};
-
-// The pinned-host twin (one allocation, never regrown).
-template <class T> struct PinnedBuf {
-    T *p = nullptr;
-    PinnedBuf() = default;
-    PinnedBuf(const PinnedBuf &) = delete;
-    PinnedBuf &operator=(const PinnedBuf &) = delete;
-    ~PinnedBuf() { if (p) (void)hipHostFree(p); }
-    int Alloc(size_t count, unsigned flags = hipHostMallocDefault)
-    {
-        HIP_CHECK(hipHostMalloc(&p, count * sizeof(T), flags));
-        return BHRT_OK;
-    }
-    operator T *() const { return p; }
-    T *operator->() const { return p; }
-};
 
 // Streams and events of a DeviceState.  A base class, so that it is destroyed AFTER the members of DeviceState: device memory is released
 // (hipFree waits for the device) before the streams go.

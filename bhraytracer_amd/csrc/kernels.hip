@@ -1627,6 +1627,37 @@ __global__ void __launch_bounds__(kBlock) k_first_hit_node(DevScene S, int W, in
     if (active) node[q] = hit.node >= 0 ? hit.node : -1;
 }
 
+// All four first-hit images from one trace (bhrt_first_hit_ex*): k_first_hit's ray, trace, attribute and albedo code and
+// k_first_hit_node's store, so z, normal and albedo are k_first_hit's bytes and node is k_first_hit_node's.  A kernel of its own beside the two,
+// which keep their signatures and their code; any pointer may be NULL.
+template <bool kFm>
+__global__ void __launch_bounds__(kBlock) k_first_hit_ex(DevScene S, FaceMtlTable T, int W, int H, float *z, float *normal, float *albedo, int32_t *node)
+{
+    __shared__ bhrt_bvh_node nodelet[BHRT_LDS_NODES];
+    const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
+    const bool active = q < (uint32_t)(W * H);
+    const int j = (int)(q / (uint32_t)W), i = (int)(q - (uint32_t)j * (uint32_t)W);
+    const V3 topLeft = ld3(S.cam.top_left), ddx = ld3(S.cam.dd_x), ddy = ld3(S.cam.dd_y), pos = ld3(S.cam.pos);
+    const V3 o = pos, d = ((topLeft + (float)i * ddx) - (float)j * ddy) - pos; // Main.cpp:145,153
+    Hit hit;
+    trace_closest(S, o, d, BHRT_HIT_FRONT, hit, active, nodelet); // uniform call: the block stages nodelets together
+    if (!active) return;
+    if (node) node[q] = hit.node >= 0 ? hit.node : -1; // before the attributes: the hit record is not needed behind them
+    V3 N = v3(0, 0, 0), kd = v3(0, 0, 0);
+    if (hit.node >= 0 && (normal || albedo)) {
+        const int mi = kFm ? resolve_material(S, T, hit.node, hit.prim) : S.nodes[hit.node].material;
+        const bool blinn = mi >= 0 && S.materials[mi].kind == BHRT_MTL_BLINN;
+        Attr a;
+        hit_attrs(S, o, d, hit.t, hit.node, hit.prim, albedo && blinn && S.materials[mi].diffuse.map >= 0, a);
+        N = a.N;
+        if (blinn) kd = tc_sample_d(S, S.materials[mi].diffuse, a.uvw, a.du, a.dv); // diffuse.Sample(uvw, duvw), MtlBlinn.cpp:393
+        else if (mi >= 0 && S.materials[mi].kind == BHRT_MTL_WHITE) kd = v3(1, 1, 1);
+    }
+    if (z) z[q] = hit.node >= 0 ? hit.t : BHRT_BIGFLOAT;
+    if (normal) st3(normal, q, N);
+    if (albedo) st3(albedo, q, kd);
+}
+
 // The sampled guide images (bhrt_guides*): k_first_hit's three values and a hit flag for every camera sample of a pixel — the
 // render's own ray of (seed, pixel, sample): camera_ray, jitter and lens included — summed per pixel in float32, in sample order.
 // A launch covers samples [P.s0, P.s0 + P.spp) (a chunk of at most kBlock) of the pass's pixels.  A workgroup holds ppb = kBlock / P.spp
@@ -3597,6 +3628,21 @@ struct FrameStage {
     }
 };
 
+// What the temporal session (temporal_session.hip, a translation unit of its own above the public entry points) needs from the scene's device
+// state: the scene's own stream, and at begin the option checks of the render entry points, before any device is touched as
+// bhrt_progressive_begin makes them (host arithmetic only).
+void *SceneStream(const bhrt_scene *scene) { return scene && scene->dev ? (void *)scene->dev->stream : nullptr; }
+int SceneDevice(const bhrt_scene *scene) { return scene && scene->dev ? scene->dev->device : -1; }
+int RenderArgsCheck(bhrt_scene *scene, const bhrt_opts *opts)
+{
+    BHRT_CHECK_LENS(scene, opts);
+    BHRT_CHECK_GLOBAL(scene);
+    if (opts->photon_map && !(scene->dev && scene->dev->cmap.d_photons)) { SetError("photon_map = 1 needs bhrt_photon_build first"); return BHRT_ERR_ARG; }
+    PassInfo P;
+    uint64_t owned_pixels = 0;
+    return FramePassInfo(scene, *opts, P, owned_pixels); // spp in 1..65535, rank, bounce counts
+}
+
 } // namespace bhrt
 
 using namespace bhrt;
@@ -3640,6 +3686,10 @@ try {
     if (scene->dev && scene->dev->device == device) { HIP_CHECK(hipSetDevice(device)); return BHRT_OK; }
     if (scene->dev && scene->prog.open && scene->dev->prog_session == scene->prog.id) { // the move would drop the device state, the session's with it
         SetError("bhrt_scene_upload: a progressive session of this scene holds its state on device " + std::to_string(scene->dev->device) + ": bhrt_progressive_end first");
+        return BHRT_ERR_ARG;
+    }
+    if (scene->dev && TemporalSessionHoldsBuffers(scene->temporal)) { // its images live on the old device
+        SetError("bhrt_scene_upload: a temporal session of this scene holds its images on device " + std::to_string(scene->dev->device) + ": bhrt_temporal_end first");
         return BHRT_ERR_ARG;
     }
     int count = 0;
@@ -4179,6 +4229,43 @@ try {
     BHRT_TRY(d.Reserve(n));
     BHRT_TRY(bhrt_first_hit_node_dev(scene, d.p, nullptr));
     HIP_CHECK(hipMemcpy(node, d, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return BHRT_OK;
+} catch (...) { return bhrt::AbiException(); }
+
+// The four images of bhrt_first_hit* and bhrt_first_hit_node* from one trace per pixel (k_first_hit_ex)
+int bhrt_first_hit_ex_dev(bhrt_scene *scene, float *d_z, float *d_normal, float *d_albedo, int32_t *d_node, void *stream)
+try {
+    if (!scene) { SetError("bhrt_first_hit_ex: null scene"); return BHRT_ERR_ARG; }
+    if (!d_z && !d_normal && !d_albedo && !d_node) { SetError("bhrt_first_hit_ex: no image is asked for"); return BHRT_ERR_ARG; }
+    int rc = EnsureUploaded(scene);
+    if (rc) return rc;
+    DeviceState *D = scene->dev;
+    const bhrt_flat_header *H = scene->flat.hdr();
+    const int W = H->camera.width, Hh = H->camera.height;
+    hipStream_t st = stream ? (hipStream_t)stream : D->stream;
+    hipLaunchKernelGGL(D->fm.tab ? k_first_hit_ex<true> : k_first_hit_ex<false>, dim3(((uint32_t)(W * Hh) + kBlock - 1) / kBlock), dim3(kBlock), 0, st, D->S, D->fm, W, Hh, d_z,
+                       d_normal, d_albedo, d_node);
+    HIP_CHECK(hipGetLastError());
+    if (!stream) HIP_CHECK(hipStreamSynchronize(st));
+    return BHRT_OK;
+} catch (...) { return bhrt::AbiException(); }
+
+int bhrt_first_hit_ex(bhrt_scene *scene, float *z, float *normal, float *albedo, int32_t *node)
+try {
+    if (!scene) { SetError("bhrt_first_hit_ex: null scene"); return BHRT_ERR_ARG; }
+    if (!z && !normal && !albedo && !node) { SetError("bhrt_first_hit_ex: no image is asked for"); return BHRT_ERR_ARG; }
+    int rc = EnsureUploaded(scene);
+    if (rc) return rc;
+    const bhrt_flat_header *H = scene->flat.hdr();
+    const size_t n = (size_t)H->camera.width * H->camera.height;
+    DevBuf<float> d; // z, normal, albedo, then the ids in the last n words
+    BHRT_TRY(d.Reserve(n * 8));
+    int32_t *d_node = (int32_t *)(d + 7 * n);
+    BHRT_TRY(bhrt_first_hit_ex_dev(scene, z ? d.p : nullptr, normal ? d + n : nullptr, albedo ? d + 4 * n : nullptr, node ? d_node : nullptr, nullptr));
+    if (z) HIP_CHECK(hipMemcpy(z, d, n * sizeof(float), hipMemcpyDeviceToHost));
+    if (normal) HIP_CHECK(hipMemcpy(normal, d + n, 3 * n * sizeof(float), hipMemcpyDeviceToHost));
+    if (albedo) HIP_CHECK(hipMemcpy(albedo, d + 4 * n, 3 * n * sizeof(float), hipMemcpyDeviceToHost));
+    if (node) HIP_CHECK(hipMemcpy(node, d_node, n * sizeof(int32_t), hipMemcpyDeviceToHost));
     return BHRT_OK;
 } catch (...) { return bhrt::AbiException(); }
 

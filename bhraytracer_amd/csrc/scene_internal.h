@@ -41,6 +41,15 @@ struct ProgressiveSession {
     uint64_t retired_samples = 0; // sum of the counts of the retired pixels
     int cur = 0;                 // which of the two device lists holds the active pixels (c > 0; the first step takes the range [0, owned))
 };
+
+// The temporal session (bhrt_temporal_*) lives in temporal_session.hip, a translation unit above the public _dev entry points; the
+// scene owns it through a pointer.  What that unit needs from the scene's device state is defined in the kernels.hip unit.
+struct TemporalSession;
+void DestroyTemporalSession(TemporalSession *t);            // frees its images on their device; nullptr: nothing
+bool TemporalSessionHoldsBuffers(const TemporalSession *t); // bhrt_scene_upload to another device is refused while it does
+void *SceneStream(const bhrt_scene *scene);                 // the scene's own hipStream_t; nullptr before the upload
+int SceneDevice(const bhrt_scene *scene);                   // the device the scene is uploaded to; -1 before the upload
+int RenderArgsCheck(bhrt_scene *scene, const bhrt_opts *opts); // what bhrt_render* refuses of its options, host arithmetic only
 } // namespace bhrt
 
 struct bhrt_scene {
@@ -48,4 +57,7 @@ struct bhrt_scene {
     uint32_t n_triangles = 0, n_bvh_nodes = 0, max_bvh_depth = 0;
     bhrt::DeviceState *dev = nullptr;
     bhrt::ProgressiveSession prog; // not carried by bhrt_scene_clone
+    bhrt::TemporalSession *temporal = nullptr; // bhrt_temporal_begin .. _end; not carried by bhrt_scene_clone
+    // how bhrt_scene_free (capi_host.cpp, which also links into host-only programs without the HIP units) releases it: set with `temporal`
+    void (*temporal_release)(bhrt::TemporalSession *) = nullptr;
 };

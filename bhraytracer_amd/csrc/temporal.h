@@ -94,4 +94,8 @@ struct SpatialVarianceJob {
 const char *SpatialVarianceArgsError(const bhrt_spatial_variance_opts *o, const float *radiance, const float *variance, const float *length, const float *out_variance);
 hipError_t SpatialVarianceLaunch(const SpatialVarianceJob &J, hipStream_t s);
 
+// the temporal session's count of the pixels with history (k_history_count): zeroes *count (device) on `s`, then adds the number of
+// the n (< 2^32) device lengths that are > 0
+hipError_t HistoryCountLaunch(const float *length, size_t n, unsigned long long *count, hipStream_t s);
+
 } // namespace bhrt

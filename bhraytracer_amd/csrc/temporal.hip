@@ -686,6 +686,37 @@ __global__ void __launch_bounds__(kTaTx *kTaTy) k_spatial_variance(int W, int H,
     I.out[3 * p] = o.x; I.out[3 * p + 1] = o.y; I.out[3 * p + 2] = o.z;
 }
 
+// The pixels with history (bhrt_temporal_status): how many of the n lengths are > 0 (a NaN is not).  Every wave counts its 64
+// lanes with one ballot and one popcount per round of the grid-stride loop, the workgroup's four wave sums meet in LDS, and one 64-bit
+// integer atomicAdd per workgroup reaches *count, which the caller has zeroed on the same stream.  Integer and order-free: exact.
+constexpr int kHcBlock = 256, kHcMaxBlocks = 2048;
+__global__ void __launch_bounds__(kHcBlock) k_history_count(const float *__restrict__ length, uint32_t n, unsigned long long *count)
+{
+    __shared__ uint32_t s_wave[kHcBlock / 64];
+    uint32_t mine = 0; // the same in every lane of a wave
+    for (uint64_t base = (uint64_t)blockIdx.x * kHcBlock; base < n; base += (uint64_t)gridDim.x * kHcBlock) { // uniform: every lane takes part in the ballot
+        const uint64_t q = base + threadIdx.x;
+        const bool has = q < n && length[q] > 0.f;
+        mine += (uint32_t)__popcll(__ballot(has));
+    }
+    if ((threadIdx.x & 63u) == 0) s_wave[threadIdx.x >> 6] = mine;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t sum = 0;
+        for (int w = 0; w < kHcBlock / 64; w++) sum += s_wave[w];
+        if (sum) atomicAdd(count, (unsigned long long)sum);
+    }
+}
+
+hipError_t HistoryCountLaunch(const float *length, size_t n, unsigned long long *count, hipStream_t s)
+{
+    hipError_t e = hipMemsetAsync(count, 0, sizeof *count, s);
+    if (e != hipSuccess || n == 0) return e;
+    const size_t blocks = (n + kHcBlock - 1) / kHcBlock;
+    hipLaunchKernelGGL(k_history_count, dim3((unsigned)(blocks < (size_t)kHcMaxBlocks ? blocks : (size_t)kHcMaxBlocks)), dim3(kHcBlock), 0, s, length, (uint32_t)n, count);
+    return hipGetLastError();
+}
+
 static inline bool Finite(float x) { return x >= -3.402823466e38f && x <= 3.402823466e38f; }
 static inline V3 H3(const float *p) { return v3(p[0], p[1], p[2]); }
 

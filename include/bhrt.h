@@ -376,6 +376,11 @@ int bhrt_first_hit(bhrt_scene *scene, float *z, float *normal, float *albedo);
  * stream the call does not synchronise.  A NULL image: BHRT_ERR_ARG. */
 int bhrt_first_hit_node_dev(bhrt_scene *scene, int32_t *d_node, void *stream);
 int bhrt_first_hit_node(bhrt_scene *scene, int32_t *node);
+/* All four images from ONE trace per pixel: z, normal and albedo are bhrt_first_hit*'s bytes and node is bhrt_first_hit_node*'s,
+ * face materials included.  A third kernel beside the two, whose code is unchanged.  Any pointer may be NULL; all four NULL: BHRT_ERR_ARG,
+ * before any device is touched.  _dev: device pointers; with a stream the call does not synchronise. */
+int bhrt_first_hit_ex_dev(bhrt_scene *scene, float *d_z, float *d_normal, float *d_albedo, int32_t *d_node, void *stream);
+int bhrt_first_hit_ex(bhrt_scene *scene, float *z, float *normal, float *albedo, int32_t *node);
 /* Sampled guide images: the same three images, and the coverage, formed by the render's own camera samples, so that they are
  * averaged over the pixel footprint the colour image is averaged over: jitter and, with bhrt_opts.lens, the aperture.  For an owned pixel inside
  * the image and n = spp, sample s = 0 .. n-1 has the camera ray the render forms for (seed, pixel, s) (what bhrt_camera_rays returns), its first
@@ -594,6 +599,92 @@ int bhrt_variance_spatial_dev(bhrt_scene *scene, const bhrt_spatial_variance_opt
                               const float *d_z, const float *d_normal, const float *d_albedo, float *d_out_variance, void *stream);
 int bhrt_variance_spatial(bhrt_scene *scene, const bhrt_spatial_variance_opts *opts, const float *radiance, const float *variance, const float *length, const float *z,
                           const float *normal, const float *albedo, float *out_variance);
+
+/* ---- temporal session: the chain above as one device-resident call per frame ---------------------------------------------------
+ * A viewport's loop while the camera or an object moves:  bhrt_temporal_begin(scene, &opts, &topts);  then per frame the scene setters
+ * (bhrt_scene_set_camera, bhrt_scene_set_node_transform, ...) and bhrt_temporal_frame(scene, rgb8, NULL, NULL);  bhrt_temporal_end(scene).
+ * A session belongs to a scene; at most one is open per scene, beside at most one progressive session.  Frame k (0-based since begin or the
+ * last reset) runs, on the scene's own stream and on images that stay in HBM:
+ *   1. bhrt_first_hit_ex_dev: z, normal, albedo of this view, and the node ids with follow_nodes (one trace per pixel)
+ *   2. bhrt_render_var_dev with carry_variance, else bhrt_render_dev, with the session's bhrt_opts and seed + k: the current frame, radiance alone
+ *   3. at spp < 2 with spatial_variance: bhrt_variance_spatial_dev(current frame, no variance, no length) is the current frame's variance
+ *   4. for k > 0: the reprojection of the kept accumulated frame, its variance and its length out of the kept view (camera frame, first hit,
+ *      albedo, and with follow_nodes the node snapshot and the ids) into this one: bhrt_reproject_dev, with follow_nodes
+ *      bhrt_reproject_moving_dev, with carry_variance bhrt_reproject_var_dev
+ *   5. bhrt_temporal_accumulate_dev / _var_dev with cur_samples = spp (frame 0: no history)
+ *   6. with spatial_variance: bhrt_variance_spatial_dev(accumulated frame, its variance, its length): the filter's variance
+ *   7. with denoise: bhrt_denoise_dev(accumulated frame, the filter's variance, this view's first hit): the displayed frame
+ *   8. the count of the pixels with history (bhrt_temporal_status)
+ *   9. bhrt_scene_get_camera_frame, and with follow_nodes bhrt_scene_get_node_transforms: the next frame's "previous"
+ *  10. previous and current images change places (pointers)
+ * and is, byte for byte, what the same host wrappers give when a host chains them that way (bhrt render --temporal is this loop).  The caller
+ * gets the displayed frame: the denoised one with denoise, else the accumulated one; rgb8 with the gamma of the stage that wrote it
+ * (denoise_opts.gamma, else temporal.gamma).  The un-denoised accumulated frame and its unmodified variance go on to the next frame.  Between two
+ * frames the host's only job is the scene setters; bhrt_render*, bhrt_denoise*, bhrt_first_hit* and the other image calls on the scene between
+ * two frames do not disturb the session (the denoiser's and the guides' scratch stays the scene's, the session's images are its own).
+ * Streams: everything runs on the scene's own stream, and every call below that touches the device synchronises that stream before it
+ * returns (the render does so anyway); calls on one scene must not overlap.
+ * Memory: all images are device memory, allocated by the first frame for the session's mode on the device the scene is uploaded to, kept over
+ * bhrt_temporal_reset, freed by bhrt_temporal_end and bhrt_scene_free.  Bytes per pixel: light only 116 (two views' first hit 56, current 12,
+ * history 12 + 4, two accumulated frames 24 + their lengths 8); carry_variance + 48 (current, history and two accumulated variances);
+ * spatial_variance + 12; follow_nodes + 8; the host variant of bhrt_temporal_frame + 3 for rgb8, and with denoise + 12 for the radiance
+ * it copies out.  While a session holds images, bhrt_scene_upload to another device returns BHRT_ERR_ARG and changes nothing.
+ * Limits, those of the stages: the guides are the pinhole ray's (no lens, no shutter in them), reflections and refractions are carried as
+ * surface light, lights do not move, one rank (world_size 1), every pixel the same spp. */
+typedef struct bhrt_temporal_session_opts {
+    bhrt_reproject_opts reproject;
+    bhrt_temporal_opts temporal;
+    bhrt_spatial_variance_opts spatial;
+    bhrt_denoise_opts denoise_opts;
+    int32_t carry_variance;   /* 0: bhrt_reproject* + bhrt_temporal_accumulate*; 1: the _var chain on bhrt_render_var* */
+    int32_t spatial_variance; /* needs carry_variance: stage 3S where the stages above name it (at spp < 2 on the rendered frame, always on the accumulated one) */
+    int32_t denoise;          /* needs carry_variance: the displayed frame is bhrt_denoise*'s */
+    int32_t follow_nodes;     /* 1: node-id images and the node snapshot; reprojection through bhrt_reproject_moving* / _var with prev_xforms */
+    int32_t reserved[4];
+} bhrt_temporal_session_opts;
+typedef struct bhrt_temporal_progress {
+    uint32_t frames;         /* complete frames since begin or the last reset */
+    int32_t failed;          /* 1: a frame failed part-way; only bhrt_temporal_reset and bhrt_temporal_end are served */
+    uint64_t history_pixels; /* pixels of the last complete frame whose reprojected length is > 0; 0 after frame 0 */
+    uint64_t pixels;         /* W * H */
+    int32_t reserved[4];
+} bhrt_temporal_progress;
+enum {
+    BHRT_TEMPORAL_IMG_ACCUMULATED = 0,      /* W*H*3 float: the un-denoised accumulated frame, what the next frame reprojects */
+    BHRT_TEMPORAL_IMG_VARIANCE = 1,         /* W*H*3 float: its carried variance (carry_variance) */
+    BHRT_TEMPORAL_IMG_LENGTH = 2,           /* W*H float: its length */
+    BHRT_TEMPORAL_IMG_HISTORY_LENGTH = 3,   /* W*H float: the reprojected length of the last frame, 0 = the pixel had no history (all 0 after frame 0) */
+    BHRT_TEMPORAL_IMG_FILTER_VARIANCE = 4,  /* W*H*3 float: the variance the denoiser was given (spatial_variance) */
+    BHRT_TEMPORAL_IMG_Z = 5,                /* W*H float    \                                                    */
+    BHRT_TEMPORAL_IMG_NORMAL = 6,           /* W*H*3 float   | the last frame's view: bhrt_first_hit_ex*'s images */
+    BHRT_TEMPORAL_IMG_ALBEDO = 7,           /* W*H*3 float   |                                                    */
+    BHRT_TEMPORAL_IMG_NODE = 8,             /* W*H int32    /  (follow_nodes)                                     */
+    BHRT_TEMPORAL_IMG_CURRENT = 9,          /* W*H*3 float: the last frame's own render */
+    BHRT_TEMPORAL_IMG_CURRENT_VARIANCE = 10 /* W*H*3 float: its variance as stage 5 read it (carry_variance) */
+};
+void bhrt_default_temporal_session_opts(bhrt_temporal_session_opts *opts); /* the four stages' defaults, the four switches 0 */
+/* begin: copies the options; needs no device.  BHRT_ERR_ARG, before any device is touched and with nothing changed: a NULL argument; a session
+ * already open on the scene; spatial_variance or denoise without carry_variance; carry_variance with spp < 2 and no spatial_variance (a 1-spp
+ * frame has no variance); what the stages refuse of their options (bhrt_reproject*, bhrt_temporal_accumulate* with cur_samples = spp,
+ * bhrt_variance_spatial*, bhrt_denoise*); what bhrt_render* refuses of its options: spp outside 1..65535, rank, bounce counts, lens, the global
+ * gather or photon_map without a map; world_size > 1.
+ * frame: rgb8 (W*H*3 bytes) and radiance (W*H*3 floats, linear) receive the displayed frame; either may be NULL.  bhrt_temporal_frame: host
+ * pointers; _dev: device pointers, written by the stages themselves (no staging copy).  *stats (may be NULL) is the frame's render's.  A frame
+ * that fails once it has launched work marks the session failed: frame, image and image_dev then return BHRT_ERR_ARG, status reports the last
+ * complete frame, and bhrt_temporal_reset or bhrt_temporal_end is the way out.
+ * reset: a cut.  The next frame is frame 0 again (no history, seed + 0); the images stay allocated; clears a failure.
+ * status: frames, the pixels with history in the last complete frame (counted on the device: k_history_count), W * H, failed.
+ * image: a copy of one kept image of the last complete frame into host memory; image_dev: its device address, borrowed: valid until the next
+ * frame, reset or end.  BHRT_ERR_ARG: an unknown `which`, an image the session's mode does not keep, no complete frame since begin or reset.
+ * Without an open session frame, reset, status, image and image_dev return BHRT_ERR_ARG; end returns BHRT_OK. */
+int bhrt_temporal_begin(bhrt_scene *scene, const bhrt_opts *opts, const bhrt_temporal_session_opts *topts);
+int bhrt_temporal_frame(bhrt_scene *scene, uint8_t *rgb8, float *radiance, bhrt_stats *stats);
+int bhrt_temporal_frame_dev(bhrt_scene *scene, uint8_t *d_rgb8, float *d_radiance, bhrt_stats *stats);
+int bhrt_temporal_reset(bhrt_scene *scene);
+int bhrt_temporal_status(const bhrt_scene *scene, bhrt_temporal_progress *progress);
+int bhrt_temporal_image(bhrt_scene *scene, int which, void *host);
+int bhrt_temporal_image_dev(bhrt_scene *scene, int which, const void **d_ptr);
+int bhrt_temporal_end(bhrt_scene *scene);
 
 /* ---- adaptive sampling: RenderImage's per-pixel sample counts (Scenes/scene.h:534,570), which BeginRender only ever sets to 0
  * (Main.cpp:214), filled by a render that stops sampling a pixel once its mean is good enough ------------------------
