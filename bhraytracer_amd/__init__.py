@@ -84,6 +84,12 @@ class SpatialVarianceOpts(C.Structure):
                 ("reserved", C.c_int32 * 3)]
 
 
+class ChangeOpts(C.Structure):
+    """bhrt_change_opts: the window, the two thresholds and the edge stops of bhrt_temporal_change (csrc/temporal.hip, stage 2C)."""
+    _fields_ = [("radius", C.c_int32), ("sigma_lo", C.c_float), ("sigma_hi", C.c_float), ("depth_tolerance", C.c_float), ("normal_threshold", C.c_float),
+                ("reserved", C.c_int32 * 3)]
+
+
 class TemporalSessionOpts(C.Structure):
     """bhrt_temporal_session_opts: the four stages' options and the four switches of a temporal session (include/bhrt.h)."""
     _fields_ = [("reproject", ReprojectOpts), ("temporal", TemporalOpts), ("spatial", SpatialVarianceOpts), ("denoise_opts", DenoiseOpts),
@@ -98,8 +104,9 @@ class TemporalProgress(C.Structure):
 
 # BHRT_TEMPORAL_IMG_* of include/bhrt.h: the images a temporal session keeps, with their element type and channels
 (TEMPORAL_IMG_ACCUMULATED, TEMPORAL_IMG_VARIANCE, TEMPORAL_IMG_LENGTH, TEMPORAL_IMG_HISTORY_LENGTH, TEMPORAL_IMG_FILTER_VARIANCE, TEMPORAL_IMG_Z,
- TEMPORAL_IMG_NORMAL, TEMPORAL_IMG_ALBEDO, TEMPORAL_IMG_NODE, TEMPORAL_IMG_CURRENT, TEMPORAL_IMG_CURRENT_VARIANCE) = range(11)
-_TEMPORAL_IMG_ONE_CHANNEL = (TEMPORAL_IMG_LENGTH, TEMPORAL_IMG_HISTORY_LENGTH, TEMPORAL_IMG_Z, TEMPORAL_IMG_NODE)
+ TEMPORAL_IMG_NORMAL, TEMPORAL_IMG_ALBEDO, TEMPORAL_IMG_NODE, TEMPORAL_IMG_CURRENT, TEMPORAL_IMG_CURRENT_VARIANCE, TEMPORAL_IMG_CHANGE,
+ TEMPORAL_IMG_USED_LENGTH) = range(13)
+_TEMPORAL_IMG_ONE_CHANNEL = (TEMPORAL_IMG_LENGTH, TEMPORAL_IMG_HISTORY_LENGTH, TEMPORAL_IMG_Z, TEMPORAL_IMG_NODE, TEMPORAL_IMG_CHANGE, TEMPORAL_IMG_USED_LENGTH)
 
 
 class XformOp(C.Structure):
@@ -161,6 +168,7 @@ EXPORTS = [
     "bhrt_first_hit_ex", "bhrt_first_hit_ex_dev",
     "bhrt_default_temporal_session_opts", "bhrt_temporal_begin", "bhrt_temporal_frame", "bhrt_temporal_frame_dev", "bhrt_temporal_reset",
     "bhrt_temporal_status", "bhrt_temporal_image", "bhrt_temporal_image_dev", "bhrt_temporal_end",
+    "bhrt_default_change_opts", "bhrt_temporal_change", "bhrt_temporal_change_dev", "bhrt_temporal_set_change",
 ]
 
 # BHRT_DENOISE_SIGMA_COVERAGE of include/bhrt.h: the default coverage tolerance of the denoiser for sampled guides
@@ -170,6 +178,9 @@ REPROJECT_DEPTH_TOLERANCE = 0.01
 REPROJECT_NORMAL_THRESHOLD = 0.99
 TEMPORAL_CLAMP_K = 1.0
 TEMPORAL_MAX_LENGTH = 16.0
+# BHRT_CHANGE_SIGMA_* of include/bhrt.h: the measured thresholds of the temporal change test
+CHANGE_SIGMA_LO = 3.0
+CHANGE_SIGMA_HI = 6.0
 
 
 def lib():
@@ -198,6 +209,7 @@ def lib():
         L.bhrt_default_temporal_opts.restype = None
         L.bhrt_default_spatial_variance_opts.restype = None
         L.bhrt_default_temporal_session_opts.restype = None
+        L.bhrt_default_change_opts.restype = None
         _lib = L
     return _lib
 
@@ -255,6 +267,15 @@ def default_spatial_variance_opts(**kw) -> SpatialVarianceOpts:
     """bhrt_default_spatial_variance_opts (radius 3, depth_tolerance 0.01, normal_threshold 0.99, min_length 4, demodulate 1: DESIGN.md 22), fields overridden by kw."""
     o = SpatialVarianceOpts()
     lib().bhrt_default_spatial_variance_opts(C.byref(o))
+    for k, v in kw.items():
+        setattr(o, k, v)
+    return o
+
+
+def default_change_opts(**kw) -> ChangeOpts:
+    """bhrt_default_change_opts (radius 3, sigma_lo and sigma_hi from DESIGN.md 24, depth_tolerance 0.01, normal_threshold 0.99), fields overridden by kw."""
+    o = ChangeOpts()
+    lib().bhrt_default_change_opts(C.byref(o))
     for k, v in kw.items():
         setattr(o, k, v)
     return o
@@ -658,6 +679,11 @@ class Scene:
         _check(lib().bhrt_temporal_image_dev(self._h, int(which), C.byref(p)))
         return p.value or 0
 
+    def temporal_set_change(self, opts: "ChangeOpts | None"):
+        """bhrt_temporal_set_change: the session's change test on with these options, None = off; legal until the first frame since
+        begin or reset has completed.  With it on, TEMPORAL_IMG_CHANGE and TEMPORAL_IMG_USED_LENGTH are kept."""
+        _check(lib().bhrt_temporal_set_change(self._h, C.byref(opts) if opts is not None else None))
+
     def temporal_end(self):
         """bhrt_temporal_end: closes the session and frees its images; fine when none is open."""
         _check(lib().bhrt_temporal_end(self._h))
@@ -919,6 +945,27 @@ class Scene:
         v = lambda x: C.c_void_p(x or None)  # noqa: E731
         _check(lib().bhrt_variance_spatial_dev(self._h, C.byref(opts), v(d_radiance), v(d_variance), v(d_length), v(d_z), v(d_normal), v(d_albedo), v(d_out_variance),
                                                v(stream)))
+
+    # ---- temporal change test --------------------------------------------------------------------------------------------------
+    def temporal_change(self, opts: ChangeOpts, radiance, variance, history, history_variance, length, z=None, normal=None, want_change=True):
+        """bhrt_temporal_change on host arrays: reproject_var()'s length shortened where history and current frame differ by more than the noise
+        both variances predict, over each pixel's window on its own surface.  z, normal None = computed here.  Returns (out_length (H, W),
+        change (H, W) or None) float32; out_length is temporal_accumulate_var()'s length."""
+        W, H = self.width, self.height
+        i = [self._image(a, sh, k) for a, sh, k in ((radiance, (H, W, 3), "radiance"), (variance, (H, W, 3), "variance"), (history, (H, W, 3), "history"),
+                                                    (history_variance, (H, W, 3), "history_variance"), (length, (H, W), "length"), (z, (H, W), "z"),
+                                                    (normal, (H, W, 3), "normal"))]
+        out, change = np.zeros((H, W), np.float32), np.zeros((H, W), np.float32) if want_change else None
+        p = lambda x: _ptr(x) if x is not None else None  # noqa: E731
+        _check(lib().bhrt_temporal_change(self._h, C.byref(opts) if opts is not None else None, *[p(a) for a in i], _ptr(out), p(change)))
+        return out, change
+
+    def temporal_change_dev(self, opts: ChangeOpts, d_radiance: int, d_variance: int, d_history: int, d_history_variance: int, d_length: int, d_z: int = 0,
+                            d_normal: int = 0, d_out_length: int = 0, d_change: int = 0, stream: int = 0):
+        """bhrt_temporal_change_dev on raw device pointers (0 = NULL); with a stream the call does not synchronise."""
+        v = lambda x: C.c_void_p(x or None)  # noqa: E731
+        _check(lib().bhrt_temporal_change_dev(self._h, C.byref(opts), v(d_radiance), v(d_variance), v(d_history), v(d_history_variance), v(d_length), v(d_z), v(d_normal),
+                                              v(d_out_length), v(d_change), v(stream)))
 
     # ---- images beside the colour image (RenderImage z-buffer, DenoiseImage inputs) ------------
     def first_hit(self):

@@ -17,7 +17,8 @@
 //               [--shutter-pos X,Y,Z] [--shutter-target X,Y,Z] [--shutter-up X,Y,Z]           (camera motion blur: the camera at the end of the exposure)
 //               [--temporal N [--to-pos X,Y,Z] [--to-target X,Y,Z] [--to-up X,Y,Z] [--node-to-translate NAME:X,Y,Z] [--frames-png PREFIX]   (N frames along a camera or object move, each carried into the next)
 //                   [--denoise [--denoise-iters K]   (each frame written denoised with its carried variance)
-//                       [--spatial-variance [--variance-radius R] [--variance-min-length X]]]]   (the variance of a short history estimated from its neighbourhood)
+//                       [--spatial-variance [--variance-radius R] [--variance-min-length X]]   (the variance of a short history estimated from its neighbourhood)
+//                       [--reject-change [--change-radius R] [--change-sigma LO,HI]]]]   (history dropped where a surface's light changed)
 //               [--node-translate NAME:X,Y,Z]   (repeatable: one translate op on that node before anything is rendered)
 //   bhrt info   <scene.xml>
 //
@@ -90,6 +91,10 @@
 // bhrt_variance_spatial(accumulated frame, its carried variance, its length): a pixel with fewer than X samples behind it (default 4 x spp: four
 // frames) is filtered with the estimate from its (2R + 1)^2 neighbourhood (R in 1..4, default 3), the others with their carried variance.  The
 // next frame gets the un-denoised accumulated frame and its carried variance, unmodified.  Without the flag every command line behaves as before.
+// --reject-change [--change-radius R] [--change-sigma LO,HI] (needs --temporal N --denoise; anywhere else, and R or LO,HI without the flag, a usage
+// error): bhrt_temporal_set_change on the session with the library's defaults, R (1..4) and the two thresholds (finite, 0 <= LO <= HI)
+// replacing theirs: from frame 1 on bhrt_temporal_change shortens the reprojected length where history and current frame differ by more than
+// their noise, before bhrt_temporal_accumulate_var reads it.  Without the flag every command line behaves as before.
 // --node-translate NAME:X,Y,Z (repeatable, any mode): one translate op appended to the node of that <object name=> through
 // bhrt_scene_set_node_transform, before anything is rendered.  --node-to-translate NAME:X,Y,Z (repeatable, needs --temporal N): frame k sets the
 // node to the record it had before frame 0 plus a translate of delta * ((float)k / (float)(N - 1)) per component in float32, and frames are
@@ -160,6 +165,11 @@ struct Args {
     int variance_radius = 0;           // --variance-radius R; 0: not given (the library's default)
     bool variance_radius_given = false;
     float variance_min_length = -1.f;  // --variance-min-length X; < 0: not given (4 x spp: four frames)
+    bool reject_change = false;        // --reject-change (with --temporal N --denoise): bhrt_temporal_set_change, the change test of DESIGN.md 24
+    int change_radius = 0;             // --change-radius R
+    bool change_radius_given = false;
+    float change_sigma[2] = {0, 0};    // --change-sigma LO,HI
+    bool change_sigma_given = false;
     // --node-translate NAME:X,Y,Z (any mode: one translate op before anything is rendered) and --node-to-translate NAME:X,Y,Z (--temporal: the
     // node's translation at the last frame); `node` is resolved once the scene is loaded
     struct NodeMove { std::string name; float v[3] = {0, 0, 0}; int32_t node = -1; };
@@ -310,6 +320,13 @@ static int render_temporal(bhrt_scene *scene, const Args &A, const bhrt_info &in
     for (size_t m = 0; m < saved.size(); m++)
         if (bhrt_scene_get_node_transform(scene, A.node_to_translate[m].node, &saved[m])) return fail("node transform");
     if (bhrt_temporal_begin(scene, &A.o, &ts)) return fail("temporal session");
+    if (A.reject_change) { // the change test between reprojection and accumulation
+        bhrt_change_opts ch;
+        bhrt_default_change_opts(&ch);
+        if (A.change_radius_given) ch.radius = A.change_radius;
+        if (A.change_sigma_given) { ch.sigma_lo = A.change_sigma[0]; ch.sigma_hi = A.change_sigma[1]; }
+        if (bhrt_temporal_set_change(scene, &ch)) return fail("temporal change test");
+    }
     for (int k = 0; k < A.temporal; k++) {
         const float s = (float)k / (float)(A.temporal - 1);
         float p[9];
@@ -633,6 +650,19 @@ int main(int argc, char **argv)
         else if (s == "--spatial-variance") A.spatial_variance = true;
         else if (s == "--variance-radius") { A.variance_radius = atoi(next()); A.variance_radius_given = true; }
         else if (s == "--variance-min-length") A.variance_min_length = number_value("--variance-min-length", next(), false);
+        else if (s == "--reject-change") A.reject_change = true;
+        else if (s == "--change-radius") { A.change_radius = atoi(next()); A.change_radius_given = true; }
+        else if (s == "--change-sigma") {
+            const char *text = next();
+            char *end = nullptr, *end2 = nullptr;
+            const float lo = strtof(text, &end);
+            const float hi = end != text && *end == ',' ? strtof(end + 1, &end2) : 0.f;
+            if (end == text || *end != ',' || end2 == end + 1 || *end2 || !(lo >= 0.f && lo <= hi && hi <= 3.402823466e38f)) {
+                fprintf(stderr, "bhrt: usage: --change-sigma needs two finite numbers LO,HI with 0 <= LO <= HI, got \"%s\"\n", text);
+                return 2;
+            }
+            A.change_sigma[0] = lo; A.change_sigma[1] = hi; A.change_sigma_given = true;
+        }
         else if (s == "--node-translate") A.node_translate.push_back(node_move_value("--node-translate", next()));
         else if (s == "--node-to-translate") A.node_to_translate.push_back(node_move_value("--node-to-translate", next()));
         else if (s == "--fov") {
@@ -684,6 +714,11 @@ int main(int argc, char **argv)
         return 2;
     }
     if (A.variance_radius_given && (A.variance_radius < 1 || A.variance_radius > 4)) { fprintf(stderr, "bhrt: usage: --variance-radius must be in 1..4\n"); return 2; }
+    if ((A.reject_change || A.change_radius_given || A.change_sigma_given) && !(A.reject_change && A.temporal_given && A.denoise)) {
+        fprintf(stderr, "bhrt: usage: --reject-change needs --temporal N --denoise, and --change-radius / --change-sigma need --reject-change\n");
+        return 2;
+    }
+    if (A.change_radius_given && (A.change_radius < 1 || A.change_radius > 4)) { fprintf(stderr, "bhrt: usage: --change-radius must be in 1..4\n"); return 2; }
     if (A.temporal_given && A.denoise && o.spp < (A.spatial_variance ? 1 : 2)) {
         fprintf(stderr, "bhrt: usage: --temporal with --denoise needs --spp >= 2 (at 1 sample per pixel a frame's variance is 0 by definition; --spatial-variance estimates one)\n");
         return 2;

@@ -89,6 +89,17 @@ void bhrt_default_spatial_variance_opts(bhrt_spatial_variance_opts *o)
     o->demodulate = 1;
 }
 
+void bhrt_default_change_opts(bhrt_change_opts *o)
+{
+    if (!o) return;
+    memset(o, 0, sizeof *o);
+    o->radius = 3; // stage 3S's window
+    o->sigma_lo = BHRT_CHANGE_SIGMA_LO;
+    o->sigma_hi = BHRT_CHANGE_SIGMA_HI; // both: the grid of tools/temporal_change_quality.py over c3_mesh_small
+    o->depth_tolerance = 0.01f; // bhrt_default_spatial_variance_opts'
+    o->normal_threshold = BHRT_REPROJECT_NORMAL_THRESHOLD;
+}
+
 void bhrt_default_temporal_session_opts(bhrt_temporal_session_opts *o)
 {
     if (!o) return;
@@ -138,6 +149,7 @@ void bhrt_scene_free(bhrt_scene *s)
 {
     if (!s) return;
     if (s->temporal && s->temporal_release) s->temporal_release(s->temporal); // an open temporal session's images, before the streams of the device state go
+    if (s->change_scratch && s->change_scratch_release) s->change_scratch_release(s->change_scratch); // likewise: the guides bhrt_temporal_change* computed itself
     if (s->dev) bhrt::DestroyDeviceState(s->dev);
     delete s;
 }

@@ -1,5 +1,5 @@
 // dev_buf.h — owned device and pinned-host memory (DevBuf, PinnedBuf) and the two error macros they return through.  Shared by the
-// kernels.hip translation unit (device_state.h includes it behind that unit's own definitions of the macros) and temporal_session.hip.
+// kernels.hip translation unit (device_state.h includes it behind that unit's own definitions of the macros), temporal_session.hip and temporal_change.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -50,6 +50,10 @@ bool TemporalSessionHoldsBuffers(const TemporalSession *t); // bhrt_scene_upload
 void *SceneStream(const bhrt_scene *scene);                 // the scene's own hipStream_t; nullptr before the upload
 int SceneDevice(const bhrt_scene *scene);                   // the device the scene is uploaded to; -1 before the upload
 int RenderArgsCheck(bhrt_scene *scene, const bhrt_opts *opts); // what bhrt_render* refuses of its options, host arithmetic only
+
+// The guides bhrt_temporal_change* computes itself (z, normal: 16 B per pixel) live in temporal_change.hip, above the public _dev entry points
+// like the session; the scene owns them through a pointer.
+struct ChangeScratch;
 } // namespace bhrt
 
 struct bhrt_scene {
@@ -60,4 +64,6 @@ struct bhrt_scene {
     bhrt::TemporalSession *temporal = nullptr; // bhrt_temporal_begin .. _end; not carried by bhrt_scene_clone
     // how bhrt_scene_free (capi_host.cpp, which also links into host-only programs without the HIP units) releases it: set with `temporal`
     void (*temporal_release)(bhrt::TemporalSession *) = nullptr;
+    bhrt::ChangeScratch *change_scratch = nullptr; // allocated by the first bhrt_temporal_change* call that is given no guides; not carried by bhrt_scene_clone
+    void (*change_scratch_release)(bhrt::ChangeScratch *) = nullptr; // set with `change_scratch`, for bhrt_scene_free
 };

@@ -94,6 +94,24 @@ struct SpatialVarianceJob {
 const char *SpatialVarianceArgsError(const bhrt_spatial_variance_opts *o, const float *radiance, const float *variance, const float *length, const float *out_variance);
 hipError_t SpatialVarianceLaunch(const SpatialVarianceJob &J, hipStream_t s);
 
+// stage 2C (k_temporal_change)
+struct TemporalChangeJob {
+    int W, H;
+    bhrt_change_opts o;
+    const float *radiance, *variance;         // W*H*3 each: the current frame and the variance of its mean
+    const float *history, *history_variance;  // W*H*3 each: stage 1V's
+    const float *length;                      // W*H: stage 1V's
+    const float *z;                           // W*H
+    const float *normal;                      // W*H*3
+    float *out_length;                        // W*H; not `length`
+    float *change;                            // W*H, or NULL
+};
+// "" when the options (the arguments) are usable, else what is wrong with them (host arithmetic only); the session checks the options alone
+const char *TemporalChangeOptsError(const bhrt_change_opts *o);
+const char *TemporalChangeArgsError(const bhrt_change_opts *o, const float *radiance, const float *variance, const float *history, const float *history_variance,
+                                    const float *length, const float *out_length);
+hipError_t TemporalChangeLaunch(const TemporalChangeJob &J, hipStream_t s);
+
 // the temporal session's count of the pixels with history (k_history_count): zeroes *count (device) on `s`, then adds the number of
 // the n (< 2^32) device lengths that are > 0
 hipError_t HistoryCountLaunch(const float *length, size_t n, unsigned long long *count, hipStream_t s);

@@ -81,6 +81,35 @@
 //            out_variance = ((1 - a) * (1 - a)) * hv + (a * a) * v      with stage 2's a: out = (1 - a) h + a c, h and c independent
 //   With the clamp off and max_length = +inf, two frames of n1 and n2 samples pool to (n1^2 vA + n2^2 vB) / (n1 + n2)^2.
 //
+// 2C. TEMPORAL CHANGE TEST (k_temporal_change<R>): between stage 1V and stage 2V.  Stage 1 notices that a pixel shows another
+//   surface; it does not notice that the same surface is lit differently (a shadow, a reflection or the indirect light of an object that moved).
+//   This stage compares history and current frame over a window on the pixel's own surface, in units of the noise both variances predict, and
+//   shortens the pixel's history length where the difference is more than noise; stages 2V, 3S and the denoiser then act on the short length
+//   untouched.  c, v = the current radiance and the variance of its mean (bhrt_render_var*'s, or stage 3S's at 1 spp); h, hv, l = history,
+//   history variance and length of stage 1V; z, n = the current first hit; R = radius (1..4).
+//   per pixel q   L(x)  = (0.2126 x.r + 0.7152 x.g) + 0.0722 x.b
+//            vL(x) = ((0.2126 * 0.2126) x.r + (0.7152 * 0.7152) x.g) + (0.0722 * 0.0722) x.b        (the denoiser's two expressions)
+//            d_q = L(c_q) - L(h_q),   w_q = vL(v_q) + vL(hv_q),   has_q = l_q > 0  (a NaN is false)
+//   no history (not l_p > 0):  out_length_p = l_p, the same bits, and change_p = 0
+//   window   taps (dx, dy) in {-R..R}^2 row-major (dy outer), q = p + (dx, dy); taps outside the image are skipped; the centre tap is always valid
+//            another tap is valid iff has_q and it passes stage 3S's surface test:
+//            p a miss (z_p >= BHRT_BIGFLOAT):  z_q >= BHRT_BIGFLOAT
+//            p a hit:  z_q < BHRT_BIGFLOAT and |z_q - z_p| <= (depth_tolerance z_p) r, r = sqrt((float)(dx dx + dy dy)),
+//                      and (n_p.x n_q.x + n_p.y n_q.y) + n_p.z n_q.z >= normal_threshold      (the normals as they are: no unit())
+//            a comparison with a NaN is false: the tap is invalid
+//   statistic over the valid taps in tap order, from 0:  s = s + d_q,  sw = sw + w_q;  then
+//            x = fabsf(s) / sqrt(sw) where sw > 0;  where sw <= 0:  x = +inf if fabsf(s) > 0, else 0;  where sw is a NaN:  x = 0
+//   result   lambda = !(x > sigma_lo) ? 0 : (x >= sigma_hi ? 1 : (x - sigma_lo) / (sigma_hi - sigma_lo))
+//            out_length_p = l_p * (1 - lambda),   change_p = lambda
+//   For independent taps x is the difference of the window's mean in standard deviations of its noise: |s / k| / sqrt(sw / k^2), and k cancels.
+//   A NaN anywhere (a radiance, a variance, a sum) gives lambda = 0: the history is kept.  A design rule: NaN radiance is the business of the
+//   render's own replacement rule, not this stage's.  Properties: lambda = 1 gives out_length = 0, so stage 2 treats the pixel as one without
+//   history (out = c, out_variance = v).  h == c bit for bit over a window gives s = 0, x = 0 and out_length == l bit for bit (l * 1).  The
+//   statistic is conservative where hv is overstated: the w-not-w^2 interpolation of stage 1V overstates it by up to 4 x, and so does the
+//   clamp's raise of stage 2V in the frames before.  It is optimistic where neighbouring histories share bilinear taps: their noise is then
+//   correlated and sw, which adds the taps' variances as if they were independent, understates the variance of s.  That is why the
+//   thresholds sigma_lo and sigma_hi are measured, not derived.
+//
 // 3S. SPATIAL VARIANCE ESTIMATE (k_spatial_variance<R>): the variance of a frame that has none it can trust — a 1-spp frame, a
 //   pixel whose history is short, an imported radiance image — estimated from the pixel's neighbourhood on its own surface, as SVGF does while
 //   a history is shorter than four frames.  Divisions and square roots are correctly rounded.  c = the radiance, v = the frame's present
@@ -118,6 +147,11 @@
 // mask in registers; pass 2 reads e alone.  demodulate, "variance given" and "length given" are uniform branches, R a template parameter (fixed
 // trip counts, no dynamically indexed array: no scratch memory).  Per pixel 28 B read (40 B with albedo; 12 B and 4 B more with v and l), times
 // ((16 + 2R) / 16)^2 for the halo (1.89 at R = 3, from the cache), 12 B written.  Fixed tap order, no atomics.
+// k_temporal_change<R>: k_spatial_variance's scheme.  16 x 16 workgroups; the (16 + 2R)^2 halo tile is staged once in LDS as seven planes
+// (d, w, z, n.x, n.y, n.z and the has-history verdict as a word), d and w evaluated once per tile pixel, rows 16 + 2R >= 18 words apart as in
+// 3S; the correctly rounded roots of dx dx + dy dy in LDS as well.  Every thread of the workgroup stages, also one outside the image.  One pass
+// over the window with fixed trip counts (R a template parameter), no dynamically indexed array, no atomics, no scratch memory.  Per pixel
+// 68 B read (c, v, h, hv 12 B each, l, z 4 B each, n 12 B), times ((16 + 2R) / 16)^2 for the halo, 4 B written (8 B with the change image).
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stddef.h>
@@ -686,6 +720,95 @@ __global__ void __launch_bounds__(kTaTx *kTaTy) k_spatial_variance(int W, int H,
     I.out[3 * p] = o.x; I.out[3 * p + 1] = o.y; I.out[3 * p + 2] = o.z;
 }
 
+// the images of one k_temporal_change call
+struct TemporalChangeImages {
+    const float *c, *v, *h, *hv, *l; // the current frame and its variance; history, its variance and its length
+    const float *z, *n;              // the current first hit
+    float *out_length, *change;      // change may be NULL
+};
+
+__device__ inline float tc_lum(const float *x, size_t q) { return (0.2126f * x[3 * q] + 0.7152f * x[3 * q + 1]) + 0.0722f * x[3 * q + 2]; }
+__device__ inline float tc_vlum(const float *x, size_t q)
+{
+    return ((0.2126f * 0.2126f) * x[3 * q] + (0.7152f * 0.7152f) * x[3 * q + 1]) + (0.0722f * 0.0722f) * x[3 * q + 2];
+}
+
+// Stage 2C.  Every thread of the workgroup, also one outside the image, takes part in staging the tile.
+template <int R>
+__global__ void __launch_bounds__(kTaTx *kTaTy) k_temporal_change(int W, int H, float sigma_lo, float sigma_hi, float depth_tolerance, float normal_threshold,
+                                                                  TemporalChangeImages I)
+{
+    constexpr int TW = kTaTx + 2 * R, TH = kTaTy + 2 * R, NT = TW * TH;
+    __shared__ float tile[6][NT];         // d, w, z, n.x, n.y, n.z of the halo tile
+    __shared__ uint32_t has[NT];          // 1: the tile pixel has history (l > 0)
+    __shared__ float root[2 * R * R + 1]; // sqrt((float)k), k = dx dx + dy dy
+    const int tid = (int)(threadIdx.y * kTaTx + threadIdx.x);
+    const int x0 = (int)(blockIdx.x * kTaTx) - R, y0 = (int)(blockIdx.y * kTaTy) - R;
+    for (int i = tid; i < NT; i += kTaTx * kTaTy) {
+        const int ly = i / TW, lx = i - ly * TW, gx = x0 + lx, gy = y0 + ly;
+        float dq = 0.f, wq = 0.f, zq = 0.f;
+        V3 nq = v3(0, 0, 0);
+        uint32_t hq = 0u;
+        if (gx >= 0 && gx < W && gy >= 0 && gy < H) { // a tile pixel outside the image is never read as a tap
+            const size_t q = (size_t)gy * W + gx;
+            dq = tc_lum(I.c, q) - tc_lum(I.h, q);
+            wq = tc_vlum(I.v, q) + tc_vlum(I.hv, q);
+            hq = I.l[q] > 0.f ? 1u : 0u;
+            zq = I.z[q];
+            nq = v3(I.n[3 * q], I.n[3 * q + 1], I.n[3 * q + 2]);
+        }
+        tile[0][i] = dq; tile[1][i] = wq;
+        tile[2][i] = zq;
+        tile[3][i] = nq.x; tile[4][i] = nq.y; tile[5][i] = nq.z;
+        has[i] = hq;
+    }
+    if (tid <= 2 * R * R) root[tid] = dm::sqrt_f((float)tid);
+    __syncthreads();
+    const int x = x0 + R + (int)threadIdx.x, y = y0 + R + (int)threadIdx.y;
+    if (x >= W || y >= H) return;
+    const size_t p = (size_t)y * W + x;
+    const float lp = I.l[p];
+    float ol = lp, lambda = 0.f; // no history: the length's own bits
+    if (lp > 0.f) {
+        const int cp = ((int)threadIdx.y + R) * TW + (int)threadIdx.x + R;
+        const float zp = tile[2][cp];
+        const V3 np = v3(tile[3][cp], tile[4][cp], tile[5][cp]);
+        const bool miss = zp >= BHRT_BIGFLOAT;
+        const float tz = depth_tolerance * zp;
+        float s = 0.f, sw = 0.f;
+        for (int dy = -R; dy <= R; dy++) {
+            const int qy = y + dy;
+            if (qy < 0 || qy >= H) continue;
+#pragma unroll
+            for (int dx = -R; dx <= R; dx++) {
+                const int qx = x + dx;
+                if (qx < 0 || qx >= W) continue;
+                const int q = cp + dy * TW + dx;
+                bool ok = true;
+                if (dx != 0 || dy != 0) {
+                    const float zq = tile[2][q];
+                    ok = has[q] != 0u;
+                    if (miss) ok = ok && zq >= BHRT_BIGFLOAT;
+                    else
+                        ok = ok && zq < BHRT_BIGFLOAT && fabsf(zq - zp) <= tz * root[dx * dx + dy * dy] &&
+                             (np.x * tile[3][q] + np.y * tile[4][q]) + np.z * tile[5][q] >= normal_threshold;
+                }
+                if (!ok) continue;
+                s = s + tile[0][q];
+                sw = sw + tile[1][q];
+            }
+        }
+        const float as = fabsf(s);
+        float xs = 0.f; // a NaN sw
+        if (sw > 0.f) xs = as / dm::sqrt_f(sw);
+        else if (sw <= 0.f && as > 0.f) xs = __builtin_huge_valf();
+        lambda = !(xs > sigma_lo) ? 0.f : (xs >= sigma_hi ? 1.f : (xs - sigma_lo) / (sigma_hi - sigma_lo));
+        ol = lp * (1.f - lambda);
+    }
+    I.out_length[p] = ol;
+    if (I.change) I.change[p] = lambda;
+}
+
 // The pixels with history (bhrt_temporal_status): how many of the n lengths are > 0 (a NaN is not).  Every wave counts its 64
 // lanes with one ballot and one popcount per round of the grid-stride loop, the workgroup's four wave sums meet in LDS, and one 64-bit
 // integer atomicAdd per workgroup reaches *count, which the caller has zeroed on the same stream.  Integer and order-free: exact.
@@ -854,6 +977,36 @@ hipError_t SpatialVarianceLaunch(const SpatialVarianceJob &J, hipStream_t s)
     const SpatialVarianceImages I = {J.radiance, J.variance, J.length, J.z, J.normal, J.albedo, J.out_variance};
     auto kernel = J.o.radius == 1 ? k_spatial_variance<1> : J.o.radius == 2 ? k_spatial_variance<2> : J.o.radius == 3 ? k_spatial_variance<3> : k_spatial_variance<4>;
     hipLaunchKernelGGL(kernel, grid, block, 0, s, J.W, J.H, J.o.depth_tolerance, J.o.normal_threshold, J.o.min_length, J.o.demodulate ? 1 : 0, I);
+    return hipGetLastError();
+}
+
+const char *TemporalChangeOptsError(const bhrt_change_opts *o)
+{
+    if (!o) return "temporal change: null options";
+    if (o->radius < 1 || o->radius > 4) return "temporal change: radius must be in 1..4";
+    if (!(o->sigma_lo >= 0.f) || !Finite(o->sigma_lo)) return "temporal change: sigma_lo must be finite and >= 0";
+    if (!(o->sigma_hi >= o->sigma_lo) || !Finite(o->sigma_hi)) return "temporal change: sigma_hi must be finite and >= sigma_lo";
+    if (!(o->depth_tolerance >= 0.f) || !Finite(o->depth_tolerance)) return "temporal change: depth_tolerance must be finite and >= 0";
+    if (o->normal_threshold != o->normal_threshold) return "temporal change: normal_threshold is not a number";
+    return "";
+}
+
+const char *TemporalChangeArgsError(const bhrt_change_opts *o, const float *radiance, const float *variance, const float *history, const float *history_variance,
+                                    const float *length, const float *out_length)
+{
+    const char *bad = TemporalChangeOptsError(o);
+    if (*bad) return bad;
+    if (!radiance || !variance || !history || !history_variance || !length || !out_length) return "temporal change: null radiance, variance, history, history_variance, length or out_length";
+    if (out_length == length) return "temporal change: out_length must not be the length image (a pixel's taps read their neighbours' lengths)";
+    return "";
+}
+
+hipError_t TemporalChangeLaunch(const TemporalChangeJob &J, hipStream_t s)
+{
+    const dim3 grid((unsigned)((J.W + kTaTx - 1) / kTaTx), (unsigned)((J.H + kTaTy - 1) / kTaTy)), block(kTaTx, kTaTy);
+    const TemporalChangeImages I = {J.radiance, J.variance, J.history, J.history_variance, J.length, J.z, J.normal, J.out_length, J.change};
+    auto kernel = J.o.radius == 1 ? k_temporal_change<1> : J.o.radius == 2 ? k_temporal_change<2> : J.o.radius == 3 ? k_temporal_change<3> : k_temporal_change<4>;
+    hipLaunchKernelGGL(kernel, grid, block, 0, s, J.W, J.H, J.o.sigma_lo, J.o.sigma_hi, J.o.depth_tolerance, J.o.normal_threshold, I);
     return hipGetLastError();
 }
 

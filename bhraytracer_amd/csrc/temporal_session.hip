@@ -2,6 +2,7 @@
 // frame on images that stay in HBM.  A translation unit above the library's own public _dev entry points: every stage is the call a host would
 // make (include/bhrt.h states the sequence), so a frame is what the chained wrappers give byte for byte; this file owns the images, the order,
 // the "previous" view and the failure state, and launches nothing itself but the count of the pixels with history (k_history_count, temporal.hip).
+// The change test (bhrt_temporal_set_change) is one more such call, bhrt_temporal_change_dev, between reprojection and accumulation.
 #include <hip/hip_runtime.h>
 
 #include <string.h>
@@ -42,6 +43,9 @@ struct TemporalSession {
     DevBuf<float> radiance, history, history_len; // the frame's render, the reprojected light and its length
     DevBuf<float> variance, history_var;         // carry_variance
     DevBuf<float> filter_var;                    // spatial_variance
+    bool change_on = false;                      // bhrt_temporal_set_change: stage 2C between reprojection and accumulation
+    bhrt_change_opts change = {};
+    DevBuf<float> change_img, used_len;          // the change test: lambda and the length stage 5 received
     DevBuf<float> display;                       // denoise, host variant: the radiance bhrt_temporal_frame copies out
     DevBuf<uint8_t> rgb;                         // host variant
     DevBuf<unsigned long long> d_count;
@@ -102,6 +106,8 @@ static int ReserveImages(bhrt_scene *scene, TemporalSession &T, bool host_rgb, b
     if (var)
         for (DevBuf<float> *b : {&T.acc_var, &T.out_var, &T.variance, &T.history_var}) BHRT_TRY(b->Reserve(n * 3));
     if (T.t.spatial_variance) BHRT_TRY(T.filter_var.Reserve(n * 3));
+    if (T.change_on)
+        for (DevBuf<float> *b : {&T.change_img, &T.used_len}) BHRT_TRY(b->Reserve(n));
     if (host_display) BHRT_TRY(T.display.Reserve(n * 3));
     if (host_rgb) BHRT_TRY(T.rgb.Reserve(n * 3));
     BHRT_TRY(T.d_count.Reserve(1));
@@ -125,8 +131,11 @@ static int RunFrame(bhrt_scene *scene, TemporalSession &T, uint8_t *d_rgb8, floa
             BHRT_TRY(bhrt_reproject_var_dev(scene, &t.reproject, T.prev_frame, moving ? T.prev_xf.data() : nullptr, P.z, P.normal, T.acc, T.acc_var, T.acc_len, P.albedo,
                                             moving ? P.node.p : nullptr, C.z, C.normal, C.albedo, moving ? C.node.p : nullptr, T.history, T.history_var, T.history_len, nullptr,
                                             st));
+        const bool change = T.change_on && !first; // step 4b: the length stage 5 receives
+        if (change)
+            BHRT_TRY(bhrt_temporal_change_dev(scene, &T.change, T.radiance, T.variance, T.history, T.history_var, T.history_len, C.z, C.normal, T.used_len, T.change_img, st));
         BHRT_TRY(bhrt_temporal_accumulate_var_dev(scene, &t.temporal, T.radiance, T.variance, (float)o.spp, first ? nullptr : T.history.p, first ? nullptr : T.history_var.p,
-                                                  first ? nullptr : T.history_len.p, T.out, T.out_var, T.out_len, t.denoise ? nullptr : d_rgb8, st));
+                                                  first ? nullptr : (change ? T.used_len.p : T.history_len.p), T.out, T.out_var, T.out_len, t.denoise ? nullptr : d_rgb8, st));
         if (t.spatial_variance) BHRT_TRY(bhrt_variance_spatial_dev(scene, &t.spatial, T.out, T.out_var, T.out_len, C.z, C.normal, C.albedo, T.filter_var, st));
         if (t.denoise)
             BHRT_TRY(bhrt_denoise_dev(scene, &t.denoise_opts, T.out, t.spatial_variance ? T.filter_var.p : T.out_var.p, C.z, C.normal, C.albedo, d_display, d_rgb8, st));
@@ -140,6 +149,8 @@ static int RunFrame(bhrt_scene *scene, TemporalSession &T, uint8_t *d_rgb8, floa
                                               d_rgb8, st));
     }
     if (first) HIP_CHECK(hipMemsetAsync(T.history_len, 0, T.npx * sizeof(float), st)); // frame 0 has no history: the kept image says so
+    if (first && T.change_on)
+        for (DevBuf<float> *b : {&T.change_img, &T.used_len}) HIP_CHECK(hipMemsetAsync(b->p, 0, T.npx * sizeof(float), st));
     HIP_CHECK(HistoryCountLaunch(T.history_len, T.npx, T.d_count, st));
     return BHRT_OK;
 }
@@ -206,6 +217,8 @@ static const void *KeptImage(const TemporalSession &T, int which, size_t &bytes)
     case BHRT_TEMPORAL_IMG_NODE: bytes = n * 4; return T.t.follow_nodes ? (const void *)T.prev.node.p : nullptr;
     case BHRT_TEMPORAL_IMG_CURRENT: return T.radiance.p;
     case BHRT_TEMPORAL_IMG_CURRENT_VARIANCE: return var ? T.variance.p : nullptr;
+    case BHRT_TEMPORAL_IMG_CHANGE: bytes = n * 4; return T.change_on ? T.change_img.p : nullptr;
+    case BHRT_TEMPORAL_IMG_USED_LENGTH: bytes = n * 4; return T.change_on ? T.used_len.p : nullptr;
     }
     return nullptr;
 }
@@ -260,6 +273,22 @@ try {
     scene->temporal->k = 0;
     scene->temporal->failed = false;
     scene->temporal->history_pixels = 0;
+    return BHRT_OK;
+} catch (...) { return bhrt::AbiException(); }
+
+int bhrt_temporal_set_change(bhrt_scene *scene, const bhrt_change_opts *opts)
+try {
+    if (!scene) { SetError("bhrt_temporal_set_change: null scene"); return BHRT_ERR_ARG; }
+    TemporalSession *T = scene->temporal;
+    if (!T) { SetError("bhrt_temporal_set_change: no temporal session is open on this scene (bhrt_temporal_begin)"); return BHRT_ERR_ARG; }
+    if (T->k > 0) { SetError("bhrt_temporal_set_change: a frame has completed since bhrt_temporal_begin or _reset"); return BHRT_ERR_ARG; }
+    if (!T->t.carry_variance) { SetError("bhrt_temporal_set_change: the change test needs carry_variance (it reads both variances)"); return BHRT_ERR_ARG; }
+    if (opts) {
+        const char *bad = TemporalChangeOptsError(opts);
+        if (*bad) { SetError(bad); return BHRT_ERR_ARG; }
+        T->change = *opts;
+    }
+    T->change_on = opts != nullptr;
     return BHRT_OK;
 } catch (...) { return bhrt::AbiException(); }
 

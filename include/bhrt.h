@@ -600,6 +600,43 @@ int bhrt_variance_spatial_dev(bhrt_scene *scene, const bhrt_spatial_variance_opt
 int bhrt_variance_spatial(bhrt_scene *scene, const bhrt_spatial_variance_opts *opts, const float *radiance, const float *variance, const float *length, const float *z,
                           const float *normal, const float *albedo, float *out_variance);
 
+/* ---- temporal change test: drop history where a surface's light changed --------------------------------------------------------
+ * bhrt_reproject* notices that a pixel shows another surface; it does not notice that the same surface is lit differently: under the shadow, the
+ * reflection and the indirect light of an object that moved the history is accepted at full length and the old light fades out over
+ * max_length frames.  bhrt_temporal_change* sits between bhrt_reproject_var* and bhrt_temporal_accumulate_var*: over the taps of a
+ * (2 radius + 1)^2 window that have history and lie on the pixel's own surface (bhrt_variance_spatial*'s depth and normal stops) it sums the
+ * luminance difference d = L(radiance) - L(history) and the luminance variance w = vL(variance) + vL(history_variance), forms
+ * x = |sum d| / sqrt(sum w), the difference of the window's mean in standard deviations of its predicted noise, and writes
+ * out_length = length * (1 - lambda), lambda = 0 up to sigma_lo, 1 from sigma_hi, linear between.  Stated exactly in csrc/temporal.hip as stage
+ * 2C and equal to its numpy restatement bit for bit.  out_length is what bhrt_temporal_accumulate_var* takes as length: it blends more of the
+ * new samples, bhrt_variance_spatial* re-estimates the variance of the shortened pixels and the denoiser filters them harder.  A pixel without
+ * history keeps its length's bits; a NaN anywhere keeps the history (lambda = 0); history == radiance gives out_length == length bit for bit.
+ *
+ * The frame is the scene's camera, W x H.  radiance, variance (W*H*3 each): the current frame and the variance of its mean (bhrt_render_var*'s,
+ * bhrt_variance_spatial*'s at 1 spp).  history, history_variance (W*H*3 each), length (W*H): bhrt_reproject_var*'s.  z (W*H), normal (W*H*3):
+ * the current first hit; each may be NULL = computed here by the kernel of bhrt_first_hit*.  out_length (W*H, required, not the length image: a
+ * pixel's taps read their neighbours' lengths).  change (W*H, may be NULL): lambda.
+ * BHRT_ERR_ARG before any device is touched: a NULL scene, options or required image; a radius outside 1..4; a sigma that is negative or not
+ * finite, sigma_hi < sigma_lo; a depth_tolerance that is negative or not finite; a NaN normal_threshold; out_length == length.
+ * _dev: device pointers; with a stream the call does not synchronise.  Scratch for guides computed here (16 B per pixel) is the scene's: calls
+ * on one scene must not overlap, a call on another stream included. */
+#define BHRT_CHANGE_SIGMA_LO 3.0f /* the measured defaults: DESIGN.md 24 */
+#define BHRT_CHANGE_SIGMA_HI 6.0f
+typedef struct bhrt_change_opts {
+    int32_t radius;         /* R: the window is (2R + 1)^2 taps, 1..4; default 3 */
+    float sigma_lo;         /* finite, >= 0: up to here the difference counts as noise (lambda = 0); default BHRT_CHANGE_SIGMA_LO */
+    float sigma_hi;         /* finite, >= sigma_lo: from here the history is dropped (lambda = 1); default BHRT_CHANGE_SIGMA_HI */
+    float depth_tolerance;  /* bhrt_spatial_variance_opts' meaning and default */
+    float normal_threshold; /* bhrt_spatial_variance_opts' meaning and default */
+    int32_t reserved[3];
+} bhrt_change_opts;
+void bhrt_default_change_opts(bhrt_change_opts *opts);
+int bhrt_temporal_change_dev(bhrt_scene *scene, const bhrt_change_opts *opts, const float *d_radiance, const float *d_variance, const float *d_history,
+                             const float *d_history_variance, const float *d_length, const float *d_z, const float *d_normal, float *d_out_length, float *d_change,
+                             void *stream);
+int bhrt_temporal_change(bhrt_scene *scene, const bhrt_change_opts *opts, const float *radiance, const float *variance, const float *history,
+                         const float *history_variance, const float *length, const float *z, const float *normal, float *out_length, float *change);
+
 /* ---- temporal session: the chain above as one device-resident call per frame ---------------------------------------------------
  * A viewport's loop while the camera or an object moves:  bhrt_temporal_begin(scene, &opts, &topts);  then per frame the scene setters
  * (bhrt_scene_set_camera, bhrt_scene_set_node_transform, ...) and bhrt_temporal_frame(scene, rgb8, NULL, NULL);  bhrt_temporal_end(scene).
@@ -611,6 +648,9 @@ int bhrt_variance_spatial(bhrt_scene *scene, const bhrt_spatial_variance_opts *o
  *   4. for k > 0: the reprojection of the kept accumulated frame, its variance and its length out of the kept view (camera frame, first hit,
  *      albedo, and with follow_nodes the node snapshot and the ids) into this one: bhrt_reproject_dev, with follow_nodes
  *      bhrt_reproject_moving_dev, with carry_variance bhrt_reproject_var_dev
+ *  4b. for k > 0 with the change test on (bhrt_temporal_set_change): bhrt_temporal_change_dev(current frame, its variance as stage 5 will read
+ *      it, history, history variance, history length, this view's z and normal): the used length and the change image; stage 5 then receives
+ *      the used length in the place of the history length
  *   5. bhrt_temporal_accumulate_dev / _var_dev with cur_samples = spp (frame 0: no history)
  *   6. with spatial_variance: bhrt_variance_spatial_dev(accumulated frame, its variance, its length): the filter's variance
  *   7. with denoise: bhrt_denoise_dev(accumulated frame, the filter's variance, this view's first hit): the displayed frame
@@ -627,7 +667,7 @@ int bhrt_variance_spatial(bhrt_scene *scene, const bhrt_spatial_variance_opts *o
  * Memory: all images are device memory, allocated by the first frame for the session's mode on the device the scene is uploaded to, kept over
  * bhrt_temporal_reset, freed by bhrt_temporal_end and bhrt_scene_free.  Bytes per pixel: light only 116 (two views' first hit 56, current 12,
  * history 12 + 4, two accumulated frames 24 + their lengths 8); carry_variance + 48 (current, history and two accumulated variances);
- * spatial_variance + 12; follow_nodes + 8; the host variant of bhrt_temporal_frame + 3 for rgb8, and with denoise + 12 for the radiance
+ * spatial_variance + 12; follow_nodes + 8; the change test + 8 (change, used length); the host variant of bhrt_temporal_frame + 3 for rgb8, and with denoise + 12 for the radiance
  * it copies out.  While a session holds images, bhrt_scene_upload to another device returns BHRT_ERR_ARG and changes nothing.
  * Limits, those of the stages: the guides are the pinhole ray's (no lens, no shutter in them), reflections and refractions are carried as
  * surface light, lights do not move, one rank (world_size 1), every pixel the same spp. */
@@ -660,7 +700,9 @@ enum {
     BHRT_TEMPORAL_IMG_ALBEDO = 7,           /* W*H*3 float   |                                                    */
     BHRT_TEMPORAL_IMG_NODE = 8,             /* W*H int32    /  (follow_nodes)                                     */
     BHRT_TEMPORAL_IMG_CURRENT = 9,          /* W*H*3 float: the last frame's own render */
-    BHRT_TEMPORAL_IMG_CURRENT_VARIANCE = 10 /* W*H*3 float: its variance as stage 5 read it (carry_variance) */
+    BHRT_TEMPORAL_IMG_CURRENT_VARIANCE = 10, /* W*H*3 float: its variance as stage 5 read it (carry_variance) */
+    BHRT_TEMPORAL_IMG_CHANGE = 11,          /* W*H float: lambda of the change test (bhrt_temporal_set_change); all 0 after frame 0 */
+    BHRT_TEMPORAL_IMG_USED_LENGTH = 12      /* W*H float: the history length stage 5 received, the change test's out_length; all 0 after frame 0 */
 };
 void bhrt_default_temporal_session_opts(bhrt_temporal_session_opts *opts); /* the four stages' defaults, the four switches 0 */
 /* begin: copies the options; needs no device.  BHRT_ERR_ARG, before any device is touched and with nothing changed: a NULL argument; a session
@@ -685,6 +727,15 @@ int bhrt_temporal_status(const bhrt_scene *scene, bhrt_temporal_progress *progre
 int bhrt_temporal_image(bhrt_scene *scene, int which, void *host);
 int bhrt_temporal_image_dev(bhrt_scene *scene, int which, const void **d_ptr);
 int bhrt_temporal_end(bhrt_scene *scene);
+/* The change test of a session: bhrt_temporal_session_opts keeps its bytes, so the switch is a call.  opts: copied; NULL = off,
+ * the state after begin.  Legal while a session is open and no frame has completed since begin or the last reset.  With the test on, frame
+ * k > 0 runs step 4b above; the two images it writes are kept (BHRT_TEMPORAL_IMG_CHANGE, _USED_LENGTH; with the test off the session's mode
+ * does not keep them).  BHRT_TEMPORAL_IMG_HISTORY_LENGTH and bhrt_temporal_progress.history_pixels stay the reprojected length's: they answer
+ * "did this pixel find its surface", which the change test does not alter.  bhrt_temporal_reset keeps the setting, bhrt_temporal_end drops it.
+ * Without this call every frame is byte for byte what it is without the stage.
+ * BHRT_ERR_ARG with nothing changed: a NULL scene; no open session; a complete frame already exists; a session without carry_variance (the
+ * test reads both variances); what bhrt_temporal_change* refuses of the options. */
+int bhrt_temporal_set_change(bhrt_scene *scene, const bhrt_change_opts *opts /* NULL = off */);
 
 /* ---- adaptive sampling: RenderImage's per-pixel sample counts (Scenes/scene.h:534,570), which BeginRender only ever sets to 0
  * (Main.cpp:214), filled by a render that stops sampling a pixel once its mean is good enough ------------------------
