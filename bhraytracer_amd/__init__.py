@@ -90,6 +90,11 @@ class ChangeOpts(C.Structure):
                 ("reserved", C.c_int32 * 3)]
 
 
+class UpsampleOpts(C.Structure):
+    """bhrt_upsample_opts: the edge stops, the demodulation switch and the output gamma of bhrt_upsample (csrc/upsample.hip, stage 4U)."""
+    _fields_ = [("depth_tolerance", C.c_float), ("normal_threshold", C.c_float), ("demodulate", C.c_int32), ("gamma", C.c_int32), ("reserved", C.c_int32 * 4)]
+
+
 class TemporalSessionOpts(C.Structure):
     """bhrt_temporal_session_opts: the four stages' options and the four switches of a temporal session (include/bhrt.h)."""
     _fields_ = [("reproject", ReprojectOpts), ("temporal", TemporalOpts), ("spatial", SpatialVarianceOpts), ("denoise_opts", DenoiseOpts),
@@ -169,6 +174,7 @@ EXPORTS = [
     "bhrt_default_temporal_session_opts", "bhrt_temporal_begin", "bhrt_temporal_frame", "bhrt_temporal_frame_dev", "bhrt_temporal_reset",
     "bhrt_temporal_status", "bhrt_temporal_image", "bhrt_temporal_image_dev", "bhrt_temporal_end",
     "bhrt_default_change_opts", "bhrt_temporal_change", "bhrt_temporal_change_dev", "bhrt_temporal_set_change",
+    "bhrt_scene_set_resolution", "bhrt_default_upsample_opts", "bhrt_upsample", "bhrt_upsample_dev",
 ]
 
 # BHRT_DENOISE_SIGMA_COVERAGE of include/bhrt.h: the default coverage tolerance of the denoiser for sampled guides
@@ -210,6 +216,7 @@ def lib():
         L.bhrt_default_spatial_variance_opts.restype = None
         L.bhrt_default_temporal_session_opts.restype = None
         L.bhrt_default_change_opts.restype = None
+        L.bhrt_default_upsample_opts.restype = None
         _lib = L
     return _lib
 
@@ -276,6 +283,15 @@ def default_change_opts(**kw) -> ChangeOpts:
     """bhrt_default_change_opts (radius 3, sigma_lo and sigma_hi from DESIGN.md 24, depth_tolerance 0.01, normal_threshold 0.99), fields overridden by kw."""
     o = ChangeOpts()
     lib().bhrt_default_change_opts(C.byref(o))
+    for k, v in kw.items():
+        setattr(o, k, v)
+    return o
+
+
+def default_upsample_opts(**kw) -> UpsampleOpts:
+    """bhrt_default_upsample_opts (depth_tolerance 0.01, normal_threshold 0.99, demodulate 1, gamma 1: DESIGN.md 25), fields overridden by kw."""
+    o = UpsampleOpts()
+    lib().bhrt_default_upsample_opts(C.byref(o))
     for k, v in kw.items():
         setattr(o, k, v)
     return o
@@ -356,6 +372,14 @@ class Scene:
         """bhrt_scene_set_lens: the camera's <focaldist> (<= 0 keeps the current one) and <dof> of the loaded scene; the camera frame is derived
         again, and an uploaded scene's camera is refreshed.  Opts.lens = 1 then renders through a thin lens of aperture radius dof."""
         _check(lib().bhrt_scene_set_lens(self._h, C.c_float(focaldist), C.c_float(dof)))
+        self._flat = None
+
+    def set_resolution(self, width: int, height: int):
+        """bhrt_scene_set_resolution: the camera's <width> and <height> of the loaded scene; the camera frame (and pose 1 of an active shutter) is
+        derived again, the blob becomes that of the edited scene file, and an uploaded scene's camera is refreshed.  Refused while a progressive
+        or temporal session is open."""
+        _check(lib().bhrt_scene_set_resolution(self._h, C.c_int32(width), C.c_int32(height)))
+        _check(lib().bhrt_scene_info(self._h, C.byref(self.info)))
         self._flat = None
 
     # ---- the camera and its shutter (DESIGN.md 18) ---------------------------------------------------------------------------------------
@@ -966,6 +990,43 @@ class Scene:
         v = lambda x: C.c_void_p(x or None)  # noqa: E731
         _check(lib().bhrt_temporal_change_dev(self._h, C.byref(opts), v(d_radiance), v(d_variance), v(d_history), v(d_history_variance), v(d_length), v(d_z), v(d_normal),
                                               v(d_out_length), v(d_change), v(stream)))
+
+    # ---- guided upsampling ----------------------------------------------------------------------------------------------------
+    def upsample(self, opts: UpsampleOpts, low_radiance, low_z, low_normal, low_albedo=None, low_variance=None, z=None, normal=None, albedo=None,
+                 want=("out", "variance", "confidence", "rgb8")):
+        """bhrt_upsample on host arrays: this (full-size) scene's frame rebuilt from a low frame (h, w, 3) with H = s h, W = s w, along the
+        full-size first hit (z, normal, albedo None = computed here).  Returns a dict of the outputs named in `want`: out (H, W, 3) float32,
+        variance (H, W, 3) float32 (needs low_variance), confidence (H, W) float32, rgb8 (H, W, 3) uint8."""
+        W, H = self.width, self.height
+        low_radiance = np.ascontiguousarray(low_radiance, np.float32)
+        if low_radiance.ndim != 3 or low_radiance.shape[2] != 3:
+            raise ValueError(f"low_radiance: expected (h, w, 3), got {low_radiance.shape}")
+        h, w = low_radiance.shape[:2]
+        i = [self._image(a, sh, k) for a, sh, k in ((low_variance, (h, w, 3), "low_variance"), (low_z, (h, w), "low_z"), (low_normal, (h, w, 3), "low_normal"),
+                                                    (low_albedo, (h, w, 3), "low_albedo"), (z, (H, W), "z"), (normal, (H, W, 3), "normal"),
+                                                    (albedo, (H, W, 3), "albedo"))]
+        res = {}
+        if "out" in want:
+            res["out"] = np.zeros((H, W, 3), np.float32)
+        if "variance" in want and low_variance is not None:
+            res["variance"] = np.zeros((H, W, 3), np.float32)
+        if "confidence" in want:
+            res["confidence"] = np.zeros((H, W), np.float32)
+        if "rgb8" in want:
+            res["rgb8"] = np.zeros((H, W, 3), np.uint8)
+        p = lambda x: _ptr(x) if x is not None else None  # noqa: E731
+        _check(lib().bhrt_upsample(self._h, C.byref(opts) if opts is not None else None, C.c_int32(w), C.c_int32(h), _ptr(low_radiance), *[p(a) for a in i],
+                                   p(res.get("out")), p(res.get("variance")), p(res.get("confidence")), p(res.get("rgb8"))))
+        return res
+
+    def upsample_dev(self, opts: UpsampleOpts, low_width: int, low_height: int, d_low_radiance: int, d_low_variance: int = 0, d_low_z: int = 0,
+                     d_low_normal: int = 0, d_low_albedo: int = 0, d_z: int = 0, d_normal: int = 0, d_albedo: int = 0, d_out: int = 0, d_out_variance: int = 0,
+                     d_confidence: int = 0, d_rgb8: int = 0, stream: int = 0):
+        """bhrt_upsample_dev on raw device pointers (0 = NULL); with a stream the call does not synchronise."""
+        v = lambda x: C.c_void_p(x or None)  # noqa: E731
+        _check(lib().bhrt_upsample_dev(self._h, C.byref(opts), C.c_int32(low_width), C.c_int32(low_height), v(d_low_radiance), v(d_low_variance), v(d_low_z),
+                                       v(d_low_normal), v(d_low_albedo), v(d_z), v(d_normal), v(d_albedo), v(d_out), v(d_out_variance), v(d_confidence),
+                                       v(d_rgb8), v(stream)))
 
     # ---- images beside the colour image (RenderImage z-buffer, DenoiseImage inputs) ------------
     def first_hit(self):

@@ -19,7 +19,7 @@ LIB = os.path.join(HERE, "libbhrt.so")
 CLI = os.path.join(HERE, "bhrt")
 
 HOST_SRCS = ["scene_host.cpp", "png_io.cpp", "capi_host.cpp", "scene_edit.cpp", "photon_host.cpp"]
-HIP_SRCS = ["kernels.hip", "bvh_build.hip", "gather_sort.hip", "denoise.hip", "temporal.hip", "temporal_change.hip", "temporal_session.hip"]
+HIP_SRCS = ["kernels.hip", "bvh_build.hip", "gather_sort.hip", "denoise.hip", "temporal.hip", "temporal_change.hip", "temporal_session.hip", "upsample.hip"]
 COMMON = ["-O3", "-ffp-contract=off", "-fPIC", "-std=c++17", "-I" + os.path.join(ROOT, "include"), "-I" + CSRC]
 
 
@@ -40,6 +40,11 @@ def build(force: bool = False, verbose: bool = True) -> str:
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     headers = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
     headers += [os.path.join(ROOT, "include", f) for f in os.listdir(os.path.join(ROOT, "include"))]
+    main_src = os.path.join(CSRC, "bhrt_main.cpp")
+    sources = [os.path.join(CSRC, s) for s in HOST_SRCS + HIP_SRCS] + headers
+    # a tree that was copied without its object files: the library and the program are newer than everything they were made from
+    if not force and not _newer(sources, LIB) and not _newer(sources + [main_src, LIB], CLI):
+        return LIB
     objs = []
     for s in HOST_SRCS:
         src, obj = os.path.join(CSRC, s), os.path.join(OUT, s + ".o")
@@ -53,7 +58,6 @@ def build(force: bool = False, verbose: bool = True) -> str:
         objs.append(obj)
     if force or _newer(objs, LIB):
         _run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC"] + objs + ["-lz", "-o", LIB])
-    main_src = os.path.join(CSRC, "bhrt_main.cpp")
     if force or _newer([main_src, LIB] + headers, CLI):  # the C++ host program above the C ABI (Main.cpp:418-431)
         # host-only program (no device code): hipcc for the HIP runtime headers, linked against the C-ABI library and RCCL
         _run([hipcc, "--offload-arch=gfx950"] + COMMON + ["-Wall", "-Wno-unused-result", main_src, "-L" + HERE, "-lbhrt", "-L/opt/rocm/lib", "-lrccl", "-lpthread",

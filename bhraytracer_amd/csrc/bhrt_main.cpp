@@ -100,6 +100,15 @@
 // node to the record it had before frame 0 plus a translate of delta * ((float)k / (float)(N - 1)) per component in float32, and frames are
 // reprojected with bhrt_reproject_moving from the previous frame's node snapshot, id image (bhrt_first_hit_node) and accumulated output; without
 // --to-* the camera stays.  An unknown name, a malformed value, or --node-to-translate without --temporal: a usage error before any device is touched.
+// --width W / --height H (any mode): bhrt_scene_set_resolution on the loaded scene, before every other setter; either flag alone
+// keeps the other value.  A value below 1 is a usage error; a size the library refuses fails with its message.
+// --upsample S [--upsample-depth-tolerance X] [--upsample-normal-threshold X]: the frame is rendered at 1/S of the size and rebuilt
+// at full size by bhrt_upsample: a clone of the scene, with every setter above applied, is set to W/S x H/S and rendered with bhrt_render_var
+// (with --spp 1 with bhrt_render: no variance), photon maps are built on that clone, both scenes' bhrt_first_hit images are taken, and
+// bhrt_upsample with the library's defaults (X replacing a stop; gamma as --no-gamma says) writes the full-size frame; with --denoise
+// bhrt_denoise then filters that frame with the upsampled variance and the full-size guides.  S outside 1..8 or not a divisor of both sides,
+// X without --upsample, and --upsample beside --temporal, --progressive, --adaptive, --guide-spp, --world or --gpus N > 1: a usage error before
+// any device is touched.
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
@@ -174,6 +183,12 @@ struct Args {
     // node's translation at the last frame); `node` is resolved once the scene is loaded
     struct NodeMove { std::string name; float v[3] = {0, 0, 0}; int32_t node = -1; };
     std::vector<NodeMove> node_translate, node_to_translate;
+    int width = 0, height = 0;         // --width W / --height H: bhrt_scene_set_resolution; 0: not given
+    bool width_given = false, height_given = false;
+    int upsample = 0;                  // --upsample S: render at 1/S of the size, bhrt_upsample to the full one
+    bool upsample_given = false;
+    float up_depth_tolerance = -1.f, up_normal_threshold = 0.f; // --upsample-depth-tolerance X (< 0: not given) / --upsample-normal-threshold X
+    bool up_normal_threshold_given = false;
     bool Camera() const { return cam_pos.given || cam_target.given || cam_up.given || fov > 0.f; }
     bool Shutter() const { return sh_pos.given || sh_target.given || sh_up.given; }
 };
@@ -297,6 +312,31 @@ static int denoise_frame(bhrt_scene *scene, const Args &A, const bhrt_info &info
     }
     if (bhrt_guides(scene, &g, z.data(), nrm.data(), alb.data(), nullptr)) return fail("guide images");
     return bhrt_denoise(scene, &A.dn, rad, var, z.data(), nrm.data(), alb.data(), nullptr, rgb) ? fail("DenoiseImage") : 0;
+}
+
+// --upsample S: `low` (the clone at W/S x H/S, uploaded, photon maps built) is rendered, `full` gives the full-size first hit; bhrt_upsample
+// writes the W x H frame, and with --denoise bhrt_denoise filters it with the upsampled variance and the same full-size guides.
+// rgb / rad: the full-size frame (rad may be empty); st: the low render's.
+static int render_upsampled(bhrt_scene *full, bhrt_scene *low, const Args &A, const bhrt_info &info, std::vector<uint8_t> &rgb, std::vector<float> &rad, bhrt_stats &st)
+{
+    const int w = info.width / A.upsample, h = info.height / A.upsample;
+    const size_t n = (size_t)w * h, N = (size_t)info.width * info.height;
+    const bool var = A.o.spp > 1; // at 1 sample per pixel a frame's variance is 0 by definition: none is carried
+    std::vector<float> lrad(n * 3), lvar(var ? n * 3 : 0), lz(n), ln(n * 3), la(n * 3), z(N), nrm(N * 3), alb(N * 3), ovar(var && A.denoise ? N * 3 : 0);
+    if (var ? bhrt_render_var(low, &A.o, nullptr, lrad.data(), lvar.data(), &st) : bhrt_render(low, &A.o, nullptr, lrad.data(), &st)) return fail("BeginRender (low frame)");
+    if (bhrt_first_hit(low, lz.data(), ln.data(), la.data()) || bhrt_first_hit(full, z.data(), nrm.data(), alb.data())) return fail("first hit");
+    bhrt_upsample_opts uo;
+    bhrt_default_upsample_opts(&uo);
+    uo.gamma = A.o.gamma;
+    if (A.up_depth_tolerance >= 0.f) uo.depth_tolerance = A.up_depth_tolerance;
+    if (A.up_normal_threshold_given) uo.normal_threshold = A.up_normal_threshold;
+    if (bhrt_upsample(full, &uo, w, h, lrad.data(), var ? lvar.data() : nullptr, lz.data(), ln.data(), la.data(), z.data(), nrm.data(), alb.data(),
+                      rad.empty() ? nullptr : rad.data(), ovar.empty() ? nullptr : ovar.data(), nullptr, rgb.data()))
+        return fail("upsample");
+    printf("upsample: %d x %d at %d spp -> %d x %d (factor %d, depth tolerance %g, normal threshold %g)\n", w, h, A.o.spp, info.width, info.height, A.upsample,
+           uo.depth_tolerance, uo.normal_threshold);
+    if (A.denoise && bhrt_denoise(full, &A.dn, rad.data(), ovar.empty() ? nullptr : ovar.data(), z.data(), nrm.data(), alb.data(), nullptr, rgb.data())) return fail("DenoiseImage");
+    return 0;
 }
 
 // --temporal N: N frames along the camera move p0 -> p1 (position, target, up), each reprojected into the next view and accumulated there.
@@ -665,6 +705,17 @@ int main(int argc, char **argv)
         }
         else if (s == "--node-translate") A.node_translate.push_back(node_move_value("--node-translate", next()));
         else if (s == "--node-to-translate") A.node_to_translate.push_back(node_move_value("--node-to-translate", next()));
+        else if (s == "--width") { A.width = atoi(next()); A.width_given = true; }
+        else if (s == "--height") { A.height = atoi(next()); A.height_given = true; }
+        else if (s == "--upsample") { A.upsample = atoi(next()); A.upsample_given = true; }
+        else if (s == "--upsample-depth-tolerance") A.up_depth_tolerance = number_value("--upsample-depth-tolerance", next(), false);
+        else if (s == "--upsample-normal-threshold") {
+            const char *text = next();
+            char *end = nullptr;
+            A.up_normal_threshold = strtof(text, &end);
+            if (end == text || *end || A.up_normal_threshold != A.up_normal_threshold) { fprintf(stderr, "bhrt: usage: --upsample-normal-threshold needs a number, got \"%s\"\n", text); return 2; }
+            A.up_normal_threshold_given = true;
+        }
         else if (s == "--fov") {
             A.fov = number_value("--fov", next(), true);
             if (!(A.fov < 180.f)) { fprintf(stderr, "bhrt: usage: --fov needs a number of degrees below 180\n"); return 2; }
@@ -727,7 +778,17 @@ int main(int argc, char **argv)
         fprintf(stderr, "bhrt: usage: --temporal with --denoise filters with the first-hit guides (no --guide-spp, --coverage-filter)\n");
         return 2;
     }
-    if (A.progressive_given && A.gpus == 1) A.gpus = 0; // one device: the session needs no communicator
+    if ((A.width_given && A.width < 1) || (A.height_given && A.height < 1)) { fprintf(stderr, "bhrt: usage: --width and --height need a size of at least 1\n"); return 2; }
+    if ((A.up_depth_tolerance >= 0.f || A.up_normal_threshold_given) && !A.upsample_given) {
+        fprintf(stderr, "bhrt: usage: --upsample-depth-tolerance and --upsample-normal-threshold need --upsample S\n");
+        return 2;
+    }
+    if (A.upsample_given && (A.upsample < 1 || A.upsample > 8)) { fprintf(stderr, "bhrt: usage: --upsample needs a factor S in 1..8\n"); return 2; }
+    if (A.upsample_given && (A.temporal_given || A.progressive_given || A.adaptive || A.guide_spp_given || A.gpus > 1 || o.world_size > 1)) { // before any device is touched
+        fprintf(stderr, "bhrt: usage: --upsample renders one whole frame on one device (no --temporal, --progressive, --adaptive, --guide-spp, --world, --gpus N > 1)\n");
+        return 2;
+    }
+    if ((A.progressive_given || A.upsample_given) && A.gpus == 1) A.gpus = 0; // one device: no communicator is needed
     A.dn.gamma = o.gamma;
     bhrt_scene *scene = nullptr;
     if (bhrt_scene_load_xml(A.scene.c_str(), &scene)) return fail("LoadScene");
@@ -736,6 +797,15 @@ int main(int argc, char **argv)
     for (uint32_t i = 0; i < info.n_warnings; i++) {
         const char *w = nullptr;
         if (!bhrt_scene_warning(scene, i, &w)) fprintf(stderr, "bhrt: warning: %s\n", w);
+    }
+    if (A.width_given || A.height_given) { // before everything else: every later setter and message sees the new size
+        if (bhrt_scene_set_resolution(scene, A.width_given ? A.width : info.width, A.height_given ? A.height : info.height)) return fail("set resolution");
+        bhrt_scene_info(scene, &info);
+    }
+    if (A.upsample_given && (info.width % A.upsample || info.height % A.upsample)) { // before any device is touched
+        fprintf(stderr, "bhrt: usage: --upsample %d does not divide the image size %d x %d\n", A.upsample, info.width, info.height);
+        bhrt_scene_free(scene);
+        return 2;
     }
     printf("Render image width: %d\nRender image height: %d\n", info.width, info.height); // Main.cpp:426-427
     printf("nodes %u, meshes %u (%u triangles, %u BVH nodes), materials %u, lights %u, textures %u, scene blob %llu bytes\n", info.n_nodes,
@@ -824,6 +894,12 @@ int main(int argc, char **argv)
         st.seconds_total = slowest;
         printf("%d GPU(s): frame %.3f s on the slowest GPU, %s tile gather %.4f s, %.3f s wall incl. set-up\n", A.gpus, slowest, A.rehearse ? "rehearsed (device-to-device)" : "RCCL", gather_s, wall);
     } else {
+        bhrt_scene *full = scene; // --upsample: `scene` becomes the low-size clone that is rendered (every setter above is in it), `full` keeps the frame's size
+        if (A.upsample_given) {
+            if (bhrt_scene_clone(full, &scene)) return fail("clone");
+            if (bhrt_scene_set_resolution(scene, info.width / A.upsample, info.height / A.upsample)) return fail("set resolution (low frame)");
+            if (bhrt_scene_upload(full, A.device)) return fail("upload");
+        }
         if (bhrt_scene_upload(scene, A.device)) return fail("upload");
         if (A.global_map) { // BuildPhotonMap, Main.cpp:196
             uint32_t stored = 0;
@@ -840,7 +916,11 @@ int main(int argc, char **argv)
             o.photon_map = 1;
         }
         if (o.photon_map && !A.photon_out.empty() && bhrt_photon_export(scene, A.photon_out.c_str())) return fail("photon export");
-        if (A.temporal_given) {
+        if (A.upsample_given) {
+            if (render_upsampled(full, scene, A, info, rgb, rad, st)) return 1;
+            bhrt_scene_free(scene);
+            scene = full;
+        } else if (A.temporal_given) {
             if (render_temporal(scene, A, info, pose0, pose1, rgb, rad, st)) return 1;
         } else if (A.progressive_given) {
             std::vector<float> var(A.denoise ? rad.size() : 0, 0.f);

@@ -100,6 +100,16 @@ void bhrt_default_change_opts(bhrt_change_opts *o)
     o->normal_threshold = BHRT_REPROJECT_NORMAL_THRESHOLD;
 }
 
+void bhrt_default_upsample_opts(bhrt_upsample_opts *o)
+{
+    if (!o) return;
+    memset(o, 0, sizeof *o);
+    o->depth_tolerance = 0.01f; // bhrt_default_spatial_variance_opts'
+    o->normal_threshold = BHRT_REPROJECT_NORMAL_THRESHOLD;
+    o->demodulate = 1;
+    o->gamma = 1; // as bhrt_opts.gamma (Main.cpp:128)
+}
+
 void bhrt_default_temporal_session_opts(bhrt_temporal_session_opts *o)
 {
     if (!o) return;
@@ -150,6 +160,7 @@ void bhrt_scene_free(bhrt_scene *s)
     if (!s) return;
     if (s->temporal && s->temporal_release) s->temporal_release(s->temporal); // an open temporal session's images, before the streams of the device state go
     if (s->change_scratch && s->change_scratch_release) s->change_scratch_release(s->change_scratch); // likewise: the guides bhrt_temporal_change* computed itself
+    if (s->upsample_scratch && s->upsample_scratch_release) s->upsample_scratch_release(s->upsample_scratch); // likewise: the guides bhrt_upsample* computed itself
     if (s->dev) bhrt::DestroyDeviceState(s->dev);
     delete s;
 }

@@ -1,4 +1,4 @@
-// scene_edit.cpp — the entry points of include/bhrt.h that read or edit a loaded scene (bhrt::FlatScene): lens, camera and shutter, node
+// scene_edit.cpp — the entry points of include/bhrt.h that read or edit a loaded scene (bhrt::FlatScene): lens, image size, camera and shutter, node
 // transforms, emission, face materials.  Host code; a setter ends in the hooks of scene_internal.h, which bring an uploaded scene's device
 // copy up to date and do nothing for a scene that is not uploaded.
 #include <stddef.h>
@@ -26,6 +26,32 @@ try {
         c1.focaldist = H->camera.focaldist; c1.dof = H->camera.dof;
         DeriveCameraFrame(c1);
     }
+    RefreshCamera(scene);
+    RefreshShutter(scene);
+    return BHRT_OK;
+} catch (...) { return bhrt::AbiException(); }
+
+// The image size.  The loader takes any positive int; the limits are the render's and the image-space entry points': a pixel
+// index is 31 bits everywhere, and a side of at most 2^24 keeps every pixel coordinate exact as a float32 and the tile arithmetic inside an int.
+int bhrt_scene_set_resolution(bhrt_scene *scene, int32_t width, int32_t height)
+try {
+    if (!scene) { SetError("bhrt_scene_set_resolution: null scene"); return BHRT_ERR_ARG; }
+    if (width < 1 || height < 1) { SetError("bhrt_scene_set_resolution: width and height must be >= 1"); return BHRT_ERR_ARG; }
+    if (width > BHRT_MAX_IMAGE_SIDE || height > BHRT_MAX_IMAGE_SIDE || (int64_t)width * height > (int64_t)BHRT_MAX_IMAGE_PIXELS) {
+        SetError("bhrt_scene_set_resolution: at most 2^24 pixels a side and 2^31 - 1 pixels in all");
+        return BHRT_ERR_ARG;
+    }
+    if (scene->prog.open) { SetError("bhrt_scene_set_resolution: a progressive session is open on this scene (bhrt_progressive_end first)"); return BHRT_ERR_ARG; }
+    if (scene->temporal) { SetError("bhrt_scene_set_resolution: a temporal session is open on this scene (bhrt_temporal_end first)"); return BHRT_ERR_ARG; }
+    bhrt_flat_header *H = reinterpret_cast<bhrt_flat_header *>(scene->flat.blob.data());
+    H->camera.width = width; H->camera.height = height;
+    DeriveCameraFrame(H->camera);
+    if (scene->flat.shutter) { // pose 1 takes the scene's size: its frame follows
+        bhrt_camera &c1 = scene->flat.shutter_cam;
+        c1.width = width; c1.height = height;
+        DeriveCameraFrame(c1);
+    }
+    // the kernels' camera and shutter are arguments; every per-pixel device buffer is sized by the call that uses it
     RefreshCamera(scene);
     RefreshShutter(scene);
     return BHRT_OK;

@@ -54,6 +54,8 @@ int RenderArgsCheck(bhrt_scene *scene, const bhrt_opts *opts); // what bhrt_rend
 // The guides bhrt_temporal_change* computes itself (z, normal: 16 B per pixel) live in temporal_change.hip, above the public _dev entry points
 // like the session; the scene owns them through a pointer.
 struct ChangeScratch;
+// Likewise the full-size guides bhrt_upsample* computes itself (z, normal, albedo: up to 28 B per pixel), in upsample.hip.
+struct UpsampleScratch;
 } // namespace bhrt
 
 struct bhrt_scene {
@@ -66,4 +68,6 @@ struct bhrt_scene {
     void (*temporal_release)(bhrt::TemporalSession *) = nullptr;
     bhrt::ChangeScratch *change_scratch = nullptr; // allocated by the first bhrt_temporal_change* call that is given no guides; not carried by bhrt_scene_clone
     void (*change_scratch_release)(bhrt::ChangeScratch *) = nullptr; // set with `change_scratch`, for bhrt_scene_free
+    bhrt::UpsampleScratch *upsample_scratch = nullptr; // allocated by the first bhrt_upsample* call that is given no full-size guides; not carried by bhrt_scene_clone
+    void (*upsample_scratch_release)(bhrt::UpsampleScratch *) = nullptr; // set with `upsample_scratch`, for bhrt_scene_free
 };

@@ -153,6 +153,18 @@ int bhrt_scene_flat(const bhrt_scene *scene, const void **blob, uint64_t *bytes)
  * afterwards byte-identical to the blob of the same XML with the two values written into its <camera>.  Needs no device; on an uploaded scene
  * the device's copy of the camera is refreshed (nothing else is uploaded again).  The pointer bhrt_scene_flat returned stays valid. */
 int bhrt_scene_set_lens(bhrt_scene *scene, float focaldist, float dof);
+/* The camera's <width> and <height> of a loaded scene (xmlload.cpp:121-122): the image size of every later render and image-space call.  The
+ * camera frame is derived again by the loader's own code, and so is pose 1 of an active shutter, so bhrt_scene_flat is afterwards byte-identical
+ * to the blob of the same XML with the two values written into its <camera>, bhrt_scene_info reports the new size and bhrt_scene_clone carries
+ * it.  The pointer bhrt_scene_flat returned stays valid.  Needs no device; on an uploaded scene only the device's copy of the camera, and of the
+ * shutter if one is on, is refreshed: every per-pixel device buffer of a scene is sized by the call that uses it (DESIGN.md 25 lists them).
+ * BHRT_ERR_ARG, with nothing changed and before any device is touched: a NULL scene; a width or height < 1; a width or height above
+ * BHRT_MAX_IMAGE_SIDE, or width * height above BHRT_MAX_IMAGE_PIXELS (the loader itself takes any positive int; these are what the render and
+ * the image-space entry points accept: a pixel index is 31 bits everywhere, and a pixel coordinate must be exact as a float32); an open
+ * progressive or temporal session on the scene, whose per-pixel state has the old size (end it first). */
+#define BHRT_MAX_IMAGE_SIDE 16777216      /* 2^24 */
+#define BHRT_MAX_IMAGE_PIXELS 2147483647  /* 2^31 - 1 */
+int bhrt_scene_set_resolution(bhrt_scene *scene, int32_t width, int32_t height);
 /* The camera's <position>, <target>, <up> and <fov> of a loaded scene (xmlload.cpp:109-127), through the loader's own operations:
  * dir = normalized(target - pos), x = dir ^ up, up = normalized(x ^ dir), then the camera frame.  fov <= 0 keeps the current fov; focaldist, dof,
  * width and height are kept.  bhrt_scene_flat is afterwards byte-identical to the blob of the same XML with the four values written into its
@@ -636,6 +648,47 @@ int bhrt_temporal_change_dev(bhrt_scene *scene, const bhrt_change_opts *opts, co
                              void *stream);
 int bhrt_temporal_change(bhrt_scene *scene, const bhrt_change_opts *opts, const float *radiance, const float *variance, const float *history,
                          const float *history_variance, const float *length, const float *z, const float *normal, float *out_length, float *change);
+
+/* ---- guided upsampling: render at 1/s of the size, restore full-size edges ----------------------------------------------------
+ * The cost of a frame is samples x pixels.  bhrt_upsample* rebuilds a W x H frame from a frame rendered at w x h, W = s w and H = s h, along
+ * the full-size first hit, which costs one trace per pixel: a joint bilateral upsampling of the demodulated light.  A full pixel takes the four
+ * low pixels around it (the low pixel's colour sits at its centre) with their bilinear weights, drops those that bhrt_variance_spatial*'s
+ * hard depth and normal stops say lie on another surface, and multiplies the full-size albedo back in, which carries the texture detail.
+ * Stated exactly in csrc/upsample.hip as stage 4U and equal to its numpy restatement on the bytes of every output.
+ *
+ * The scene is the full-size one, W x H; the low frame's size is given: an integer s in 1..8 with W == s * low_width and H == s * low_height.
+ * The low frame is that of the same scene at the low size (bhrt_scene_clone + bhrt_scene_set_resolution), so that low pixel (I, J) covers the
+ * full pixels [s I, s I + s) x [s J, s J + s) and its first-hit ray is that of the full pixel (s I, s J).
+ * low_radiance (w*h*3, required).  low_variance (w*h*3, may be NULL): the variance of each low pixel's mean.  low_z (w*h), low_normal (w*h*3),
+ * required: the low scene's bhrt_first_hit* or bhrt_guides* images, or a low-size session's BHRT_TEMPORAL_IMG_Z / _NORMAL.  low_albedo
+ * (w*h*3): required with opts.demodulate, else not read.  z (W*H), normal (W*H*3), albedo (W*H*3): the full-size first hit; each may be NULL =
+ * computed here by bhrt_first_hit_dev on the call's stream; albedo is read or computed only with opts.demodulate.
+ * Outputs, each may be NULL but not all: out (W*H*3); out_variance (W*H*3; needs low_variance); confidence (W*H): the sum of the bilinear
+ * weights of the taps that passed, 0 where the pixel fell back to taps that did not; rgb8 (W*H*3 bytes: gamma and Color24 of out, as the other
+ * stages').  A NaN guide fails the stops; a NaN radiance propagates into the pixels that weigh it.  With s == 1, the same guides on both
+ * sides, demodulate == 0 and a radiance without -0, out is the radiance bit for bit.
+ * out_variance is each pixel's own variance: sum k^2 v / (sum k)^2 over its taps.  Neighbouring full pixels share taps, so their values are
+ * correlated and the frame's noise is NOT independent across pixels: a filter that reads out_variance as independent per-pixel noise
+ * (bhrt_denoise*) understates the noise of an average over neighbours by up to s^2.
+ * BHRT_ERR_ARG before any device is touched: a NULL scene, options or required image; low_width or low_height < 1, or no s in 1..8 with
+ * W == s * low_width and H == s * low_height; a depth_tolerance that is negative or not finite; a NaN normal_threshold; all outputs NULL;
+ * out_variance without low_variance; an output that is also an input (or another output).
+ * _dev: device pointers; with a stream the call does not synchronise.  Scratch for guides computed here (up to 28 B per pixel) is the
+ * scene's: calls on one scene must not overlap, a call on another stream included. */
+typedef struct bhrt_upsample_opts {
+    float depth_tolerance;  /* bhrt_spatial_variance_opts' meaning and default (0.01f), with the distance to the tap's guide pixel, at least 1 */
+    float normal_threshold; /* bhrt_spatial_variance_opts' meaning and default */
+    int32_t demodulate;     /* 1 (default): interpolate radiance / divisor(albedo) and multiply divisor(full albedo) back; 0: the radiance, no albedo read or computed */
+    int32_t gamma;          /* of rgb8; default 1, as bhrt_opts.gamma */
+    int32_t reserved[4];
+} bhrt_upsample_opts;
+void bhrt_default_upsample_opts(bhrt_upsample_opts *opts);
+int bhrt_upsample_dev(bhrt_scene *scene, const bhrt_upsample_opts *opts, int32_t low_width, int32_t low_height, const float *d_low_radiance,
+                      const float *d_low_variance, const float *d_low_z, const float *d_low_normal, const float *d_low_albedo, const float *d_z,
+                      const float *d_normal, const float *d_albedo, float *d_out, float *d_out_variance, float *d_confidence, uint8_t *d_rgb8, void *stream);
+int bhrt_upsample(bhrt_scene *scene, const bhrt_upsample_opts *opts, int32_t low_width, int32_t low_height, const float *low_radiance,
+                  const float *low_variance, const float *low_z, const float *low_normal, const float *low_albedo, const float *z, const float *normal,
+                  const float *albedo, float *out, float *out_variance, float *confidence, uint8_t *rgb8);
 
 /* ---- temporal session: the chain above as one device-resident call per frame ---------------------------------------------------
  * A viewport's loop while the camera or an object moves:  bhrt_temporal_begin(scene, &opts, &topts);  then per frame the scene setters
