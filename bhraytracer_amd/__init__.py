@@ -136,6 +136,16 @@ def translate(x, y, z):
     return XformOp(XFORM_TRANSLATE, (x, y, z, 0.0))
 
 
+class LightInfo(C.Structure):
+    """bhrt_light_info: one light of a loaded scene as the loader read it, and where it stands in the blob's sorted lights[]."""
+    _fields_ = [("type", C.c_int32), ("intensity", C.c_float * 3), ("vec", C.c_float * 3), ("size", C.c_float), ("blob_index", C.c_int32),
+                ("reserved", C.c_int32 * 5)]
+
+
+# BHRT_LIGHT_* of include/bhrt_flat.h
+LIGHT_AMBIENT, LIGHT_DIRECT, LIGHT_POINT = 0, 1, 2
+
+
 class Hits(C.Structure):
     _fields_ = [("t", C.c_void_p), ("node", C.c_void_p), ("prim", C.c_void_p), ("front", C.c_void_p)]
 
@@ -175,6 +185,7 @@ EXPORTS = [
     "bhrt_temporal_status", "bhrt_temporal_image", "bhrt_temporal_image_dev", "bhrt_temporal_end",
     "bhrt_default_change_opts", "bhrt_temporal_change", "bhrt_temporal_change_dev", "bhrt_temporal_set_change",
     "bhrt_scene_set_resolution", "bhrt_default_upsample_opts", "bhrt_upsample", "bhrt_upsample_dev",
+    "bhrt_scene_light_count", "bhrt_scene_light_index", "bhrt_scene_get_light", "bhrt_scene_set_light",
 ]
 
 # BHRT_DENOISE_SIGMA_COVERAGE of include/bhrt.h: the default coverage tolerance of the denoiser for sampled guides
@@ -433,6 +444,32 @@ class Scene:
         _check(lib().bhrt_scene_set_node_transform(self._h, int(node), v[0], v[1], arr, C.c_uint32(0 if ops is None else len(ops))))
         self._flat = None
 
+    # ---- lights: named by their index in document order; the blob holds them sorted by Gray() -----------------------------
+    def light_count(self) -> int:
+        """bhrt_scene_light_count: the number of lights."""
+        n = C.c_int32(-1)
+        _check(lib().bhrt_scene_light_count(self._h, C.byref(n)))
+        return n.value
+
+    def light_index(self, name: str) -> int:
+        """bhrt_scene_light_index: the first light named `name` in document order (BhrtError, BHRT_ERR_ARG, when there is none)."""
+        i = C.c_int32(-1)
+        _check(lib().bhrt_scene_light_index(self._h, None if name is None else name.encode(), C.byref(i)))
+        return i.value
+
+    def light(self, light: int) -> LightInfo:
+        """bhrt_scene_get_light: the light as the loader read it (type, intensity, vec, size) and its blob_index."""
+        out = LightInfo()
+        _check(lib().bhrt_scene_get_light(self._h, int(light), C.byref(out)))
+        return out
+
+    def set_light(self, light: int, intensity=None, vec=None, size: float = -1.0):
+        """bhrt_scene_set_light: None keeps the intensity / the position or direction, size < 0 the size; the loader's own sort and sum run
+        again, the blob becomes that of the edited scene file, and an uploaded scene's lights, pick table and summed intensity are refreshed."""
+        v = [None if a is None else (C.c_float * 3)(*[float(x) for x in a]) for a in (intensity, vec)]
+        _check(lib().bhrt_scene_set_light(self._h, int(light), v[0], v[1], C.c_float(size)))
+        self._flat = None
+
     # ---- the emission term (DESIGN.md 12): scene state beside the flat blob, which keeps its bytes --------------------
     def set_emissive(self, on: bool = True):
         """bhrt_scene_set_emissive: with the term on, every Shade() frame of a Blinn material adds its <emission> (colour x optional texture) last,
@@ -519,8 +556,8 @@ class Scene:
         return irr, d
 
     def clone(self) -> "Scene":
-        """bhrt_scene_clone: a second handle on the same loaded scene (host state only: the emission, face-material, global-gather and shutter state, node names and edited node transforms included;
-        no device state, so no photon map)."""
+        """bhrt_scene_clone: a second handle on the same loaded scene (host state only: the emission, face-material, global-gather and shutter state, node names and edited node transforms,
+        light names and edited lights included; no device state, so no photon map)."""
         other = Scene.__new__(Scene)
         other._h = C.c_void_p()
         other._flat = None

@@ -15,11 +15,12 @@
 //               [--progressive N [--time-limit SECONDS] [--live-png path]]       (BeginRender .. StopRender, Main.cpp:178,243: the frame in steps)
 //               [--camera-pos X,Y,Z] [--camera-target X,Y,Z] [--camera-up X,Y,Z] [--fov F]   (the <camera> tags, xmlload.cpp:109-127, replaced)
 //               [--shutter-pos X,Y,Z] [--shutter-target X,Y,Z] [--shutter-up X,Y,Z]           (camera motion blur: the camera at the end of the exposure)
-//               [--temporal N [--to-pos X,Y,Z] [--to-target X,Y,Z] [--to-up X,Y,Z] [--node-to-translate NAME:X,Y,Z] [--frames-png PREFIX]   (N frames along a camera or object move, each carried into the next)
+//               [--temporal N [--to-pos X,Y,Z] [--to-target X,Y,Z] [--to-up X,Y,Z] [--node-to-translate NAME:X,Y,Z] [--light-to-pos NAME:X,Y,Z] [--frames-png PREFIX]   (N frames along a camera, object or light move, each carried into the next)
 //                   [--denoise [--denoise-iters K]   (each frame written denoised with its carried variance)
 //                       [--spatial-variance [--variance-radius R] [--variance-min-length X]]   (the variance of a short history estimated from its neighbourhood)
 //                       [--reject-change [--change-radius R] [--change-sigma LO,HI]]]]   (history dropped where a surface's light changed)
 //               [--node-translate NAME:X,Y,Z]   (repeatable: one translate op on that node before anything is rendered)
+//               [--light-pos NAME:X,Y,Z] [--light-dir NAME:X,Y,Z] [--light-intensity NAME:R,G,B] [--light-size NAME:S]   (repeatable: that <light> edited before anything is rendered)
 //   bhrt info   <scene.xml>
 //
 // --gpus N: ONE process drives N GPUs of the node (the reference's one process drives 16 OpenMP threads, Main.cpp:422): the
@@ -100,6 +101,13 @@
 // node to the record it had before frame 0 plus a translate of delta * ((float)k / (float)(N - 1)) per component in float32, and frames are
 // reprojected with bhrt_reproject_moving from the previous frame's node snapshot, id image (bhrt_first_hit_node) and accumulated output; without
 // --to-* the camera stays.  An unknown name, a malformed value, or --node-to-translate without --temporal: a usage error before any device is touched.
+// --light-pos NAME:X,Y,Z (a point light's <position>), --light-dir NAME:X,Y,Z (a direct light's <direction>, normalised by the library),
+// --light-intensity NAME:R,G,B and --light-size NAME:S (a point light's <size>) (each repeatable, any mode): bhrt_scene_set_light on
+// the light of that <light name=>, in command-line order, before anything is rendered and before --gpus N clones the scene.  --light-to-pos
+// NAME:X,Y,Z (repeatable, needs --temporal N): frame k sets the point light to p0 + (p1 - p0) * ((float)k / (float)(N - 1)) per component in
+// float32, p0 its position before frame 0, between the session's frames; the session notices it only through --reject-change.  An unknown name,
+// a light of another kind than the option's, a malformed value, or --light-to-pos without --temporal: a usage error before any device is
+// touched; values the library refuses (a negative intensity, a direction of length 0) fail with its message, before the upload too.
 // --width W / --height H (any mode): bhrt_scene_set_resolution on the loaded scene, before every other setter; either flag alone
 // keeps the other value.  A value below 1 is a usage error; a size the library refuses fails with its message.
 // --upsample S [--upsample-depth-tolerance X] [--upsample-normal-threshold X]: the frame is rendered at 1/S of the size and rebuilt
@@ -183,6 +191,11 @@ struct Args {
     // node's translation at the last frame); `node` is resolved once the scene is loaded
     struct NodeMove { std::string name; float v[3] = {0, 0, 0}; int32_t node = -1; };
     std::vector<NodeMove> node_translate, node_to_translate;
+    // --light-pos / --light-dir / --light-intensity NAME:X,Y,Z and --light-size NAME:S (any mode: bhrt_scene_set_light before anything is rendered, in
+    // command-line order) and --light-to-pos NAME:X,Y,Z (--temporal: the point light's position at the last frame); `light` is resolved once the
+    // scene is loaded
+    struct LightEdit { const char *opt = ""; std::string name; float v[3] = {0, 0, 0}; int32_t light = -1; };
+    std::vector<LightEdit> light_edits, light_to_pos;
     int width = 0, height = 0;         // --width W / --height H: bhrt_scene_set_resolution; 0: not given
     bool width_given = false, height_given = false;
     int upsample = 0;                  // --upsample S: render at 1/S of the size, bhrt_upsample to the full one
@@ -225,6 +238,32 @@ static Args::NodeMove node_move_value(const char *opt, const char *text)
     const Args::Vec v = vector_value(opt, colon + 1);
     for (int k = 0; k < 3; k++) m.v[k] = v.v[k];
     return m;
+}
+
+// "NAME:X,Y,Z" (--light-pos, --light-dir, --light-intensity, --light-to-pos) or, with scalar, "NAME:S" (--light-size): a light's name and three
+// finite numbers or one, else a usage error
+static Args::LightEdit light_edit_value(const char *opt, const char *text, bool scalar = false)
+{
+    Args::LightEdit e;
+    e.opt = opt;
+    const char *colon = strrchr(text, ':');
+    if (!colon || colon == text) {
+        fprintf(stderr, "bhrt: usage: %s needs %s, got \"%s\"\n", opt, scalar ? "NAME:S" : "NAME:X,Y,Z", text);
+        exit(2);
+    }
+    e.name.assign(text, colon);
+    if (scalar) {
+        char *end = nullptr;
+        e.v[0] = strtof(colon + 1, &end);
+        if (end == colon + 1 || *end || !(e.v[0] >= 0.f && e.v[0] <= 3.402823466e38f)) {
+            fprintf(stderr, "bhrt: usage: %s needs NAME:S with a finite number S >= 0, got \"%s\"\n", opt, text);
+            exit(2);
+        }
+    } else {
+        const Args::Vec v = vector_value(opt, colon + 1);
+        for (int k = 0; k < 3; k++) e.v[k] = v.v[k];
+    }
+    return e;
 }
 
 // a finite number >= 0 (--dof, --time-limit) or > 0 (--focaldist, --global-radius), else a usage error
@@ -359,6 +398,10 @@ static int render_temporal(bhrt_scene *scene, const Args &A, const bhrt_info &in
     std::vector<bhrt_xform> saved(A.node_to_translate.size());
     for (size_t m = 0; m < saved.size(); m++)
         if (bhrt_scene_get_node_transform(scene, A.node_to_translate[m].node, &saved[m])) return fail("node transform");
+    // --light-to-pos: the moved point lights' positions as they stand before frame 0
+    std::vector<bhrt_light_info> lights0(A.light_to_pos.size());
+    for (size_t m = 0; m < lights0.size(); m++)
+        if (bhrt_scene_get_light(scene, A.light_to_pos[m].light, &lights0[m])) return fail("get light");
     if (bhrt_temporal_begin(scene, &A.o, &ts)) return fail("temporal session");
     if (A.reject_change) { // the change test between reprojection and accumulation
         bhrt_change_opts ch;
@@ -376,6 +419,12 @@ static int render_temporal(bhrt_scene *scene, const Args &A, const bhrt_info &in
             const Args::NodeMove &mv = A.node_to_translate[m];
             bhrt_xform_op op = {BHRT_XFORM_TRANSLATE, {mv.v[0] * s, mv.v[1] * s, mv.v[2] * s, 0.f}};
             if (bhrt_scene_set_node_transform(scene, mv.node, saved[m].tm, saved[m].pos, &op, 1)) return fail("set node transform");
+        }
+        for (size_t m = 0; m < lights0.size(); m++) { // the point light in equal steps from its position to --light-to-pos
+            const Args::LightEdit &e = A.light_to_pos[m];
+            float q[3];
+            for (int c = 0; c < 3; c++) q[c] = lights0[m].vec[c] + (e.v[c] - lights0[m].vec[c]) * s;
+            if (bhrt_scene_set_light(scene, e.light, nullptr, q, -1.f)) return fail("set light");
         }
         bhrt_stats one;
         if (bhrt_temporal_frame(scene, rgb.data(), nullptr, &one)) return fail("temporal frame");
@@ -705,6 +754,11 @@ int main(int argc, char **argv)
         }
         else if (s == "--node-translate") A.node_translate.push_back(node_move_value("--node-translate", next()));
         else if (s == "--node-to-translate") A.node_to_translate.push_back(node_move_value("--node-to-translate", next()));
+        else if (s == "--light-pos") A.light_edits.push_back(light_edit_value("--light-pos", next()));
+        else if (s == "--light-dir") A.light_edits.push_back(light_edit_value("--light-dir", next()));
+        else if (s == "--light-intensity") A.light_edits.push_back(light_edit_value("--light-intensity", next()));
+        else if (s == "--light-size") A.light_edits.push_back(light_edit_value("--light-size", next(), true));
+        else if (s == "--light-to-pos") A.light_to_pos.push_back(light_edit_value("--light-to-pos", next()));
         else if (s == "--width") { A.width = atoi(next()); A.width_given = true; }
         else if (s == "--height") { A.height = atoi(next()); A.height_given = true; }
         else if (s == "--upsample") { A.upsample = atoi(next()); A.upsample_given = true; }
@@ -756,6 +810,7 @@ int main(int argc, char **argv)
         return 2;
     }
     if (!A.temporal_given && !A.node_to_translate.empty()) { fprintf(stderr, "bhrt: usage: --node-to-translate needs --temporal N\n"); return 2; }
+    if (!A.temporal_given && !A.light_to_pos.empty()) { fprintf(stderr, "bhrt: usage: --light-to-pos needs --temporal N\n"); return 2; }
     if (A.temporal_given && (A.temporal < 2 || A.progressive_given || A.adaptive || A.gpus > 0 || o.world_size > 1)) { // before any device is touched
         fprintf(stderr, "bhrt: usage: --temporal needs N >= 2 frames and renders whole frames on one device (no --progressive, --adaptive, --gpus, --world)\n");
         return 2;
@@ -817,7 +872,29 @@ int main(int argc, char **argv)
                 bhrt_scene_free(scene);
                 return 2;
             }
+    for (std::vector<Args::LightEdit> *edits : {&A.light_edits, &A.light_to_pos}) // before any device is touched: the name, and the kind the option needs
+        for (Args::LightEdit &e : *edits) {
+            if (bhrt_scene_light_index(scene, e.name.c_str(), &e.light)) {
+                fprintf(stderr, "bhrt: usage: %s: the scene has no light named \"%s\"\n", e.opt, e.name.c_str());
+                bhrt_scene_free(scene);
+                return 2;
+            }
+            bhrt_light_info li;
+            if (bhrt_scene_get_light(scene, e.light, &li)) return fail("get light");
+            const bool dir = !strcmp(e.opt, "--light-dir"), any = !strcmp(e.opt, "--light-intensity");
+            if (!any && li.type != (dir ? BHRT_LIGHT_DIRECT : BHRT_LIGHT_POINT)) {
+                fprintf(stderr, "bhrt: usage: %s: the light \"%s\" is not a %s light\n", e.opt, e.name.c_str(), dir ? "direct" : "point");
+                bhrt_scene_free(scene);
+                return 2;
+            }
+        }
     if (!render) { bhrt_scene_free(scene); return 0; }
+    for (const Args::LightEdit &e : A.light_edits) { // in command-line order, before the upload and before --gpus N clones the scene
+        const bool size = !strcmp(e.opt, "--light-size"), intensity = !strcmp(e.opt, "--light-intensity");
+        if (bhrt_scene_set_light(scene, e.light, intensity ? e.v : nullptr, size || intensity ? nullptr : e.v, size ? e.v[0] : -1.f)) return fail(e.opt);
+        if (size) printf("light %s (%d): %s %g\n", e.name.c_str(), e.light, e.opt + 8, e.v[0]);
+        else printf("light %s (%d): %s %g,%g,%g\n", e.name.c_str(), e.light, e.opt + 8, e.v[0], e.v[1], e.v[2]);
+    }
     for (const Args::NodeMove &m : A.node_translate) { // one translate op appended to the node, before the upload and before --gpus N clones the scene
         bhrt_xform xf;
         bhrt_xform_op op = {BHRT_XFORM_TRANSLATE, {m.v[0], m.v[1], m.v[2], 0.f}};

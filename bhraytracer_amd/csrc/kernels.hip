@@ -2432,7 +2432,36 @@ static int UploadCamChain(bhrt_scene *scene)
     return BHRT_OK;
 }
 
-// These three and RefreshShutter, RefreshEmission, RefreshFaceMaterials are what the setters of scene_edit.cpp end in (scene_internal.h)
+// DevScene::light_pick of the scene's lights: Gray_l / all_light_intensity in the blob's (sorted) order.  pick: n_lights floats.  The upload
+// and RefreshLights share it.
+static void FillLightPick(const bhrt::FlatScene &flat, float *pick)
+{
+    const bhrt_flat_header *H = flat.hdr();
+    const bhrt_light *lts = (const bhrt_light *)(flat.blob.data() + H->off_lights);
+    for (uint32_t l = 0; l < H->n_lights; l++) pick[l] = ((lts[l].intensity[0] + lts[l].intensity[1] + lts[l].intensity[2]) / 3.0f) / H->all_light_intensity;
+}
+
+// The device's copy of everything derived from the scene's lights, after bhrt_scene_set_light: the lights block of the blob and
+// the header word beside it (the device blob stays the host blob), the n_lights entries of the pick table, and the kernels' argument copy of
+// all_light_intensity.  Between renders, as RefreshEmission.  PhotonLights is formed from the host blob by every photon build: nothing to do.
+int RefreshLights(bhrt_scene *scene)
+{
+    DeviceState *D = scene->dev;
+    if (!D) return BHRT_OK;
+    HIP_CHECK(hipSetDevice(D->device));
+    const bhrt_flat_header *H = scene->flat.hdr();
+    if (H->n_lights == 0) return BHRT_OK;
+    const uint8_t *blob = scene->flat.blob.data();
+    HIP_CHECK(hipMemcpy(D->d_blob.p + H->off_lights, blob + H->off_lights, (size_t)H->n_lights * sizeof(bhrt_light), hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(D->d_blob.p + offsetof(bhrt_flat_header, all_light_intensity), &H->all_light_intensity, sizeof(float), hipMemcpyHostToDevice));
+    std::vector<float> pick(H->n_lights);
+    FillLightPick(scene->flat, pick.data());
+    HIP_CHECK(hipMemcpy(const_cast<float *>(D->S.light_pick), pick.data(), pick.size() * sizeof(float), hipMemcpyHostToDevice));
+    D->S.all_light_intensity = H->all_light_intensity;
+    return BHRT_OK;
+}
+
+// These four and RefreshShutter, RefreshEmission, RefreshFaceMaterials are what the setters of scene_edit.cpp end in (scene_internal.h)
 int RefreshCamChain(bhrt_scene *scene)
 {
     DeviceState *D = scene->dev;
@@ -3757,7 +3786,6 @@ try {
     S.all_light_intensity = H->all_light_intensity;
     {
         const bhrt_material *mats = (const bhrt_material *)(scene->flat.blob.data() + H->off_materials);
-        const bhrt_light *lts = (const bhrt_light *)(scene->flat.blob.data() + H->off_lights);
         const size_t n_cam = (size_t)std::max<uint32_t>(H->n_nodes, 1) * BHRT_MAX_NODE_DEPTH * 3;
         std::vector<float> aux(H->n_materials + H->n_lights + 1 + n_cam, 0.f);
         FillCamChain(scene->flat, aux.data() + H->n_materials + H->n_lights + 1);
@@ -3766,7 +3794,7 @@ try {
             const double r0d = (double)((1 - ior) / (1 + ior));
             aux[m] = (float)(r0d * r0d);
         }
-        for (uint32_t l = 0; l < H->n_lights; l++) aux[H->n_materials + l] = ((lts[l].intensity[0] + lts[l].intensity[1] + lts[l].intensity[2]) / 3.0f) / H->all_light_intensity;
+        FillLightPick(scene->flat, aux.data() + H->n_materials);
         BHRT_TRY(D->d_aux.Reserve(aux.size()));
         HIP_CHECK(hipMemcpy(D->d_aux, aux.data(), aux.size() * sizeof(float), hipMemcpyHostToDevice));
         S.mat_r0 = D->d_aux;

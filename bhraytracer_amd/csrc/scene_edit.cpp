@@ -1,5 +1,5 @@
 // scene_edit.cpp — the entry points of include/bhrt.h that read or edit a loaded scene (bhrt::FlatScene): lens, image size, camera and shutter, node
-// transforms, emission, face materials.  Host code; a setter ends in the hooks of scene_internal.h, which bring an uploaded scene's device
+// transforms, lights, emission, face materials.  Host code; a setter ends in the hooks of scene_internal.h, which bring an uploaded scene's device
 // copy up to date and do nothing for a scene that is not uploaded.
 #include <stddef.h>
 #include <string.h>
@@ -179,6 +179,45 @@ try {
     const size_t off = (size_t)H->off_nodes + (size_t)node * sizeof(bhrt_node) + offsetof(bhrt_node, xf);
     memcpy(scene->flat.blob.data() + off, &xf, sizeof xf); // nothing above changed the scene
     return RefreshNodeXform(scene, off, xf); // the node's 84 bytes and the camera position through every node's chain; nothing else is uploaded again
+} catch (...) { return bhrt::AbiException(); }
+
+// ---- lights: named by their index in document order (FlatScene::lights); the blob holds them sorted
+int bhrt_scene_light_count(const bhrt_scene *scene, int32_t *n)
+try {
+    if (!scene || !n) { SetError("bhrt_scene_light_count: null argument"); return BHRT_ERR_ARG; }
+    *n = (int32_t)scene->flat.lights.size();
+    return BHRT_OK;
+} catch (...) { return bhrt::AbiException(); }
+
+int bhrt_scene_light_index(const bhrt_scene *scene, const char *name, int32_t *index)
+try {
+    if (!scene || !name || !index) { SetError("bhrt_scene_light_index: null argument"); return BHRT_ERR_ARG; }
+    const std::vector<bhrt::FlatScene::Light> &lights = scene->flat.lights;
+    for (size_t i = 0; i < lights.size(); i++) // the first of that name in document order
+        if (lights[i].name == name) { *index = (int32_t)i; return BHRT_OK; }
+    SetError(std::string("bhrt_scene_light_index: no light named \"") + name + "\"");
+    return BHRT_ERR_ARG;
+} catch (...) { return bhrt::AbiException(); }
+
+int bhrt_scene_get_light(const bhrt_scene *scene, int32_t light, bhrt_light_info *out)
+try {
+    if (!scene || !out) { SetError("bhrt_scene_get_light: null argument"); return BHRT_ERR_ARG; }
+    if (light < 0 || (size_t)light >= scene->flat.lights.size()) { SetError("bhrt_scene_get_light: light index out of range"); return BHRT_ERR_ARG; }
+    const bhrt::FlatScene::Light &l = scene->flat.lights[(size_t)light];
+    memset(out, 0, sizeof *out);
+    out->type = l.type;
+    for (int k = 0; k < 3; k++) { out->intensity[k] = l.intensity[k]; out->vec[k] = l.vec[k]; }
+    out->size = l.size;
+    out->blob_index = l.blob_index;
+    return BHRT_OK;
+} catch (...) { return bhrt::AbiException(); }
+
+int bhrt_scene_set_light(bhrt_scene *scene, int32_t light, const float intensity[3], const float vec[3], float size)
+try {
+    if (!scene) { SetError("bhrt_scene_set_light: null scene"); return BHRT_ERR_ARG; }
+    const char *bad = bhrt::SetLight(scene->flat, light, intensity, vec, size);
+    if (*bad) { SetError(std::string("bhrt_scene_set_light: ") + bad); return BHRT_ERR_ARG; }
+    return RefreshLights(scene); // the lights block, the pick table and the kernels' all_light_intensity; nothing else is uploaded again
 } catch (...) { return bhrt::AbiException(); }
 
 // ---- the emission term: scene state beside the blob

@@ -206,8 +206,41 @@ struct LightData {
     Col intensity = {0, 0, 0};
     V3 vec = {0, 0, 0};
     float size = 0;
+    int doc = 0; // its index among the accepted <light> elements, in document order: what bhrt_scene_*_light names it by (FlatScene::lights)
     float Gray() const { return (intensity.r + intensity.g + intensity.b) / 3.0f; } // cyColor.h Gray()
 };
+// CalculateLightsIntensity (Main.cpp:116-123): std::sort ascending by Gray(), then a float sum.  The loader and SetLight both come here with the
+// lights in document order, so an edited scene's order, ties included, is that of the edited file
+float SortAndSumLights(std::vector<LightData> &lights)
+{
+    std::sort(lights.begin(), lights.end(), [](const LightData &a, const LightData &b) { return a.Gray() < b.Gray(); });
+    float allLight = 0;
+    for (auto &l : lights) allLight += l.Gray();
+    return allLight;
+}
+// the blob's record of a light; the loader and SetLight both store through it
+void StoreLight(bhrt_light &o, const LightData &l)
+{
+    memset(&o, 0, sizeof o);
+    o.type = l.type;
+    o.intensity[0] = l.intensity.r; o.intensity[1] = l.intensity.g; o.intensity[2] = l.intensity.b;
+    o.vec[0] = l.vec.x; o.vec[1] = l.vec.y; o.vec[2] = l.vec.z;
+    o.size = l.size;
+}
+// FlatScene::lights, the document-order records beside the blob, from the loader's lights before the sort; names: the <light name=> of each
+void KeepLights(FlatScene &out, const std::vector<LightData> &lights, const std::vector<std::string> &names)
+{
+    out.lights.assign(lights.size(), FlatScene::Light());
+    for (size_t i = 0; i < lights.size(); i++) {
+        FlatScene::Light &o = out.lights[i];
+        const LightData &l = lights[i];
+        o.name = names[i];
+        o.type = l.type;
+        o.intensity[0] = l.intensity.r; o.intensity[1] = l.intensity.g; o.intensity[2] = l.intensity.b;
+        o.vec[0] = l.vec.x; o.vec[1] = l.vec.y; o.vec[2] = l.vec.z;
+        o.size = l.size;
+    }
+}
 struct NodeData {
     Xform xf;
     int parent = -1, depth = 1, obj_type = BHRT_OBJ_NONE, mesh = -1, material = -1;
@@ -226,6 +259,7 @@ struct Loader {
     std::vector<std::pair<int, std::string>> node_mtl_list; // xmlload.cpp:55-61
     std::vector<MaterialData> materials;
     std::vector<LightData> lights;
+    std::vector<std::string> light_names; // [lights.size()], document order
     std::vector<std::unique_ptr<HostMesh>> meshes;
     std::map<std::string, int> mesh_by_name; // objList.Find (scene.h:187)
     std::vector<TexData> textures;
@@ -386,7 +420,10 @@ struct Loader {
             }
         } else
             return;
+        const char *name = e->Attribute("name"); // not kept by the reference; beside the blob (FlatScene::lights)
+        l.doc = (int)lights.size();
         lights.push_back(l);
+        light_names.push_back(name ? name : "");
     }
 
     // MultiMtl built from a mesh's .mtl (xmlload.cpp:219-250).  Shade() dispatches on hInfo.mtlID,
@@ -1156,10 +1193,8 @@ int LoadSceneXml(const char *path, FlatScene &out, std::string &err, int bvh_dev
         (void)SetCameraPose(C, p3, t3, u3, fov);
     }
 
-    // CalculateLightsIntensity (Main.cpp:116-123): std::sort ascending by Gray(), then a float sum
-    std::sort(L.lights.begin(), L.lights.end(), [](const LightData &a, const LightData &b) { return a.Gray() < b.Gray(); });
-    float allLight = 0;
-    for (auto &l : L.lights) allLight += l.Gray();
+    KeepLights(out, L.lights, L.light_names); // document order, before the sort
+    const float allLight = SortAndSumLights(L.lights);
 
     unsigned maxDepth = 0;
     for (auto &n : L.nodes) if ((unsigned)n.depth > maxDepth) maxDepth = (unsigned)n.depth;
@@ -1338,12 +1373,8 @@ int LoadSceneXml(const char *path, FlatScene &out, std::string &err, int bvh_dev
 
     std::vector<bhrt_light> lights(L.lights.size());
     for (size_t i = 0; i < L.lights.size(); i++) {
-        bhrt_light &o = lights[i];
-        memset(&o, 0, sizeof o);
-        o.type = L.lights[i].type;
-        o.intensity[0] = L.lights[i].intensity.r; o.intensity[1] = L.lights[i].intensity.g; o.intensity[2] = L.lights[i].intensity.b;
-        o.vec[0] = L.lights[i].vec.x; o.vec[1] = L.lights[i].vec.y; o.vec[2] = L.lights[i].vec.z;
-        o.size = L.lights[i].size;
+        StoreLight(lights[i], L.lights[i]);
+        out.lights[(size_t)L.lights[i].doc].blob_index = (int32_t)i;
     }
     H.n_lights = (uint32_t)lights.size();
     H.off_lights = W.Append(lights.data(), lights.size() * sizeof(bhrt_light));
@@ -1392,6 +1423,57 @@ const char *BuildNodeXform(const float tm[9], const float pos[3], const bhrt_xfo
     t.Store(r);
     if (!finite(r.tm, 9) || !finite(r.pos, 3) || !finite(r.itm, 9)) return "a transform that is not finite (a singular matrix)";
     out = r;
+    return "";
+}
+
+const char *SetLight(FlatScene &F, int32_t light, const float intensity[3], const float vec[3], float size)
+{
+    auto finite3 = [](const float *v) { return std::isfinite(v[0]) && std::isfinite(v[1]) && std::isfinite(v[2]); };
+    if (light < 0 || (size_t)light >= F.lights.size()) return "light index out of range";
+    FlatScene::Light rec = F.lights[(size_t)light];
+    if (intensity) {
+        if (!finite3(intensity)) return "a component that is not finite";
+        if (intensity[0] < 0.f || intensity[1] < 0.f || intensity[2] < 0.f) return "a negative intensity component";
+        for (int k = 0; k < 3; k++) rec.intensity[k] = intensity[k];
+    }
+    if (vec) {
+        if (rec.type == BHRT_LIGHT_AMBIENT) return "an ambient light has neither position nor direction (vec must be NULL)";
+        if (!finite3(vec)) return "a component that is not finite";
+        V3 v = v3(vec[0], vec[1], vec[2]);
+        if (rec.type == BHRT_LIGHT_DIRECT) { // LoadLight's own treatment of <direction>
+            if (!(length(v) > 0.f)) return "a direction of length 0";
+            v = normalized(v);
+            if (!std::isfinite(v.x) || !std::isfinite(v.y) || !std::isfinite(v.z)) return "a direction whose normalisation is not finite";
+        }
+        rec.vec[0] = v.x; rec.vec[1] = v.y; rec.vec[2] = v.z;
+    }
+    if (!(size < 0.f)) { // size < 0 keeps it; a NaN is no size
+        if (!std::isfinite(size)) return "a size that is not finite";
+        if (rec.type != BHRT_LIGHT_POINT) return "only a point light has a size (size must be < 0)";
+        rec.size = size;
+    }
+    // the loader's lights as they stood before its sort, with the edited record among them
+    std::vector<LightData> ls(F.lights.size());
+    for (size_t i = 0; i < ls.size(); i++) {
+        const FlatScene::Light &s = i == (size_t)light ? rec : F.lights[i];
+        LightData &l = ls[i];
+        l.type = s.type;
+        l.intensity = {s.intensity[0], s.intensity[1], s.intensity[2]};
+        l.vec = v3(s.vec[0], s.vec[1], s.vec[2]);
+        l.size = s.size;
+        l.doc = (int)i;
+    }
+    const float allLight = SortAndSumLights(ls);
+    if (!(std::isfinite(allLight) && allLight > 0.f)) return "the lights' summed intensity would not be finite and > 0 (the pick table divides by it)";
+    // nothing above changed the scene
+    F.lights[(size_t)light] = rec;
+    bhrt_flat_header *H = reinterpret_cast<bhrt_flat_header *>(F.blob.data());
+    bhrt_light *out = reinterpret_cast<bhrt_light *>(F.blob.data() + H->off_lights);
+    for (size_t i = 0; i < ls.size(); i++) {
+        StoreLight(out[i], ls[i]);
+        F.lights[(size_t)ls[i].doc].blob_index = (int32_t)i;
+    }
+    H->all_light_intensity = allLight;
     return "";
 }
 

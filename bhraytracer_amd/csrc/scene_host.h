@@ -39,6 +39,16 @@ struct FlatScene {
     int shutter = 0;
     float shutter_pos[3] = {0, 0, 0}, shutter_target[3] = {0, 0, 0}, shutter_up[3] = {0, 0, 0};
     bhrt_camera shutter_cam = {};
+    // The lights, beside the blob too: every <light> the loader accepted, in document order, as LoadLight read it (a direct
+    // light's vec normalised), with its name= ("" when absent).  The blob's lights[] is this list sorted by Gray() (CalculateLightsIntensity);
+    // blob_index says where each light stands there now.  SetLight edits a record and derives the blob's lights[] and all_light_intensity again.
+    struct Light {
+        std::string name;
+        int32_t type = 0; // BHRT_LIGHT_*
+        float intensity[3] = {0, 0, 0}, vec[3] = {0, 0, 0}, size = 0;
+        int32_t blob_index = 0;
+    };
+    std::vector<Light> lights; // [n_lights]
     const bhrt_flat_header *hdr() const { return reinterpret_cast<const bhrt_flat_header *>(blob.data()); }
 };
 
@@ -59,6 +69,11 @@ const char *ShutterPairError(const bhrt_camera &a, const bhrt_camera &b);
 // order through LoadTransform's own Scale / Rotate / Translate, stored as the loader stores a node's.  "" and `out` written when every input
 // and every value of the result is finite, else what is wrong and `out` untouched.
 const char *BuildNodeXform(const float tm[9], const float pos[3], const bhrt_xform_op *ops, uint32_t n_ops, bhrt_xform &out);
+
+// What bhrt_scene_set_light does to the host scene: the values given (intensity / vec NULL, size < 0: kept; a direct light's vec
+// through the loader's normalized()) go into F.lights[light], then the loader's own sort-and-sum and store run on the document-order list and
+// rewrite the blob's lights[] and all_light_intensity in place.  "" when done, else what is wrong and F untouched.
+const char *SetLight(FlatScene &F, int32_t light, const float intensity[3], const float vec[3], float size);
 
 // OBJ mesh -> arrays, same face/index rules as cyTriMesh::LoadFromFileObj (cyTriMesh.h:263-547)
 struct HostMesh {

@@ -21,6 +21,7 @@ void RefreshCamera(bhrt_scene *scene);       // the kernels' camera (DevScene::c
 void RefreshShutter(bhrt_scene *scene);      // the kernels' shutter (DeviceState::shutter) from FlatScene::shutter*
 int RefreshCamChain(bhrt_scene *scene);      // DevScene::cam_chain, filled and uploaded again: the camera has moved
 int RefreshNodeXform(bhrt_scene *scene, size_t off, const bhrt_xform &xf); // a node's record, at byte off of the blob, then cam_chain: the node is on some chain
+int RefreshLights(bhrt_scene *scene);        // the blob's lights[], DevScene::light_pick and ::all_light_intensity: a light was edited
 int RefreshEmission(bhrt_scene *scene);      // FlatScene::emission / emissive
 int RefreshFaceMaterials(bhrt_scene *scene); // FlatScene::face_materials
 

@@ -217,7 +217,8 @@ int bhrt_scene_get_camera_frame(const bhrt_scene *scene, float frame[12]);
  * the other setters do: the host calls it when the scene's renders and image calls on its own streams have finished.  On an uploaded scene the node's 84 bytes in the device's blob and the camera position
  * carried through every node's chain are refreshed, and nothing else is uploaded again: between two steps of a progressive session later
  * samples see the new transform, as with the other setters.  Stated limits: an installed caustic or global photon map is the old scene's (the
- * host builds it again); the shutter does not interpolate nodes, so there is no object motion blur; lights do not move.  bhrt_scene_clone
+ * host builds it again); the shutter does not interpolate nodes, so there is no object motion blur; lights are moved by
+ * bhrt_scene_set_light, not by this call.  bhrt_scene_clone
  * carries the names and the edits. */
 enum { BHRT_XFORM_SCALE = 0, BHRT_XFORM_ROTATE = 1, BHRT_XFORM_TRANSLATE = 2 };
 typedef struct bhrt_xform_op {
@@ -229,6 +230,40 @@ int bhrt_scene_node_index(const bhrt_scene *scene, const char *name, int32_t *in
 int bhrt_scene_get_node_transform(const bhrt_scene *scene, int32_t node, struct bhrt_xform *out);
 int bhrt_scene_get_node_transforms(const bhrt_scene *scene, struct bhrt_xform *out, uint32_t capacity, uint32_t *n);
 int bhrt_scene_set_node_transform(bhrt_scene *scene, int32_t node, const float tm[9], const float pos[3], const bhrt_xform_op *ops, uint32_t n_ops);
+/* Lights: the <light> elements of a loaded scene, found, read and set without a reload.  A light is named by its index in document
+ * order: the order of the XML's accepted <light> elements (type ambient, direct or point; xmlload.cpp:394-474).  The blob's lights[] is that list
+ * sorted ascending by Gray() (CalculateLightsIntensity, Main.cpp:116-123), so an intensity edit can permute the blob; the index does not change.
+ *   light_count   the number of lights (bhrt_info.n_lights)
+ *   light_index   the first light whose <light name=> is `name`, in document order; an unknown name or a NULL argument: BHRT_ERR_ARG
+ *   get_light     the light as the loader read it (a direct light's vec normalised) and blob_index, where it stands in the blob's lights[] now
+ *   set_light     intensity == NULL keeps the intensity, vec == NULL the position (point) or direction (direct), size < 0 the size.  A direct
+ *                 light's vec goes through the loader's own normalized(); kind and count never change; a light is switched off by a zero
+ *                 intensity.  The loader's own sort and float sum then run again on the document-order list and the blob's lights[] and
+ *                 all_light_intensity are rewritten in place: bhrt_scene_flat is afterwards byte-identical, ties in Gray() included, to the blob
+ *                 of the same XML with <intensity r g b> (no value=), <position x y z> / <direction x y z> (the caller's un-normalised vector) and
+ *                 <size value> written into that <light>.  The pointer bhrt_scene_flat returned stays valid and total_bytes is unchanged.
+ * BHRT_ERR_ARG, with nothing changed and before any device is touched: a NULL scene; an index outside [0, n); a component that is not finite; a
+ * negative intensity component; a vec for an ambient light; a size >= 0 for a light that is not a point light; a direct vec of length 0, or one
+ * whose normalisation is not finite; a size that is NaN or +inf; an edit after which all_light_intensity is not finite and > 0 (the light-pick
+ * table divides by it: a stated limit, although the loader itself takes such a file).  None of the calls needs a device.  On an uploaded scene
+ * the lights block of the device's blob, the n_lights entries of the light-pick table and the kernels' copy of all_light_intensity are
+ * refreshed, and nothing else is uploaded again, with blocking copies, as the other setters do: the host calls it when the scene's renders and
+ * image calls on its own streams have finished.  Between two steps of a progressive session or two frames of a temporal session later samples
+ * see the new light, as with the other setters.  Stated limits: an installed caustic or global photon map is the old light's (the host builds it
+ * again); the shutter does not interpolate lights, so there is no light motion blur; a temporal session notices the change only through the
+ * change test, which is off unless bhrt_temporal_set_change switched it on.  bhrt_scene_clone carries the names and the edits. */
+typedef struct bhrt_light_info {
+    int32_t type;        /* BHRT_LIGHT_* of include/bhrt_flat.h */
+    float intensity[3];
+    float vec[3];        /* point: position; direct: the normalised direction; ambient: 0 */
+    float size;          /* point: the radius; else 0 */
+    int32_t blob_index;  /* where the light stands in the blob's lights[] now */
+    int32_t reserved[5]; /* 0 */
+} bhrt_light_info; /* 56 B */
+int bhrt_scene_light_count(const bhrt_scene *scene, int32_t *n);
+int bhrt_scene_light_index(const bhrt_scene *scene, const char *name, int32_t *index);
+int bhrt_scene_get_light(const bhrt_scene *scene, int32_t light, bhrt_light_info *out);
+int bhrt_scene_set_light(bhrt_scene *scene, int32_t light, const float intensity[3], const float vec[3], float size);
 /* The emission term.  Every Blinn material carries the <emission> of its XML (xmlload.cpp:344-348: a colour, optionally a texture
  * map); the reference parses it and never shades it, and so does a scene here until it is switched on.  With the term on, every Shade() frame of
  * a Blinn material evaluates to  Shade(hit) + emission.Sample(uvw, duvw)  — one float addition per channel, behind everything Shade() does, on
@@ -723,7 +758,7 @@ int bhrt_upsample(bhrt_scene *scene, const bhrt_upsample_opts *opts, int32_t low
  * spatial_variance + 12; follow_nodes + 8; the change test + 8 (change, used length); the host variant of bhrt_temporal_frame + 3 for rgb8, and with denoise + 12 for the radiance
  * it copies out.  While a session holds images, bhrt_scene_upload to another device returns BHRT_ERR_ARG and changes nothing.
  * Limits, those of the stages: the guides are the pinhole ray's (no lens, no shutter in them), reflections and refractions are carried as
- * surface light, lights do not move, one rank (world_size 1), every pixel the same spp. */
+ * surface light, a light edited between two frames (bhrt_scene_set_light) is noticed only by the change test, one rank (world_size 1), every pixel the same spp. */
 typedef struct bhrt_temporal_session_opts {
     bhrt_reproject_opts reproject;
     bhrt_temporal_opts temporal;
