@@ -91,8 +91,17 @@ class ChangeOpts(C.Structure):
 
 
 class UpsampleOpts(C.Structure):
-    """bhrt_upsample_opts: the edge stops, the demodulation switch and the output gamma of bhrt_upsample (csrc/upsample.hip, stage 4U)."""
+    """bhrt_upsample_opts: the edge stops, the demodulation switch and the output gamma of bhrt_upsample (csrc/upsample.hip, stage 4U).
+    `fallback` (UPSAMPLE_FALLBACK_*) is the header's field in the place of reserved[0]; the header's reserved[3] is reserved[1:] here."""
     _fields_ = [("depth_tolerance", C.c_float), ("normal_threshold", C.c_float), ("demodulate", C.c_int32), ("gamma", C.c_int32), ("reserved", C.c_int32 * 4)]
+
+    @property
+    def fallback(self) -> int:
+        return self.reserved[0]
+
+    @fallback.setter
+    def fallback(self, value: int):
+        self.reserved[0] = value
 
 
 class TemporalSessionOpts(C.Structure):
@@ -188,6 +197,8 @@ EXPORTS = [
     "bhrt_scene_light_count", "bhrt_scene_light_index", "bhrt_scene_get_light", "bhrt_scene_set_light",
 ]
 
+# BHRT_UPSAMPLE_FALLBACK_* of include/bhrt.h: what a pixel no tap passes takes from its taps
+UPSAMPLE_FALLBACK_ALBEDO, UPSAMPLE_FALLBACK_LIGHT = 0, 1
 # BHRT_DENOISE_SIGMA_COVERAGE of include/bhrt.h: the default coverage tolerance of the denoiser for sampled guides
 DENOISE_SIGMA_COVERAGE = 0.5
 # BHRT_REPROJECT_* and BHRT_TEMPORAL_* of include/bhrt.h: the measured defaults of temporal reprojection
@@ -300,7 +311,8 @@ def default_change_opts(**kw) -> ChangeOpts:
 
 
 def default_upsample_opts(**kw) -> UpsampleOpts:
-    """bhrt_default_upsample_opts (depth_tolerance 0.01, normal_threshold 0.99, demodulate 1, gamma 1: DESIGN.md 25), fields overridden by kw."""
+    """bhrt_default_upsample_opts (depth_tolerance 0.01, normal_threshold 0.99, demodulate 1, gamma 1, fallback UPSAMPLE_FALLBACK_ALBEDO: DESIGN.md 25), fields
+    overridden by kw."""
     o = UpsampleOpts()
     lib().bhrt_default_upsample_opts(C.byref(o))
     for k, v in kw.items():

@@ -110,12 +110,12 @@
 // touched; values the library refuses (a negative intensity, a direction of length 0) fail with its message, before the upload too.
 // --width W / --height H (any mode): bhrt_scene_set_resolution on the loaded scene, before every other setter; either flag alone
 // keeps the other value.  A value below 1 is a usage error; a size the library refuses fails with its message.
-// --upsample S [--upsample-depth-tolerance X] [--upsample-normal-threshold X]: the frame is rendered at 1/S of the size and rebuilt
+// --upsample S [--upsample-depth-tolerance X] [--upsample-normal-threshold X] [--upsample-fallback albedo|light]: the frame is rendered at 1/S of the size and rebuilt
 // at full size by bhrt_upsample: a clone of the scene, with every setter above applied, is set to W/S x H/S and rendered with bhrt_render_var
 // (with --spp 1 with bhrt_render: no variance), photon maps are built on that clone, both scenes' bhrt_first_hit images are taken, and
-// bhrt_upsample with the library's defaults (X replacing a stop; gamma as --no-gamma says) writes the full-size frame; with --denoise
+// bhrt_upsample with the library's defaults (X replacing a stop; bhrt_upsample_opts.fallback as --upsample-fallback says; gamma as --no-gamma says) writes the full-size frame; with --denoise
 // bhrt_denoise then filters that frame with the upsampled variance and the full-size guides.  S outside 1..8 or not a divisor of both sides,
-// X without --upsample, and --upsample beside --temporal, --progressive, --adaptive, --guide-spp, --world or --gpus N > 1: a usage error before
+// X or --upsample-fallback without --upsample, another word than albedo or light, and --upsample beside --temporal, --progressive, --adaptive, --guide-spp, --world or --gpus N > 1: a usage error before
 // any device is touched.
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
@@ -202,6 +202,8 @@ struct Args {
     bool upsample_given = false;
     float up_depth_tolerance = -1.f, up_normal_threshold = 0.f; // --upsample-depth-tolerance X (< 0: not given) / --upsample-normal-threshold X
     bool up_normal_threshold_given = false;
+    int up_fallback = BHRT_UPSAMPLE_FALLBACK_ALBEDO; // --upsample-fallback albedo|light: bhrt_upsample_opts.fallback
+    bool up_fallback_given = false;
     bool Camera() const { return cam_pos.given || cam_target.given || cam_up.given || fov > 0.f; }
     bool Shutter() const { return sh_pos.given || sh_target.given || sh_up.given; }
 };
@@ -369,11 +371,12 @@ static int render_upsampled(bhrt_scene *full, bhrt_scene *low, const Args &A, co
     uo.gamma = A.o.gamma;
     if (A.up_depth_tolerance >= 0.f) uo.depth_tolerance = A.up_depth_tolerance;
     if (A.up_normal_threshold_given) uo.normal_threshold = A.up_normal_threshold;
+    uo.fallback = A.up_fallback;
     if (bhrt_upsample(full, &uo, w, h, lrad.data(), var ? lvar.data() : nullptr, lz.data(), ln.data(), la.data(), z.data(), nrm.data(), alb.data(),
                       rad.empty() ? nullptr : rad.data(), ovar.empty() ? nullptr : ovar.data(), nullptr, rgb.data()))
         return fail("upsample");
-    printf("upsample: %d x %d at %d spp -> %d x %d (factor %d, depth tolerance %g, normal threshold %g)\n", w, h, A.o.spp, info.width, info.height, A.upsample,
-           uo.depth_tolerance, uo.normal_threshold);
+    printf("upsample: %d x %d at %d spp -> %d x %d (factor %d, depth tolerance %g, normal threshold %g, fallback %s)\n", w, h, A.o.spp, info.width, info.height,
+           A.upsample, uo.depth_tolerance, uo.normal_threshold, uo.fallback == BHRT_UPSAMPLE_FALLBACK_LIGHT ? "light" : "albedo");
     if (A.denoise && bhrt_denoise(full, &A.dn, rad.data(), ovar.empty() ? nullptr : ovar.data(), z.data(), nrm.data(), alb.data(), nullptr, rgb.data())) return fail("DenoiseImage");
     return 0;
 }
@@ -770,6 +773,13 @@ int main(int argc, char **argv)
             if (end == text || *end || A.up_normal_threshold != A.up_normal_threshold) { fprintf(stderr, "bhrt: usage: --upsample-normal-threshold needs a number, got \"%s\"\n", text); return 2; }
             A.up_normal_threshold_given = true;
         }
+        else if (s == "--upsample-fallback") {
+            const std::string word = next();
+            if (word == "albedo") A.up_fallback = BHRT_UPSAMPLE_FALLBACK_ALBEDO;
+            else if (word == "light") A.up_fallback = BHRT_UPSAMPLE_FALLBACK_LIGHT;
+            else { fprintf(stderr, "bhrt: usage: --upsample-fallback needs albedo or light, got \"%s\"\n", word.c_str()); return 2; }
+            A.up_fallback_given = true;
+        }
         else if (s == "--fov") {
             A.fov = number_value("--fov", next(), true);
             if (!(A.fov < 180.f)) { fprintf(stderr, "bhrt: usage: --fov needs a number of degrees below 180\n"); return 2; }
@@ -834,8 +844,8 @@ int main(int argc, char **argv)
         return 2;
     }
     if ((A.width_given && A.width < 1) || (A.height_given && A.height < 1)) { fprintf(stderr, "bhrt: usage: --width and --height need a size of at least 1\n"); return 2; }
-    if ((A.up_depth_tolerance >= 0.f || A.up_normal_threshold_given) && !A.upsample_given) {
-        fprintf(stderr, "bhrt: usage: --upsample-depth-tolerance and --upsample-normal-threshold need --upsample S\n");
+    if ((A.up_depth_tolerance >= 0.f || A.up_normal_threshold_given || A.up_fallback_given) && !A.upsample_given) {
+        fprintf(stderr, "bhrt: usage: --upsample-depth-tolerance, --upsample-normal-threshold and --upsample-fallback need --upsample S\n");
         return 2;
     }
     if (A.upsample_given && (A.upsample < 1 || A.upsample > 8)) { fprintf(stderr, "bhrt: usage: --upsample needs a factor S in 1..8\n"); return 2; }

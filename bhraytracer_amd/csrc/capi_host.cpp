@@ -108,6 +108,7 @@ void bhrt_default_upsample_opts(bhrt_upsample_opts *o)
     o->normal_threshold = BHRT_REPROJECT_NORMAL_THRESHOLD;
     o->demodulate = 1;
     o->gamma = 1; // as bhrt_opts.gamma (Main.cpp:128)
+    o->fallback = BHRT_UPSAMPLE_FALLBACK_ALBEDO; // 0: the rule as it was before the switch existed
 }
 
 void bhrt_default_temporal_session_opts(bhrt_temporal_session_opts *o)

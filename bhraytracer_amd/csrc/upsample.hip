@@ -2,7 +2,7 @@
 // first hit.  A translation unit above the library's public _dev entry points, like temporal_change.hip: full-size guides the caller leaves out
 // are bhrt_first_hit_dev's, into scratch the scene owns through a pointer (scene_internal.h).
 //
-// 4U. GUIDED UPSAMPLING (k_upsample<kVar>).  All arithmetic is IEEE float32, evaluated left to right as written, IEEE division, no contraction, the
+// 4U. GUIDED UPSAMPLING (k_upsample<kVar, kLight>).  All arithmetic is IEEE float32, evaluated left to right as written, IEEE division, no contraction, the
 // correctly rounded square root dm::sqrt_f; positions are integers (tests/test_upsample.py restates the stage in numpy with the same order).
 //   divisor(a) = dn_divisor of denoise.hip, as in temporal.hip: max(a', 1e-3) per channel, a' = a if max(a.r, a.g, a.b) >= 1e-3, else (1, 1, 1)
 //   The scene's frame is W x H; the low frame is w x h, W = s w, H = s h, s an integer in 1..8.  c, v = the low radiance and the variance of its
@@ -26,6 +26,14 @@
 //   result   over the taps with k_t > 0, in tap order, per channel, from 0:  m = m + k_t e_q,  u = u + (k_t k_t) vv_q
 //            out_p = m / S;  out_variance_p = u / (S S);  with demodulate g = divisor(a_p):  out_p = out_p g,  out_variance_p = out_variance_p (g g)
 //            rgb8_p = store_color24(out_p) (device_color24.h: the gamma and Color24 of k_resolve)
+//   fallback = BHRT_UPSAMPLE_FALLBACK_LIGHT (opts.fallback; the rule above is BHRT_UPSAMPLE_FALLBACK_ALBEDO, the default).  Position, taps, b_t, the
+//            test, k_t, the first S and confidence_p = S are the same, and a pixel whose first S is not 0 is the same in every byte of every
+//            output.  A pixel whose first S == 0 chooses its weights as above (its own kind, then all four) and sums the raw low images, in tap
+//            order from 0, over the taps with k_t > 0:  m = m + k_t c_q,  u = u + (k_t k_t) v_q;  out_p = m / S;  out_variance_p = u / (S S);
+//            NO multiplication by divisor(a_p);  rgb8_p = store_color24(out_p).  A pixel none of whose taps lies on its surface would otherwise
+//            get light that was divided by another surface's albedo times its own: a floor of albedo 0.9 under taps on glass of albedo 0.02
+//            comes out 45 times too bright.  That light was never divided by an albedo the pixel shares, so it is taken as it
+//            was rendered.  With demodulate == 0 e_q = c_q and vv_q = v_q: the two rules are the same arithmetic and the same kernel runs.
 //   A tap of weight 0 takes no part: a NaN radiance propagates into exactly the pixels that weigh it.  With s = 1 every tx is even, fx = fy = 0,
 //   tap 0 is the pixel itself with b_0 = 1: with the same guides on both sides and demodulate = 0, out = (0 + 1 c) / 1 = c bit for bit for a c
 //   that is not -0 (where the pixel fails its own test — a zero normal, a NaN depth — the first fallback gives the same tap).
@@ -41,7 +49,10 @@
 // starts 18 banks on: no two lanes of a half share a bank; at s = 1 (nothing is upsampled) the 17th word of a row meets the next row's first
 // two banks.  The roots of dx dx + dy dy <= 2 * 11^2 (|dx| < 3s / 2) sit in LDS as well, one correctly rounded square root each.  Four taps
 // with fixed trip counts, no dynamically indexed array, no atomics, no scratch memory.  kVar removes the variance planes, their loads and the
-// store; the other outputs are uniform branches.  Per full pixel 16 B read (28 B with albedo) and up to 12 + 12 + 4 + 3 B written; per low pixel
+// store; the other outputs are uniform branches.  kLight (fallback = LIGHT with demodulate) adds one divergent branch for the pixels whose first
+// S == 0, about 1 % of a frame: the staged e_q d_q is not c_q bit for bit, so the branch reads its up to four clamped low pixels again from
+// global memory (they were read while staging: L2 hits) instead of staging three to six more planes for every workgroup; LDS stays as it is.
+// The instantiations without kLight are the kernel as it was.  Per full pixel 16 B read (28 B with albedo) and up to 12 + 12 + 4 + 3 B written; per low pixel
 // 28 B (40 B with albedo, 12 B more with a variance), 1 / s^2 of that per full pixel plus the tile's overlap.
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -90,7 +101,7 @@ __device__ inline V3 up_divisor(const float *albedo, size_t p)
 __device__ inline int up_floor_div(int t, int d) { return (int)((unsigned)(t + d) / (unsigned)d) - 1; }
 
 // Stage 4U.  Every thread of the workgroup, also one outside the image, takes part in staging the tile.
-template <bool kVar>
+template <bool kVar, bool kLight>
 __global__ void __launch_bounds__(kUpTx *kUpTy) k_upsample(UpsampleJob J)
 {
     __shared__ float tile[kVar ? 10 : 7][kUpPlane]; // e.r, e.g, e.b, z, n.x, n.y, n.z, then vv.r, vv.g, vv.b of the low tile
@@ -155,7 +166,8 @@ __global__ void __launch_bounds__(kUpTx *kUpTy) k_upsample(UpsampleJob J)
         S = S + k[t];
     }
     if (J.confidence) J.confidence[p] = S;
-    if (S == 0.f) { // no tap on the pixel's surface: the taps of its own kind
+    const bool lost = S == 0.f; // no tap passed: the pixel falls back
+    if (lost) { // no tap on the pixel's surface: the taps of its own kind
 #pragma unroll
         for (int t = 0; t < 4; t++) {
             k[t] = (zq[t] >= BHRT_BIGFLOAT) == miss ? b[t] : 0.f;
@@ -178,7 +190,20 @@ __global__ void __launch_bounds__(kUpTx *kUpTy) k_upsample(UpsampleJob J)
     }
     V3 o = m / S, ov = v3(0, 0, 0);
     if (kVar) ov = u / (S * S);
-    if (J.demodulate) {
+    if (kLight && lost) { // the taps' light as it was rendered, and no albedo of the pixel's own
+        m = v3(0, 0, 0);
+        u = v3(0, 0, 0);
+#pragma unroll
+        for (int t = 0; t < 4; t++) {
+            if (!(k[t] > 0.f)) continue;
+            const int gi = min(max(I0 + (t & 1), 0), J.w - 1), gj = min(max(J0 + (t >> 1), 0), J.h - 1); // as staged: inside the low image
+            const size_t g = (size_t)gj * J.w + gi;
+            m = m + v3(J.c[3 * g], J.c[3 * g + 1], J.c[3 * g + 2]) * k[t];
+            if constexpr (kVar) u = u + v3(J.v[3 * g], J.v[3 * g + 1], J.v[3 * g + 2]) * (k[t] * k[t]);
+        }
+        o = m / S;
+        if (kVar) ov = u / (S * S);
+    } else if (J.demodulate) {
         const V3 g = up_divisor(J.a, p);
         o = v3(o.x * g.x, o.y * g.y, o.z * g.z);
         if (kVar) ov = v3(ov.x * (g.x * g.x), ov.y * (g.y * g.y), ov.z * (g.z * g.z));
@@ -188,11 +213,15 @@ __global__ void __launch_bounds__(kUpTx *kUpTy) k_upsample(UpsampleJob J)
     if (J.rgb8) store_color24(J.rgb8, p, o, J.gamma);
 }
 
-static hipError_t UpsampleLaunch(const UpsampleJob &J, hipStream_t st)
+// light: fallback = BHRT_UPSAMPLE_FALLBACK_LIGHT
+static hipError_t UpsampleLaunch(const UpsampleJob &J, bool light, hipStream_t st)
 {
     const dim3 grid((unsigned)((J.W + kUpTx - 1) / kUpTx), (unsigned)((J.H + kUpTy - 1) / kUpTy)), block(kUpTx, kUpTy);
-    if (J.out_variance) hipLaunchKernelGGL(k_upsample<true>, grid, block, 0, st, J);
-    else hipLaunchKernelGGL(k_upsample<false>, grid, block, 0, st, J);
+    if (light && J.demodulate) { // without demodulate the two fallbacks are the same arithmetic: the kernel without kLight serves both
+        if (J.out_variance) hipLaunchKernelGGL((k_upsample<true, true>), grid, block, 0, st, J);
+        else hipLaunchKernelGGL((k_upsample<false, true>), grid, block, 0, st, J);
+    } else if (J.out_variance) hipLaunchKernelGGL((k_upsample<true, false>), grid, block, 0, st, J);
+    else hipLaunchKernelGGL((k_upsample<false, false>), grid, block, 0, st, J);
     return hipGetLastError();
 }
 
@@ -249,6 +278,8 @@ static int UpsampleArgs(const bhrt_scene *scene, const bhrt_upsample_opts *o, in
     if ((uint64_t)W * (uint64_t)Hh > 0x7fffffffull) return bad("frame size out of range");
     if (!(o->depth_tolerance >= 0.f) || !UpFinite(o->depth_tolerance)) return bad("depth_tolerance must be finite and >= 0");
     if (o->normal_threshold != o->normal_threshold) return bad("normal_threshold is NaN");
+    if (o->fallback != BHRT_UPSAMPLE_FALLBACK_ALBEDO && o->fallback != BHRT_UPSAMPLE_FALLBACK_LIGHT)
+        return bad("fallback must be BHRT_UPSAMPLE_FALLBACK_ALBEDO or BHRT_UPSAMPLE_FALLBACK_LIGHT");
     if (!out && !out_variance && !confidence && !rgb8) return bad("no output is asked for");
     if (out_variance && !low_variance) return bad("out_variance needs low_variance");
     // an output may be neither an input nor another output: a pixel's taps are other pixels' inputs
@@ -307,7 +338,7 @@ try {
         if (gn) J.n = gn;
         if (ga) J.a = ga;
     }
-    HIP_CHECK(UpsampleLaunch(J, st));
+    HIP_CHECK(UpsampleLaunch(J, opts->fallback == BHRT_UPSAMPLE_FALLBACK_LIGHT, st));
     if (!stream) HIP_CHECK(hipStreamSynchronize(st));
     return BHRT_OK;
 } catch (...) { return bhrt::AbiException(); }

@@ -699,23 +699,32 @@ int bhrt_temporal_change(bhrt_scene *scene, const bhrt_change_opts *opts, const 
  * (w*h*3): required with opts.demodulate, else not read.  z (W*H), normal (W*H*3), albedo (W*H*3): the full-size first hit; each may be NULL =
  * computed here by bhrt_first_hit_dev on the call's stream; albedo is read or computed only with opts.demodulate.
  * Outputs, each may be NULL but not all: out (W*H*3); out_variance (W*H*3; needs low_variance); confidence (W*H): the sum of the bilinear
- * weights of the taps that passed, 0 where the pixel fell back to taps that did not; rgb8 (W*H*3 bytes: gamma and Color24 of out, as the other
- * stages').  A NaN guide fails the stops; a NaN radiance propagates into the pixels that weigh it.  With s == 1, the same guides on both
+ * weights of the taps that passed, 0 where no tap passed and opts.fallback decided the pixel (below); rgb8 (W*H*3 bytes: gamma and Color24 of
+ * out, as the other stages').  A NaN guide fails the stops; a NaN radiance propagates into the pixels that weigh it.  With s == 1, the same guides on both
  * sides, demodulate == 0 and a radiance without -0, out is the radiance bit for bit.
  * out_variance is each pixel's own variance: sum k^2 v / (sum k)^2 over its taps.  Neighbouring full pixels share taps, so their values are
  * correlated and the frame's noise is NOT independent across pixels: a filter that reads out_variance as independent per-pixel noise
  * (bhrt_denoise*) understates the noise of an average over neighbours by up to s^2.
+ * A pixel no tap passes (confidence == 0) takes the taps of its own kind (hit or miss) with their bilinear weights, or all four if there is none.
+ * opts.fallback says what it takes from them.  BHRT_UPSAMPLE_FALLBACK_ALBEDO (0, the default): the same sums as every other pixel, so with
+ * demodulate the taps' demodulated light times the pixel's own divisor(albedo): light of a surface with another albedo comes out scaled by the
+ * ratio of the two.  BHRT_UPSAMPLE_FALLBACK_LIGHT (1): the taps' light as rendered, out = sum k c / S and out_variance =
+ * sum k^2 v / S^2 over the raw low_radiance and low_variance, and no albedo is multiplied in: that light was never divided by an albedo the
+ * pixel shares.  Pixels with confidence > 0 are the same bytes in both modes, and so is every pixel with demodulate == 0.
  * BHRT_ERR_ARG before any device is touched: a NULL scene, options or required image; low_width or low_height < 1, or no s in 1..8 with
- * W == s * low_width and H == s * low_height; a depth_tolerance that is negative or not finite; a NaN normal_threshold; all outputs NULL;
- * out_variance without low_variance; an output that is also an input (or another output).
+ * W == s * low_width and H == s * low_height; a depth_tolerance that is negative or not finite; a NaN normal_threshold; a fallback that is neither
+ * of the two values; all outputs NULL; out_variance without low_variance; an output that is also an input (or another output).
  * _dev: device pointers; with a stream the call does not synchronise.  Scratch for guides computed here (up to 28 B per pixel) is the
  * scene's: calls on one scene must not overlap, a call on another stream included. */
+enum { BHRT_UPSAMPLE_FALLBACK_ALBEDO = 0,   /* a pixel no tap passes is summed like every other pixel: the default */
+       BHRT_UPSAMPLE_FALLBACK_LIGHT = 1 }; /* a pixel no tap passes takes the taps' modulated light */
 typedef struct bhrt_upsample_opts {
     float depth_tolerance;  /* bhrt_spatial_variance_opts' meaning and default (0.01f), with the distance to the tap's guide pixel, at least 1 */
     float normal_threshold; /* bhrt_spatial_variance_opts' meaning and default */
     int32_t demodulate;     /* 1 (default): interpolate radiance / divisor(albedo) and multiply divisor(full albedo) back; 0: the radiance, no albedo read or computed */
     int32_t gamma;          /* of rgb8; default 1, as bhrt_opts.gamma */
-    int32_t reserved[4];
+    int32_t fallback;       /* BHRT_UPSAMPLE_FALLBACK_*: what a pixel with confidence == 0 takes; default BHRT_UPSAMPLE_FALLBACK_ALBEDO */
+    int32_t reserved[3];
 } bhrt_upsample_opts;
 void bhrt_default_upsample_opts(bhrt_upsample_opts *opts);
 int bhrt_upsample_dev(bhrt_scene *scene, const bhrt_upsample_opts *opts, int32_t low_width, int32_t low_height, const float *d_low_radiance,
